@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the candidate-bucket filter on MI355X: mapped reads/sec + % of the HBM roofline.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,11 +16,17 @@ rank its own 1 M reads instead, and the strong run reports that leg too, as `wea
 
 Rank 0 prints ONE JSON line.  `roofline` prices the vote kernel: algorithmic bytes = (index rows the
 reference ANDs, both orientations) x ceil(NB/8)   / mean kernel time from HIP events on
-the kernel's own stream.  `cpu_baseline` = the CPU oracle (a port: the reference cannot be built
-here) timed on one host core over a bounded sample of the same reads.
+the kernel's own stream.
 
-Beside the headline, the default N = 1 run reports more legs on the same card (never as `value`; each is guarded: a leg that
-fails is recorded under its key and costs nothing else):
+A plain run only sets up, warms up, times the `--steps` steps and prints that line (headline, `roofline` from the
+timed steps' own HIP events, `setup`).  `--dump-outputs DIR` also writes what the last timed step computed as .npy
+files (dump_outputs below), so that two builds can be compared output for output on identical seeded inputs.
+
+Everything else runs with `--full` only: `checks` against the simulated truth, `cpu_baseline` = the CPU oracle (a
+port: the reference cannot be built here) timed on one host core over a bounded sample of the same reads, with the
+GPU == oracle parity sample, `roofline.traffic` measured live by a rocprofv3 child, `pcie_inclusive`, the `pruned`
+leg (BMF_FLAG_EARLY_EXIT), the `weak_scaling` leg of a strong N > 1 run, and, beside the headline, more N = 1 legs on
+the same card (never as `value`; each is guarded: a leg that fails is recorded under its key and costs nothing else):
   `locator`               north_star's second replaced subsystem, `bucket_map/locator`'s candidate scan: bml_locate over EVERY
                           candidate the filter produced for the batch -- scan and vote-replay kernel times (HIP events inside the
                           library), occurrences, algorithmic bytes and the fraction of the HBM peak they amount to, the scan's VALU
@@ -196,6 +202,32 @@ def candidate_checks(inputs, counts, buckets, shard):
     return {"reads_with_candidates": float((counts.sum(axis=1) > 0).mean()),
             "source_bucket_recovered": float(((own == rd.truth_bucket[shard][:, None]) & valid).any(axis=1).mean()),
             "candidates_per_read_per_strand": float(counts.mean())}
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SEED = 20240005
+
+
+def dump_outputs(out_dir, counts, buckets, nb, budget=DUMP_BYTES):
+    """Writes the batch's outputs as bmf_batch_download returns them, as float .npy files within `budget` bytes:
+    `windows` (float64, the window indices kept), `counts` (float32, windows x 2 strands) and `buckets` (float32, or
+    float64 once NB reaches 2^24, windows x 2 x max_candidates; slots past a list's count hold -1, since the library
+    leaves them undefined).  A batch too large for the budget is cut to a fixed sample of windows (seed DUMP_SEED), in
+    ascending order, so that two runs with the same arguments write the same windows.  Returns the bytes written."""
+    import numpy as np
+    n, mc = counts.shape[0], buckets.shape[-1]
+    id_type = np.float32 if nb < 1 << 24 else np.float64
+    per_window = 8 + 2 * 4 + 2 * mc * np.dtype(id_type).itemsize
+    keep = min(n, (budget - 4096) // per_window)                     # (4096: the three .npy headers)
+    win = np.arange(n) if keep == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    c = counts[win]
+    b = buckets[win].astype(id_type)
+    b[np.arange(mc)[None, None, :] >= c[:, :, None]] = -1
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"windows": win.astype(np.float64), "counts": c.astype(np.float32), "buckets": b}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in arrays)
 
 
 def pruned_leg(inputs, cli, device, k2i, steps, want, shard=None, all_reduce_max=None, barrier=None):
@@ -645,8 +677,16 @@ def main():
                          "default); weak = every rank maps its own full batch")
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not spawn the rocprofv3 --pmc FETCH_SIZE child that measures roofline.traffic live")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the timed steps: checks, CPU baselines and parity samples, the live "
+                         "rocprofv3 traffic child, pcie_inclusive, the pruned / weak-scaling / locator / skewed / large-index / "
+                         "verifier legs (the leg options above take effect with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's batch)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload.endswith("-skewed"):        # `--workload egu-skewed` = `--workload egu --genome-profile genome`
         args.workload, args.genome_profile = args.workload[: -len("-skewed")], "genome"
     if args.pmc_child:
@@ -752,7 +792,12 @@ def main():
         dist.barrier()
 
     rows_anded = batch.rows_anded()
-    counts, buckets = batch.download()
+    counts = buckets = None
+    if args.full or (args.dump_outputs and rank == 0):
+        counts, buckets = batch.download()
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, counts, buckets, nb)
+        log(f"outputs of the last timed step: {nbytes / 1e6:.1f} MB in {args.dump_outputs}")
 
     # per-rank view of the timed region (N > 1): the slowest rank sets `value`; whether the others were waiting for it
     # (jitter) or every rank lost the same time (a serial part, launch gaps) is read off these.
@@ -776,7 +821,7 @@ def main():
 
     # the other scaling mode, beside the headline (strong runs only): every rank maps the whole batch
     weak_leg = None
-    if scaling == "strong" and world > 1:
+    if args.full and scaling == "strong" and world > 1:
         wb = inp.batch(flt)
         w_elapsed, _, _ = timed_steps(flt, wb, args.steps, 1, barrier)
         weak_s = all_reduce_max(w_elapsed)
@@ -800,14 +845,14 @@ def main():
         return best
     host_pinned_s = host_buffer_s = None
     pinned_b = pinned_q = None
-    if world == 1:
+    if args.full and world == 1:
         pinned_b, pinned_q = bma.pinned_copy(reads.bases), bma.pinned_copy(reads.quals)
         host_pinned_s = time_map_windows(flt, pinned_b.array, pinned_q.array)
         host_buffer_s = time_map_windows(flt, reads.bases, reads.quals)
 
     # Second leg, reported beside the headline, never instead of it: the same batch with BMF_FLAG_EARLY_EXIT.
     pruned = None
-    if not args.early_exit and not args.no_pruned_leg:
+    if args.full and not args.early_exit and not args.no_pruned_leg:
         pruned, fp, bp = pruned_leg(inp, cli, device, k2i, args.steps, (counts, buckets), shard, all_reduce_max,
                                     (dist.barrier if world > 1 else None))
         pruned["value"] = reads_per_step / (pruned["ms_per_step"] * 1e-3)
@@ -836,10 +881,10 @@ def main():
                             f"(k={params.k} q={params.q} S={params.num_samples} F={params.num_fault})",
                 "reads_per_gpu": int(n_mine), "global_reads_per_step": int(reads_per_step),
                 "parallelism": f"reads sharded over {world} GPU(s) in contiguous ranges, index replicated, no collective",
-                "early_exit": bool(args.early_exit),
+                "early_exit": bool(args.early_exit), "full": bool(args.full),
             },
             "roofline": roof,
-            "checks": candidate_checks(inp, counts, buckets, shard),
+            "checks": candidate_checks(inp, counts, buckets, shard) if args.full else None,
             "pruned": pruned,
             "weak_scaling": weak_leg,
             "per_rank": per_rank,
@@ -854,7 +899,7 @@ def main():
                                                 "(ms) and pageable source (ms_pageable)"}
 
         # ---------------- CPU baseline (oracle = port of the reference algorithm, 1 thread) + parity sample
-        if args.cpu_sample > 0 and world == 1:               # the CPU baseline is an N=1 leg only
+        if args.full and args.cpu_sample > 0 and world == 1:     # the CPU baseline is an N=1 leg only
             from oracle import oracle_c
             n_cpu = min(args.cpu_sample, reads.n)
             rows_host = index.rows() if index is not None else flt.index_download()
@@ -890,7 +935,7 @@ def main():
     # every GPU resource of the headline is released before the other legs and the profiler child start
     batch.close()
     flt.close()
-    if rank == 0 and world == 1 and not args.no_locator_leg and not args.no_extra_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_locator_leg and not args.no_extra_legs:
         try:
             result["locator"] = locator_leg(inp, cli, device, counts, buckets, min(args.steps, 3), args.locator_cpu_seconds, log,
                                             pmc=not args.no_pmc and not args.reads and not args.total_bp and not args.bucket_len)
@@ -899,17 +944,17 @@ def main():
     del inp, reads, genome, index
 
     if rank == 0:
-        extra = world == 1 and not args.no_extra_legs and not args.early_exit and args.kmer_frac == 1.0
+        extra = args.full and world == 1 and not args.no_extra_legs and not args.early_exit and args.kmer_frac == 1.0
         # HBM-side traffic of the vote kernel, measured NOW: PMC counters cannot be read in-process, so a child
         # runs the same workload's vote kernel under `rocprofv3 --pmc FETCH_SIZE` (its own pass, no tracing) and the
         # per-dispatch values are corrected as MI355X_MICROARCH.md prescribes (KiB -> bytes, x2 on gfx950 for wide
         # streaming reads).  If the profiler cannot run here the committed pass of the same workload is quoted,
         # and traffic_source says so.
-        if world == 1 and not args.no_pmc and not args.early_exit:
+        if args.full and world == 1 and not args.no_pmc and not args.early_exit:
             live = live_pmc_traffic(args, log)
             if live:
                 result["roofline"].update(live)
-        if result["roofline"]["traffic"] is None:
+        if args.full and result["roofline"]["traffic"] is None:
             try:
                 with open(os.path.join(ROOT, "profiles", "pmc_latest.json")) as f:
                     pmc = json.load(f)

@@ -1,4 +1,5 @@
-"""bench.py's contract, on a small workload: the N = 1 line carries `roofline` (with traffic measured live by the
+"""bench.py's contract, on a small workload: a plain run times the steps and prints the headline, and --dump-outputs
+writes what its last step computed (checked against the CPU oracle); with --full, the N = 1 line carries `roofline` (with traffic measured live by the
 rocprofv3 child), `cpu_baseline` and the `skewed` leg (genome-like genome); several ranks (gloo, all on device 0: the
 rehearsal of the N > 1 path one GPU allows -- two ranks, and four: the GPU box lets six processes on its card at once,
 and the test runner itself is one of them) run BASELINE configs[2]'s STRONG scaling -- the same reads cut into contiguous shards -- and report the weak leg
@@ -8,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +21,7 @@ def _line(out):
 
 
 def test_single_gpu_line_has_roofline_traffic_and_cpu_baseline():
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "mini", "--steps", "3", "--warmup", "1", "--cpu-sample", "5000", "--locator-cpu-seconds", "2"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--workload", "mini", "--steps", "3", "--warmup", "1", "--cpu-sample", "5000", "--locator-cpu-seconds", "2"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -64,7 +66,7 @@ def test_single_gpu_line_has_roofline_traffic_and_cpu_baseline():
 def test_strong_scaling_rehearsal(ranks):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(29533 + ranks), "bench.py", "--gpus", str(ranks), "--backend", "gloo", "--device-override", "0",
-           "--workload", "mini", "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-pmc"]
+           "--workload", "mini", "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-pmc", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -82,3 +84,39 @@ def test_strong_scaling_rehearsal(ranks):
     assert abs(max(pr["step_ms"]) - d["ms_per_step"]) < 0.002               # the headline is the slowest rank (3 decimals kept)
     assert all(0 < k <= s + 0.002 for k, s in zip(pr["kernel_ms_mean"], pr["step_ms"]))
     assert all(a <= b for a, b in zip(pr["kernel_ms_min"], pr["kernel_ms_max"])) and all(s > 0 for s in pr["setup_wall_s"])
+
+
+def test_plain_run_times_only_and_dumps_the_last_step(tmp_path):
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--workload", "mini", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "reads/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u32" and d["metric"].startswith("mapped reads/sec")
+    assert abs(d["value"] - d["config"]["global_reads_per_step"] * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    roof = d["roofline"]
+    assert roof["bound"] == "hbm" and 0 < roof["frac"] < 1.05 and roof["traffic"] is None        # no profiler child
+    assert d["checks"] is None and d["cpu_baseline"] is None and d["pruned"] is None and d["weak_scaling"] is None
+    for leg in ("pcie_inclusive", "cpu_baseline_all_cores", "locator", "skewed", "roofline_large_index", "verifier"):
+        assert leg not in d
+    got = {name: np.load(out / f"{name}.npy") for name in ("windows", "counts", "buckets")}
+    assert sum(os.path.getsize(out / f"{name}.npy") for name in got) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    # what the last timed step computed = what the CPU oracle computes for the same seeded inputs
+    import bench
+    from bucket_map_amd import host
+    from oracle import oracle_c
+    from conftest import oracle_map_windows
+    total_bp, bucket_len, read_len, n_reads = bench.WORKLOADS["mini"]
+    inp = bench.Inputs("mini", total_bp, bucket_len, read_len, n_reads, "uniform", bench.usable_cores())
+    assert np.array_equal(got["windows"], np.arange(len(inp.win_start)))          # the whole batch fits the budget
+    cli = bench.cli_params("default", read_len)
+    index = host.Index(inp.genome, inp.nb, bucket_len, read_len, q=cli["index_seed"], threads=bench.usable_cores())
+    ora = oracle_c.Index(oracle_c.params_from_cli(inp.nb, **cli), rows_ptr=index.rows_ptr, n_rows=index.num_rows,
+                         k2i_ptr=index.k2i_ptr, n_kmers=index.num_kmers)
+    n = 4000
+    c_ref, b_ref, _ = oracle_map_windows(ora, inp.reads.bases, inp.reads.quals, inp.win_start[:n], inp.win_len[:n])
+    assert np.array_equal(got["counts"][:n], c_ref)
+    mask = np.arange(b_ref.shape[-1])[None, None, :] < c_ref[:, :, None]
+    assert np.array_equal(got["buckets"][:n][mask], b_ref[mask]) and (got["buckets"][:n][~mask] == -1).all()

@@ -14,14 +14,14 @@ import pytest
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 REF_MAPPER_H = "/root/reference/bucket_map/mapper/mapper.h"
-EXE = os.path.join(ROOT, "integration", "_build", "ref_binding")
+EXE = os.path.join(ROOT, "oracle", "_ref", "ref_binding")
 
 
 @pytest.mark.skipif(not os.path.exists(REF_MAPPER_H), reason="the reference tree is only in the build container")
 def test_binding_compiles_against_the_reference_mapper_h(tmp_path):
     if os.path.exists(EXE):
         os.remove(EXE)          # compile it NOW (not `make -B`: that would rebuild libbmf.so too)
-    subprocess.run(["make", "-C", ROOT, "integration/_build/ref_binding"], check=True, capture_output=True)
+    subprocess.run(["make", "-C", ROOT, "oracle/_ref/ref_binding"], check=True, capture_output=True)
     assert os.path.exists(EXE)
     # the TU really saw the reference's header: the class in it is abstract with exactly these members
     src = open(REF_MAPPER_H).read()
@@ -41,7 +41,7 @@ def test_binding_compiles_against_the_reference_mapper_h(tmp_path):
 @pytest.mark.parametrize("long_reads", [False, True])
 def test_binding_lists_equal_the_c_abi(tmp_path, long_reads):
     if not os.path.exists(EXE):
-        pytest.skip("integration/_build/ref_binding was not built (it needs /root/reference: build container only)")
+        pytest.skip("oracle/_ref/ref_binding was not built (build() makes it only where the reference tree is at hand)")
     import bucket_map_amd as bma
     from bucket_map_amd import host
     bucket_len, read_len = 4096, 150

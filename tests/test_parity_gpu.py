@@ -233,12 +233,12 @@ def test_pruning_form_is_measured_on_the_first_large_batch():
     flt.close()
 
 
-def test_repeats_overflow_max_candidates():
+def test_repeats_overflow_max_candidates(tmp_path):
     # 40 identical records -> a read matches > 30 buckets equally well -> list cleared (q_gram_mapper.h:471-476)
     from bucket_map_amd import host
     g1 = host.Genome.synth(5, [3000])
     seq = bytes(g1.record_seq(0))
-    path = "/tmp/bm_repeat_genome.fa"
+    path = str(tmp_path / "repeat_genome.fa")
     with open(path, "w") as f:
         for i in range(40):
             f.write(f">rep{i}\n{seq.decode()}\n")
@@ -255,7 +255,7 @@ def test_repeats_overflow_max_candidates():
 
 
 @pytest.mark.parametrize("copies,expect_cleared", [(3, False), (40, True)])
-def test_ties_across_slices(copies, expect_cleared):
+def test_ties_across_slices(tmp_path, copies, expect_cleared):
     # NB > 65 536: identical records far apart put equally good buckets into DIFFERENT 65 536-bucket slices;
     # the merge must concatenate them in ascending order, and clear the list when the slices together
     # exceed max_candidates although no single slice does (q_gram_mapper.h:471-476).
@@ -263,7 +263,7 @@ def test_ties_across_slices(copies, expect_cleared):
     per_copy = 140_000 // copies
     g1 = host.Genome.synth(6, [per_copy * 256])          # keep alive: record_seq is a view into it
     unit = bytes(g1.record_seq(0)).decode()
-    path = f"/tmp/bm_slices_{copies}.fa"
+    path = str(tmp_path / f"slices_{copies}.fa")
     with open(path, "w") as f:
         for i in range(copies):
             f.write(f">copy{i}\n{unit}\n")

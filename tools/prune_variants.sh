@@ -1,8 +1,10 @@
 set -e
 cd $GRAFT_REPO_ROOT
-run() { name=$1; shift; env "$@" python3 bench.py --no-extra-legs --no-pmc --cpu-sample 0 --genome-profile genome --steps 3 > gpurun_out/pv_$name.json 2> gpurun_out/pv_$name.err || echo "$name failed"; python3 - <<PY
+OUT=${OUT:-runs}      # output folder (relative to the repository root)
+mkdir -p "$OUT"
+run() { name=$1; shift; env "$@" python3 bench.py --full --no-extra-legs --no-pmc --cpu-sample 0 --genome-profile genome --steps 3 > "$OUT/pv_$name.json" 2> "$OUT/pv_$name.err" || echo "$name failed"; python3 - <<PY
 import json
-d=json.load(open("gpurun_out/pv_$name.json"))
+d=json.load(open("$OUT/pv_$name.json"))
 p=d["pruned"]
 print("$name", round(p["ms_per_step"],2), p.get("form"), p.get("pass1_rows"), p.get("pass1_fold"), p.get("pass1_fold_rows"), p.get("items_recounted"), p.get("items_slow_path"), p.get("recount_column_loads"), p["outputs_identical_to_headline_run"])
 PY

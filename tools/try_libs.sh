@@ -5,14 +5,15 @@
 #   gpurun -- 'bash tools/try_libs.sh'
 set -e
 shopt -s nullglob
-mkdir -p gpurun_out
+OUT=${OUT:-runs}      # output folder (relative to the repository root)
+mkdir -p "$OUT"
 cp bucket-map_amd/libbmf.so /tmp/libbmf_main.so
 for lib in /tmp/libbmf_main.so bucket-map_amd/alt/*.so /tmp/libbmf_main.so; do
     cp "$lib" bucket-map_amd/libbmf.so
-    python bench.py --no-pmc --no-extra-legs --steps 10 --warmup 3 > gpurun_out/try_$(basename $lib .so).json
-    python - "$lib" <<'PY'
+    python bench.py --full --no-pmc --no-extra-legs --steps 10 --warmup 3 > "$OUT/try_$(basename $lib .so).json"
+    python - "$lib" "$OUT" <<'PY'
 import json, sys, os
-d = json.load(open("gpurun_out/try_" + os.path.basename(sys.argv[1])[:-3] + ".json"))
+d = json.load(open(os.path.join(sys.argv[2], "try_" + os.path.basename(sys.argv[1])[:-3] + ".json")))
 print(os.path.basename(sys.argv[1]), "default", d["ms_per_step"], "pruned", {k: v for k, v in d["pruned"].items() if "ms" in k or "reads" in k})
 PY
 done
