@@ -2,7 +2,7 @@
 // Host side only: validation, choice of the kernel shape for the longest query of the batch, chunking so
 // that the traceback bits of one chunk fit the scratch budget, offsets of the packed CIGAR output
 // (bm_scan.hip.h's exclusive sum).
-#include "bmv_kernels.hip.h"
+#include "bmv_long.hip.h"
 
 namespace bmv {
 // instantiated in bmv_variants.hip
@@ -25,6 +25,10 @@ extern template __global__ void bmv_align_lane_kernel<5>(Job);
 extern template __global__ void bmv_align_lane_kernel<6>(Job);
 extern template __global__ void bmv_align_lane_kernel<7>(Job);
 extern template __global__ void bmv_align_lane_kernel<8>(Job);
+// instantiated in bmv_long.hip
+extern template __global__ void bmv_long_prep_kernel<kLongCw>(LongJob, uint32_t);
+extern template __global__ void bmv_long_tile_kernel<kLongCw>(LongJob);
+extern template __global__ void bmv_long_traceback_kernel<kLongCw>(LongJob);
 
 // CIGAR entries of one chunk, reversed into reading order at their final offsets.
 __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t ops_stride,
@@ -199,6 +203,8 @@ struct bmv_ctx {
     DevBuf<uint64_t> text_start, query_start, trace;
     DevBuf<uint32_t> text_len, query_len, ops_rev, nops, offsets, packed, out_begin, order;
     DevBuf<int32_t> out_score;
+    DevBuf<uint8_t> long_slots;                // bmv_align_long: the slots of a piece ...
+    DevBuf<uint32_t> long_tiles;               // ... and its tiles, launch by launch
     // results of the last bmv_align, host side
     uint32_t n_last = 0;
     std::vector<int32_t> h_score;
@@ -269,6 +275,7 @@ void bmv_destroy(bmv_ctx *c) {
     c->text_start.release(); c->query_start.release(); c->trace.release();
     c->text_len.release(); c->query_len.release(); c->ops_rev.release(); c->nops.release(); c->offsets.release();
     c->packed.release(); c->out_begin.release(); c->out_score.release(); c->order.release();
+    c->long_slots.release(); c->long_tiles.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -614,6 +621,267 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
     HIP_TRY(hipMemcpy(c->h_score.data(), c->out_score.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(c->h_begin.data(), c->out_begin.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     *total_cigar = c->h_cigar.size();
+    return BMV_OK;
+}
+
+// Alignments beyond the context's limits (bmv_long.hip.h): the batch is split, what bmv_align takes goes through bmv_align
+// unchanged, the rest through tiles of 64 lanes x kLongCw words x `chunk` steps launched by anti-diagonal.  Their scratch
+// (checkpoints, deltas, planes, packed text; reversed CIGAR entries) is planned against scratch_bytes: they are taken in
+// pieces that fit it, and one that does not fit alone fails the call before anything runs.
+int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                   const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                   uint32_t n, uint64_t *total_cigar) {
+    if (!c || !total_cigar) return fail(BMV_ERR_ARG, "bmv_align_long: null argument");
+    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_align_long before bmv_load_genome");
+    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || (n_read_bytes && !reads)))
+        return fail(BMV_ERR_ARG, "bmv_align_long: null argument");
+    // experiment / test knob: every query of at least this many bases takes the long path (0: off)
+    const uint32_t long_from = getenv("BMV_LONG_FROM") ? (uint32_t)strtoul(getenv("BMV_LONG_FROM"), nullptr, 10) : 0u;
+    std::vector<uint32_t> shorts, longs;
+    uint64_t cells = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
+        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
+        cells += (uint64_t)query_len[a] * text_len[a];
+        const bool beyond = query_len[a] > c->p.max_query_len || text_len[a] > c->p.max_text_len || (long_from && query_len[a] >= long_from);
+        (beyond ? longs : shorts).push_back(a);
+    }
+    if (longs.empty())                                          // nothing beyond the limits: bmv_align's own path
+        return bmv_align(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, total_cigar);
+
+    // the long ones: tile shape and scratch of each, refused before anything runs if one cannot fit the budget on its own
+    constexpr uint32_t CW = (uint32_t)bmv::kLongCw;
+    uint32_t max_chunk = 8192;                                  // time steps per tile (BMV_LONG_CHUNK: experiments)
+    if (const char *env = getenv("BMV_LONG_CHUNK")) max_chunk = (uint32_t)std::min<long>(std::max<long>(atol(env), 16), 65536) / 16u * 16u;
+    const uint64_t budget = c->scratch_bytes;
+    struct Long {
+        bmv::LongSlot s;
+        uint64_t bytes, ops_stride;
+    };
+    std::vector<Long> todo;
+    std::vector<uint32_t> empty_query;                          // (score 0, begin n, no CIGAR: nothing to run)
+    for (uint32_t a : longs) {
+        const uint32_t m = query_len[a], nn = text_len[a];
+        if (m == 0) {
+            empty_query.push_back(a);
+            continue;
+        }
+        bmv::LongSlot s{};
+        s.a = a;
+        s.m = m;
+        s.n = nn;
+        s.W = (uint32_t)(((uint64_t)m + 63u) / 64u);
+        const uint32_t lanes = (s.W + CW - 1u) / CW;
+        s.n_strips = (lanes + 63u) / 64u;
+        const uint64_t span = (uint64_t)nn + lanes - 1u;        // time steps: the last lane passes column n at n + lanes - 1
+        s.chunk = (uint32_t)std::min<uint64_t>(max_chunk, std::max<uint64_t>(16u, (span + 15u) / 16u * 16u));
+        const uint64_t n_chunks = std::max<uint64_t>(1u, (span + s.chunk - 1u) / s.chunk);
+        if (n_chunks * s.chunk + 64u >= ((uint64_t)1 << 32))
+            return fail(BMV_ERR_UNSUPPORTED, "alignment %u: a query of %u bases against %u text bases does not fit the 32-bit step counter", a, m, nn);
+        s.n_chunks = (uint32_t)n_chunks;
+        s.n_blocks = (uint32_t)(n_chunks * s.chunk / 16u + 1u);
+        const uint64_t bytes = bmv::long_region_bytes(s.W, nn, s.n_blocks), ops_stride = (uint64_t)m + nn + 1u;
+        if (bytes + ops_stride * 4u > budget)
+            return fail(BMV_ERR_UNSUPPORTED, "alignment %u: a query of %u bases against %u text bases needs %llu bytes of trace; the scratch holds %llu (BMV_SCRATCH_MB)",
+                        a, m, nn, (unsigned long long)(bytes + ops_stride * 4u), (unsigned long long)budget);
+        todo.push_back({s, bytes, ops_stride});
+    }
+
+    std::vector<int32_t> score(n, 0);
+    std::vector<uint32_t> begin(n, 0);
+    std::vector<uint64_t> cig_at(n, 0), cig_len(n, 0);
+    std::vector<uint32_t> pool;                                 // CIGAR entries, alignment by alignment in any order
+    float ms_total = 0.f;
+    if (!shorts.empty()) {                                      // exactly what bmv_align does with them on their own
+        const size_t ns = shorts.size();
+        std::vector<uint64_t> ts(ns), qs(ns);
+        std::vector<uint32_t> tl(ns), ql(ns);
+        std::vector<uint8_t> trc(ns);
+        for (size_t k = 0; k < ns; k++) {
+            const uint32_t a = shorts[k];
+            ts[k] = text_start[a];
+            tl[k] = text_len[a];
+            trc[k] = text_rc[a];
+            qs[k] = query_start[a];
+            ql[k] = query_len[a];
+        }
+        uint64_t tot = 0;
+        if (int rc = bmv_align(c, reads, n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), (uint32_t)ns, &tot)) return rc;
+        for (size_t k = 0; k < ns; k++) {
+            const uint32_t a = shorts[k];
+            score[a] = c->h_score[k];
+            begin[a] = c->h_begin[k];
+            cig_at[a] = c->h_offset[k];
+            cig_len[a] = c->h_offset[k + 1] - c->h_offset[k];
+        }
+        pool = c->h_cigar;
+        ms_total += c->ms_kernels;
+    }
+    for (uint32_t a : empty_query) begin[a] = text_len[a];      // H[0][j] = 0 everywhere: the last column
+
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(c->reads.need((size_t)n_read_bytes + 64u));
+    HIP_TRY(c->text_start.need(n));
+    HIP_TRY(c->text_rc.need(n));
+    HIP_TRY(c->query_start.need(n));
+    HIP_TRY(c->out_score.need(n));
+    HIP_TRY(c->out_begin.need(n));
+    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    std::vector<bmv::LongSlot> slots;
+    std::vector<uint32_t> tiles, h_nops, h_packed;
+    std::vector<uint64_t> tile_at;
+    std::vector<int32_t> h_score(n);
+    std::vector<uint32_t> h_begin(n);
+    // pieces: as many as fit the budget together (at least one; the uniform CIGAR stride is the longest's), planned before
+    // the scratch is sized once for the largest (growing a 90-GB buffer piece by piece costs seconds in hipMalloc)
+    struct LongPiece {
+        size_t p0, p1;
+        uint64_t sum, ops_stride;
+    };
+    std::vector<LongPiece> pieces;
+    uint64_t max_sum = 0, max_ops = 0, max_count = 0;
+    for (size_t p0 = 0; p0 < todo.size();) {
+        LongPiece pc{p0, p0, 0, 0};
+        while (pc.p1 < todo.size()) {
+            const uint64_t st = std::max(pc.ops_stride, todo[pc.p1].ops_stride);
+            if (pc.p1 > p0 && pc.sum + todo[pc.p1].bytes + (pc.p1 - p0 + 1u) * st * 4u > budget) break;
+            pc.sum += todo[pc.p1].bytes;
+            pc.ops_stride = st;
+            pc.p1++;
+        }
+        max_sum = std::max(max_sum, pc.sum);
+        max_ops = std::max<uint64_t>(max_ops, (pc.p1 - p0) * pc.ops_stride);
+        max_count = std::max<uint64_t>(max_count, pc.p1 - p0);
+        pieces.push_back(pc);
+        p0 = pc.p1;
+    }
+    HIP_TRY(c->trace.need((size_t)(max_sum + 7u) / 8u));
+    HIP_TRY(c->ops_rev.need((size_t)max_ops));
+    HIP_TRY(c->nops.need((size_t)max_count));
+    HIP_TRY(c->offsets.need((size_t)max_count + 1u));
+    for (const LongPiece &pc : pieces) {
+        const size_t p0 = pc.p0, p1 = pc.p1;
+        const uint64_t sum = pc.sum, ops_stride = pc.ops_stride;
+        const uint32_t count = (uint32_t)(p1 - p0);
+        slots.clear();
+        uint64_t at = 0, max_items = 1;
+        uint32_t max_d = 0, chunk = 16;
+        for (size_t q = p0; q < p1; q++) {
+            bmv::LongSlot s = todo[q].s;
+            s.at = at;
+            at += todo[q].bytes;
+            slots.push_back(s);
+            max_d = std::max(max_d, s.n_strips + s.n_chunks - 2u);
+            max_items = std::max<uint64_t>(max_items, std::max(s.W, bmv::long_text_words(s.n)));
+            chunk = std::max(chunk, s.chunk);
+        }
+        // the tiles of launch d: every (slot, strip) with strip + chunk = d
+        tiles.clear();
+        tile_at.assign((size_t)max_d + 2u, 0);
+        for (uint32_t d = 0; d <= max_d; d++) {
+            tile_at[d] = tiles.size() / 2u;
+            for (uint32_t q = 0; q < count; q++) {
+                const bmv::LongSlot &s = slots[q];
+                const uint32_t lo = d + 1u > s.n_chunks ? d + 1u - s.n_chunks : 0u, hi = std::min(d, s.n_strips - 1u);
+                for (uint32_t st = lo; st <= hi && lo <= hi; st++) {
+                    tiles.push_back(q);
+                    tiles.push_back(st);
+                }
+            }
+        }
+        tile_at[(size_t)max_d + 1u] = tiles.size() / 2u;
+        HIP_TRY(c->long_slots.need(slots.size() * sizeof(bmv::LongSlot)));
+        HIP_TRY(c->long_tiles.need(tiles.size()));
+        HIP_TRY(hipMemcpyAsync(c->long_slots.p, slots.data(), slots.size() * sizeof(bmv::LongSlot), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->long_tiles.p, tiles.data(), tiles.size() * 4u, hipMemcpyHostToDevice, c->stream));
+        bmv::LongJob j{};
+        j.genome = c->genome.p;
+        j.reads = c->reads.p;
+        j.lut = c->lut.p;
+        j.text_start = c->text_start.p;
+        j.text_rc = c->text_rc.p;
+        j.query_start = c->query_start.p;
+        j.slots = reinterpret_cast<const bmv::LongSlot *>(c->long_slots.p);
+        j.count = count;
+        j.scratch = reinterpret_cast<uint8_t *>(c->trace.p);
+        j.ops_rev = c->ops_rev.p;
+        j.ops_stride = (uint32_t)ops_stride;
+        j.out_score = c->out_score.p;
+        j.out_begin = c->out_begin.p;
+        j.out_nops = c->nops.p;
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        const uint32_t per_slot = (uint32_t)std::min<uint64_t>(256u, (max_items + 255u) / 256u);
+        hipLaunchKernelGGL(bmv::bmv_long_prep_kernel<bmv::kLongCw>, dim3(count * per_slot), dim3(256), 0, c->stream, j, per_slot);
+        HIP_TRY(hipGetLastError());
+        const size_t lds = ((size_t)chunk / 16u + 5u) * 4u;
+        for (uint32_t d = 0; d <= max_d; d++) {
+            const uint64_t nt = tile_at[(size_t)d + 1u] - tile_at[d];
+            if (nt == 0) continue;
+            j.tiles = c->long_tiles.p + 2u * tile_at[d];
+            j.d = d;
+            hipLaunchKernelGGL(bmv::bmv_long_tile_kernel<bmv::kLongCw>, dim3((uint32_t)nt), dim3(bmv::kWave), lds, c->stream, j);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(bmv::bmv_long_traceback_kernel<bmv::kLongCw>, dim3((count + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0,
+                           c->stream, j);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        // CIGARs of the piece -> the host: one exclusive sum, one gather
+        HIP_TRY(c->scan_tmp.need(bmscan::tmp_elems(count) * sizeof(uint32_t)));
+        HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->nops.p, c->offsets.p, count, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
+        uint32_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, c->offsets.p + count, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->packed.need(total));
+        hipLaunchKernelGGL(bmv::bmv_gather_kernel, dim3((count + 31u) / 32u), dim3(256), 0, c->stream, c->ops_rev.p, (uint32_t)ops_stride,
+                           c->nops.p, c->offsets.p, count, c->packed.p);
+        HIP_TRY(hipGetLastError());
+        h_nops.resize(count);
+        h_packed.resize(total);
+        HIP_TRY(hipMemcpyAsync(h_nops.data(), c->nops.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+        if (total) HIP_TRY(hipMemcpyAsync(h_packed.data(), c->packed.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        uint64_t from = pool.size();
+        for (uint32_t q = 0; q < count; q++) {
+            cig_at[slots[q].a] = from;
+            cig_len[slots[q].a] = h_nops[q];
+            from += h_nops[q];
+        }
+        pool.insert(pool.end(), h_packed.begin(), h_packed.end());
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_total += ms;
+        if (getenv("BMV_LOG_CLASSES"))
+            fprintf(stderr, "[bmv] long piece of %u alignment(s), %zu tiles in %u launches, %.2f GB of scratch, %.2f ms\n", count,
+                    tiles.size() / 2u, max_d + 1u, (double)sum / 1e9, ms);
+    }
+    HIP_TRY(hipMemcpy(h_score.data(), c->out_score.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_begin.data(), c->out_begin.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (const Long &l : todo) {
+        score[l.s.a] = h_score[l.s.a];
+        begin[l.s.a] = h_begin[l.s.a];
+    }
+    // the results in batch order, as bmv_align leaves them
+    c->n_last = n;
+    c->n_cells = cells;
+    c->ms_kernels = ms_total;
+    c->h_score = std::move(score);
+    c->h_begin = std::move(begin);
+    c->h_offset.assign((size_t)n + 1, 0);
+    c->h_cigar.resize(pool.size());
+    uint64_t at = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        c->h_offset[a] = at;
+        std::copy_n(pool.data() + cig_at[a], cig_len[a], c->h_cigar.data() + at);
+        at += cig_len[a];
+    }
+    c->h_offset[n] = at;
+    *total_cigar = at;
     return BMV_OK;
 }
 

@@ -4,6 +4,8 @@
 // Several devices: the genome is replicated and the block's alignments -- independent of each other, the
 // reference runs them one by one (:560-589) -- are cut into contiguous ranges of equal cell count, one per
 // device; each device is handed only the span of the read buffer its queries cover.
+// A share that holds a candidate beyond the contexts' limits (reads of more than 65 536 bases, windows of more than
+// 81 920) goes through bmv_align_long; every other share through bmv_align, exactly as before.
 // Fails loudly (throws) when the device path fails: no CPU fallback.
 #pragma once
 
@@ -14,6 +16,7 @@
 namespace bm {
 
 class gpu_alignment_verifier : public alignment_verifier {
+    static constexpr uint32_t kMaxQuery = 65536, kMaxText = 81920;   // the ABI's limits: reads are not known yet
     std::vector<bmv_ctx *> ctx_;
 
     static void check(int rc, const char *what) {
@@ -23,8 +26,8 @@ class gpu_alignment_verifier : public alignment_verifier {
 public:
     explicit gpu_alignment_verifier(std::vector<int> devices = {0}) {
         bmv_params p{};
-        p.max_query_len = 65536;   // the ABI's limits: reads are not known yet
-        p.max_text_len = 81920;
+        p.max_query_len = kMaxQuery;
+        p.max_text_len = kMaxText;
         for (int dev : devices) {
             p.device = dev;
             bmv_ctx *c = nullptr;
@@ -63,8 +66,11 @@ public:
         for_each_device(D, [&](size_t d) {
             const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
             if (m == 0) return;
+            bool beyond = false;                                // a candidate bmv_align cannot take: the share goes long
+            for (uint32_t a = a0; a < a0 + m; a++) beyond = beyond || query_len[a] > kMaxQuery || text_len[a] > kMaxText;
+            const auto align_fn = beyond ? bmv_align_long : bmv_align;
             if (D == 1) {
-                check(bmv_align(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, &total[0]),
+                check(align_fn(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, &total[0]),
                       "the GPU alignment verifier failed: ");
             } else {
                 uint64_t lo = ~0ull, hi = 0;
@@ -74,7 +80,7 @@ public:
                 }
                 std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
                 for (uint64_t &s : rebased) s -= lo;
-                check(bmv_align(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
+                check(align_fn(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
                                 query_len + a0, m, &total[d]), "the GPU alignment verifier failed: ");
             }
             bmv_last_stats(ctx_[d], &ms[d], &cells[d]);

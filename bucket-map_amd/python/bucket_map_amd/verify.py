@@ -29,6 +29,7 @@ SYMBOLS = {
     "bmv_load_genome": (C.c_int, [C.c_void_p, _u8p, C.c_uint64]),
     "bmv_load_genome_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_uint32]),
     "bmv_align": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u64p]),
+    "bmv_align_long": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u64p]),
     "bmv_results": (C.c_int, [C.c_void_p, _i32p, _u32p, _u64p, _u32p]),
     "bmv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
 }
@@ -74,14 +75,22 @@ class Verifier:
 
     def align(self, reads, text_start, text_len, text_rc, query_start, query_len):
         """Returns (score i32[n], begin u32[n], cigar_offset u64[n+1], cigar u32[total])."""
+        return self._align(lib().bmv_align, reads, text_start, text_len, text_rc, query_start, query_len)
+
+    def align_long(self, reads, text_start, text_len, text_rc, query_start, query_len):
+        """As align, without max_query_len / max_text_len: longer alignments go through the tiled long path
+        (bmv_align_long); those within the limits through align's own kernels."""
+        return self._align(lib().bmv_align_long, reads, text_start, text_len, text_rc, query_start, query_len)
+
+    def _align(self, fn, reads, text_start, text_len, text_rc, query_start, query_len):
         r = np.ascontiguousarray(reads, np.uint8)
         ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
         trc = np.ascontiguousarray(text_rc, np.uint8)
         qs, ql = np.ascontiguousarray(query_start, np.uint64), np.ascontiguousarray(query_len, np.uint32)
         n = len(ts)
         total = C.c_uint64()
-        _check(lib().bmv_align(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
-                               _p(ql, _u32p), n, C.byref(total)))
+        _check(fn(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
+                  _p(ql, _u32p), n, C.byref(total)))
         score, begin = np.zeros(n, np.int32), np.zeros(n, np.uint32)
         off = np.zeros(n + 1, np.uint64)
         cg = np.zeros(max(total.value, 1), np.uint32)

@@ -11,6 +11,7 @@
  *   text window = bucket_seq[bucket][offset, +width)  :549-550    (text_start, text_len) views, chosen by
  *   reverse complement of the text for strand 16      :562-567      the caller; text_rc
  *   align_pairwise(text, query)                       :569        bmv_align, all candidates in one batch
+ *     (query.size() and the window of any width)      :549-589    bmv_align_long, beyond max_query_len / max_text_len
  *   alignment.score(), sequence1_begin_position(),    :570-576    out_score, out_begin, CIGAR entries
  *     cigar_from_alignment
  *
@@ -70,7 +71,19 @@ int  bmv_align(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const 
                const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
                const uint32_t *query_len, uint32_t n, uint64_t *total_cigar);
 
-/* Results of the last bmv_align:
+/* The same batch without the context's limits: any lengths that fit uint32.  Alignments within max_query_len and
+ * max_text_len go through bmv_align itself (the same kernels, bit-identical results); longer ones through tiles of
+ * 64 lanes x 8 words (32 768 query rows) x up to 8 192 text columns launched by anti-diagonal, with checkpoints in
+ * the scratch (about 1.25 B per 64-row word and text column) and a traceback with the same tie rules.  The long ones
+ * are taken in pieces that fit the scratch; one whose trace alone does not fit fails the call with BMV_ERR_UNSUPPORTED
+ * (the message names it and the bytes it needs) before anything runs, and the context stays usable.  Results through
+ * bmv_results / bmv_last_stats as for bmv_align.  BMV_LONG_FROM=<bases> (experiments, tests): every query of at least
+ * that many bases takes the long path. */
+int  bmv_align_long(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                    const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
+                    const uint32_t *query_len, uint32_t n, uint64_t *total_cigar);
+
+/* Results of the last bmv_align or bmv_align_long:
  *   out_score[a]        alignment.score() = -(edit distance)                       (bucket_locator.h:570)
  *   out_begin[a]        alignment.sequence1_begin_position(), 0-based in the text  (:576)
  *   out_cigar_offset    n + 1 entries; alignment a owns out_cigar[offset[a] .. offset[a+1])
@@ -78,7 +91,7 @@ int  bmv_align(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const 
 int  bmv_results(bmv_ctx *ctx, int32_t *out_score, uint32_t *out_begin, uint64_t *out_cigar_offset,
                  uint32_t *out_cigar);
 
-/* Kernel time of the last bmv_align in ms (edit-distance columns + traceback, all chunks) and the number
+/* Kernel time of the last bmv_align (or bmv_align_long) in ms (edit-distance columns + traceback, all chunks) and the number
  * of dynamic-programming cells it stands for (sum of query_len * text_len). */
 int  bmv_last_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells);
 

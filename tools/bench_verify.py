@@ -3,10 +3,15 @@
 work on BASELINE configs[1]: one located candidate per read, text window = read + 1 + 2 % (bucket_locator.h:550).
 
     python tools/bench_verify.py [--reads 1000000] [--len 300] [--indel-rate 0.02] [--cpu-sample 2000]
+    python tools/bench_verify.py --long [--long-reads 1000] [--long-len 100000]
 
 Prints one JSON line: alignments/s and cell updates/s of the device kernels (HIP events inside bmv_align),
 the wall time of the call (host buffers in, results out), and the CPU restatement (oracle, full DP matrix,
 1 core) on a sample beside it.
+
+--long: Verifier.align_long (bmv_align_long, reads beyond 65 536 bases): --long-reads alignments of --long-len bases against
+text = len + 1 + 10 % at ONT-like error rates (3 % substitutions, 2.5 % insertions, 2.5 % deletions), then one lone
+1 048 576-base query against a 1.15 Mbp text; one JSON line each.
 """
 import argparse
 import json
@@ -21,6 +26,61 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "bucket-map_amd", "python"))
 
 
+def _ont(rng, src, sub=0.03, ins=0.025, dele=0.025):
+    """ONT-like noise, vectorised: per base a deletion, else an optional inserted base before it and a substitution."""
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    r = rng.random(len(src))
+    out = np.where(rng.random(len(src)) < sub, bases[rng.integers(0, 4, len(src))], src)
+    pair = np.stack([np.where((r >= dele) & (r < dele + ins), bases[rng.integers(0, 4, len(src))], 0),
+                     np.where(r >= dele, out, 0)], 1).ravel()
+    return pair[pair != 0].astype(np.uint8)
+
+
+def long_main(args):
+    from bucket_map_amd import verify
+
+    rng = np.random.default_rng(20241005)
+    genome = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 16 << 20, dtype=np.uint8)]
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    v = verify.Verifier()
+    v.load_genome(genome)
+
+    def run(reads, ts, tl, rc, qs, ql, what, extra):
+        best = None
+        for _ in range(args.repeat):
+            t0 = time.perf_counter()
+            score, _, _, cg = v.align_long(reads, ts, tl, rc, qs, ql)
+            wall = time.perf_counter() - t0
+            st = v.stats()
+            if best is None or st["ms_kernels"] < best[0]:
+                best = (st["ms_kernels"], wall)
+        print(json.dumps({
+            "metric": f"bmv_align_long: {what}", "value": st["cells"] / (best[0] * 1e-3), "unit": "cell updates/s",
+            "ms_kernels": best[0], "wall_ms": best[1] * 1e3, "cells": st["cells"], "alignments": len(ts),
+            "mean_edits_per_base": float((-score / ql).mean()), "cigar_entries": int(len(cg)), **extra}), flush=True)
+
+    # many: ONT-like reads of --long-len bases, either strand
+    m, n = args.long_len, args.long_len + 1 + args.long_len // 10
+    ts = rng.integers(0, len(genome) - n - 8, args.long_reads).astype(np.uint64)
+    rc = rng.integers(0, 2, args.long_reads).astype(np.uint8)
+    parts = []
+    for a in range(args.long_reads):
+        src = genome[int(ts[a]) + 1: int(ts[a]) + 1 + m]
+        parts.append(_ont(rng, comp[src][::-1] if rc[a] else src))
+    ql = np.array([len(p) for p in parts], np.uint32)
+    qs = np.concatenate([[0], np.cumsum(ql[:-1], dtype=np.uint64)]).astype(np.uint64)
+    run(np.concatenate(parts), ts, np.full(args.long_reads, n, np.uint32), rc, qs, ql,
+        f"{args.long_reads} x ({m} x {n}), ONT-like errors", {"query_len": m, "text_len": n})
+    del parts
+    # one: a lone 1 048 576-base query against a 1.15 Mbp text
+    m, n = 1 << 20, 1_150_000
+    t0 = int(rng.integers(0, len(genome) - n))
+    q = _ont(rng, genome[t0 + 40_000: t0 + 40_000 + m])[:m]
+    run(q, np.array([t0], np.uint64), np.array([n], np.uint32), np.zeros(1, np.uint8), np.zeros(1, np.uint64),
+        np.array([len(q)], np.uint32), f"one {len(q)} x {n} alignment, ONT-like errors", {"query_len": len(q), "text_len": n})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1_000_000)
@@ -31,10 +91,15 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--mixed", type=int, default=0,
                     help="query lengths log-uniform in [MIXED, --len] (forward strand only): a batch of several length classes")
+    ap.add_argument("--long", action="store_true", help="Verifier.align_long on reads beyond 65 536 bases (see above)")
+    ap.add_argument("--long-reads", type=int, default=1000)
+    ap.add_argument("--long-len", type=int, default=100_000)
     args = ap.parse_args()
 
     import torch  # noqa: F401  (HIP runtime first, as in bench.py)
     from bucket_map_amd import verify
+    if args.long:
+        return long_main(args)
 
     rng = np.random.default_rng(20240003)
     m = args.len
