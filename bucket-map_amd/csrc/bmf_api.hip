@@ -12,7 +12,6 @@
 #include "../../include/bmf.h"
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,39 +20,33 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
+#define HIP_TRY(expr) BM_HIP_TRY(expr, BMF_ERR_HIP)
+
+using bmhip::DevBuf;
+using bmhip::PinnedBuf;
+
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(BMF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                        __LINE__);                                                                \
-    } while (0)
-
-// SeqAn3 dna4 assign_char folding; built once, uploaded per context.
-void build_dna4_lut(uint8_t *lut) {
-    memset(lut, 0, 256);
-    const char *m[4] = {"AaRrWwMmDdHhVv", "CcYySsBb", "GgKk", "TtUu"};
-    for (int r = 0; r < 4; r++)
-        for (const char *c = m[r]; *c; c++) lut[(uint8_t)*c] = (uint8_t)r;
-}
 
 template <typename T>
 hipError_t dev_alloc(T **p, size_t n) {
     return hipMalloc(reinterpret_cast<void **>(p), (n ? n : 1) * sizeof(T));
+}
+
+// Calls f(std::integral_constant<int, v>{}) for the runtime value v in [Lo, Hi]: one instantiation of f per value.  Outside
+// the range: a value-initialised result (a null kernel).
+template <int Lo, typename F, int... I>
+auto with_int_of(int v, F &f, std::integer_sequence<int, I...>) {
+    decltype(f(std::integral_constant<int, Lo>{})) r{};
+    (void)((v == Lo + I && ((r = f(std::integral_constant<int, Lo + I>{})), true)) || ...);
+    return r;
+}
+template <int Lo, int Hi, typename F>
+auto with_int(int v, F &&f) {
+    return with_int_of<Lo>(v, f, std::make_integer_sequence<int, Hi - Lo + 1>{});
 }
 
 using vote_fn = void (*)(bmf::DevParams, const uint8_t *, const uint32_t *, const uint32_t *, uint32_t *,
@@ -62,41 +55,21 @@ using vote_fn = void (*)(bmf::DevParams, const uint8_t *, const uint32_t *, cons
 // rows in flight per wave: about 12-16 KB of row data per wave whatever the row length
 constexpr int depth_for(int cpl) { return cpl <= 2 ? 8 : (cpl <= 4 ? 4 : (cpl <= 6 ? 3 : 2)); }
 
-template <int CPL>
-vote_fn pick_planes(int planes, bool prune) {
-    constexpr int D = depth_for(CPL);
-    switch (planes) {
-    case 2: return prune ? bmf::bmf_vote_kernel<CPL, 2, D, false, true> : bmf::bmf_vote_kernel<CPL, 2, D, false, false>;
-    case 3: return prune ? bmf::bmf_vote_kernel<CPL, 3, D, false, true> : bmf::bmf_vote_kernel<CPL, 3, D, false, false>;
-    case 4: return prune ? bmf::bmf_vote_kernel<CPL, 4, D, false, true> : bmf::bmf_vote_kernel<CPL, 4, D, false, false>;
-    case 5: return prune ? bmf::bmf_vote_kernel<CPL, 5, D, false, true> : bmf::bmf_vote_kernel<CPL, 5, D, false, false>;
-    }
-    return nullptr;
+vote_fn pick_vote(int cpl, int planes, bool prune) {
+    return with_int<1, 8>(cpl, [&](auto c) {
+        return with_int<2, 5>(planes, [&](auto pl) -> vote_fn {
+            constexpr int CPL = decltype(c)::value, P = decltype(pl)::value, D = depth_for(CPL);
+            return prune ? bmf::bmf_vote_kernel<CPL, P, D, false, true> : bmf::bmf_vote_kernel<CPL, P, D, false, false>;
+        });
+    });
 }
 
 // NB > 65 536: every wave takes one slice of 8 chunks per lane
 vote_fn pick_sliced(int planes, bool prune) {
-    switch (planes) {
-    case 2: return prune ? bmf::bmf_vote_kernel<8, 2, 2, true, true> : bmf::bmf_vote_kernel<8, 2, 2, true, false>;
-    case 3: return prune ? bmf::bmf_vote_kernel<8, 3, 2, true, true> : bmf::bmf_vote_kernel<8, 3, 2, true, false>;
-    case 4: return prune ? bmf::bmf_vote_kernel<8, 4, 2, true, true> : bmf::bmf_vote_kernel<8, 4, 2, true, false>;
-    case 5: return prune ? bmf::bmf_vote_kernel<8, 5, 2, true, true> : bmf::bmf_vote_kernel<8, 5, 2, true, false>;
-    }
-    return nullptr;
-}
-
-vote_fn pick_vote(int cpl, int planes, bool prune) {
-    switch (cpl) {
-    case 1: return pick_planes<1>(planes, prune);
-    case 2: return pick_planes<2>(planes, prune);
-    case 3: return pick_planes<3>(planes, prune);
-    case 4: return pick_planes<4>(planes, prune);
-    case 5: return pick_planes<5>(planes, prune);
-    case 6: return pick_planes<6>(planes, prune);
-    case 7: return pick_planes<7>(planes, prune);
-    case 8: return pick_planes<8>(planes, prune);
-    }
-    return nullptr;
+    return with_int<2, 5>(planes, [&](auto pl) -> vote_fn {
+        constexpr int P = decltype(pl)::value;
+        return prune ? bmf::bmf_vote_kernel<8, P, 2, true, true> : bmf::bmf_vote_kernel<8, P, 2, true, false>;
+    });
 }
 
 // two-pass exact pruning (bmf_vote2.hip.h), unsliced geometries only
@@ -112,66 +85,28 @@ struct TwoPass {
     finish_fn finish = nullptr;
 };
 
-template <int CPL, int PLANES>
-TwoPass two_pass_of(int max_live) {
-    constexpr int D = depth_for(CPL);
-    pass1_fn p1 = bmf::bmf_pass1_kernel<CPL, PLANES, D>;
-    if constexpr (D > 2) {
-        const char *env = getenv("BMF_PASS1_SHALLOW");
-        if (env && env[0] == '1') p1 = bmf::bmf_pass1_kernel<CPL, PLANES, D - 1>;
-    }
-    recount_fn rc = max_live <= 16 ? bmf::bmf_recount_kernel<PLANES, 16> : bmf::bmf_recount_kernel<PLANES, 32>;
-    return {p1, rc, bmf::bmf_vote2_slow_kernel<CPL, PLANES, D>, bmf::bmf_finish_kernel<PLANES>};
-}
-
-template <int CPL>
-TwoPass pick_planes2(int planes, int max_live) {
-    switch (planes) {
-    case 2: return two_pass_of<CPL, 2>(max_live);
-    case 3: return two_pass_of<CPL, 3>(max_live);
-    case 4: return two_pass_of<CPL, 4>(max_live);
-    case 5: return two_pass_of<CPL, 5>(max_live);
-    }
-    return {};
-}
-
 TwoPass pick_vote2(int cpl, int planes, int max_live) {
-    switch (cpl) {
-    case 1: return pick_planes2<1>(planes, max_live);
-    case 2: return pick_planes2<2>(planes, max_live);
-    case 3: return pick_planes2<3>(planes, max_live);
-    case 4: return pick_planes2<4>(planes, max_live);
-    case 5: return pick_planes2<5>(planes, max_live);
-    case 6: return pick_planes2<6>(planes, max_live);
-    case 7: return pick_planes2<7>(planes, max_live);
-    case 8: return pick_planes2<8>(planes, max_live);
-    }
-    return {};
+    return with_int<1, 8>(cpl, [&](auto c) {
+        return with_int<2, 5>(planes, [&](auto pl) {
+            constexpr int CPL = decltype(c)::value, P = decltype(pl)::value, D = depth_for(CPL);
+            recount_fn rc = max_live <= 16 ? bmf::bmf_recount_kernel<P, 16> : bmf::bmf_recount_kernel<P, 32>;
+            return TwoPass{bmf::bmf_pass1_kernel<CPL, P, D>, rc, bmf::bmf_vote2_slow_kernel<CPL, P, D>, bmf::bmf_finish_kernel<P>};
+        });
+    });
 }
 
 // first pass over a folded index: NB <= 65 536 folds by 4 to at most 128 chunks per row (CPL 1, 2), by 2 to 256 (1..4)
-template <int CPL, int FOLD>
-pass1_fn pick_fold_planes(int planes) {
-    constexpr int D = depth_for(CPL);
-    switch (planes) {
-    case 2: return bmf::bmf_pass1_kernel<CPL, 2, D, FOLD>;
-    case 3: return bmf::bmf_pass1_kernel<CPL, 3, D, FOLD>;
-    case 4: return bmf::bmf_pass1_kernel<CPL, 4, D, FOLD>;
-    case 5: return bmf::bmf_pass1_kernel<CPL, 5, D, FOLD>;
-    }
-    return nullptr;
-}
 pass1_fn pick_pass1_fold(int fold, int cpl, int planes) {
-    if (fold == 4) return cpl == 1 ? pick_fold_planes<1, 4>(planes) : (cpl == 2 ? pick_fold_planes<2, 4>(planes) : nullptr);
-    if (fold == 2) {
-        switch (cpl) {
-        case 1: return pick_fold_planes<1, 2>(planes);
-        case 2: return pick_fold_planes<2, 2>(planes);
-        case 3: return pick_fold_planes<3, 2>(planes);
-        case 4: return pick_fold_planes<4, 2>(planes);
-        }
-    }
-    return nullptr;
+    return with_int<1, 4>(cpl, [&](auto c) {
+        return with_int<2, 5>(planes, [&](auto pl) -> pass1_fn {
+            constexpr int CPL = decltype(c)::value, P = decltype(pl)::value, D = depth_for(CPL);
+            if (fold == 2) return bmf::bmf_pass1_kernel<CPL, P, D, 2>;
+            if constexpr (CPL <= 2) {
+                if (fold == 4) return bmf::bmf_pass1_kernel<CPL, P, D, 4>;
+            }
+            return nullptr;
+        });
+    });
 }
 
 // P[Bin(n, p) >= m]
@@ -188,28 +123,6 @@ double binom_tail(uint32_t n, double p, uint32_t m) {
 }
 
 }  // namespace
-
-// Grow-only device buffer (a batch that is reused keeps its allocations).
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = (n ? n : 1) + n / 8;   // headroom: batches of a file differ a little in size
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 struct bmf_batch {
     uint32_t n_windows = 0;
@@ -263,7 +176,6 @@ struct bmf_ctx {
     uint32_t tune_windows = 32768;
     double guard_baseline = -1.0;    // share of slow-path items of the first run after tuning (< 0: not sampled yet)
     unsigned recount_waves = 4096;   // waves of the recount kernel the device holds at once (CUs x 4 SIMDs x BMF_RECOUNT_OCC)
-    bool no_finish = false;          // BMF_NO_FINISH=1: every item through the recount kernel (experiments)
     size_t sample_lds = 0;
     bmf::SampleGeom sample_geom{};
     bool sample_bitmap_lds = false;
@@ -277,12 +189,9 @@ struct bmf_ctx {
     struct MapSlot {
         bmf_batch dev;
         DevBuf<uint32_t> pack;           // [total | ids of all lists back to back]
-        uint8_t *h_views = nullptr;      // pinned: rebased win_start (u64 x n) then win_len (u32 x n)
-        size_t h_views_cap = 0;
-        uint32_t *h_out = nullptr;       // pinned: counts (2n) then the head of `pack`
-        size_t h_out_cap = 0;
-        uint8_t *h_bases = nullptr, *h_quals = nullptr;   // pinned: the piece's windows gathered back to back (bmf_map_text_windows_compact)
-        size_t h_bases_cap = 0, h_quals_cap = 0;
+        PinnedBuf<uint8_t> h_views;      // rebased win_start (u64 x n) then win_len (u32 x n)
+        PinnedBuf<uint32_t> h_out;       // counts (2n) then the head of `pack`
+        PinnedBuf<uint8_t> h_bases, h_quals;   // the piece's windows gathered back to back (bmf_map_text_windows_compact)
         hipEvent_t uploaded = nullptr, ran = nullptr, landed = nullptr;
         // the piece in flight
         uint32_t first = 0, n = 0;
@@ -359,10 +268,6 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
     int planes = 0;
     while (((1u << planes) - 1u) < p.num_fault) planes++;
     if (planes < 2) planes = 2;
-    if (const char *env = getenv("BMF_MIN_PLANES")) {   // experiments: a wider counter than F needs (same outputs)
-        const int v = atoi(env);
-        if (v >= 2 && v <= 5 && v > planes) planes = v;
-    }
 
     int n_dev = 0;
     HIP_TRY(hipGetDeviceCount(&n_dev));
@@ -380,8 +285,6 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p.device) == hipSuccess && cus > 0)
             c->recount_waves = (unsigned)cus * 4u * BMF_RECOUNT_OCC;
-        if (const char *env = getenv("BMF_RECOUNT_WAVES")) c->recount_waves = (unsigned)std::max(64, atoi(env));   // experiments
-        c->no_finish = getenv("BMF_NO_FINISH") != nullptr;
     }
     const bool prune = (p.flags & BMF_FLAG_EARLY_EXIT) != 0;
     c->vote = n_slices > 1 ? pick_sliced(planes, prune) : pick_vote(cpl, planes, prune);
@@ -486,7 +389,7 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
         tab[(size_t)n * d.S + d.S - 1] = (uint16_t)ub;
     }
     uint8_t lut[256];
-    build_dna4_lut(lut);
+    bmhip::build_dna4_lut(lut);
     if (dev_alloc(&c->d_pos_table, tab.size()) != hipSuccess || dev_alloc(&c->d_lut, 256) != hipSuccess ||
         hipMemcpy(c->d_pos_table, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->d_lut, lut, 256, hipMemcpyHostToDevice) != hipSuccess) {
@@ -713,10 +616,10 @@ static void free_map_slots(bmf_ctx *c) {
         if (!sl) continue;
         release_batch(&sl->dev);
         sl->pack.release();
-        if (sl->h_views) (void)hipHostFree(sl->h_views);
-        if (sl->h_out) (void)hipHostFree(sl->h_out);
-        if (sl->h_bases) (void)hipHostFree(sl->h_bases);
-        if (sl->h_quals) (void)hipHostFree(sl->h_quals);
+        sl->h_views.release();
+        sl->h_out.release();
+        sl->h_bases.release();
+        sl->h_quals.release();
         for (hipEvent_t e : {sl->uploaded, sl->ran, sl->landed})
             if (e) (void)hipEventDestroy(e);
         delete sl;
@@ -1163,12 +1066,9 @@ static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
         const size_t n_items = 2 * (size_t)n_windows;
         if (c->sort_rows && c->dp.G >= 2) {                      // each sample's rows sparsest first
             using order_fn = void (*)(bmf::DevParams, uint32_t, const uint32_t *, const uint32_t *, uint32_t *);
-            static const order_fn order[9] = {nullptr, nullptr, bmf::bmf_order_rows_kernel<2>, bmf::bmf_order_rows_kernel<3>,
-                                              bmf::bmf_order_rows_kernel<4>, bmf::bmf_order_rows_kernel<5>,
-                                              bmf::bmf_order_rows_kernel<6>, bmf::bmf_order_rows_kernel<7>,
-                                              bmf::bmf_order_rows_kernel<8>};
+            const order_fn order = with_int<2, 8>((int)c->dp.G, [](auto g) -> order_fn { return bmf::bmf_order_rows_kernel<decltype(g)::value>; });
             const uint64_t threads = (uint64_t)n_items * c->dp.S;
-            hipLaunchKernelGGL(order[c->dp.G], dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream, c->dp,
+            hipLaunchKernelGGL(order, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream, c->dp,
                                (uint32_t)n_items, b->list_n.p, c->d_zeros, b->lists.p);
         }
         HIP_TRY(b->q_counters.need(4));
@@ -1224,7 +1124,7 @@ static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
             // items with ONE stored chunk: a lane each (bmf_finish_kernel); the rest, queued by it, go through the recount
             // kernel.  (Not with BMF_SLICES: the slices' kernels overlap and would share the queue.)
             const size_t finish_lds = (size_t)bmf::kWave * ((size_t)(c->dp.S * c->dp.G) | 1u) * sizeof(uint32_t);
-            const bool finish = n_sl == 1 && finish_lds <= 150 * 1024 && !c->no_finish;
+            const bool finish = n_sl == 1 && finish_lds <= 150 * 1024;
             if (finish) {
                 if (finish_lds > 48 * 1024)
                     HIP_TRY(bmhip::raise_dynamic_lds(reinterpret_cast<const void *>(c->two_pass.finish), finish_lds));
@@ -1559,17 +1459,6 @@ static int map_slots_init(bmf_ctx *c) {
     return BMF_OK;
 }
 
-static hipError_t pinned_need(void **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap && *p) return hipSuccess;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 8 + 64;
-    const hipError_t e = hipHostMalloc(p, want, hipHostMallocDefault);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
 // ids copied back with the counts, per (window, orientation): lists hold < 1 id on average; the rare piece with
 // more fetches the rest in a second copy
 constexpr size_t kIdsPerItemCopied = 2;
@@ -1610,11 +1499,11 @@ static int map_piece_issue(bmf_ctx *c, bmf_ctx::MapSlot *sl, const uint8_t *base
     const size_t n_items = 2 * (size_t)n, mc = c->p.max_candidates;
     HIP_TRY(b->offsets.need(n_items + 1));
     HIP_TRY(sl->pack.need(1 + n_items * mc));
-    HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_views), &sl->h_views_cap, (size_t)n * 12));
+    HIP_TRY(sl->h_views.need((size_t)n * 12));
     sl->ids_copied = kIdsPerItemCopied * n_items;
-    HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_out), &sl->h_out_cap, (n_items + 1 + sl->ids_copied) * sizeof(uint32_t)));
-    uint64_t *hs = reinterpret_cast<uint64_t *>(sl->h_views);
-    uint32_t *hl = reinterpret_cast<uint32_t *>(sl->h_views + (size_t)n * 8);
+    HIP_TRY(sl->h_out.need(n_items + 1 + sl->ids_copied));
+    uint64_t *hs = reinterpret_cast<uint64_t *>(sl->h_views.p);
+    uint32_t *hl = reinterpret_cast<uint32_t *>(sl->h_views.p + (size_t)n * 8);
     memcpy(hl, win_len + first, (size_t)n * sizeof(uint32_t));
     if (qual_start) {
         uint64_t at = 0;
@@ -1622,12 +1511,12 @@ static int map_piece_issue(bmf_ctx *c, bmf_ctx::MapSlot *sl, const uint8_t *base
             hs[w] = at;
             at += hl[w];
         }
-        HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_bases), &sl->h_bases_cap, span + 64));
-        HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_quals), &sl->h_quals_cap, span + 64));
+        HIP_TRY(sl->h_bases.need(span + 64));
+        HIP_TRY(sl->h_quals.need(span + 64));
         auto gather = [&](uint32_t w0, uint32_t w1) {
             for (uint32_t w = w0; w < w1; w++) {
-                memcpy(sl->h_bases + hs[w], bases + win_start[first + w], hl[w]);
-                memcpy(sl->h_quals + hs[w], quals + qual_start[first + w], hl[w]);
+                memcpy(sl->h_bases.p + hs[w], bases + win_start[first + w], hl[w]);
+                memcpy(sl->h_quals.p + hs[w], quals + qual_start[first + w], hl[w]);
             }
         };
         const unsigned T = gather_threads(n);
@@ -1640,8 +1529,8 @@ static int map_piece_issue(bmf_ctx *c, bmf_ctx::MapSlot *sl, const uint8_t *base
             for (auto &t : pool) t.join();
         }
         if (span) {
-            HIP_TRY(hipMemcpyAsync(b->bases.p, sl->h_bases, span, hipMemcpyHostToDevice, c->h2d));
-            HIP_TRY(hipMemcpyAsync(b->quals.p, sl->h_quals, span, hipMemcpyHostToDevice, c->h2d));
+            HIP_TRY(hipMemcpyAsync(b->bases.p, sl->h_bases.p, span, hipMemcpyHostToDevice, c->h2d));
+            HIP_TRY(hipMemcpyAsync(b->quals.p, sl->h_quals.p, span, hipMemcpyHostToDevice, c->h2d));
         }
     } else {
         for (uint32_t w = 0; w < n; w++) hs[w] = win_start[first + w] - lo;
@@ -1665,9 +1554,9 @@ static int map_piece_issue(bmf_ctx *c, bmf_ctx::MapSlot *sl, const uint8_t *base
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl->ran, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->d2h, sl->ran, 0));
-    HIP_TRY(hipMemcpyAsync(sl->h_out, b->counts.p, n_items * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h));
+    HIP_TRY(hipMemcpyAsync(sl->h_out.p, b->counts.p, n_items * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h));
     const size_t head = std::min(1 + sl->ids_copied, 1 + n_items * mc);
-    HIP_TRY(hipMemcpyAsync(sl->h_out + n_items, sl->pack.p, head * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h));
+    HIP_TRY(hipMemcpyAsync(sl->h_out.p + n_items, sl->pack.p, head * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h));
     HIP_TRY(hipEventRecord(sl->landed, c->d2h));
     return BMF_OK;
 }
@@ -1685,8 +1574,8 @@ struct MapOut {
 static int map_piece_finish(bmf_ctx *c, bmf_ctx::MapSlot *sl, MapOut &out) {
     HIP_TRY(hipEventSynchronize(sl->landed));
     const size_t n_items = 2 * (size_t)sl->n, mc = c->p.max_candidates;
-    const uint32_t *counts = sl->h_out, *ids = sl->h_out + n_items + 1;
-    const size_t total = sl->h_out[n_items];
+    const uint32_t *counts = sl->h_out.p, *ids = sl->h_out.p + n_items + 1;
+    const size_t total = sl->h_out.p[n_items];
     uint64_t sum = 0;
     for (size_t i = 0; i < n_items; i++) {
         if (counts[i] > mc) return fail(BMF_ERR_HIP, "device returned count %u > max_candidates", counts[i]);
@@ -1764,11 +1653,11 @@ int bmf_map_reserve(bmf_ctx *c, uint32_t max_windows_per_call, int text_windows)
         HIP_TRY(b->offsets.need(n_items + 1));
         HIP_TRY(sl->pack.need(1 + n_items * mc));
         HIP_TRY(b->scan_tmp.need(bmscan::tmp_elems(n_items) * sizeof(uint32_t)));
-        HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_views), &sl->h_views_cap, n * 12));
-        HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_out), &sl->h_out_cap, (n_items + 1 + kIdsPerItemCopied * n_items) * sizeof(uint32_t)));
+        HIP_TRY(sl->h_views.need(n * 12));
+        HIP_TRY(sl->h_out.need(n_items + 1 + kIdsPerItemCopied * n_items));
         if (text_windows) {
-            HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_bases), &sl->h_bases_cap, span + 64));
-            HIP_TRY(pinned_need(reinterpret_cast<void **>(&sl->h_quals), &sl->h_quals_cap, span + 64));
+            HIP_TRY(sl->h_bases.need(span + 64));
+            HIP_TRY(sl->h_quals.need(span + 64));
         }
     }
     return BMF_OK;

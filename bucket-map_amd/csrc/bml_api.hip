@@ -8,7 +8,6 @@
 #include "../../include/bml.h"
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,55 +17,10 @@
 #include <thread>
 #include <vector>
 
-namespace {
+#define HIP_TRY(expr) BM_HIP_TRY(expr, BML_ERR_HIP)
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(BML_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-void build_dna4_lut(uint8_t *lut) {
-    memset(lut, 0, 256);
-    const char *m[4] = {"AaRrWwMmDdHhVv", "CcYySsBb", "GgKk", "TtUu"};
-    for (int r = 0; r < 4; r++)
-        for (const char *c = m[r]; *c; c++) lut[(uint8_t)*c] = (uint8_t)r;
-}
-
-// Device buffer that only grows.
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = (n ? n : 1) + n / 8;   // headroom: batches of a file differ a little in size
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-}  // namespace
+using bmhip::DevBuf;
+using bmhip::PinnedBuf;
 
 struct bml_ctx {
     bml_params p{};
@@ -96,8 +50,7 @@ struct bml_ctx {
     DevBuf<uint16_t> s_pos, s_table;
     uint32_t s_table_len = 0;        // windows up to this length are tabulated
     // bml_sample_text_windows: two page-locked slots for the gathered windows, two for the results
-    uint8_t *t_bases[2] = {nullptr, nullptr}, *t_quals[2] = {nullptr, nullptr}, *t_out[2] = {nullptr, nullptr};
-    size_t t_cap[2] = {0, 0}, t_out_cap[2] = {0, 0};
+    PinnedBuf<uint8_t> t_bases[2], t_quals[2], t_out[2];
     hipEvent_t t_done[2] = {nullptr, nullptr};
     DevBuf<unsigned long long> occ_count;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // scan | (gap) | light replay | heavy replay
@@ -123,6 +76,32 @@ static int sampler_table(bml_ctx *c, uint32_t max_len) {
     HIP_TRY(c->s_table.need(tab.size()));
     HIP_TRY(hipMemcpy(c->s_table.p, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     c->s_table_len = max_len;
+    return BML_OK;
+}
+
+// bml_load_genome(_records) after their argument checks: the genome is the n_records records back to back (n_bases in all)
+static int load_genome(bml_ctx *c, const uint8_t *const *rec, const uint64_t *rec_len, uint32_t n_records, uint64_t n_bases,
+                       const uint64_t *bucket_start, const uint32_t *bucket_len, uint32_t n_buckets) {
+    for (uint32_t b = 0; b < n_buckets; b++) {
+        if (bucket_len[b] > c->p.max_bucket_bases)
+            return fail(BML_ERR_ARG, "bucket %u has %u bases, more than max_bucket_bases = %u", b, bucket_len[b], c->p.max_bucket_bases);
+        if (bucket_start[b] > n_bases || bucket_len[b] > n_bases - bucket_start[b])
+            return fail(BML_ERR_ARG, "bucket %u lies outside the genome buffer", b);
+    }
+    HIP_TRY(hipSetDevice(c->p.device));
+    // the scan kernel packs a bucket with aligned 16-byte loads, which read up to 15 bytes past its last base
+    HIP_TRY(c->genome.need((size_t)n_bases + 64));
+    HIP_TRY(hipMemset(c->genome.p + n_bases, 'A', 64));
+    HIP_TRY(c->bucket_start.need(n_buckets));
+    HIP_TRY(c->bucket_len.need(n_buckets));
+    HIP_TRY(bmhip::upload_pageable_records(c->genome.p, rec, rec_len, n_records));
+    if (n_buckets) {
+        HIP_TRY(hipMemcpy(c->bucket_start.p, bucket_start, (size_t)n_buckets * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->bucket_len.p, bucket_len, (size_t)n_buckets * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    c->n_buckets = n_buckets;
+    c->h_bucket_len.assign(bucket_len, bucket_len + n_buckets);
+    c->loaded = true;
     return BML_OK;
 }
 
@@ -161,7 +140,7 @@ int bml_create(const bml_params *params, bml_ctx **out) {
     if (e == hipSuccess && lds > 48 * 1024)
         e = bmhip::raise_dynamic_lds(reinterpret_cast<const void *>(bml::bml_scan_kernel), lds);
     uint8_t lut[256];
-    build_dna4_lut(lut);
+    bmhip::build_dna4_lut(lut);
     if (e == hipSuccess) e = c->lut.need(256);
     if (e == hipSuccess) e = hipMemcpy(c->lut.p, lut, 256, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = c->occ_count.need(2);
@@ -190,9 +169,9 @@ void bml_destroy(bml_ctx *c) {
     c->s_bases.release(); c->s_quals.release(); c->s_has.release(); c->s_win_start.release(); c->s_win_len.release();
     c->s_hash.release(); c->s_pos.release(); c->s_table.release();
     for (int i = 0; i < 2; i++) {
-        if (c->t_bases[i]) (void)hipHostFree(c->t_bases[i]);
-        if (c->t_quals[i]) (void)hipHostFree(c->t_quals[i]);
-        if (c->t_out[i]) (void)hipHostFree(c->t_out[i]);
+        c->t_bases[i].release();
+        c->t_quals[i].release();
+        c->t_out[i].release();
         if (c->t_done[i]) (void)hipEventDestroy(c->t_done[i]);
     }
     for (auto &e : c->ev)
@@ -272,18 +251,9 @@ int bml_sample_text_windows(bml_ctx *c, const uint8_t *text, uint64_t n_bytes, c
     const size_t out_bytes = res_bytes + (size_t)piece * 12;                         // start u64[piece] | len u32[piece]
     for (int i = 0; i < 2; i++) {
         if (!c->t_done[i]) HIP_TRY(hipEventCreateWithFlags(&c->t_done[i], hipEventDisableTiming));
-        if (c->t_cap[i] < (size_t)piece * max_len + 64 || c->t_out_cap[i] < out_bytes) {
-            if (c->t_bases[i]) (void)hipHostFree(c->t_bases[i]);
-            if (c->t_quals[i]) (void)hipHostFree(c->t_quals[i]);
-            if (c->t_out[i]) (void)hipHostFree(c->t_out[i]);
-            c->t_bases[i] = c->t_quals[i] = c->t_out[i] = nullptr;
-            c->t_cap[i] = c->t_out_cap[i] = 0;
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->t_bases[i]), (size_t)piece * max_len + 64, hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->t_quals[i]), (size_t)piece * max_len + 64, hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->t_out[i]), out_bytes, hipHostMallocDefault));
-            c->t_cap[i] = (size_t)piece * max_len + 64;
-            c->t_out_cap[i] = out_bytes;
-        }
+        HIP_TRY(c->t_bases[i].need_exact((size_t)piece * max_len + 64));
+        HIP_TRY(c->t_quals[i].need_exact((size_t)piece * max_len + 64));
+        HIP_TRY(c->t_out[i].need_exact(out_bytes));
     }
     // the device buffers at a piece's largest, once: the pieces follow each other on the stream, none may be re-allocated
     // under the one before
@@ -301,7 +271,7 @@ int bml_sample_text_windows(bml_ctx *c, const uint8_t *text, uint64_t n_bytes, c
         if (!fl[slot].busy) return BML_OK;
         HIP_TRY(hipEventSynchronize(c->t_done[slot]));
         const uint32_t first = fl[slot].first, n = fl[slot].n;
-        const uint8_t *o = c->t_out[slot];
+        const uint8_t *o = c->t_out[slot].p;
         memcpy(out_hash + (size_t)first * p, o, (size_t)n * p * 4);
         memcpy(out_pos + (size_t)first * p, o + (size_t)piece * p * 4, (size_t)n * p * 2);
         memcpy(out_has + first, o + (size_t)piece * p * 6, n);
@@ -313,8 +283,8 @@ int bml_sample_text_windows(bml_ctx *c, const uint8_t *text, uint64_t n_bytes, c
         const int slot = (int)(n_piece & 1);
         if (int rc = finish(slot)) return rc;                    // (also: the slot's upload has left its buffers)
         const uint32_t n = std::min(piece, n_windows - first);
-        uint64_t *start = reinterpret_cast<uint64_t *>(c->t_out[slot] + res_bytes);
-        uint32_t *lens = reinterpret_cast<uint32_t *>(c->t_out[slot] + res_bytes + (size_t)piece * 8);
+        uint64_t *start = reinterpret_cast<uint64_t *>(c->t_out[slot].p + res_bytes);
+        uint32_t *lens = reinterpret_cast<uint32_t *>(c->t_out[slot].p + res_bytes + (size_t)piece * 8);
         uint64_t at = 0;
         for (uint32_t w = 0; w < n; w++) {
             start[w] = at;
@@ -323,8 +293,8 @@ int bml_sample_text_windows(bml_ctx *c, const uint8_t *text, uint64_t n_bytes, c
         }
         auto gather = [&](uint32_t w0, uint32_t w1) {
             for (uint32_t w = w0; w < w1; w++) {
-                memcpy(c->t_bases[slot] + start[w], text + seq_start[first + w], win_len[first + w]);
-                memcpy(c->t_quals[slot] + start[w], text + qual_start[first + w], win_len[first + w]);
+                memcpy(c->t_bases[slot].p + start[w], text + seq_start[first + w], win_len[first + w]);
+                memcpy(c->t_quals[slot].p + start[w], text + qual_start[first + w], win_len[first + w]);
             }
         };
         const unsigned T = std::min(hw, std::max(1u, n / 2048u));
@@ -343,15 +313,15 @@ int bml_sample_text_windows(bml_ctx *c, const uint8_t *text, uint64_t n_bytes, c
         if (lds > 48 * 1024)
             HIP_TRY(bmhip::raise_dynamic_lds(reinterpret_cast<const void *>(bml::bml_sample_kernel), lds));
         if (at) {
-            HIP_TRY(hipMemcpyAsync(c->s_bases.p, c->t_bases[slot], (size_t)at, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->s_quals.p, c->t_quals[slot], (size_t)at, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->s_bases.p, c->t_bases[slot].p, (size_t)at, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->s_quals.p, c->t_quals[slot].p, (size_t)at, hipMemcpyHostToDevice, c->stream));
         }
         HIP_TRY(hipMemcpyAsync(c->s_win_start.p, start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->s_win_len.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(bml::bml_sample_kernel, dim3(n), dim3(64), lds, c->stream, k, p, min_base_quality, max_len, c->s_bases.p,
                            c->s_quals.p, c->s_win_start.p, c->s_win_len.p, c->lut.p, c->s_table.p, c->s_hash.p, c->s_pos.p, c->s_has.p);
         HIP_TRY(hipGetLastError());
-        uint8_t *o = c->t_out[slot];
+        uint8_t *o = c->t_out[slot].p;
         HIP_TRY(hipMemcpyAsync(o, c->s_hash.p, (size_t)n * p * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(o + (size_t)piece * p * 4, c->s_pos.p, (size_t)n * p * 2, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(o + (size_t)piece * p * 6, c->s_has.p, n, hipMemcpyDeviceToHost, c->stream));
@@ -369,27 +339,7 @@ int bml_load_genome(bml_ctx *c, const uint8_t *bases, uint64_t n_bases, const ui
                     const uint32_t *bucket_len, uint32_t n_buckets) {
     if (!c || (n_bases && !bases) || (n_buckets && (!bucket_start || !bucket_len)))
         return fail(BML_ERR_ARG, "bml_load_genome: null argument");
-    for (uint32_t b = 0; b < n_buckets; b++) {
-        if (bucket_len[b] > c->p.max_bucket_bases)
-            return fail(BML_ERR_ARG, "bucket %u has %u bases, more than max_bucket_bases = %u", b, bucket_len[b], c->p.max_bucket_bases);
-        if (bucket_start[b] > n_bases || bucket_len[b] > n_bases - bucket_start[b])
-            return fail(BML_ERR_ARG, "bucket %u lies outside the genome buffer", b);
-    }
-    HIP_TRY(hipSetDevice(c->p.device));
-    // the scan kernel packs a bucket with aligned 16-byte loads, which read up to 15 bytes past its last base
-    HIP_TRY(c->genome.need((size_t)n_bases + 64));
-    HIP_TRY(hipMemset(c->genome.p + n_bases, 'A', 64));
-    HIP_TRY(c->bucket_start.need(n_buckets));
-    HIP_TRY(c->bucket_len.need(n_buckets));
-    if (n_bases) HIP_TRY(bmhip::upload_pageable(c->genome.p, bases, (size_t)n_bases));
-    if (n_buckets) {
-        HIP_TRY(hipMemcpy(c->bucket_start.p, bucket_start, (size_t)n_buckets * sizeof(uint64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->bucket_len.p, bucket_len, (size_t)n_buckets * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    c->n_buckets = n_buckets;
-    c->h_bucket_len.assign(bucket_len, bucket_len + n_buckets);
-    c->loaded = true;
-    return BML_OK;
+    return load_genome(c, &bases, &n_bases, 1, n_bases, bucket_start, bucket_len, n_buckets);
 }
 
 // The same for a genome whose records are buffers of their own on the host (no flattened copy needed): the records go
@@ -403,26 +353,7 @@ int bml_load_genome_records(bml_ctx *c, const uint8_t *const *rec, const uint64_
         if (rec_len[r] && !rec[r]) return fail(BML_ERR_ARG, "bml_load_genome_records: record %u is null", r);
         n_bases += rec_len[r];
     }
-    for (uint32_t b = 0; b < n_buckets; b++) {
-        if (bucket_len[b] > c->p.max_bucket_bases)
-            return fail(BML_ERR_ARG, "bucket %u has %u bases, more than max_bucket_bases = %u", b, bucket_len[b], c->p.max_bucket_bases);
-        if (bucket_start[b] > n_bases || bucket_len[b] > n_bases - bucket_start[b])
-            return fail(BML_ERR_ARG, "bucket %u lies outside the genome buffer", b);
-    }
-    HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->genome.need((size_t)n_bases + 64));
-    HIP_TRY(hipMemset(c->genome.p + n_bases, 'A', 64));
-    HIP_TRY(c->bucket_start.need(n_buckets));
-    HIP_TRY(c->bucket_len.need(n_buckets));
-    HIP_TRY(bmhip::upload_pageable_records(c->genome.p, rec, rec_len, n_records));
-    if (n_buckets) {
-        HIP_TRY(hipMemcpy(c->bucket_start.p, bucket_start, (size_t)n_buckets * sizeof(uint64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->bucket_len.p, bucket_len, (size_t)n_buckets * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    c->n_buckets = n_buckets;
-    c->h_bucket_len.assign(bucket_len, bucket_len + n_buckets);
-    c->loaded = true;
-    return BML_OK;
+    return load_genome(c, rec, rec_len, n_records, n_bases, bucket_start, bucket_len, n_buckets);
 }
 
 int bml_locate(bml_ctx *c, const uint32_t *sample_hash, const uint16_t *sample_pos, const uint32_t *seg_len,
@@ -541,8 +472,8 @@ int bml_locate(bml_ctx *c, const uint32_t *sample_hash, const uint16_t *sample_p
             // The three bitmaps in LDS while two workgroups still fit a CU (3 x 8 KB at 65 536-base buckets: six workgroups a CU,
             // 20 ms per million reads in repeats against 52 ms with the bitmaps -- and their atomics -- in global memory); beyond
             // that, global scratch and eight workgroups a CU (3 x 34 KB at 262 144: 25 ms for configs[4]'s 20 000 reads against
-            // 30 ms at one workgroup a CU).  BML_LDS_BITMAP_KB moves the limit (experiments).
-            const size_t lds_limit = getenv("BML_LDS_BITMAP_KB") ? (size_t)atoi(getenv("BML_LDS_BITMAP_KB")) * 1024 : (size_t)64 * 1024;
+            // 30 ms at one workgroup a CU).
+            constexpr size_t lds_limit = (size_t)64 * 1024;
             const bool in_lds = (size_t)3 * words * sizeof(uint32_t) <= lds_limit;
             const size_t lds = in_lds ? (size_t)3 * words * sizeof(uint32_t) : 16;
             if (lds > 48 * 1024)

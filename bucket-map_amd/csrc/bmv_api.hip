@@ -49,7 +49,6 @@ __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t
 
 #include "bm_scan.hip.h"
 
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -57,51 +56,11 @@ __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t
 #include <algorithm>
 #include <vector>
 
+#define HIP_TRY(expr) BM_HIP_TRY(expr, BMV_ERR_HIP)
+
+using bmhip::DevBuf;
+
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(BMV_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-void build_dna4_lut(uint8_t *lut) {
-    memset(lut, 0, 256);
-    const char *m[4] = {"AaRrWwMmDdHhVv", "CcYySsBb", "GgKk", "TtUu"};
-    for (int r = 0; r < 4; r++)
-        for (const char *c = m[r]; *c; c++) lut[(uint8_t)*c] = (uint8_t)r;
-}
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T));
-        if (e == hipSuccess) cap = n ? n : 1;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 using align_fn = void (*)(bmv::Job);
 
@@ -150,8 +109,7 @@ Shape pick_shape(uint32_t words, uint32_t max_n) {
     // SLOTS = 4 kernels (GROUP / 4 cells), groups of 2..7 lanes the SLOTS = 8 ones (GROUP / 2 cells: 1 kbp as 4 lanes x 4
     // words 12.7 -> 11.8 ms, 600 bases as 2 x 5 instead of 4 x 3 8.6 -> 6.7 ms), a lone lane SLOTS = 16 (CW = 1; only with
     // BMV_LANE_MAX=0 or a text window too long for the lane kernel).
-    // (experiment knob; never below 4: a cell of the SLOTS = 4 kernels needs four lanes)
-    const uint32_t kEightBelow = getenv("BMV_EIGHT_BELOW") ? std::max(4u, (uint32_t)atoi(getenv("BMV_EIGHT_BELOW"))) : 8u;
+    constexpr uint32_t kEightBelow = 8;
     static const align_fn four_cols[kMaxCw + 1] = {nullptr,
                                                    bmv::bmv_align_kernel<4, 1, false>, bmv::bmv_align_kernel<4, 2, false>,
                                                    bmv::bmv_align_kernel<4, 3, false>, bmv::bmv_align_kernel<4, 4, false>,
@@ -214,6 +172,16 @@ struct bmv_ctx {
     uint64_t n_cells = 0;
 };
 
+// bmv_load_genome(_records) after their argument checks: the genome is the n_records records back to back (n_bases in all)
+static int load_genome(bmv_ctx *c, const uint8_t *const *rec, const uint64_t *rec_len, uint32_t n_records, uint64_t n_bases) {
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(c->genome.need_exact((size_t)n_bases + 64u));       // (slack: an empty text window at the very end is still fetched from)
+    HIP_TRY(bmhip::upload_pageable_records(c->genome.p, rec, rec_len, n_records));
+    c->n_genome = n_bases;
+    c->loaded = true;
+    return BMV_OK;
+}
+
 extern "C" {
 
 const char *bmv_last_error(void) { return g_err; }
@@ -245,14 +213,14 @@ int bmv_create(const bmv_params *params, bmv_ctx **out) {
         if (v > 0) c->scratch_bytes = (size_t)v << 20;
     }
     uint8_t lut[256];
-    build_dna4_lut(lut);
+    bmhip::build_dna4_lut(lut);
     bool side_ok = true;
     for (uint32_t k = 0; k < kSideStreams; k++)
         side_ok = side_ok && hipStreamCreateWithFlags(&c->side[k], hipStreamNonBlocking) == hipSuccess &&
                   hipEventCreateWithFlags(&c->side_done[k], hipEventDisableTiming) == hipSuccess;
     if (!side_ok || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        c->lut.need(256) != hipSuccess || hipMemcpy(c->lut.p, lut, 256, hipMemcpyHostToDevice) != hipSuccess) {
+        c->lut.need_exact(256) != hipSuccess || hipMemcpy(c->lut.p, lut, 256, hipMemcpyHostToDevice) != hipSuccess) {
         bmv_destroy(c);
         return fail(BMV_ERR_HIP, "bmv_create: %s", hipGetErrorString(hipGetLastError()));
     }
@@ -284,12 +252,7 @@ void bmv_destroy(bmv_ctx *c) {
 
 int bmv_load_genome(bmv_ctx *c, const uint8_t *bases, uint64_t n_bases) {
     if (!c || (n_bases && !bases)) return fail(BMV_ERR_ARG, "bmv_load_genome: null argument");
-    HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->genome.need((size_t)n_bases + 64u));             // (slack: an empty text window at the very end is still fetched from)
-    if (n_bases) HIP_TRY(bmhip::upload_pageable(c->genome.p, bases, (size_t)n_bases));
-    c->n_genome = n_bases;
-    c->loaded = true;
-    return BMV_OK;
+    return load_genome(c, &bases, &n_bases, 1, n_bases);
 }
 
 int bmv_load_genome_records(bmv_ctx *c, const uint8_t *const *rec, const uint64_t *rec_len, uint32_t n_records) {
@@ -299,12 +262,7 @@ int bmv_load_genome_records(bmv_ctx *c, const uint8_t *const *rec, const uint64_
         if (rec_len[r] && !rec[r]) return fail(BMV_ERR_ARG, "bmv_load_genome_records: record %u is null", r);
         n_bases += rec_len[r];
     }
-    HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->genome.need((size_t)n_bases + 64u));
-    HIP_TRY(bmhip::upload_pageable_records(c->genome.p, rec, rec_len, n_records));
-    c->n_genome = n_bases;
-    c->loaded = true;
-    return BMV_OK;
+    return load_genome(c, rec, rec_len, n_records, n_bases);
 }
 
 int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
@@ -337,14 +295,14 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
     if (n == 0) return BMV_OK;
 
     HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->reads.need((size_t)n_read_bytes + 64u));         // (slack: so is an empty query)
-    HIP_TRY(c->text_start.need(n));
-    HIP_TRY(c->text_len.need(n));
-    HIP_TRY(c->text_rc.need(n));
-    HIP_TRY(c->query_start.need(n));
-    HIP_TRY(c->query_len.need(n));
-    HIP_TRY(c->out_score.need(n));
-    HIP_TRY(c->out_begin.need(n));
+    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));   // (slack: so is an empty query)
+    HIP_TRY(c->text_start.need_exact(n));
+    HIP_TRY(c->text_len.need_exact(n));
+    HIP_TRY(c->text_rc.need_exact(n));
+    HIP_TRY(c->query_start.need_exact(n));
+    HIP_TRY(c->query_len.need_exact(n));
+    HIP_TRY(c->out_score.need_exact(n));
+    HIP_TRY(c->out_begin.need_exact(n));
     if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -380,7 +338,7 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
         for (uint32_t a = 0; a < n; a++) order[at[class_of(query_len[a])]++] = a;      // stable: file order within a class
     }
     const bool one_class = n_classes == 1;                      // then order is the identity and the CIGARs arrive in place
-    HIP_TRY(c->order.need(n));
+    HIP_TRY(c->order.need_exact(n));
     HIP_TRY(hipMemcpyAsync(c->order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     std::vector<uint32_t> h_nops, h_packed, cigar_len, stash;
     std::vector<uint64_t> stash_at;
@@ -494,12 +452,12 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
         uint32_t *ops_rev;
     };
     auto collect = [&](const std::vector<Piece> &pieces, uint32_t slots) -> int {
-        HIP_TRY(c->scan_tmp.need(bmscan::tmp_elems(slots) * sizeof(uint32_t)));
+        HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(slots) * sizeof(uint32_t)));
         HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->nops.p, c->offsets.p, slots, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
         uint32_t total = 0;                                     // the scan writes slots + 1 values: the last is the total
         HIP_TRY(hipMemcpyAsync(&total, c->offsets.p + slots, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->packed.need(with_headroom(total, c->packed.cap)));
+        HIP_TRY(c->packed.need_exact(with_headroom(total, c->packed.cap)));
         for (const Piece &pc : pieces) {
             hipLaunchKernelGGL(bmv::bmv_gather_kernel, dim3((pc.count + 31u) / 32u), dim3(256), 0, c->stream, pc.ops_rev,
                                pc.pl->ops_stride, c->nops.p + pc.slot0, c->offsets.p + pc.slot0, pc.count, c->packed.p);
@@ -569,10 +527,10 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
             slots += todo[end].count;
             end++;
         }
-        HIP_TRY(c->trace.need(with_headroom(sum_trace, c->trace.cap)));
-        HIP_TRY(c->ops_rev.need(with_headroom(sum_ops, c->ops_rev.cap)));
-        HIP_TRY(c->nops.need(with_headroom(slots, c->nops.cap)));
-        HIP_TRY(c->offsets.need(with_headroom(slots + 1, c->offsets.cap)));
+        HIP_TRY(c->trace.need_exact(with_headroom(sum_trace, c->trace.cap)));
+        HIP_TRY(c->ops_rev.need_exact(with_headroom(sum_ops, c->ops_rev.cap)));
+        HIP_TRY(c->nops.need_exact(with_headroom(slots, c->nops.cap)));
+        HIP_TRY(c->offsets.need_exact(with_headroom(slots + 1, c->offsets.cap)));
         HIP_TRY(hipEventRecord(c->ev0, c->stream));             // the uploads above / the round before
         std::vector<Piece> pieces;
         size_t trace_at = 0, ops_at = 0;
@@ -722,12 +680,12 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
     for (uint32_t a : empty_query) begin[a] = text_len[a];      // H[0][j] = 0 everywhere: the last column
 
     HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->reads.need((size_t)n_read_bytes + 64u));
-    HIP_TRY(c->text_start.need(n));
-    HIP_TRY(c->text_rc.need(n));
-    HIP_TRY(c->query_start.need(n));
-    HIP_TRY(c->out_score.need(n));
-    HIP_TRY(c->out_begin.need(n));
+    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
+    HIP_TRY(c->text_start.need_exact(n));
+    HIP_TRY(c->text_rc.need_exact(n));
+    HIP_TRY(c->query_start.need_exact(n));
+    HIP_TRY(c->out_score.need_exact(n));
+    HIP_TRY(c->out_begin.need_exact(n));
     if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
@@ -760,10 +718,10 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
         pieces.push_back(pc);
         p0 = pc.p1;
     }
-    HIP_TRY(c->trace.need((size_t)(max_sum + 7u) / 8u));
-    HIP_TRY(c->ops_rev.need((size_t)max_ops));
-    HIP_TRY(c->nops.need((size_t)max_count));
-    HIP_TRY(c->offsets.need((size_t)max_count + 1u));
+    HIP_TRY(c->trace.need_exact((size_t)(max_sum + 7u) / 8u));
+    HIP_TRY(c->ops_rev.need_exact((size_t)max_ops));
+    HIP_TRY(c->nops.need_exact((size_t)max_count));
+    HIP_TRY(c->offsets.need_exact((size_t)max_count + 1u));
     for (const LongPiece &pc : pieces) {
         const size_t p0 = pc.p0, p1 = pc.p1;
         const uint64_t sum = pc.sum, ops_stride = pc.ops_stride;
@@ -795,8 +753,8 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
             }
         }
         tile_at[(size_t)max_d + 1u] = tiles.size() / 2u;
-        HIP_TRY(c->long_slots.need(slots.size() * sizeof(bmv::LongSlot)));
-        HIP_TRY(c->long_tiles.need(tiles.size()));
+        HIP_TRY(c->long_slots.need_exact(slots.size() * sizeof(bmv::LongSlot)));
+        HIP_TRY(c->long_tiles.need_exact(tiles.size()));
         HIP_TRY(hipMemcpyAsync(c->long_slots.p, slots.data(), slots.size() * sizeof(bmv::LongSlot), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->long_tiles.p, tiles.data(), tiles.size() * 4u, hipMemcpyHostToDevice, c->stream));
         bmv::LongJob j{};
@@ -832,12 +790,12 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ev1, c->stream));
         // CIGARs of the piece -> the host: one exclusive sum, one gather
-        HIP_TRY(c->scan_tmp.need(bmscan::tmp_elems(count) * sizeof(uint32_t)));
+        HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(count) * sizeof(uint32_t)));
         HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->nops.p, c->offsets.p, count, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
         uint32_t total = 0;
         HIP_TRY(hipMemcpyAsync(&total, c->offsets.p + count, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->packed.need(total));
+        HIP_TRY(c->packed.need_exact(total));
         hipLaunchKernelGGL(bmv::bmv_gather_kernel, dim3((count + 31u) / 32u), dim3(256), 0, c->stream, c->ops_rev.p, (uint32_t)ops_stride,
                            c->nops.p, c->offsets.p, count, c->packed.p);
         HIP_TRY(hipGetLastError());
