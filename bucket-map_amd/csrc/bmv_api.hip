@@ -3,6 +3,7 @@
 // that the traceback bits of one chunk fit the scratch budget, offsets of the packed CIGAR output
 // (bm_scan.hip.h's exclusive sum).
 #include "bmv_long.hip.h"
+#include "bmv_screen.hip.h"
 
 namespace bmv {
 // instantiated in bmv_variants.hip
@@ -29,6 +30,19 @@ extern template __global__ void bmv_align_lane_kernel<8>(Job);
 extern template __global__ void bmv_long_prep_kernel<kLongCw>(LongJob, uint32_t);
 extern template __global__ void bmv_long_tile_kernel<kLongCw>(LongJob);
 extern template __global__ void bmv_long_traceback_kernel<kLongCw>(LongJob);
+
+// instantiated in bmv_screen.hip
+extern template __global__ void bmv_screen_lane_kernel<1>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<2>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<3>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<4>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<5>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<6>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<7>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<8>(ScreenJob);
+extern template __global__ void bmv_screen_wave_kernel<1>(ScreenJob);
+extern template __global__ void bmv_screen_wave_kernel<2>(ScreenJob);
+extern template __global__ void bmv_screen_wave_kernel<4>(ScreenJob);
 
 // CIGAR entries of one chunk, reversed into reading order at their final offsets.
 __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t ops_stride,
@@ -170,6 +184,12 @@ struct bmv_ctx {
     std::vector<uint64_t> h_offset;
     float ms_kernels = 0.f;
     uint64_t n_cells = 0;
+    // bmv_align_bounded: the screen's buffers and what bmv_last_bounded_stats reports
+    DevBuf<uint32_t> max_edits, keep, keep_at, survivors, screen_list;
+    DevBuf<unsigned long long> screen_count;
+    uint32_t n_rejected = 0;
+    uint64_t screen_cells = 0;
+    float ms_screen = 0.f;
 };
 
 // bmv_load_genome(_records) after their argument checks: the genome is the n_records records back to back (n_bases in all)
@@ -244,6 +264,8 @@ void bmv_destroy(bmv_ctx *c) {
     c->text_len.release(); c->query_len.release(); c->ops_rev.release(); c->nops.release(); c->offsets.release();
     c->packed.release(); c->out_begin.release(); c->out_score.release(); c->order.release();
     c->long_slots.release(); c->long_tiles.release();
+    c->max_edits.release(); c->keep.release(); c->keep_at.release(); c->survivors.release(); c->screen_list.release();
+    c->screen_count.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -840,6 +862,195 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
     }
     c->h_offset[n] = at;
     *total_cigar = at;
+    return BMV_OK;
+}
+
+// The batch under an edit bound per alignment (include/bmv.h).  A screen (bmv_screen.hip.h) rejects what it can prove to be
+// beyond its bound, the survivors' indices are compacted on the device, the survivors go through bmv_align_long -- which is
+// bmv_align itself for everything within the context's limits -- as a batch of their own, and the results are scattered back
+// to batch order.  The screen only ever rejects: the bound is applied to every survivor's score afterwards, which is what
+// makes the contract exact for the alignments the screen does not take (k >= query length: nothing to reject; beyond the
+// limits, or from BMV_LONG_FROM on) or gives up on (a band that outgrows the wave).
+int bmv_align_bounded(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                      const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                      const uint32_t *max_edits, uint32_t n, uint64_t *total_cigar) {
+    if (!c || !total_cigar) return fail(BMV_ERR_ARG, "bmv_align_bounded: null argument");
+    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_align_bounded before bmv_load_genome");
+    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || !max_edits || (n_read_bytes && !reads)))
+        return fail(BMV_ERR_ARG, "bmv_align_bounded: null argument");
+    const uint32_t long_from = getenv("BMV_LONG_FROM") ? (uint32_t)strtoul(getenv("BMV_LONG_FROM"), nullptr, 10) : 0u;
+    constexpr uint32_t kWaveCw[] = {1, 2, 4};                   // bmv_screen_wave_kernel's variants
+    std::vector<uint32_t> lane_list, wave_list[3];
+    uint32_t lane_words = 1;
+    uint64_t cells = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
+        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
+        cells += (uint64_t)query_len[a] * text_len[a];
+        const uint32_t m = query_len[a], k = max_edits[a];
+        const bool beyond = m > c->p.max_query_len || text_len[a] > c->p.max_text_len || (long_from && m >= long_from);
+        if (beyond || k >= m) continue;                         // not screened: the bound is applied to the score
+        const uint32_t words = (m + 63u) / 64u;
+        if (words <= kLaneWords) {
+            lane_list.push_back(a);
+            lane_words = std::max(lane_words, words);
+        } else {
+            // a wrong locus keeps about 2 k rows within the bound (random bases: D grows by about half a row's worth per
+            // row): the smallest variant whose 64 lanes hold that, or the whole query
+            const uint64_t band = std::min<uint64_t>(words, ((uint64_t)k * 9u / 4u + 128u) / 64u + 2u);
+            uint32_t v = 0;
+            while (v + 1u < 3u && band > 64u * kWaveCw[v]) v++;
+            wave_list[v].push_back(a);
+        }
+    }
+    c->n_rejected = 0;
+    c->screen_cells = 0;
+    c->ms_screen = 0.f;
+    if (n == 0) return bmv_align_long(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, total_cigar);
+
+    std::vector<uint32_t> survivors;
+    const size_t n_screened = lane_list.size() + wave_list[0].size() + wave_list[1].size() + wave_list[2].size();
+    if (n_screened == 0) {
+        survivors.resize(n);
+        for (uint32_t a = 0; a < n; a++) survivors[a] = a;
+    } else {
+        HIP_TRY(hipSetDevice(c->p.device));
+        HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
+        HIP_TRY(c->text_start.need_exact(n));
+        HIP_TRY(c->text_len.need_exact(n));
+        HIP_TRY(c->text_rc.need_exact(n));
+        HIP_TRY(c->query_start.need_exact(n));
+        HIP_TRY(c->query_len.need_exact(n));
+        HIP_TRY(c->max_edits.need_exact(n));
+        HIP_TRY(c->keep.need_exact(n));
+        HIP_TRY(c->keep_at.need_exact((size_t)n + 1u));
+        HIP_TRY(c->survivors.need_exact(n));
+        HIP_TRY(c->screen_list.need_exact(n_screened));
+        HIP_TRY(c->screen_count.need_exact(1));
+        HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n) * sizeof(uint32_t)));
+        if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->max_edits.p, max_edits, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        std::vector<uint32_t> ones(n, 1u), list;
+        list.reserve(n_screened);
+        list.insert(list.end(), lane_list.begin(), lane_list.end());
+        for (const auto &w : wave_list) list.insert(list.end(), w.begin(), w.end());
+        HIP_TRY(hipMemcpyAsync(c->keep.p, ones.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->screen_list.p, list.data(), n_screened * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(c->screen_count.p, 0, sizeof(unsigned long long), c->stream));
+        bmv::ScreenJob j{};
+        j.genome = c->genome.p;
+        j.reads = c->reads.p;
+        j.lut = c->lut.p;
+        j.text_start = c->text_start.p;
+        j.text_len = c->text_len.p;
+        j.text_rc = c->text_rc.p;
+        j.query_start = c->query_start.p;
+        j.query_len = c->query_len.p;
+        j.max_edits = c->max_edits.p;
+        j.keep = c->keep.p;
+        j.cells = c->screen_count.p;
+        using screen_fn = void (*)(bmv::ScreenJob);
+        static const screen_fn per_lane[kLaneWords + 1] = {nullptr,
+                                                           bmv::bmv_screen_lane_kernel<1>, bmv::bmv_screen_lane_kernel<2>,
+                                                           bmv::bmv_screen_lane_kernel<3>, bmv::bmv_screen_lane_kernel<4>,
+                                                           bmv::bmv_screen_lane_kernel<5>, bmv::bmv_screen_lane_kernel<6>,
+                                                           bmv::bmv_screen_lane_kernel<7>, bmv::bmv_screen_lane_kernel<8>};
+        static const screen_fn per_wave[3] = {bmv::bmv_screen_wave_kernel<1>, bmv::bmv_screen_wave_kernel<2>, bmv::bmv_screen_wave_kernel<4>};
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        size_t at = 0;
+        if (!lane_list.empty()) {
+            j.list = c->screen_list.p;
+            j.count = (uint32_t)lane_list.size();
+            hipLaunchKernelGGL(per_lane[lane_words], dim3((j.count + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, j);
+            HIP_TRY(hipGetLastError());
+            at += lane_list.size();
+        }
+        for (uint32_t v = 0; v < 3u; v++) {
+            if (wave_list[v].empty()) continue;
+            j.list = c->screen_list.p + at;
+            j.count = (uint32_t)wave_list[v].size();
+            hipLaunchKernelGGL(per_wave[v], dim3(j.count), dim3(bmv::kWave), 0, c->stream, j);
+            HIP_TRY(hipGetLastError());
+            at += wave_list[v].size();
+        }
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        // the survivors' indices, compacted on the device
+        HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->keep.p, c->keep_at.p, n, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
+        hipLaunchKernelGGL(bmv::bmv_screen_compact_kernel, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->keep.p, c->keep_at.p, n,
+                           c->survivors.p);
+        HIP_TRY(hipGetLastError());
+        uint32_t n_keep = 0;
+        unsigned long long steps = 0;
+        HIP_TRY(hipMemcpyAsync(&n_keep, c->keep_at.p + n, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&steps, c->screen_count.p, sizeof steps, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        survivors.resize(n_keep);
+        if (n_keep) HIP_TRY(hipMemcpy(survivors.data(), c->survivors.p, (size_t)n_keep * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventElapsedTime(&c->ms_screen, c->ev0, c->ev1));
+        c->screen_cells = 64u * (uint64_t)steps;
+        if (getenv("BMV_LOG_CLASSES"))
+            fprintf(stderr, "[bmv] screen: %zu per lane, %zu / %zu / %zu per wave at 1 / 2 / 4 words a lane; %u of %u let through, %.2f ms\n",
+                    lane_list.size(), wave_list[0].size(), wave_list[1].size(), wave_list[2].size(), n_keep, n, c->ms_screen);
+    }
+
+    // the survivors as a batch of their own, in batch order
+    const size_t ns = survivors.size();
+    std::vector<uint64_t> ts(ns), qs(ns);
+    std::vector<uint32_t> tl(ns), ql(ns);
+    std::vector<uint8_t> trc(ns);
+    for (size_t s = 0; s < ns; s++) {
+        const uint32_t a = survivors[s];
+        ts[s] = text_start[a];
+        tl[s] = text_len[a];
+        trc[s] = text_rc[a];
+        qs[s] = query_start[a];
+        ql[s] = query_len[a];
+    }
+    uint64_t tot = 0;
+    const float ms_screen = c->ms_screen;
+    if (int rc = bmv_align_long(c, reads, n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), (uint32_t)ns, &tot)) return rc;
+    // back to batch order; the bound applied to what was let through
+    std::vector<int32_t> score(n, BMV_REJECTED);
+    std::vector<uint32_t> begin(n, 0), cig;
+    std::vector<uint64_t> offset((size_t)n + 1, 0);
+    cig.reserve(c->h_cigar.size());
+    std::vector<uint32_t> slot_of(n, 0xFFFFFFFFu);
+    for (size_t s = 0; s < ns; s++) slot_of[survivors[s]] = (uint32_t)s;
+    uint32_t accepted = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        offset[a] = cig.size();
+        const uint32_t s = slot_of[a];
+        if (s == 0xFFFFFFFFu || -(int64_t)c->h_score[s] > (int64_t)max_edits[a]) continue;   // rejected: an empty CIGAR
+        score[a] = c->h_score[s];
+        begin[a] = c->h_begin[s];
+        cig.insert(cig.end(), c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s], c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s + 1]);
+        accepted++;
+    }
+    offset[n] = cig.size();
+    c->n_last = n;
+    c->n_cells = cells;
+    c->ms_kernels += ms_screen;
+    c->n_rejected = n - accepted;
+    c->h_score = std::move(score);
+    c->h_begin = std::move(begin);
+    c->h_offset = std::move(offset);
+    c->h_cigar = std::move(cig);
+    *total_cigar = c->h_cigar.size();
+    return BMV_OK;
+}
+
+int bmv_last_bounded_stats(bmv_ctx *c, uint32_t *n_rejected, uint64_t *screen_cells, float *ms_screen) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_bounded_stats: null context");
+    if (n_rejected) *n_rejected = c->n_rejected;
+    if (screen_cells) *screen_cells = c->screen_cells;
+    if (ms_screen) *ms_screen = c->ms_screen;
     return BMV_OK;
 }
 

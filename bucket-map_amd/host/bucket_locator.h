@@ -106,6 +106,29 @@ public:
                        const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
                        std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
                        std::vector<uint32_t> &cigar) = 0;
+    // The same under an edit bound per alignment (bmv_align_bounded's contract, include/bmv.h): alignment a is kept iff
+    // -score <= max_edits[a]; a rejected one comes back with score kRejected, begin 0 and no CIGAR entries.  This default
+    // aligns everything and marks the rejections afterwards; the GPU verifier screens first.
+    static constexpr int32_t kRejected = INT32_MIN;
+    virtual void align_bounded(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                               const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                               const uint32_t *max_edits, uint32_t n, std::vector<int32_t> &score, std::vector<uint32_t> &begin,
+                               std::vector<uint64_t> &cigar_offset, std::vector<uint32_t> &cigar) {
+        align(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, score, begin, cigar_offset, cigar);
+        uint64_t at = 0;
+        for (uint32_t a = 0; a < n; a++) {
+            const uint64_t from = cigar_offset[a], to = cigar_offset[a + 1];
+            cigar_offset[a] = at;
+            if (-static_cast<int64_t>(score[a]) > static_cast<int64_t>(max_edits[a])) {
+                score[a] = kRejected;
+                begin[a] = 0;
+                continue;
+            }
+            for (uint64_t x = from; x < to; x++) cigar[at++] = cigar[x];
+        }
+        cigar_offset[n] = at;
+        cigar.resize(at);
+    }
 };
 
 // SAM text as seqan3::sam_file_output lays it out: records are appended to one buffer with
@@ -204,6 +227,7 @@ private:
     mapper *_m;
     offset_scanner *_s;
     alignment_verifier *_v = nullptr;            // non-null: the BM_ALIGN behaviour
+    float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     const Genome *genome_ = nullptr;
     std::vector<Bucket> buckets_;
     std::vector<uint64_t> bstart_;               // bucket views into the records laid back to back
@@ -398,6 +422,8 @@ public:
 
     // bucketmap_align: every located candidate is verified by a pairwise alignment before it is written
     void set_verifier(alignment_verifier *v) { _v = v; }
+    // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
+    void set_max_edit_rate(float r) { _max_edit_rate = r; }
 
     int get_allowed_mismatch() const { return allowed_mismatch; }
     int get_allowed_indel() const { return allowed_indel; }
@@ -689,7 +715,7 @@ private:
             std::vector<held> reads;
             std::vector<uint8_t> bases;
             std::vector<uint64_t> text_start, query_start, cigar_offset;
-            std::vector<uint32_t> text_len, query_len, begin, cigar;
+            std::vector<uint32_t> text_len, query_len, begin, cigar, max_edits;
             std::vector<uint8_t> text_rc;
             std::vector<int32_t> score;
             unsigned int first_read = 0;
@@ -702,9 +728,14 @@ private:
         int cur = 0, in_flight = -1, to_write = -1;
         blocks[0].first_read = read_id;
         std::thread worker;
+        const bool bounded = _max_edit_rate >= 0.f;             // --max-edit-rate: rejected alignments leave no record
         auto align = [&](Block &b) {                            // on the worker thread
             try {
-                if (!b.text_start.empty())
+                if (!b.text_start.empty() && bounded)
+                    _v->align_bounded(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
+                                      b.query_start.data(), b.query_len.data(), b.max_edits.data(),
+                                      static_cast<uint32_t>(b.text_start.size()), b.score, b.begin, b.cigar_offset, b.cigar);
+                else if (!b.text_start.empty())
                     _v->align(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                               b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.score, b.begin,
                               b.cigar_offset, b.cigar);
@@ -731,7 +762,8 @@ private:
                     }
                     const unsigned int wrapped = 60u + static_cast<unsigned int>(b.score[a]);        // :570
                     const size_t map_qual = wrapped;
-                    if (!(map_qual < quality_threshold)) {                                            // :571-573
+                    const bool over_bound = bounded && b.score[a] == alignment_verifier::kRejected;
+                    if (!over_bound && !(map_qual < quality_threshold)) {                                            // :571-573
                         const int clipped = offset < 0 ? 0 : offset;
                         const size_t ref_offset = static_cast<size_t>(b.begin[a]) + h.bucket_offsets[bucket_id] + clipped;   // :576
                         cg.clear();
@@ -749,6 +781,7 @@ private:
             }
             b.reads.clear(); b.bases.clear();
             b.text_start.clear(); b.text_len.clear(); b.text_rc.clear(); b.query_start.clear(); b.query_len.clear();
+            b.max_edits.clear();
         };
         // the block just filled goes to the verifier as soon as the one before has left it; that one's records are written
         // while the verifier works
@@ -784,6 +817,7 @@ private:
                     b.text_rc.push_back(is_original ? 0 : 1);                                               // :563-567
                     b.query_start.push_back(b.reads.back().start);
                     b.query_len.push_back(static_cast<uint32_t>(len));
+                    if (bounded) b.max_edits.push_back(static_cast<uint32_t>(std::min(_max_edit_rate * static_cast<float>(len), 4e9f)));
                 }
                 read_id++;
                 if (b.reads.size() >= block_reads || b.bases.size() >= block_bases) flush();

@@ -31,6 +31,8 @@ struct cmd_arguments {
     float locator_sample_size = 10;
     unsigned int locator_quality_threshold = 40;
     float frac_min_hash = 0.25f;
+    float max_edit_rate = -1.f;   // --max-edit-rate R (bucketmap_align): only alignments within R * read length edits are
+                                  // written; negative = unset, every located candidate is written as before
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -144,6 +146,11 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         else if (opt == "-p" || opt == "--locator-samples") a.locator_sample_size = as_float(value());
         else if (opt == "-u" || opt == "--quality") a.locator_quality_threshold = static_cast<unsigned>(as_uint(value()));
         else if (opt == "-f" || opt == "--kmer-frac") a.frac_min_hash = as_float(value());
+        else if (opt == "--max-edit-rate") {
+            const std::string s = value();
+            a.max_edit_rate = as_float(s);
+            if (!(a.max_edit_rate >= 0.f)) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number >= 0.");
+        }
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));

@@ -54,6 +54,22 @@ public:
                const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
                std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
                std::vector<uint32_t> &cigar) override {
+        run(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, nullptr, n, score, begin, cigar_offset, cigar);
+    }
+    // bmv_align_bounded per device: the same cut, the same stitching
+    void align_bounded(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                       const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *max_edits,
+                       uint32_t n, std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
+                       std::vector<uint32_t> &cigar) override {
+        run(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, max_edits, n, score, begin, cigar_offset, cigar);
+    }
+
+private:
+    // max_edits == nullptr: bmv_align / bmv_align_long, exactly as before
+    void run(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+             const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *max_edits, uint32_t n,
+             std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
+             std::vector<uint32_t> &cigar) {
         const size_t D = ctx_.size();
         const auto t0 = std::chrono::steady_clock::now();
         score.assign(n, 0);
@@ -63,13 +79,18 @@ public:
             cut_by_cost(n, D, [&](uint32_t a) { return static_cast<uint64_t>(query_len[a]) * text_len[a] + 1u; });
         std::vector<uint64_t> total(D, 0), cells(D, 0);
         std::vector<float> ms(D, 0.f);
+        std::vector<uint32_t> rejected(D, 0);
+        std::vector<uint64_t> screened(D, 0);
         for_each_device(D, [&](size_t d) {
             const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
             if (m == 0) return;
             bool beyond = false;                                // a candidate bmv_align cannot take: the share goes long
             for (uint32_t a = a0; a < a0 + m; a++) beyond = beyond || query_len[a] > kMaxQuery || text_len[a] > kMaxText;
             const auto align_fn = beyond ? bmv_align_long : bmv_align;
-            if (D == 1) {
+            if (D == 1 && max_edits) {
+                check(bmv_align_bounded(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, max_edits, n,
+                                        &total[0]), "the GPU alignment verifier failed: ");
+            } else if (D == 1) {
                 check(align_fn(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, &total[0]),
                       "the GPU alignment verifier failed: ");
             } else {
@@ -80,10 +101,15 @@ public:
                 }
                 std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
                 for (uint64_t &s : rebased) s -= lo;
-                check(align_fn(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
-                                query_len + a0, m, &total[d]), "the GPU alignment verifier failed: ");
+                if (max_edits)
+                    check(bmv_align_bounded(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
+                                            query_len + a0, max_edits + a0, m, &total[d]), "the GPU alignment verifier failed: ");
+                else
+                    check(align_fn(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
+                                   query_len + a0, m, &total[d]), "the GPU alignment verifier failed: ");
             }
             bmv_last_stats(ctx_[d], &ms[d], &cells[d]);
+            if (max_edits) bmv_last_bounded_stats(ctx_[d], &rejected[d], &screened[d], nullptr);
         });
         // CIGARs of the ranges back to back, in range order; a range's offsets count from its own first entry
         std::vector<uint64_t> at(D + 1, 0);
@@ -99,13 +125,18 @@ public:
         });
         cigar_offset[n] = at[D];
         float slowest = 0;
-        uint64_t all_cells = 0;
+        uint64_t all_cells = 0, all_rejected = 0, all_screened = 0;
         for (size_t d = 0; d < D; d++) {
             slowest = std::max(slowest, ms[d]);
             all_cells += cells[d];
+            all_rejected += rejected[d];
+            all_screened += screened[d];
         }
         const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        std::cerr << "[BENCHMARK]\tGPU alignment verification: " << n << " alignments, " << all_cells << " cells; kernels " << slowest
+        std::cerr << "[BENCHMARK]\tGPU alignment verification: " << n << " alignments, " << all_cells << " cells"
+                  << (max_edits ? ", " + std::to_string(all_rejected) + " rejected by the edit bound after " + std::to_string(all_screened) +
+                                      " screen cells" : std::string())
+                  << "; kernels " << slowest
                   << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of " << call_ms
                   << " ms in the call.\n";
     }

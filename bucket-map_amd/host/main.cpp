@@ -127,6 +127,7 @@ int main(int argc, char **argv) {
 #ifdef BM_ALIGN
         std::unique_ptr<bm::alignment_verifier> verifier = bm_make_verifier(args);
         loc.set_verifier(verifier.get());
+        loc.set_max_edit_rate(args.max_edit_rate);
 #endif
         run_indexer();
         loc.initialize(genome, cwd, args.index_indicator);                                    // main.cpp:221

@@ -8,6 +8,7 @@ import numpy as np
 from . import lib as _bmf_lib
 
 BMV_OK = 0
+REJECTED = -(2 ** 31)     # BMV_REJECTED: the score of an alignment beyond its edit bound (align_bounded)
 
 
 class BmvError(RuntimeError):
@@ -30,6 +31,8 @@ SYMBOLS = {
     "bmv_load_genome_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_uint32]),
     "bmv_align": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u64p]),
     "bmv_align_long": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u64p]),
+    "bmv_align_bounded": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, C.c_uint32, _u64p]),
+    "bmv_last_bounded_stats": (C.c_int, [C.c_void_p, _u32p, _u64p, C.POINTER(C.c_float)]),
     "bmv_results": (C.c_int, [C.c_void_p, _i32p, _u32p, _u64p, _u32p]),
     "bmv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
 }
@@ -82,15 +85,34 @@ class Verifier:
         (bmv_align_long); those within the limits through align's own kernels."""
         return self._align(lib().bmv_align_long, reads, text_start, text_len, text_rc, query_start, query_len)
 
-    def _align(self, fn, reads, text_start, text_len, text_rc, query_start, query_len):
+    def align_bounded(self, reads, text_start, text_len, text_rc, query_start, query_len, max_edits):
+        """As align_long, under an edit bound per alignment (bmv_align_bounded): an alignment whose edit distance
+        exceeds max_edits[a] comes back with score REJECTED, begin 0 and no CIGAR entries; every other one exactly
+        as align / align_long return it."""
+        return self._align(lib().bmv_align_bounded, reads, text_start, text_len, text_rc, query_start, query_len,
+                           max_edits)
+
+    def bounded_stats(self) -> dict:
+        """Of the last align_bounded: rejected alignments, cells the screen evaluated, the screen's kernel ms."""
+        rej, cells, ms = C.c_uint32(), C.c_uint64(), C.c_float()
+        _check(lib().bmv_last_bounded_stats(self._h, C.byref(rej), C.byref(cells), C.byref(ms)))
+        return {"n_rejected": rej.value, "screen_cells": cells.value, "ms_screen": ms.value}
+
+    def _align(self, fn, reads, text_start, text_len, text_rc, query_start, query_len, max_edits=None):
         r = np.ascontiguousarray(reads, np.uint8)
         ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
         trc = np.ascontiguousarray(text_rc, np.uint8)
         qs, ql = np.ascontiguousarray(query_start, np.uint64), np.ascontiguousarray(query_len, np.uint32)
         n = len(ts)
         total = C.c_uint64()
+        bound = []
+        if max_edits is not None:
+            me = np.ascontiguousarray(max_edits, np.uint32)
+            if len(me) != n:
+                raise ValueError("max_edits must hold one bound per alignment")
+            bound = [_p(me, _u32p)]
         _check(fn(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
-                  _p(ql, _u32p), n, C.byref(total)))
+                  _p(ql, _u32p), *bound, n, C.byref(total)))
         score, begin = np.zeros(n, np.int32), np.zeros(n, np.uint32)
         off = np.zeros(n + 1, np.uint64)
         cg = np.zeros(max(total.value, 1), np.uint32)

@@ -83,7 +83,27 @@ int  bmv_align_long(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, c
                     const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
                     const uint32_t *query_len, uint32_t n, uint64_t *total_cigar);
 
-/* Results of the last bmv_align or bmv_align_long:
+/* The same batch under an edit bound per alignment: alignment a is ACCEPTED iff its semi-global edit distance is at most
+ * max_edits[a] -- exactly, not as a heuristic.  An accepted alignment has the score, begin and CIGAR bmv_align (or
+ * bmv_align_long) gives it, bit for bit; a rejected one has score BMV_REJECTED, begin 0 and no CIGAR entries (its two offsets
+ * are equal), and *total_cigar counts accepted entries only.  Argument checks and error codes are bmv_align_long's, so
+ * lengths beyond the context's limits are allowed.
+ * How: a score-only screen (bmv_screen_* kernels: the same recurrence with Ukkonen's cut-off at the lower end of the
+ * column, no checkpoints, no traceback) rejects what it can prove to lie beyond its bound after the top-left corner of its
+ * matrix; the survivors are aligned as a batch of their own by the unchanged kernels and the bound is applied to their
+ * scores.  max_edits[a] >= query_len[a] can reject nothing and skips the screen.  Alignments beyond max_query_len /
+ * max_text_len (or from BMV_LONG_FROM on) skip the screen too and take the bmv_align_long path: the same contract, no
+ * saving. */
+#define BMV_REJECTED INT32_MIN
+int  bmv_align_bounded(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                       const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
+                       const uint32_t *query_len, const uint32_t *max_edits, uint32_t n, uint64_t *total_cigar);
+/* Of the last bmv_align_bounded: how many alignments were rejected, 64 x the (64-row word, text column) steps the screen
+ * evaluated summed over alignments, and the screen's kernel time in ms (part of bmv_last_stats' ms_kernels, which covers
+ * the whole call). */
+int  bmv_last_bounded_stats(bmv_ctx *ctx, uint32_t *n_rejected, uint64_t *screen_cells, float *ms_screen);
+
+/* Results of the last bmv_align, bmv_align_long or bmv_align_bounded:
  *   out_score[a]        alignment.score() = -(edit distance)                       (bucket_locator.h:570)
  *   out_begin[a]        alignment.sequence1_begin_position(), 0-based in the text  (:576)
  *   out_cigar_offset    n + 1 entries; alignment a owns out_cigar[offset[a] .. offset[a+1])

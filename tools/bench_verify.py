@@ -91,6 +91,11 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--mixed", type=int, default=0,
                     help="query lengths log-uniform in [MIXED, --len] (forward strand only): a batch of several length classes")
+    ap.add_argument("--bounded", type=float, default=None, metavar="RATE",
+                    help="also run Verifier.align_bounded on the same batch with max_edits = RATE * query length: kernels ms of "
+                         "both (every repeat), the screen's ms and cells, the rejected share")
+    ap.add_argument("--decoys", type=float, default=0.0, metavar="F",
+                    help="this share of the alignments takes its text window from an unrelated place (a wrong locus)")
     ap.add_argument("--long", action="store_true", help="Verifier.align_long on reads beyond 65 536 bases (see above)")
     ap.add_argument("--long-reads", type=int, default=1000)
     ap.add_argument("--long-len", type=int, default=100_000)
@@ -125,17 +130,44 @@ def main():
         ql = np.exp(rng.uniform(np.log(args.mixed), np.log(m), args.reads)).astype(np.uint32)
         tl = (ql + 1 + (np.float32(args.indel_rate) * ql.astype(np.float32)).astype(np.uint32)).astype(np.uint32)
 
+    if args.decoys > 0:                                # wrong loci: the read stays, its window moves
+        decoy = rng.random(args.reads) < args.decoys
+        start = np.where(decoy, rng.integers(0, len(genome) - width - 8, args.reads).astype(np.uint64), start)
+
     v = verify.Verifier()
     v.load_genome(genome)
-    best_ms, best_wall = None, None
+    best_ms, best_wall, all_ms = None, None, []
     for _ in range(args.repeat):
         t0 = time.perf_counter()
         score, begin, off, cg = v.align(reads, start, tl, rc, qs, ql)
         wall = time.perf_counter() - t0
         st = v.stats()
+        all_ms.append(st["ms_kernels"])
         if best_ms is None or st["ms_kernels"] < best_ms:
             best_ms, best_wall = st["ms_kernels"], wall
     cells = st["cells"]
+    bounded = None
+    if args.bounded is not None:
+        bound = (np.float32(args.bounded) * ql.astype(np.float32)).astype(np.uint32)
+        b_ms, b_wall, b_screen = [], [], []
+        for _ in range(args.repeat):
+            t0 = time.perf_counter()
+            bs, bb, bo, bc = v.align_bounded(reads, start, tl, rc, qs, ql, bound)
+            b_wall.append(time.perf_counter() - t0)
+            b_ms.append(v.stats()["ms_kernels"])
+            bst = v.bounded_stats()
+            b_screen.append(bst["ms_screen"])
+        expect = -score.astype(np.int64) > bound
+        acc = ~expect
+        lens, lens_all = np.diff(bo.astype(np.int64)), np.diff(off.astype(np.int64))
+        bounded = {"rate": args.bounded, "decoys": args.decoys, "ms_kernels_align": all_ms, "ms_kernels_bounded": b_ms,
+                   "ms_screen": b_screen, "wall_s_bounded": b_wall, "screen_cells": bst["screen_cells"],
+                   "screen_cells_share": bst["screen_cells"] / max(cells, 1), "rejected_share": bst["n_rejected"] / args.reads,
+                   "bounded_over_align": min(b_ms) / min(all_ms),
+                   "checks": {"rejected_set_is_score_beyond_bound": bool(np.array_equal(bs == verify.REJECTED, expect)),
+                              "accepted_identical_to_align": bool(np.array_equal(bs[acc], score[acc]) and np.array_equal(bb[acc], begin[acc])
+                                                                  and np.array_equal(lens[acc], lens_all[acc])
+                                                                  and int(lens.sum()) == len(bc))}}
 
     ns = min(args.cpu_sample, args.reads)
     same, cpu = None, None
@@ -153,6 +185,7 @@ def main():
         "ms_kernels": best_ms, "cell_updates_per_s": cells / (best_ms * 1e-3), "wall_s_host_buffers": best_wall,
         "mean_edits": float(-score.mean()), "cigar_entries": int(len(cg)),
         "cpu_baseline": cpu,
+        "bounded": bounded,
         "checks": {"sample_identical_to_oracle": same},
     }))
 
