@@ -2,6 +2,7 @@
 // Host side only: validation, choice of the kernel shape for the longest query of the batch, chunking so
 // that the traceback bits of one chunk fit the scratch budget, offsets of the packed CIGAR output
 // (bm_scan.hip.h's exclusive sum).
+#include "bmv_annotate.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_screen.hip.h"
 
@@ -43,6 +44,10 @@ extern template __global__ void bmv_screen_lane_kernel<8>(ScreenJob);
 extern template __global__ void bmv_screen_wave_kernel<1>(ScreenJob);
 extern template __global__ void bmv_screen_wave_kernel<2>(ScreenJob);
 extern template __global__ void bmv_screen_wave_kernel<4>(ScreenJob);
+
+// instantiated in bmv_annotate.hip
+extern template __global__ void bmv_annotate_kernel<false>(AnnotateJob);
+extern template __global__ void bmv_annotate_kernel<true>(AnnotateJob);
 
 // CIGAR entries of one chunk, reversed into reading order at their final offsets.
 __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t ops_stride,
@@ -190,6 +195,15 @@ struct bmv_ctx {
     uint32_t n_rejected = 0;
     uint64_t screen_cells = 0;
     float ms_screen = 0.f;
+    // bmv_annotate: its own device buffers and host results (bmv_results / bmv_last_stats keep what the last align left)
+    DevBuf<uint32_t> an_begin, an_cigar, an_nm, an_pos, an_ref_len, an_n_xcigar, an_n_ref, an_xcigar;
+    DevBuf<uint64_t> an_cigar_offset, an_xcigar_offset, an_ref_offset;
+    DevBuf<uint8_t> an_ref_bases;
+    std::vector<uint32_t> h_an_nm, h_an_pos, h_an_ref_len, h_an_xcigar;
+    std::vector<uint64_t> h_an_xcigar_offset, h_an_ref_offset;
+    std::vector<uint8_t> h_an_ref_bases;
+    float ms_annotate = 0.f;
+    uint64_t n_columns = 0;
 };
 
 // bmv_load_genome(_records) after their argument checks: the genome is the n_records records back to back (n_bases in all)
@@ -266,6 +280,9 @@ void bmv_destroy(bmv_ctx *c) {
     c->long_slots.release(); c->long_tiles.release();
     c->max_edits.release(); c->keep.release(); c->keep_at.release(); c->survivors.release(); c->screen_list.release();
     c->screen_count.release();
+    c->an_begin.release(); c->an_cigar.release(); c->an_nm.release(); c->an_pos.release(); c->an_ref_len.release();
+    c->an_n_xcigar.release(); c->an_n_ref.release(); c->an_xcigar.release(); c->an_cigar_offset.release();
+    c->an_xcigar_offset.release(); c->an_ref_offset.release(); c->an_ref_bases.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1051,6 +1068,174 @@ int bmv_last_bounded_stats(bmv_ctx *c, uint32_t *n_rejected, uint64_t *screen_ce
     if (n_rejected) *n_rejected = c->n_rejected;
     if (screen_cells) *screen_cells = c->screen_cells;
     if (ms_screen) *ms_screen = c->ms_screen;
+    return BMV_OK;
+}
+
+// The annotation pass (include/bmv.h, bmv_annotate.hip.h).  Everything a kernel relies on is checked here first -- the
+// views, the CIGAR alphabet, that every CIGAR consumes exactly its query and stays inside its window -- so that the
+// kernels index without bounds checks.  Then: upload, the count pass, two exclusive sums, the write pass, download.
+int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                 const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                 const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint64_t *total_xcigar, uint64_t *total_ref_bases) {
+    if (!c || !total_xcigar || !total_ref_bases) return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
+    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_annotate before bmv_load_genome");
+    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || !begin || !cigar_offset || (n_read_bytes && !reads)))
+        return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
+    uint64_t columns = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
+        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
+        if (cigar_offset[a + 1] < cigar_offset[a] || cigar_offset[a + 1] - cigar_offset[a] > 0xFFFFFFFFull - query_len[a])
+            return fail(BMV_ERR_ARG, "alignment %u: CIGAR offsets %llu .. %llu", a, (unsigned long long)cigar_offset[a],
+                        (unsigned long long)cigar_offset[a + 1]);
+        if (cigar_offset[a + 1] > cigar_offset[a] && !cigar) return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
+        if (cigar_offset[a + 1] == cigar_offset[a]) continue;   // an empty CIGAR: zeros and no entries, whatever the views hold
+        uint64_t in_query = 0, in_text = 0, cols = 0;
+        uint32_t before = 0xFFFFFFFFu;
+        for (uint64_t x = cigar_offset[a]; x < cigar_offset[a + 1]; x++) {
+            const uint32_t op = cigar[x] & 15u, len = cigar[x] >> 4;
+            const unsigned long long k = (unsigned long long)(x - cigar_offset[a]);
+            if (op > BMV_OP_D) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entry %llu has op code %u (M, I and D are taken)", a, k, op);
+            if (len == 0) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entry %llu has length 0", a, k);
+            if (op == before) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entries %llu and %llu share an op", a, k - 1u, k);
+            before = op;
+            if (op != BMV_OP_D) in_query += len;
+            if (op != BMV_OP_I) in_text += len;
+            cols += len;
+        }
+        if (in_query != query_len[a])
+            return fail(BMV_ERR_ARG, "alignment %u: the CIGAR consumes %llu query bases, the query has %u", a,
+                        (unsigned long long)in_query, query_len[a]);
+        if ((uint64_t)begin[a] + in_text > text_len[a])
+            return fail(BMV_ERR_ARG, "alignment %u: begin %u + %llu reference bases run past the window of %u", a, begin[a],
+                        (unsigned long long)in_text, text_len[a]);
+        columns += cols;
+    }
+    c->h_an_nm.assign(n, 0);
+    c->h_an_pos.assign(n, 0);
+    c->h_an_ref_len.assign(n, 0);
+    c->h_an_xcigar_offset.assign((size_t)n + 1, 0);
+    c->h_an_ref_offset.assign((size_t)n + 1, 0);
+    c->h_an_xcigar.clear();
+    c->h_an_ref_bases.clear();
+    c->ms_annotate = 0.f;
+    c->n_columns = columns;
+    *total_xcigar = 0;
+    *total_ref_bases = 0;
+    if (n == 0) return BMV_OK;
+
+    const uint64_t cig0 = cigar_offset[0], n_cigar = cigar_offset[n] - cig0;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
+    HIP_TRY(c->text_start.need_exact(n));
+    HIP_TRY(c->text_len.need_exact(n));
+    HIP_TRY(c->text_rc.need_exact(n));
+    HIP_TRY(c->query_start.need_exact(n));
+    HIP_TRY(c->query_len.need_exact(n));
+    HIP_TRY(c->an_begin.need_exact(n));
+    HIP_TRY(c->an_cigar_offset.need_exact((size_t)n + 1u));
+    HIP_TRY(c->an_cigar.need((size_t)n_cigar));
+    HIP_TRY(c->an_nm.need_exact(n));
+    HIP_TRY(c->an_pos.need_exact(n));
+    HIP_TRY(c->an_ref_len.need_exact(n));
+    HIP_TRY(c->an_n_xcigar.need_exact(n));
+    HIP_TRY(c->an_n_ref.need_exact(n));
+    HIP_TRY(c->an_xcigar_offset.need_exact((size_t)n + 1u));
+    HIP_TRY(c->an_ref_offset.need_exact((size_t)n + 1u));
+    HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n) * sizeof(uint64_t)));
+    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->an_begin.p, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint64_t> rebased(cigar_offset, cigar_offset + (size_t)n + 1u);    // the device holds cigar[cig0 ..) only
+    for (uint64_t &o : rebased) o -= cig0;
+    HIP_TRY(hipMemcpyAsync(c->an_cigar_offset.p, rebased.data(), ((size_t)n + 1u) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_cigar) HIP_TRY(hipMemcpyAsync(c->an_cigar.p, cigar + cig0, (size_t)n_cigar * 4, hipMemcpyHostToDevice, c->stream));
+
+    bmv::AnnotateJob j{};
+    j.genome = c->genome.p;
+    j.reads = c->reads.p;
+    j.text_start = c->text_start.p;
+    j.text_len = c->text_len.p;
+    j.text_rc = c->text_rc.p;
+    j.query_start = c->query_start.p;
+    j.query_len = c->query_len.p;
+    j.begin = c->an_begin.p;
+    j.cigar_offset = c->an_cigar_offset.p;
+    j.cigar = c->an_cigar.p;
+    j.count = n;
+    j.nm = c->an_nm.p;
+    j.pos = c->an_pos.p;
+    j.ref_len = c->an_ref_len.p;
+    j.n_xcigar = c->an_n_xcigar.p;
+    j.n_ref = c->an_n_ref.p;
+    const dim3 grid((n + bmv::kAnnotateWaves - 1u) / bmv::kAnnotateWaves), block(64u * bmv::kAnnotateWaves);
+    uint64_t *scan_tmp = reinterpret_cast<uint64_t *>(c->scan_tmp.p);
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_annotate_kernel<false>, grid, block, 0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->an_n_xcigar.p, c->an_xcigar_offset.p, n, scan_tmp, c->stream));
+    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->an_n_ref.p, c->an_ref_offset.p, n, scan_tmp, c->stream));
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_an_xcigar_offset.data(), c->an_xcigar_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_an_ref_offset.data(), c->an_ref_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms_count = 0.f, ms_write = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_count, c->ev0, c->ev1));
+    const uint64_t n_x = c->h_an_xcigar_offset[n], n_r = c->h_an_ref_offset[n];
+    auto with_headroom = [](size_t need, size_t have) { return need <= have ? have : need + need / 4; };
+    HIP_TRY(c->an_xcigar.need_exact(with_headroom((size_t)n_x, c->an_xcigar.cap)));
+    HIP_TRY(c->an_ref_bases.need_exact(with_headroom((size_t)n_r, c->an_ref_bases.cap)));
+    j.xcigar_offset = c->an_xcigar_offset.p;
+    j.ref_offset = c->an_ref_offset.p;
+    j.xcigar = c->an_xcigar.p;
+    j.ref_bases = c->an_ref_bases.p;
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_annotate_kernel<true>, grid, block, 0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    c->h_an_xcigar.resize((size_t)n_x);
+    c->h_an_ref_bases.resize((size_t)n_r);
+    HIP_TRY(hipMemcpyAsync(c->h_an_nm.data(), c->an_nm.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_an_pos.data(), c->an_pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_an_ref_len.data(), c->an_ref_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_x) HIP_TRY(hipMemcpyAsync(c->h_an_xcigar.data(), c->an_xcigar.p, (size_t)n_x * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_r) HIP_TRY(hipMemcpyAsync(c->h_an_ref_bases.data(), c->an_ref_bases.p, (size_t)n_r, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&ms_write, c->ev0, c->ev1));
+    c->ms_annotate = ms_count + ms_write;
+    if (getenv("BMV_LOG_CLASSES"))
+        fprintf(stderr, "[bmv] annotate: %u alignments, count pass and scans %.3f ms, write pass %.3f ms\n", n, ms_count, ms_write);
+    *total_xcigar = n_x;
+    *total_ref_bases = n_r;
+    return BMV_OK;
+}
+
+int bmv_annotations(bmv_ctx *c, uint32_t *out_nm, uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset,
+                    uint32_t *out_xcigar, uint64_t *out_ref_offset, uint8_t *out_ref_bases) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_annotations: null context");
+    auto copy = [](auto *dst, const auto &src) {
+        if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof src[0]);
+    };
+    copy(out_nm, c->h_an_nm);
+    copy(out_pos, c->h_an_pos);
+    copy(out_ref_len, c->h_an_ref_len);
+    copy(out_xcigar_offset, c->h_an_xcigar_offset);
+    copy(out_xcigar, c->h_an_xcigar);
+    copy(out_ref_offset, c->h_an_ref_offset);
+    copy(out_ref_bases, c->h_an_ref_bases);
+    return BMV_OK;
+}
+
+int bmv_last_annotate_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_annotate_stats: null context");
+    if (ms_kernels) *ms_kernels = c->ms_annotate;
+    if (n_columns) *n_columns = c->n_columns;
     return BMV_OK;
 }
 

@@ -15,6 +15,7 @@
 
 #include "bm_genome.h"
 #include "mapper.h"
+#include "sam_tags.h"
 
 #include <algorithm>
 #include <array>
@@ -129,6 +130,16 @@ public:
         cigar_offset[n] = at;
         cigar.resize(at);
     }
+    // What a SAM record needs beyond that (bmv_annotate's contract, include/bmv.h): forward-strand pos, =/X/I/D entries, NM
+    // and the reference bases under X and D columns, for alignments given with their begin and M/I/D CIGAR.  The GPU
+    // verifier's pass; a verifier without one says so.
+    virtual void annotate(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                          const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                          const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, annotation &out) {
+        (void)reads; (void)n_read_bytes; (void)text_start; (void)text_len; (void)text_rc; (void)query_start; (void)query_len;
+        (void)begin; (void)cigar_offset; (void)cigar; (void)n; (void)out;
+        throw std::runtime_error("--annotate: this build's alignment verifier has no annotation pass");
+    }
 };
 
 // SAM text as seqan3::sam_file_output lays it out: records are appended to one buffer with
@@ -193,9 +204,9 @@ public:
             buf_ += '\n';
         }
     }
-    // QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL
+    // QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL [tags: "NM:i:3\tMD:Z:..." -- appended after a tab when not empty]
     static void format(std::string &buf, std::string_view qname, unsigned flag, std::string_view rname, uint64_t pos, unsigned mapq,
-                       std::string_view cigar, std::string_view seq, std::string_view qual) {
+                       std::string_view cigar, std::string_view seq, std::string_view qual, std::string_view tags = {}) {
         buf.append(qname); buf += '\t';
         number(buf, flag); buf += '\t';
         buf.append(rname); buf += '\t';
@@ -204,11 +215,16 @@ public:
         buf.append(cigar);
         buf += "\t*\t0\t0\t";
         buf.append(seq); buf += '\t';
-        buf.append(qual); buf += '\n';
+        buf.append(qual);
+        if (!tags.empty()) {
+            buf += '\t';
+            buf.append(tags);
+        }
+        buf += '\n';
     }
     void record(std::string_view qname, unsigned flag, std::string_view rname, uint64_t pos, unsigned mapq, std::string_view cigar,
-                std::string_view seq, std::string_view qual) {
-        format(buf_, qname, flag, rname, pos, mapq, cigar, seq, qual);
+                std::string_view seq, std::string_view qual, std::string_view tags = {}) {
+        format(buf_, qname, flag, rname, pos, mapq, cigar, seq, qual, tags);
         if (buf_.size() > (4u << 20)) flush();
     }
     // records formatted elsewhere (format(): a few threads, each a block of reads), appended in order
@@ -228,6 +244,7 @@ private:
     offset_scanner *_s;
     alignment_verifier *_v = nullptr;            // non-null: the BM_ALIGN behaviour
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
+    bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     const Genome *genome_ = nullptr;
     std::vector<Bucket> buckets_;
     std::vector<uint64_t> bstart_;               // bucket views into the records laid back to back
@@ -424,6 +441,8 @@ public:
     void set_verifier(alignment_verifier *v) { _v = v; }
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
+    // --annotate: write_verified writes every record on the forward strand (POS, SEQ, QUAL, =/X/I/D CIGAR) with NM and MD
+    void set_annotate(bool on) { _annotate = on; }
 
     int get_allowed_mismatch() const { return allowed_mismatch; }
     int get_allowed_indel() const { return allowed_indel; }
@@ -703,7 +722,12 @@ private:
     //   * map_qual = 60u + score in UNSIGNED arithmetic: below -60 it wraps to ~2^32 and so passes the
     //     `< quality_threshold` test (:570-573); the SAM field is 8 bits wide, hence the truncation;
     //   * POS = begin + bucket offset + offset + 1, also on the reverse strand, where `begin` counts in the
-    //     reverse-complemented window (:576) -- kept as the reference computes it.
+    //     reverse-complemented window (:576) -- kept as the reference computes it.  Flag-16 records therefore carry a POS
+    //     counted from the wrong end of the window, the read as sequenced and a CIGAR in read direction: not usable SAM.
+    // --annotate (set_annotate) is where the tool leaves that layout: the written alignments of a block go through the
+    // verifier's annotation pass and their records become POS = bucket offset + clipped offset + forward pos + 1, the
+    // =/X/I/D CIGAR along the forward strand, for flag 16 the reverse complement of the folded read and the reversed
+    // qualities, and NM:i / MD:Z tags.  MAPQ, flags, RNAME, record order and which records exist stay as they are.
     // Deviation: a negative `offset` indexes before the bucket in the reference (undefined behaviour); here
     // the window is clipped to start at the bucket's first base.
     unsigned int write_verified(const std::string &sequence_file, const std::vector<std::vector<locate_t>> &locate_res,
@@ -718,6 +742,8 @@ private:
             std::vector<uint32_t> text_len, query_len, begin, cigar, max_edits;
             std::vector<uint8_t> text_rc;
             std::vector<int32_t> score;
+            std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
+            annotation ann;
             unsigned int first_read = 0;
             std::exception_ptr failed;
         } blocks[2];
@@ -729,6 +755,10 @@ private:
         blocks[0].first_read = read_id;
         std::thread worker;
         const bool bounded = _max_edit_rate >= 0.f;             // --max-edit-rate: rejected alignments leave no record
+        auto is_written = [&](const Block &b, size_t a) {       // :570-573, and the edit bound
+            const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
+            return !(bounded && b.score[a] == alignment_verifier::kRejected) && !(map_qual < quality_threshold);
+        };
         auto align = [&](Block &b) {                            // on the worker thread
             try {
                 if (!b.text_start.empty() && bounded)
@@ -739,6 +769,24 @@ private:
                     _v->align(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                               b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.score, b.begin,
                               b.cigar_offset, b.cigar);
+                if (_annotate && !b.text_start.empty()) {       // the alignments that will be written, as a batch of their own
+                    const size_t n = b.text_start.size();
+                    std::vector<uint64_t> ts, qs, co{0};
+                    std::vector<uint32_t> tl, ql, bg, cg;
+                    std::vector<uint8_t> trc;
+                    b.ann_slot.assign(n, ~0u);
+                    for (size_t a = 0; a < n; a++) {
+                        if (!is_written(b, a)) continue;
+                        b.ann_slot[a] = static_cast<uint32_t>(ts.size());
+                        ts.push_back(b.text_start[a]); tl.push_back(b.text_len[a]); trc.push_back(b.text_rc[a]);
+                        qs.push_back(b.query_start[a]); ql.push_back(b.query_len[a]); bg.push_back(b.begin[a]);
+                        cg.insert(cg.end(), b.cigar.begin() + static_cast<ptrdiff_t>(b.cigar_offset[a]),
+                                  b.cigar.begin() + static_cast<ptrdiff_t>(b.cigar_offset[a + 1]));
+                        co.push_back(cg.size());
+                    }
+                    _v->annotate(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
+                                 co.data(), cg.data(), static_cast<uint32_t>(ts.size()), b.ann);
+                }
             } catch (...) {
                 b.failed = std::current_exception();
             }
@@ -750,8 +798,9 @@ private:
         auto write = [&](Block &b) {
             if (b.failed) std::rethrow_exception(b.failed);
             size_t a = 0;
-            std::string cg;
+            std::string cg, tags, rc_seq, rc_qual;
             for (size_t r = 0; r < b.reads.size(); r++) {
+                rc_seq.clear();                                 // (--annotate: made for the read's first flag-16 record)
                 for (auto &[bucket_id, offset, segment_offset, votes, is_original] : locate_res[b.first_read + r]) {
                     (void)segment_offset; (void)votes;
                     if (dump.is_open()) {
@@ -762,8 +811,27 @@ private:
                     }
                     const unsigned int wrapped = 60u + static_cast<unsigned int>(b.score[a]);        // :570
                     const size_t map_qual = wrapped;
-                    const bool over_bound = bounded && b.score[a] == alignment_verifier::kRejected;
-                    if (!over_bound && !(map_qual < quality_threshold)) {                                            // :571-573
+                    if (is_written(b, a) && _annotate) {
+                        const uint32_t s = b.ann_slot[a];
+                        const int clipped = offset < 0 ? 0 : offset;
+                        const size_t ref_offset = static_cast<size_t>(b.ann.pos[s]) + h.bucket_offsets[bucket_id] + clipped;
+                        const uint32_t *entry = b.ann.xcigar.data() + b.ann.xcigar_offset[s];
+                        const size_t n_entries = b.ann.xcigar_offset[s + 1] - b.ann.xcigar_offset[s];
+                        cg.clear();
+                        sam_tags::append_cigar(cg, entry, n_entries);
+                        if (cg.empty()) cg = "*";
+                        tags = "NM:i:";
+                        sam_tags::number(tags, b.ann.nm[s]);
+                        tags += "\tMD:Z:";
+                        sam_tags::append_md(tags, entry, n_entries, b.ann.ref_bases.data() + b.ann.ref_offset[s]);
+                        if (!is_original && rc_seq.empty()) {
+                            sam_tags::append_revcomp(rc_seq, b.reads[r].seq);
+                            rc_qual.assign(b.reads[r].qual.rbegin(), b.reads[r].qual.rend());
+                        }
+                        sam.record(b.reads[r].id, is_original ? 0 : 16, h.bucket_name[bucket_id], ref_offset + 1, static_cast<uint8_t>(map_qual),
+                                   cg, is_original ? b.reads[r].seq : rc_seq, is_original ? b.reads[r].qual : rc_qual, tags);
+                        mapped_locations++;
+                    } else if (is_written(b, a)) {
                         const int clipped = offset < 0 ? 0 : offset;
                         const size_t ref_offset = static_cast<size_t>(b.begin[a]) + h.bucket_offsets[bucket_id] + clipped;   // :576
                         cg.clear();

@@ -33,6 +33,7 @@ struct cmd_arguments {
     float frac_min_hash = 0.25f;
     float max_edit_rate = -1.f;   // --max-edit-rate R (bucketmap_align): only alignments within R * read length edits are
                                   // written; negative = unset, every located candidate is written as before
+    bool annotate = false;        // --annotate (bucketmap_align): records on the forward strand with =/X CIGAR, NM and MD
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -151,6 +152,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.max_edit_rate = as_float(s);
             if (!(a.max_edit_rate >= 0.f)) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number >= 0.");
         }
+        else if (opt == "--annotate") a.annotate = true;
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));

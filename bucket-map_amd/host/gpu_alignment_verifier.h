@@ -64,6 +64,74 @@ public:
         run(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, max_edits, n, score, begin, cigar_offset, cigar);
     }
 
+    // bmv_annotate per device: the batch is cut exactly as run() cuts it and the packed arrays are stitched the same way
+    void annotate(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                  const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                  const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, annotation &out) override {
+        const size_t D = ctx_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        out.nm.assign(n, 0);
+        out.pos.assign(n, 0);
+        out.ref_len.assign(n, 0);
+        out.xcigar_offset.assign(static_cast<size_t>(n) + 1, 0);
+        out.ref_offset.assign(static_cast<size_t>(n) + 1, 0);
+        const std::vector<uint32_t> cut =
+            cut_by_cost(n, D, [&](uint32_t a) { return static_cast<uint64_t>(query_len[a]) * text_len[a] + 1u; });
+        std::vector<uint64_t> n_x(D, 0), n_r(D, 0), columns(D, 0);
+        std::vector<float> ms(D, 0.f);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
+            if (m == 0) return;
+            if (D == 1) {
+                check(bmv_annotate(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin,
+                                   cigar_offset, cigar, n, &n_x[0], &n_r[0]), "the GPU annotation pass failed: ");
+            } else {
+                uint64_t lo = ~0ull, hi = 0;
+                for (uint32_t a = a0; a < a0 + m; a++) {
+                    lo = std::min(lo, query_start[a]);
+                    hi = std::max(hi, query_start[a] + query_len[a]);
+                }
+                std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
+                for (uint64_t &s : rebased) s -= lo;
+                check(bmv_annotate(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
+                                   query_len + a0, begin + a0, cigar_offset + a0, cigar, m, &n_x[d], &n_r[d]),
+                      "the GPU annotation pass failed: ");
+            }
+            bmv_last_annotate_stats(ctx_[d], &ms[d], &columns[d]);
+        });
+        std::vector<uint64_t> at_x(D + 1, 0), at_r(D + 1, 0);
+        for (size_t d = 0; d < D; d++) {
+            at_x[d + 1] = at_x[d] + n_x[d];
+            at_r[d + 1] = at_r[d] + n_r[d];
+        }
+        out.xcigar.assign(at_x[D], 0);
+        out.ref_bases.assign(at_r[D], 0);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
+            if (m == 0) return;
+            std::vector<uint64_t> xo(static_cast<size_t>(m) + 1), ro(static_cast<size_t>(m) + 1);
+            check(bmv_annotations(ctx_[d], out.nm.data() + a0, out.pos.data() + a0, out.ref_len.data() + a0, xo.data(),
+                                  out.xcigar.data() + at_x[d], ro.data(), out.ref_bases.data() + at_r[d]),
+                  "reading the annotations failed: ");
+            for (uint32_t a = 0; a < m; a++) {
+                out.xcigar_offset[a0 + a] = at_x[d] + xo[a];
+                out.ref_offset[a0 + a] = at_r[d] + ro[a];
+            }
+        });
+        out.xcigar_offset[n] = at_x[D];
+        out.ref_offset[n] = at_r[D];
+        float slowest = 0;
+        uint64_t all_columns = 0;
+        for (size_t d = 0; d < D; d++) {
+            slowest = std::max(slowest, ms[d]);
+            all_columns += columns[d];
+        }
+        const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::cerr << "[BENCHMARK]\tGPU alignment annotation: " << n << " alignments, " << all_columns << " columns; kernels " << slowest
+                  << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of " << call_ms
+                  << " ms in the call.\n";
+    }
+
 private:
     // max_edits == nullptr: bmv_align / bmv_align_long, exactly as before
     void run(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,

@@ -1,6 +1,7 @@
 // main.cpp -- the `bucketmap` command-line tool (bucket_map/main.cpp:135-234), MI355X edition.
 // Compiled a second time with -DBM_ALIGN it is `bucketmap_align` (bucket_map/CMakeLists.txt:138): every
-// located candidate is verified by a pairwise alignment and written with MAPQ = 60 + score and a CIGAR.
+// located candidate is verified by a pairwise alignment and written with MAPQ = 60 + score and a CIGAR
+// (--annotate: as forward-strand records with an =/X CIGAR, NM and MD).
 //
 //   bucketmap -x -i <name> --genome ref.fa                       index only (writes into the cwd)
 //   bucketmap -i <name> -q reads.fq -o out.sam --genome ref.fa    map (indexes first if needed)
@@ -128,6 +129,7 @@ int main(int argc, char **argv) {
         std::unique_ptr<bm::alignment_verifier> verifier = bm_make_verifier(args);
         loc.set_verifier(verifier.get());
         loc.set_max_edit_rate(args.max_edit_rate);
+        loc.set_annotate(args.annotate);
 #endif
         run_indexer();
         loc.initialize(genome, cwd, args.index_indicator);                                    // main.cpp:221

@@ -35,6 +35,10 @@ SYMBOLS = {
     "bmv_last_bounded_stats": (C.c_int, [C.c_void_p, _u32p, _u64p, C.POINTER(C.c_float)]),
     "bmv_results": (C.c_int, [C.c_void_p, _i32p, _u32p, _u64p, _u32p]),
     "bmv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
+    "bmv_annotate": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32,
+                               _u64p, _u64p]),
+    "bmv_annotations": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u64p, _u32p, _u64p, _u8p]),
+    "bmv_last_annotate_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
 }
 _ready = False
 
@@ -61,6 +65,36 @@ def _p(a, ty):
 
 def cigar_string(packed) -> str:
     return "".join(f"{int(e) >> 4}{'MID'[int(e) & 15]}" for e in packed)
+
+
+def xcigar_string(packed) -> str:
+    """Annotated entries (Verifier.annotate) as SAM text: BAM op codes, so M I D = X all print."""
+    return "".join(f"{int(e) >> 4}{'MIDNSHP=X'[int(e) & 15]}" for e in packed)
+
+
+def md_string(xcigar, ref_bases) -> str:
+    """SAM's MD tag of one alignment from its annotated entries and the reference bases under its X and D columns, as
+    samtools writes it: a running count of matches; before every X base and before every D entry the count (also 0), then
+    the base -- or '^' and the entry's bases --, and the count starts again; I adds nothing; the count once more at the
+    end.  The rule of host/sam_tags.h, for users of the ABI."""
+    ref = bytes(bytearray(ref_bases)).decode("ascii")
+    out, run, at = [], 0, 0
+    for e in xcigar:
+        op, n = int(e) & 15, int(e) >> 4
+        if op == 7:
+            run += n
+        elif op == 8:
+            for x in range(n):
+                out.append(f"{run}{ref[at + x]}")
+                run = 0
+            at += n
+        elif op == 2:
+            out.append(f"{run}^{ref[at: at + n]}")
+            run = 0
+            at += n
+    if at != len(ref):
+        raise ValueError(f"the entries cover {at} reference bases under X and D, {len(ref)} were given")
+    return "".join(out) + str(run)
 
 
 class Verifier:
@@ -118,6 +152,37 @@ class Verifier:
         cg = np.zeros(max(total.value, 1), np.uint32)
         _check(lib().bmv_results(self._h, _p(score, _i32p), _p(begin, _u32p), _p(off, _u64p), _p(cg, _u32p)))
         return score, begin, off, cg[: total.value]
+
+    def annotate(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar):
+        """bmv_annotate on alignments given with their begin and M/I/D CIGAR (what align* returned, or hand-made): returns
+        (nm u32[n], pos u32[n], ref_len u32[n], xcigar_offset u64[n+1], xcigar u32[..], ref_offset u64[n+1], ref_bases
+        u8[..]) in forward-strand coordinates; see include/bmv.h.  Leaves the results of the last align* untouched."""
+        r = np.ascontiguousarray(reads, np.uint8)
+        ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
+        trc = np.ascontiguousarray(text_rc, np.uint8)
+        qs, ql = np.ascontiguousarray(query_start, np.uint64), np.ascontiguousarray(query_len, np.uint32)
+        bg, co = np.ascontiguousarray(begin, np.uint32), np.ascontiguousarray(cigar_offset, np.uint64)
+        cg = np.ascontiguousarray(cigar, np.uint32)
+        n = len(ts)
+        if not (len(tl) == len(trc) == len(qs) == len(ql) == len(bg) == n and len(co) == n + 1):
+            raise ValueError("one entry per alignment in every array, n + 1 in cigar_offset")
+        if n and int(co[n]) > len(cg):
+            raise ValueError("cigar_offset runs past the CIGAR entries")
+        n_x, n_r = C.c_uint64(), C.c_uint64()
+        _check(lib().bmv_annotate(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
+                                  _p(ql, _u32p), _p(bg, _u32p), _p(co, _u64p), _p(cg, _u32p), n, C.byref(n_x), C.byref(n_r)))
+        nm, pos, ref_len = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        xo, ro = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        xc, rb = np.zeros(max(n_x.value, 1), np.uint32), np.zeros(max(n_r.value, 1), np.uint8)
+        _check(lib().bmv_annotations(self._h, _p(nm, _u32p), _p(pos, _u32p), _p(ref_len, _u32p), _p(xo, _u64p), _p(xc, _u32p),
+                                     _p(ro, _u64p), _p(rb, _u8p)))
+        return nm, pos, ref_len, xo, xc[: n_x.value], ro, rb[: n_r.value]
+
+    def annotate_stats(self) -> dict:
+        """Of the last annotate: kernel ms (count pass, prefix sums, write pass) and the alignment columns walked."""
+        ms, cols = C.c_float(), C.c_uint64()
+        _check(lib().bmv_last_annotate_stats(self._h, C.byref(ms), C.byref(cols)))
+        return {"ms_kernels": ms.value, "columns": cols.value}
 
     def stats(self) -> dict:
         ms, cells = C.c_float(), C.c_uint64()

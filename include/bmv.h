@@ -43,7 +43,7 @@ extern "C" {
 enum { BMV_OK = 0, BMV_ERR_ARG = 1, BMV_ERR_HIP = 2, BMV_ERR_STATE = 3, BMV_ERR_UNSUPPORTED = 5 };
 
 /* CIGAR entries are packed as in BAM: length << 4 | op. */
-enum { BMV_OP_M = 0, BMV_OP_I = 1, BMV_OP_D = 2 };
+enum { BMV_OP_M = 0, BMV_OP_I = 1, BMV_OP_D = 2, BMV_OP_EQ = 7, BMV_OP_X = 8 };   /* = and X: bmv_annotate's output only */
 
 typedef struct bmv_params {
     uint32_t max_query_len;   /* longest read handed to bmv_align (<= 65536)                        */
@@ -114,6 +114,40 @@ int  bmv_results(bmv_ctx *ctx, int32_t *out_score, uint32_t *out_begin, uint64_t
 /* Kernel time of the last bmv_align (or bmv_align_long) in ms (edit-distance columns + traceback, all chunks) and the number
  * of dynamic-programming cells it stands for (sum of query_len * text_len). */
 int  bmv_last_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells);
+
+/* The annotation pass: what a SAM record needs beyond score, begin and an M/I/D CIGAR, for alignments whose CIGARs are known.
+ * A call of its own: it does not care which of bmv_align, bmv_align_long or bmv_align_bounded produced the CIGARs (or whether a
+ * caller wrote them by hand), and it leaves what bmv_results, bmv_last_stats and bmv_last_bounded_stats return untouched.
+ * Input per alignment a: the views bmv_align takes, plus begin[a] and the entries cigar[cigar_offset[a] .. cigar_offset[a+1])
+ * as bmv_results returns them -- M/I/D, 5' to 3' of the query, begin counted in the text as the aligner saw it (in the reverse
+ * complement when text_rc[a] != 0).  Output per alignment, in FORWARD-strand coordinates, with R = sum of the M and D lengths:
+ *   out_pos[a]          begin when text_rc == 0, else text_len - begin - R: 0-based in the forward window
+ *   out_ref_len[a]      R
+ *   out_xcigar          every M run split into maximal runs of equal (BMV_OP_EQ) and unequal (BMV_OP_X) bases, I and D as they
+ *                       are; equality is on dna4 ranks on both sides (N and IUPAC fold, either case), the comparison the aligner
+ *                       scored with; for text_rc != 0 the entries come in reversed order, so that they read along the forward
+ *                       strand; adjacent entries never share an op.  out_xcigar_offset: n + 1 entries
+ *   out_nm[a]           sum of the X, I and D lengths (= -score for a CIGAR that came from the aligner)
+ *   out_ref_bases       the forward-strand reference base under every X and D column, in forward order, one folded letter
+ *                       (A C G T) each -- for text_rc != 0 the complement of what the aligner compared against; the payload of
+ *                       SAM's MD tag, whose text is formatted on the host.  out_ref_offset: n + 1 entries
+ * An empty CIGAR (an alignment bmv_align_bounded rejected, a zero-length query) gives nm = pos = ref_len = 0 and no entries.
+ * The batch is checked on the host before anything is launched: views inside `reads` and the genome, every op M, I or D, every
+ * length > 0, adjacent entries of different ops, M + I lengths = query_len, begin + R <= text_len, fewer than 2^32 - query_len
+ * entries per alignment.  A failure returns BMV_ERR_ARG, the message names the alignment, nothing ran and the context stays
+ * usable.  Any lengths that fit uint32 (entry lengths: 28 bits); no scratch beyond the inputs and outputs.
+ * How: a wave per alignment walks text and query once in forward-strand order, 64 columns a step (bmv_annotate.hip.h); sizes are
+ * counted first, two prefix sums place the packed outputs, a second walk writes them. */
+int  bmv_annotate(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                  const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                  const uint32_t *begin, const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n,
+                  uint64_t *total_xcigar, uint64_t *total_ref_bases);
+/* Results of the last bmv_annotate; any pointer may be NULL. */
+int  bmv_annotations(bmv_ctx *ctx, uint32_t *out_nm, uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset,
+                     uint32_t *out_xcigar, uint64_t *out_ref_offset, uint8_t *out_ref_bases);
+/* Kernel time of the last bmv_annotate in ms (count pass, prefix sums, write pass) and the alignment columns it walked (sum of
+ * all CIGAR entry lengths). */
+int  bmv_last_annotate_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_columns);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
 
     python tools/bench_verify.py [--reads 1000000] [--len 300] [--indel-rate 0.02] [--cpu-sample 2000]
     python tools/bench_verify.py --long [--long-reads 1000] [--long-len 100000]
+    python tools/bench_verify.py --annotate [--reads 20000 --len 10000 --indel-rate 0.1]
 
 Prints one JSON line: alignments/s and cell updates/s of the device kernels (HIP events inside bmv_align),
 the wall time of the call (host buffers in, results out), and the CPU restatement (oracle, full DP matrix,
@@ -94,6 +95,9 @@ def main():
     ap.add_argument("--bounded", type=float, default=None, metavar="RATE",
                     help="also run Verifier.align_bounded on the same batch with max_edits = RATE * query length: kernels ms of "
                          "both (every repeat), the screen's ms and cells, the rejected share")
+    ap.add_argument("--annotate", action="store_true",
+                    help="also run Verifier.annotate on the batch's results: kernels ms of every repeat, bytes read (text + query, "
+                         "each once), bytes / time, and the ratio to align's kernels ms on the same batch")
     ap.add_argument("--decoys", type=float, default=0.0, metavar="F",
                     help="this share of the alignments takes its text window from an unrelated place (a wrong locus)")
     ap.add_argument("--long", action="store_true", help="Verifier.align_long on reads beyond 65 536 bases (see above)")
@@ -169,6 +173,22 @@ def main():
                                                                   and np.array_equal(lens[acc], lens_all[acc])
                                                                   and int(lens.sum()) == len(bc))}}
 
+    annotate = None
+    if args.annotate:
+        a_ms, a_wall = [], []
+        for _ in range(args.repeat):
+            t0 = time.perf_counter()
+            nm, pos, ref_len, xo, xc, ro, rb = v.annotate(reads, start, tl, rc, qs, ql, begin, off, cg)
+            a_wall.append(time.perf_counter() - t0)
+            a_ms.append(v.annotate_stats()["ms_kernels"])
+        covered = np.diff(off.astype(np.int64)) > 0                    # (an empty CIGAR reads nothing)
+        n_bytes = int(ref_len.sum()) + int(ql[covered].sum())
+        annotate = {"ms_kernels_annotate": a_ms, "ms_kernels_align": all_ms, "wall_s_annotate": a_wall,
+                    "columns": v.annotate_stats()["columns"], "bytes_read": n_bytes,
+                    "bytes_per_s": n_bytes / (min(a_ms) * 1e-3), "spread": (max(a_ms) - min(a_ms)) / min(a_ms),
+                    "annotate_over_align": min(a_ms) / min(all_ms), "xcigar_entries": int(len(xc)), "ref_bases": int(len(rb)),
+                    "checks": {"nm_is_minus_score": bool(np.array_equal(nm.astype(np.int64), -score.astype(np.int64)))}}
+
     ns = min(args.cpu_sample, args.reads)
     same, cpu = None, None
     if ns > 0:                                         # (--cpu-sample 0: no oracle in the process at all -- bench.py's leg)
@@ -186,6 +206,7 @@ def main():
         "mean_edits": float(-score.mean()), "cigar_entries": int(len(cg)),
         "cpu_baseline": cpu,
         "bounded": bounded,
+        "annotate": annotate,
         "checks": {"sample_identical_to_oracle": same},
     }))
 
