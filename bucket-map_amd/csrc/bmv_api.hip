@@ -3,6 +3,7 @@
 // that the traceback bits of one chunk fit the scratch budget, offsets of the packed CIGAR output
 // (bm_scan.hip.h's exclusive sum).
 #include "bmv_annotate.hip.h"
+#include "bmv_clip.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_screen.hip.h"
 
@@ -48,6 +49,11 @@ extern template __global__ void bmv_screen_wave_kernel<4>(ScreenJob);
 // instantiated in bmv_annotate.hip
 extern template __global__ void bmv_annotate_kernel<false>(AnnotateJob);
 extern template __global__ void bmv_annotate_kernel<true>(AnnotateJob);
+
+// instantiated in bmv_clip.hip
+extern template __global__ void bmv_clip_range_kernel<kAnnotateWaves>(ClipJob);
+extern template __global__ void bmv_clip_emit_kernel<false>(ClipJob);
+extern template __global__ void bmv_clip_emit_kernel<true>(ClipJob);
 
 // CIGAR entries of one chunk, reversed into reading order at their final offsets.
 __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t ops_stride,
@@ -204,6 +210,18 @@ struct bmv_ctx {
     std::vector<uint8_t> h_an_ref_bases;
     float ms_annotate = 0.f;
     uint64_t n_columns = 0;
+    // bmv_clip: the inputs go through bmv_annotate's device buffers (its results are on the host by then), the outputs and
+    // the host results are its own (bmv_annotations keeps what the last bmv_annotate left)
+    DevBuf<int64_t> cl_score;
+    DevBuf<uint64_t> cl_l, cl_r, cl_xcigar_offset, cl_ref_offset;
+    DevBuf<uint32_t> cl_pos0, cl_left, cl_right, cl_nm, cl_pos, cl_ref_len, cl_n_xcigar, cl_n_ref, cl_xcigar;
+    DevBuf<uint8_t> cl_ref_bases;
+    std::vector<int64_t> h_cl_score;
+    std::vector<uint32_t> h_cl_left, h_cl_right, h_cl_nm, h_cl_pos, h_cl_ref_len, h_cl_xcigar;
+    std::vector<uint64_t> h_cl_xcigar_offset, h_cl_ref_offset;
+    std::vector<uint8_t> h_cl_ref_bases;
+    float ms_clip = 0.f;
+    uint64_t n_clip_columns = 0;
 };
 
 // bmv_load_genome(_records) after their argument checks: the genome is the n_records records back to back (n_bases in all)
@@ -283,6 +301,9 @@ void bmv_destroy(bmv_ctx *c) {
     c->an_begin.release(); c->an_cigar.release(); c->an_nm.release(); c->an_pos.release(); c->an_ref_len.release();
     c->an_n_xcigar.release(); c->an_n_ref.release(); c->an_xcigar.release(); c->an_cigar_offset.release();
     c->an_xcigar_offset.release(); c->an_ref_offset.release(); c->an_ref_bases.release();
+    c->cl_score.release(); c->cl_l.release(); c->cl_r.release(); c->cl_xcigar_offset.release(); c->cl_ref_offset.release();
+    c->cl_pos0.release(); c->cl_left.release(); c->cl_right.release(); c->cl_nm.release(); c->cl_pos.release();
+    c->cl_ref_len.release(); c->cl_n_xcigar.release(); c->cl_n_ref.release(); c->cl_xcigar.release(); c->cl_ref_bases.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1071,16 +1092,16 @@ int bmv_last_bounded_stats(bmv_ctx *c, uint32_t *n_rejected, uint64_t *screen_ce
     return BMV_OK;
 }
 
-// The annotation pass (include/bmv.h, bmv_annotate.hip.h).  Everything a kernel relies on is checked here first -- the
-// views, the CIGAR alphabet, that every CIGAR consumes exactly its query and stays inside its window -- so that the
-// kernels index without bounds checks.  Then: upload, the count pass, two exclusive sums, the write pass, download.
-int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
-                 const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
-                 const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint64_t *total_xcigar, uint64_t *total_ref_bases) {
-    if (!c || !total_xcigar || !total_ref_bases) return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
-    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_annotate before bmv_load_genome");
+// The annotation pass (include/bmv.h, bmv_annotate.hip.h) and the clipping pass (bmv_clip.hip.h) take the same batch.
+// Everything a kernel relies on is checked here first -- the views, the CIGAR alphabet, that every CIGAR consumes exactly
+// its query and stays inside its window -- so that the kernels index without bounds checks.  `who`: the call, for the message.
+static int check_annotate_batch(bmv_ctx *c, const char *who, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                                const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
+                                const uint32_t *query_len, const uint32_t *begin, const uint64_t *cigar_offset,
+                                const uint32_t *cigar, uint32_t n, uint64_t *out_columns) {
+    if (!c->loaded) return fail(BMV_ERR_STATE, "%s before bmv_load_genome", who);
     if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || !begin || !cigar_offset || (n_read_bytes && !reads)))
-        return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
+        return fail(BMV_ERR_ARG, "%s: null argument", who);
     uint64_t columns = 0;
     for (uint32_t a = 0; a < n; a++) {
         if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
@@ -1090,7 +1111,7 @@ int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const 
         if (cigar_offset[a + 1] < cigar_offset[a] || cigar_offset[a + 1] - cigar_offset[a] > 0xFFFFFFFFull - query_len[a])
             return fail(BMV_ERR_ARG, "alignment %u: CIGAR offsets %llu .. %llu", a, (unsigned long long)cigar_offset[a],
                         (unsigned long long)cigar_offset[a + 1]);
-        if (cigar_offset[a + 1] > cigar_offset[a] && !cigar) return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
+        if (cigar_offset[a + 1] > cigar_offset[a] && !cigar) return fail(BMV_ERR_ARG, "%s: null argument", who);
         if (cigar_offset[a + 1] == cigar_offset[a]) continue;   // an empty CIGAR: zeros and no entries, whatever the views hold
         uint64_t in_query = 0, in_text = 0, cols = 0;
         uint32_t before = 0xFFFFFFFFu;
@@ -1113,6 +1134,62 @@ int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const 
                         (unsigned long long)in_text, text_len[a]);
         columns += cols;
     }
+    *out_columns = columns;
+    return BMV_OK;
+}
+
+// The checked batch (n > 0) on its way to the device, on the context's stream; j receives the input pointers.  `rebased` is
+// the caller's: the copy out of it may still be under way on return.
+static int upload_annotate_batch(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                                 const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
+                                 const uint32_t *query_len, const uint32_t *begin, const uint64_t *cigar_offset,
+                                 const uint32_t *cigar, uint32_t n, std::vector<uint64_t> &rebased, bmv::AnnotateJob &j) {
+    const uint64_t cig0 = cigar_offset[0], n_cigar = cigar_offset[n] - cig0;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
+    HIP_TRY(c->text_start.need_exact(n));
+    HIP_TRY(c->text_len.need_exact(n));
+    HIP_TRY(c->text_rc.need_exact(n));
+    HIP_TRY(c->query_start.need_exact(n));
+    HIP_TRY(c->query_len.need_exact(n));
+    HIP_TRY(c->an_begin.need_exact(n));
+    HIP_TRY(c->an_cigar_offset.need_exact((size_t)n + 1u));
+    HIP_TRY(c->an_cigar.need((size_t)n_cigar));
+    HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n) * sizeof(uint64_t)));
+    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->an_begin.p, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    rebased.assign(cigar_offset, cigar_offset + (size_t)n + 1u);                    // the device holds cigar[cig0 ..) only
+    for (uint64_t &o : rebased) o -= cig0;
+    HIP_TRY(hipMemcpyAsync(c->an_cigar_offset.p, rebased.data(), ((size_t)n + 1u) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_cigar) HIP_TRY(hipMemcpyAsync(c->an_cigar.p, cigar + cig0, (size_t)n_cigar * 4, hipMemcpyHostToDevice, c->stream));
+    j.genome = c->genome.p;
+    j.reads = c->reads.p;
+    j.text_start = c->text_start.p;
+    j.text_len = c->text_len.p;
+    j.text_rc = c->text_rc.p;
+    j.query_start = c->query_start.p;
+    j.query_len = c->query_len.p;
+    j.begin = c->an_begin.p;
+    j.cigar_offset = c->an_cigar_offset.p;
+    j.cigar = c->an_cigar.p;
+    j.count = n;
+    return BMV_OK;
+}
+
+// bmv_annotate: upload, the count pass, two exclusive sums, the write pass, download.
+int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                 const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                 const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint64_t *total_xcigar, uint64_t *total_ref_bases) {
+    if (!c || !total_xcigar || !total_ref_bases) return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
+    uint64_t columns = 0;
+    if (const int rc = check_annotate_batch(c, "bmv_annotate", reads, n_read_bytes, text_start, text_len, text_rc, query_start,
+                                            query_len, begin, cigar_offset, cigar, n, &columns))
+        return rc;
     c->h_an_nm.assign(n, 0);
     c->h_an_pos.assign(n, 0);
     c->h_an_ref_len.assign(n, 0);
@@ -1126,17 +1203,11 @@ int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const 
     *total_ref_bases = 0;
     if (n == 0) return BMV_OK;
 
-    const uint64_t cig0 = cigar_offset[0], n_cigar = cigar_offset[n] - cig0;
-    HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
-    HIP_TRY(c->text_start.need_exact(n));
-    HIP_TRY(c->text_len.need_exact(n));
-    HIP_TRY(c->text_rc.need_exact(n));
-    HIP_TRY(c->query_start.need_exact(n));
-    HIP_TRY(c->query_len.need_exact(n));
-    HIP_TRY(c->an_begin.need_exact(n));
-    HIP_TRY(c->an_cigar_offset.need_exact((size_t)n + 1u));
-    HIP_TRY(c->an_cigar.need((size_t)n_cigar));
+    bmv::AnnotateJob j{};
+    std::vector<uint64_t> rebased;
+    if (const int rc = upload_annotate_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin,
+                                             cigar_offset, cigar, n, rebased, j))
+        return rc;
     HIP_TRY(c->an_nm.need_exact(n));
     HIP_TRY(c->an_pos.need_exact(n));
     HIP_TRY(c->an_ref_len.need_exact(n));
@@ -1144,31 +1215,6 @@ int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const 
     HIP_TRY(c->an_n_ref.need_exact(n));
     HIP_TRY(c->an_xcigar_offset.need_exact((size_t)n + 1u));
     HIP_TRY(c->an_ref_offset.need_exact((size_t)n + 1u));
-    HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n) * sizeof(uint64_t)));
-    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->an_begin.p, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    std::vector<uint64_t> rebased(cigar_offset, cigar_offset + (size_t)n + 1u);    // the device holds cigar[cig0 ..) only
-    for (uint64_t &o : rebased) o -= cig0;
-    HIP_TRY(hipMemcpyAsync(c->an_cigar_offset.p, rebased.data(), ((size_t)n + 1u) * 8, hipMemcpyHostToDevice, c->stream));
-    if (n_cigar) HIP_TRY(hipMemcpyAsync(c->an_cigar.p, cigar + cig0, (size_t)n_cigar * 4, hipMemcpyHostToDevice, c->stream));
-
-    bmv::AnnotateJob j{};
-    j.genome = c->genome.p;
-    j.reads = c->reads.p;
-    j.text_start = c->text_start.p;
-    j.text_len = c->text_len.p;
-    j.text_rc = c->text_rc.p;
-    j.query_start = c->query_start.p;
-    j.query_len = c->query_len.p;
-    j.begin = c->an_begin.p;
-    j.cigar_offset = c->an_cigar_offset.p;
-    j.cigar = c->an_cigar.p;
-    j.count = n;
     j.nm = c->an_nm.p;
     j.pos = c->an_pos.p;
     j.ref_len = c->an_ref_len.p;
@@ -1236,6 +1282,140 @@ int bmv_last_annotate_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) 
     if (!c) return fail(BMV_ERR_ARG, "bmv_last_annotate_stats: null context");
     if (ms_kernels) *ms_kernels = c->ms_annotate;
     if (n_columns) *n_columns = c->n_columns;
+    return BMV_OK;
+}
+
+// The clipping pass (include/bmv.h, bmv_clip.hip.h): bmv_annotate's checks and upload, then the range pass, the count pass,
+// two exclusive sums, the write pass, download -- into results of its own.
+int bmv_clip(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+             const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+             const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t penalty,
+             uint64_t *total_xcigar, uint64_t *total_ref_bases) {
+    if (!c || !total_xcigar || !total_ref_bases) return fail(BMV_ERR_ARG, "bmv_clip: null argument");
+    if (match < 1u || match > 1024u || penalty < 1u || penalty > 1024u)
+        return fail(BMV_ERR_ARG, "bmv_clip: match and penalty must be in 1..1024 (got %u and %u)", match, penalty);
+    uint64_t columns = 0;
+    if (const int rc = check_annotate_batch(c, "bmv_clip", reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len,
+                                            begin, cigar_offset, cigar, n, &columns))
+        return rc;
+    c->h_cl_score.assign(n, 0);
+    c->h_cl_left.assign(n, 0);
+    c->h_cl_right.assign(n, 0);
+    c->h_cl_nm.assign(n, 0);
+    c->h_cl_pos.assign(n, 0);
+    c->h_cl_ref_len.assign(n, 0);
+    c->h_cl_xcigar_offset.assign((size_t)n + 1, 0);
+    c->h_cl_ref_offset.assign((size_t)n + 1, 0);
+    c->h_cl_xcigar.clear();
+    c->h_cl_ref_bases.clear();
+    c->ms_clip = 0.f;
+    c->n_clip_columns = columns;
+    *total_xcigar = 0;
+    *total_ref_bases = 0;
+    if (n == 0) return BMV_OK;
+
+    bmv::ClipJob j{};
+    std::vector<uint64_t> rebased;
+    if (const int rc = upload_annotate_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin,
+                                             cigar_offset, cigar, n, rebased, j.a))
+        return rc;
+    HIP_TRY(c->cl_score.need_exact(n));
+    HIP_TRY(c->cl_l.need_exact(n));
+    HIP_TRY(c->cl_r.need_exact(n));
+    HIP_TRY(c->cl_pos0.need_exact(n));
+    HIP_TRY(c->cl_left.need_exact(n));
+    HIP_TRY(c->cl_right.need_exact(n));
+    HIP_TRY(c->cl_nm.need_exact(n));
+    HIP_TRY(c->cl_pos.need_exact(n));
+    HIP_TRY(c->cl_ref_len.need_exact(n));
+    HIP_TRY(c->cl_n_xcigar.need_exact(n));
+    HIP_TRY(c->cl_n_ref.need_exact(n));
+    HIP_TRY(c->cl_xcigar_offset.need_exact((size_t)n + 1u));
+    HIP_TRY(c->cl_ref_offset.need_exact((size_t)n + 1u));
+    j.match = match;
+    j.penalty = penalty;
+    j.score = c->cl_score.p;
+    j.l = c->cl_l.p;
+    j.r = c->cl_r.p;
+    j.pos0 = c->cl_pos0.p;
+    j.clip_left = c->cl_left.p;
+    j.clip_right = c->cl_right.p;
+    j.a.nm = c->cl_nm.p;
+    j.a.pos = c->cl_pos.p;
+    j.a.ref_len = c->cl_ref_len.p;
+    j.a.n_xcigar = c->cl_n_xcigar.p;
+    j.a.n_ref = c->cl_n_ref.p;
+    const dim3 grid((n + bmv::kAnnotateWaves - 1u) / bmv::kAnnotateWaves), block(64u * bmv::kAnnotateWaves);
+    uint64_t *scan_tmp = reinterpret_cast<uint64_t *>(c->scan_tmp.p);
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_clip_range_kernel<bmv::kAnnotateWaves>, grid, block, 0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<false>, grid, block, 0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->cl_n_xcigar.p, c->cl_xcigar_offset.p, n, scan_tmp, c->stream));
+    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->cl_n_ref.p, c->cl_ref_offset.p, n, scan_tmp, c->stream));
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cl_xcigar_offset.data(), c->cl_xcigar_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cl_ref_offset.data(), c->cl_ref_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms_count = 0.f, ms_write = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_count, c->ev0, c->ev1));
+    const uint64_t n_x = c->h_cl_xcigar_offset[n], n_r = c->h_cl_ref_offset[n];
+    auto with_headroom = [](size_t need, size_t have) { return need <= have ? have : need + need / 4; };
+    HIP_TRY(c->cl_xcigar.need_exact(with_headroom((size_t)n_x, c->cl_xcigar.cap)));
+    HIP_TRY(c->cl_ref_bases.need_exact(with_headroom((size_t)n_r, c->cl_ref_bases.cap)));
+    j.a.xcigar_offset = c->cl_xcigar_offset.p;
+    j.a.ref_offset = c->cl_ref_offset.p;
+    j.a.xcigar = c->cl_xcigar.p;
+    j.a.ref_bases = c->cl_ref_bases.p;
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<true>, grid, block, 0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    c->h_cl_xcigar.resize((size_t)n_x);
+    c->h_cl_ref_bases.resize((size_t)n_r);
+    HIP_TRY(hipMemcpyAsync(c->h_cl_score.data(), c->cl_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cl_left.data(), c->cl_left.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cl_right.data(), c->cl_right.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cl_nm.data(), c->cl_nm.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cl_pos.data(), c->cl_pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_cl_ref_len.data(), c->cl_ref_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_x) HIP_TRY(hipMemcpyAsync(c->h_cl_xcigar.data(), c->cl_xcigar.p, (size_t)n_x * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_r) HIP_TRY(hipMemcpyAsync(c->h_cl_ref_bases.data(), c->cl_ref_bases.p, (size_t)n_r, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&ms_write, c->ev0, c->ev1));
+    c->ms_clip = ms_count + ms_write;
+    if (getenv("BMV_LOG_CLASSES"))
+        fprintf(stderr, "[bmv] clip: %u alignments, range and count passes and scans %.3f ms, write pass %.3f ms\n", n, ms_count, ms_write);
+    *total_xcigar = n_x;
+    *total_ref_bases = n_r;
+    return BMV_OK;
+}
+
+int bmv_clipped(bmv_ctx *c, int64_t *out_score, uint32_t *out_clip_left, uint32_t *out_clip_right, uint32_t *out_nm,
+                uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset, uint32_t *out_xcigar,
+                uint64_t *out_ref_offset, uint8_t *out_ref_bases) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_clipped: null context");
+    auto copy = [](auto *dst, const auto &src) {
+        if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof src[0]);
+    };
+    copy(out_score, c->h_cl_score);
+    copy(out_clip_left, c->h_cl_left);
+    copy(out_clip_right, c->h_cl_right);
+    copy(out_nm, c->h_cl_nm);
+    copy(out_pos, c->h_cl_pos);
+    copy(out_ref_len, c->h_cl_ref_len);
+    copy(out_xcigar_offset, c->h_cl_xcigar_offset);
+    copy(out_xcigar, c->h_cl_xcigar);
+    copy(out_ref_offset, c->h_cl_ref_offset);
+    copy(out_ref_bases, c->h_cl_ref_bases);
+    return BMV_OK;
+}
+
+int bmv_last_clip_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_clip_stats: null context");
+    if (ms_kernels) *ms_kernels = c->ms_clip;
+    if (n_columns) *n_columns = c->n_clip_columns;
     return BMV_OK;
 }
 

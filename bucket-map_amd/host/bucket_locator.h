@@ -140,6 +140,17 @@ public:
         (void)begin; (void)cigar_offset; (void)cigar; (void)n; (void)out;
         throw std::runtime_error("--annotate: this build's alignment verifier has no annotation pass");
     }
+    // The same with low-identity ends soft-clipped (bmv_clip's contract, include/bmv.h): the best-scoring contiguous stretch of
+    // columns under +match per = column and -penalty per X, I or D column is kept, the rest of the query becomes S entries.
+    // The GPU verifier's pass; a verifier without one says so.
+    virtual void clip(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                      const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                      const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t penalty,
+                      clipping &out) {
+        (void)reads; (void)n_read_bytes; (void)text_start; (void)text_len; (void)text_rc; (void)query_start; (void)query_len;
+        (void)begin; (void)cigar_offset; (void)cigar; (void)n; (void)match; (void)penalty; (void)out;
+        throw std::runtime_error("--clip: this build's alignment verifier has no clipping pass");
+    }
 };
 
 // SAM text as seqan3::sam_file_output lays it out: records are appended to one buffer with
@@ -245,6 +256,8 @@ private:
     alignment_verifier *_v = nullptr;            // non-null: the BM_ALIGN behaviour
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
+    bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
+    uint32_t _clip_match = 1, _clip_penalty = 2;
     const Genome *genome_ = nullptr;
     std::vector<Bucket> buckets_;
     std::vector<uint64_t> bstart_;               // bucket views into the records laid back to back
@@ -443,6 +456,13 @@ public:
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
     // --annotate: write_verified writes every record on the forward strand (POS, SEQ, QUAL, =/X/I/D CIGAR) with NM and MD
     void set_annotate(bool on) { _annotate = on; }
+    // --clip: the --annotate layout, the written alignments through the verifier's clipping pass instead (POS, CIGAR, NM and MD
+    // of the kept part, S entries, AS:i); an alignment of which nothing is kept writes no record
+    void set_clip(uint32_t match, uint32_t penalty) {
+        _clip = _annotate = true;
+        _clip_match = match;
+        _clip_penalty = penalty;
+    }
 
     int get_allowed_mismatch() const { return allowed_mismatch; }
     int get_allowed_indel() const { return allowed_indel; }
@@ -728,6 +748,9 @@ private:
     // verifier's annotation pass and their records become POS = bucket offset + clipped offset + forward pos + 1, the
     // =/X/I/D CIGAR along the forward strand, for flag 16 the reverse complement of the folded read and the reversed
     // qualities, and NM:i / MD:Z tags.  MAPQ, flags, RNAME, record order and which records exist stay as they are.
+    // --clip (set_clip) sends them through the clipping pass instead: POS, CIGAR, NM and MD describe the kept part, the
+    // clipped ends are S entries (SEQ and QUAL stay whole), AS:i carries the kept part's score, and an alignment of which
+    // nothing is kept has no record.
     // Deviation: a negative `offset` indexes before the bucket in the reference (undefined behaviour); here
     // the window is clipped to start at the bucket's first base.
     unsigned int write_verified(const std::string &sequence_file, const std::vector<std::vector<locate_t>> &locate_res,
@@ -743,7 +766,7 @@ private:
             std::vector<uint8_t> text_rc;
             std::vector<int32_t> score;
             std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
-            annotation ann;
+            clipping ann;                        // (--clip fills score and the clips too)
             unsigned int first_read = 0;
             std::exception_ptr failed;
         } blocks[2];
@@ -784,8 +807,12 @@ private:
                                   b.cigar.begin() + static_cast<ptrdiff_t>(b.cigar_offset[a + 1]));
                         co.push_back(cg.size());
                     }
-                    _v->annotate(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
-                                 co.data(), cg.data(), static_cast<uint32_t>(ts.size()), b.ann);
+                    if (_clip)
+                        _v->clip(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
+                                 co.data(), cg.data(), static_cast<uint32_t>(ts.size()), _clip_match, _clip_penalty, b.ann);
+                    else
+                        _v->annotate(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
+                                     co.data(), cg.data(), static_cast<uint32_t>(ts.size()), b.ann);
                 }
             } catch (...) {
                 b.failed = std::current_exception();
@@ -811,7 +838,9 @@ private:
                     }
                     const unsigned int wrapped = 60u + static_cast<unsigned int>(b.score[a]);        // :570
                     const size_t map_qual = wrapped;
-                    if (is_written(b, a) && _annotate) {
+                    if (is_written(b, a) && _clip && b.ann.score[b.ann_slot[a]] == 0) {
+                        // --clip: the kept range is empty (a kept column scores at least `match`): no record
+                    } else if (is_written(b, a) && _annotate) {
                         const uint32_t s = b.ann_slot[a];
                         const int clipped = offset < 0 ? 0 : offset;
                         const size_t ref_offset = static_cast<size_t>(b.ann.pos[s]) + h.bucket_offsets[bucket_id] + clipped;
@@ -824,6 +853,10 @@ private:
                         sam_tags::number(tags, b.ann.nm[s]);
                         tags += "\tMD:Z:";
                         sam_tags::append_md(tags, entry, n_entries, b.ann.ref_bases.data() + b.ann.ref_offset[s]);
+                        if (_clip) {
+                            tags += "\tAS:i:";
+                            sam_tags::number(tags, static_cast<uint64_t>(b.ann.score[s]));
+                        }
                         if (!is_original && rc_seq.empty()) {
                             sam_tags::append_revcomp(rc_seq, b.reads[r].seq);
                             rc_qual.assign(b.reads[r].qual.rbegin(), b.reads[r].qual.rend());

@@ -34,6 +34,8 @@ struct cmd_arguments {
     float max_edit_rate = -1.f;   // --max-edit-rate R (bucketmap_align): only alignments within R * read length edits are
                                   // written; negative = unset, every located candidate is written as before
     bool annotate = false;        // --annotate (bucketmap_align): records on the forward strand with =/X CIGAR, NM and MD
+    bool clip = false;            // --clip (bucketmap_align): --annotate's records with low-identity ends soft-clipped (S) and AS
+    unsigned int clip_match = 1, clip_penalty = 2;   // --clip-scores M,P (implies --clip): bmv_clip's scores, 1..1024 each
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -153,6 +155,17 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             if (!(a.max_edit_rate >= 0.f)) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number >= 0.");
         }
         else if (opt == "--annotate") a.annotate = true;
+        else if (opt == "--clip") a.clip = true;
+        else if (opt == "--clip-scores") {
+            const std::string s = value();
+            const size_t comma = s.find(',');
+            if (comma == std::string::npos) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be M,P such as 1,2.");
+            a.clip_match = static_cast<unsigned>(as_uint(s.substr(0, comma)));
+            a.clip_penalty = static_cast<unsigned>(as_uint(s.substr(comma + 1)));
+            if (a.clip_match < 1 || a.clip_match > 1024 || a.clip_penalty < 1 || a.clip_penalty > 1024)
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be two numbers in 1..1024.");
+            a.clip = true;
+        }
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));

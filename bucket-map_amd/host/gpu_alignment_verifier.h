@@ -68,23 +68,51 @@ public:
     void annotate(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
                   const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
                   const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, annotation &out) override {
+        post_pass(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, n, out, nullptr, 0, 0);
+    }
+    // bmv_clip per device: the same cut, the same stitching, with the score and the two clips per alignment
+    void clip(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+              const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+              const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t penalty, clipping &out) override {
+        post_pass(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, n, out, &out,
+                  match, penalty);
+    }
+
+private:
+    // clipped == nullptr: bmv_annotate; else bmv_clip under (match, penalty), `clipped` being `out` itself
+    void post_pass(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                   const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                   const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, annotation &out, clipping *clipped,
+                   uint32_t match, uint32_t penalty) {
         const size_t D = ctx_.size();
         const auto t0 = std::chrono::steady_clock::now();
+        const char *failed = clipped ? "the GPU clipping pass failed: " : "the GPU annotation pass failed: ";
         out.nm.assign(n, 0);
         out.pos.assign(n, 0);
         out.ref_len.assign(n, 0);
         out.xcigar_offset.assign(static_cast<size_t>(n) + 1, 0);
         out.ref_offset.assign(static_cast<size_t>(n) + 1, 0);
+        if (clipped) {
+            clipped->score.assign(n, 0);
+            clipped->clip_left.assign(n, 0);
+            clipped->clip_right.assign(n, 0);
+        }
         const std::vector<uint32_t> cut =
             cut_by_cost(n, D, [&](uint32_t a) { return static_cast<uint64_t>(query_len[a]) * text_len[a] + 1u; });
         std::vector<uint64_t> n_x(D, 0), n_r(D, 0), columns(D, 0);
         std::vector<float> ms(D, 0.f);
+        auto pass = [&](size_t d, const uint8_t *rd, uint64_t n_rd, const uint64_t *ts, const uint32_t *tl, const uint8_t *trc,
+                        const uint64_t *qs, const uint32_t *ql, const uint32_t *bg, const uint64_t *co, uint32_t m) {
+            if (clipped)
+                check(bmv_clip(ctx_[d], rd, n_rd, ts, tl, trc, qs, ql, bg, co, cigar, m, match, penalty, &n_x[d], &n_r[d]), failed);
+            else
+                check(bmv_annotate(ctx_[d], rd, n_rd, ts, tl, trc, qs, ql, bg, co, cigar, m, &n_x[d], &n_r[d]), failed);
+        };
         for_each_device(D, [&](size_t d) {
             const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
             if (m == 0) return;
             if (D == 1) {
-                check(bmv_annotate(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin,
-                                   cigar_offset, cigar, n, &n_x[0], &n_r[0]), "the GPU annotation pass failed: ");
+                pass(0, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, n);
             } else {
                 uint64_t lo = ~0ull, hi = 0;
                 for (uint32_t a = a0; a < a0 + m; a++) {
@@ -93,11 +121,13 @@ public:
                 }
                 std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
                 for (uint64_t &s : rebased) s -= lo;
-                check(bmv_annotate(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
-                                   query_len + a0, begin + a0, cigar_offset + a0, cigar, m, &n_x[d], &n_r[d]),
-                      "the GPU annotation pass failed: ");
+                pass(d, reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(), query_len + a0, begin + a0,
+                     cigar_offset + a0, m);
             }
-            bmv_last_annotate_stats(ctx_[d], &ms[d], &columns[d]);
+            if (clipped)
+                bmv_last_clip_stats(ctx_[d], &ms[d], &columns[d]);
+            else
+                bmv_last_annotate_stats(ctx_[d], &ms[d], &columns[d]);
         });
         std::vector<uint64_t> at_x(D + 1, 0), at_r(D + 1, 0);
         for (size_t d = 0; d < D; d++) {
@@ -110,9 +140,15 @@ public:
             const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
             if (m == 0) return;
             std::vector<uint64_t> xo(static_cast<size_t>(m) + 1), ro(static_cast<size_t>(m) + 1);
-            check(bmv_annotations(ctx_[d], out.nm.data() + a0, out.pos.data() + a0, out.ref_len.data() + a0, xo.data(),
+            if (clipped)
+                check(bmv_clipped(ctx_[d], clipped->score.data() + a0, clipped->clip_left.data() + a0, clipped->clip_right.data() + a0,
+                                  out.nm.data() + a0, out.pos.data() + a0, out.ref_len.data() + a0, xo.data(),
                                   out.xcigar.data() + at_x[d], ro.data(), out.ref_bases.data() + at_r[d]),
-                  "reading the annotations failed: ");
+                      "reading the clipped alignments failed: ");
+            else
+                check(bmv_annotations(ctx_[d], out.nm.data() + a0, out.pos.data() + a0, out.ref_len.data() + a0, xo.data(),
+                                      out.xcigar.data() + at_x[d], ro.data(), out.ref_bases.data() + at_r[d]),
+                      "reading the annotations failed: ");
             for (uint32_t a = 0; a < m; a++) {
                 out.xcigar_offset[a0 + a] = at_x[d] + xo[a];
                 out.ref_offset[a0 + a] = at_r[d] + ro[a];
@@ -127,12 +163,12 @@ public:
             all_columns += columns[d];
         }
         const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        std::cerr << "[BENCHMARK]\tGPU alignment annotation: " << n << " alignments, " << all_columns << " columns; kernels " << slowest
+        std::cerr << "[BENCHMARK]\tGPU alignment " << (clipped ? "clipping: " : "annotation: ") << n << " alignments, " << all_columns
+                  << " columns; kernels " << slowest
                   << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of " << call_ms
                   << " ms in the call.\n";
     }
 
-private:
     // max_edits == nullptr: bmv_align / bmv_align_long, exactly as before
     void run(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
              const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *max_edits, uint32_t n,

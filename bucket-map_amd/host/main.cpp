@@ -1,7 +1,7 @@
 // main.cpp -- the `bucketmap` command-line tool (bucket_map/main.cpp:135-234), MI355X edition.
 // Compiled a second time with -DBM_ALIGN it is `bucketmap_align` (bucket_map/CMakeLists.txt:138): every
 // located candidate is verified by a pairwise alignment and written with MAPQ = 60 + score and a CIGAR
-// (--annotate: as forward-strand records with an =/X CIGAR, NM and MD).
+// (--annotate: as forward-strand records with an =/X CIGAR, NM and MD; --clip: those with low-identity ends soft-clipped).
 //
 //   bucketmap -x -i <name> --genome ref.fa                       index only (writes into the cwd)
 //   bucketmap -i <name> -q reads.fq -o out.sam --genome ref.fa    map (indexes first if needed)
@@ -130,6 +130,7 @@ int main(int argc, char **argv) {
         loc.set_verifier(verifier.get());
         loc.set_max_edit_rate(args.max_edit_rate);
         loc.set_annotate(args.annotate);
+        if (args.clip) loc.set_clip(args.clip_match, args.clip_penalty);
 #endif
         run_indexer();
         loc.initialize(genome, cwd, args.index_indicator);                                    // main.cpp:221

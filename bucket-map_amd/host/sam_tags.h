@@ -1,6 +1,6 @@
-// sam_tags.h -- what `bucketmap_align --annotate` puts into a record beyond the reference's fields, from the verifier's
-// annotation of an alignment (include/bmv.h, bmv_annotate): the =/X/I/D CIGAR string, the MD tag, and the reverse
-// complement of a folded read.  Text formatting only; the walk over text and query that produces the annotation runs on
+// sam_tags.h -- what `bucketmap_align --annotate` and `--clip` put into a record beyond the reference's fields, from the
+// verifier's annotation of an alignment (include/bmv.h, bmv_annotate; with soft clips: bmv_clip): the =/X/I/D/S CIGAR
+// string, the MD tag, and the reverse complement of a folded read.  Text formatting only; the walk over text and query that produces the annotation runs on
 // the device.
 #pragma once
 
@@ -22,6 +22,12 @@ struct annotation {
     std::vector<uint8_t> ref_bases;
 };
 
+// The same of the kept part of every alignment as bmv_clipped returns it: S entries (op 4) may stand first and last.
+struct clipping : annotation {
+    std::vector<int64_t> score;
+    std::vector<uint32_t> clip_left, clip_right;
+};
+
 namespace sam_tags {
 
 inline void number(std::string &out, uint64_t v) {
@@ -30,7 +36,7 @@ inline void number(std::string &out, uint64_t v) {
     out.append(tmp, static_cast<size_t>(r.ptr - tmp));
 }
 
-// "5=1X3I2D": BAM's op letters
+// "2S5=1X3I2D4S": BAM's op letters
 inline void append_cigar(std::string &out, const uint32_t *entry, size_t n) {
     for (size_t i = 0; i < n; i++) {
         number(out, entry[i] >> 4);
@@ -40,7 +46,8 @@ inline void append_cigar(std::string &out, const uint32_t *entry, size_t n) {
 
 // MD as samtools writes it: a running count of matching bases; before every X base and before every D entry the count
 // (also when it is 0), then the reference base -- or '^' and the deleted bases --, and the count starts again; I adds
-// nothing; the count once more at the end.  ref_bases: the reference base of every X and D column, in CIGAR order.
+// nothing, and neither does S (clipped bases are not aligned); the count once more at the end.  ref_bases: the reference base
+// of every X and D column, in CIGAR order.
 inline void append_md(std::string &out, const uint32_t *entry, size_t n, const uint8_t *ref_bases) {
     uint64_t run = 0;
     for (size_t i = 0; i < n; i++) {

@@ -21,7 +21,7 @@ class _Params(C.Structure):
     _fields_ = [("max_query_len", C.c_uint32), ("max_text_len", C.c_uint32), ("device", C.c_int32)]
 
 
-_u8p, _u32p, _u64p, _i32p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint32, C.c_uint64, C.c_int32))
+_u8p, _u32p, _u64p, _i32p, _i64p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint32, C.c_uint64, C.c_int32, C.c_int64))
 
 SYMBOLS = {
     "bmv_last_error": (C.c_char_p, []),
@@ -39,6 +39,10 @@ SYMBOLS = {
                                _u64p, _u64p]),
     "bmv_annotations": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u64p, _u32p, _u64p, _u8p]),
     "bmv_last_annotate_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
+    "bmv_clip": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32,
+                           C.c_uint32, C.c_uint32, _u64p, _u64p]),
+    "bmv_clipped": (C.c_int, [C.c_void_p, _i64p, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p, _u64p, _u8p]),
+    "bmv_last_clip_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
 }
 _ready = False
 
@@ -68,15 +72,15 @@ def cigar_string(packed) -> str:
 
 
 def xcigar_string(packed) -> str:
-    """Annotated entries (Verifier.annotate) as SAM text: BAM op codes, so M I D = X all print."""
+    """Annotated entries (Verifier.annotate, Verifier.clip) as SAM text: BAM op codes, so M I D S = X all print."""
     return "".join(f"{int(e) >> 4}{'MIDNSHP=X'[int(e) & 15]}" for e in packed)
 
 
 def md_string(xcigar, ref_bases) -> str:
     """SAM's MD tag of one alignment from its annotated entries and the reference bases under its X and D columns, as
     samtools writes it: a running count of matches; before every X base and before every D entry the count (also 0), then
-    the base -- or '^' and the entry's bases --, and the count starts again; I adds nothing; the count once more at the
-    end.  The rule of host/sam_tags.h, for users of the ABI."""
+    the base -- or '^' and the entry's bases --, and the count starts again; I adds nothing and neither does S
+    (Verifier.clip's soft clips); the count once more at the end.  The rule of host/sam_tags.h, for users of the ABI."""
     ref = bytes(bytearray(ref_bases)).decode("ascii")
     out, run, at = [], 0, 0
     for e in xcigar:
@@ -153,10 +157,8 @@ class Verifier:
         _check(lib().bmv_results(self._h, _p(score, _i32p), _p(begin, _u32p), _p(off, _u64p), _p(cg, _u32p)))
         return score, begin, off, cg[: total.value]
 
-    def annotate(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar):
-        """bmv_annotate on alignments given with their begin and M/I/D CIGAR (what align* returned, or hand-made): returns
-        (nm u32[n], pos u32[n], ref_len u32[n], xcigar_offset u64[n+1], xcigar u32[..], ref_offset u64[n+1], ref_bases
-        u8[..]) in forward-strand coordinates; see include/bmv.h.  Leaves the results of the last align* untouched."""
+    @staticmethod
+    def _annotate_args(reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar):
         r = np.ascontiguousarray(reads, np.uint8)
         ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
         trc = np.ascontiguousarray(text_rc, np.uint8)
@@ -168,9 +170,18 @@ class Verifier:
             raise ValueError("one entry per alignment in every array, n + 1 in cigar_offset")
         if n and int(co[n]) > len(cg):
             raise ValueError("cigar_offset runs past the CIGAR entries")
+        keep = (r, ts, tl, trc, qs, ql, bg, co, cg)
+        return keep, n, (_p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p), _p(ql, _u32p),
+                         _p(bg, _u32p), _p(co, _u64p), _p(cg, _u32p), n)
+
+    def annotate(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar):
+        """bmv_annotate on alignments given with their begin and M/I/D CIGAR (what align* returned, or hand-made): returns
+        (nm u32[n], pos u32[n], ref_len u32[n], xcigar_offset u64[n+1], xcigar u32[..], ref_offset u64[n+1], ref_bases
+        u8[..]) in forward-strand coordinates; see include/bmv.h.  Leaves the results of the last align* untouched."""
+        _keep, n, args = self._annotate_args(reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset,
+                                             cigar)
         n_x, n_r = C.c_uint64(), C.c_uint64()
-        _check(lib().bmv_annotate(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
-                                  _p(ql, _u32p), _p(bg, _u32p), _p(co, _u64p), _p(cg, _u32p), n, C.byref(n_x), C.byref(n_r)))
+        _check(lib().bmv_annotate(self._h, *args, C.byref(n_x), C.byref(n_r)))
         nm, pos, ref_len = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         xo, ro = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
         xc, rb = np.zeros(max(n_x.value, 1), np.uint32), np.zeros(max(n_r.value, 1), np.uint8)
@@ -182,6 +193,32 @@ class Verifier:
         """Of the last annotate: kernel ms (count pass, prefix sums, write pass) and the alignment columns walked."""
         ms, cols = C.c_float(), C.c_uint64()
         _check(lib().bmv_last_annotate_stats(self._h, C.byref(ms), C.byref(cols)))
+        return {"ms_kernels": ms.value, "columns": cols.value}
+
+    def clip(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, match=1,
+             penalty=2) -> dict:
+        """bmv_clip on the alignments annotate takes: of each, the contiguous range of columns that scores best under
+        +match per = column and -penalty per X, I or D column is kept and the rest of the query soft-clipped (include/bmv.h).
+        Returns a dict of annotate's seven arrays by name -- nm, pos, ref_len, xcigar_offset, xcigar (with S entries),
+        ref_offset, ref_bases, all of the kept part -- plus score i64[n], clip_left u32[n] and clip_right u32[n].  Leaves the
+        results of the last align* and of the last annotate untouched."""
+        _keep, n, args = self._annotate_args(reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset,
+                                             cigar)
+        n_x, n_r = C.c_uint64(), C.c_uint64()
+        _check(lib().bmv_clip(self._h, *args, int(match), int(penalty), C.byref(n_x), C.byref(n_r)))
+        score = np.zeros(n, np.int64)
+        left, right, nm, pos, ref_len = (np.zeros(n, np.uint32) for _ in range(5))
+        xo, ro = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        xc, rb = np.zeros(max(n_x.value, 1), np.uint32), np.zeros(max(n_r.value, 1), np.uint8)
+        _check(lib().bmv_clipped(self._h, _p(score, _i64p), _p(left, _u32p), _p(right, _u32p), _p(nm, _u32p), _p(pos, _u32p),
+                                 _p(ref_len, _u32p), _p(xo, _u64p), _p(xc, _u32p), _p(ro, _u64p), _p(rb, _u8p)))
+        return {"score": score, "clip_left": left, "clip_right": right, "nm": nm, "pos": pos, "ref_len": ref_len,
+                "xcigar_offset": xo, "xcigar": xc[: n_x.value], "ref_offset": ro, "ref_bases": rb[: n_r.value]}
+
+    def clip_stats(self) -> dict:
+        """Of the last clip: kernel ms (range pass, count pass, prefix sums, write pass) and the alignment columns walked."""
+        ms, cols = C.c_float(), C.c_uint64()
+        _check(lib().bmv_last_clip_stats(self._h, C.byref(ms), C.byref(cols)))
         return {"ms_kernels": ms.value, "columns": cols.value}
 
     def stats(self) -> dict:

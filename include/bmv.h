@@ -43,7 +43,8 @@ extern "C" {
 enum { BMV_OK = 0, BMV_ERR_ARG = 1, BMV_ERR_HIP = 2, BMV_ERR_STATE = 3, BMV_ERR_UNSUPPORTED = 5 };
 
 /* CIGAR entries are packed as in BAM: length << 4 | op. */
-enum { BMV_OP_M = 0, BMV_OP_I = 1, BMV_OP_D = 2, BMV_OP_EQ = 7, BMV_OP_X = 8 };   /* = and X: bmv_annotate's output only */
+enum { BMV_OP_M = 0, BMV_OP_I = 1, BMV_OP_D = 2, BMV_OP_S = 4, BMV_OP_EQ = 7, BMV_OP_X = 8 };
+/* = and X: the output of bmv_annotate and bmv_clip only; S (a soft clip): bmv_clip's output only */
 
 typedef struct bmv_params {
     uint32_t max_query_len;   /* longest read handed to bmv_align (<= 65536)                        */
@@ -148,6 +149,46 @@ int  bmv_annotations(bmv_ctx *ctx, uint32_t *out_nm, uint32_t *out_pos, uint32_t
 /* Kernel time of the last bmv_annotate in ms (count pass, prefix sums, write pass) and the alignment columns it walked (sum of
  * all CIGAR entry lengths). */
 int  bmv_last_annotate_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_columns);
+
+/* The clipping pass: bmv_annotate's record with low-identity ends soft-clipped.  The aligners align the WHOLE query (unit
+ * costs: free end gaps in the query would make clipping everything optimal), so a read that overhangs its window, carries an
+ * adapter or has a chimeric or low-quality end gets those bases spread over X, I and D columns at an end of its alignment.  This
+ * post-pass over the edit path keeps the best-scoring contiguous stretch of alignment columns and reports the rest as S.
+ * A call of its own, the sibling of bmv_annotate: the same inputs (CIGARs M/I/D from any of the three align calls or written by
+ * hand), the same checks on the host before anything is launched (BMV_ERR_ARG, the message names the alignment, nothing ran, the
+ * context stays usable), plus 1 <= match, penalty <= 1024 (else BMV_ERR_ARG).  It leaves untouched what bmv_results,
+ * bmv_annotations, bmv_last_stats, bmv_last_bounded_stats and bmv_last_annotate_stats return.
+ * Semantics.  Take alignment a's columns in FORWARD-strand order, the order bmv_annotate emits its entries in: 0 .. C-1.  Column
+ * i weighs w(i) = +match when it is an = column, -penalty when it is an X, I or D column (equality on dna4 ranks, as in
+ * bmv_annotate).  P[0] = 0, P[i+1] = P[i] + w(i), in signed 64-bit arithmetic.  The kept range [l, r) maximises P[r] - P[l] over
+ * 0 <= l <= r <= C; among the maximisers it has the smallest r, then the largest l.  So a non-empty range begins and ends on an
+ * = column, and an alignment without any = column keeps the empty range l = r = 0.  Output per alignment:
+ *   out_score[a]        P[r] - P[l]
+ *   out_clip_left[a]    the query-consuming columns (=, X, I) before l;  out_clip_right[a]: those from r on
+ *   out_pos[a]          bmv_annotate's pos plus the reference-consuming columns (=, X, D) before l
+ *   out_ref_len[a]      the reference-consuming columns inside [l, r)
+ *   out_nm[a]           the X, I and D columns inside [l, r)
+ *   out_xcigar          an S entry (BMV_OP_S) of clip_left when that is > 0; bmv_annotate's = / X / I / D entries restricted to
+ *                       [l, r), an entry the range cuts through shortened; an S entry of clip_right when that is > 0.  Adjacent
+ *                       entries never share an op.  out_xcigar_offset: n + 1 entries
+ *   out_ref_bases       the forward-strand reference letter under the kept X and D columns.  out_ref_offset: n + 1 entries
+ * Always: clip_left + the kept =, X and I lengths + clip_right = query_len, and pos + ref_len <= text_len.
+ * An empty range with query_len > 0 gives one S entry of query_len (clip_left 0, clip_right query_len) and pos = ref_len = nm =
+ * score = 0.  An empty CIGAR gives no entries and zeros everywhere, as in bmv_annotate.
+ * How: a wave per alignment and bmv_annotate's walk, three times (bmv_clip.hip.h): the range pass finds [l, r) with a prefix
+ * minimum and a maximum across the wave per 64 columns, then sizes are counted, two prefix sums place the packed outputs, and a
+ * last walk writes them.  No scratch beyond the inputs and outputs. */
+int  bmv_clip(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+              const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+              const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t penalty,
+              uint64_t *total_xcigar, uint64_t *total_ref_bases);
+/* Results of the last bmv_clip; any pointer may be NULL. */
+int  bmv_clipped(bmv_ctx *ctx, int64_t *out_score, uint32_t *out_clip_left, uint32_t *out_clip_right, uint32_t *out_nm,
+                 uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset, uint32_t *out_xcigar,
+                 uint64_t *out_ref_offset, uint8_t *out_ref_bases);
+/* Kernel time of the last bmv_clip in ms (range pass, count pass, prefix sums, write pass) and the alignment columns it walked
+ * (sum of all CIGAR entry lengths). */
+int  bmv_last_clip_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_columns);
 
 #ifdef __cplusplus
 }

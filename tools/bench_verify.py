@@ -5,6 +5,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py [--reads 1000000] [--len 300] [--indel-rate 0.02] [--cpu-sample 2000]
     python tools/bench_verify.py --long [--long-reads 1000] [--long-len 100000]
     python tools/bench_verify.py --annotate [--reads 20000 --len 10000 --indel-rate 0.1]
+    python tools/bench_verify.py --clip [--reads 20000 --len 10000 --indel-rate 0.1]
 
 Prints one JSON line: alignments/s and cell updates/s of the device kernels (HIP events inside bmv_align),
 the wall time of the call (host buffers in, results out), and the CPU restatement (oracle, full DP matrix,
@@ -98,6 +99,10 @@ def main():
     ap.add_argument("--annotate", action="store_true",
                     help="also run Verifier.annotate on the batch's results: kernels ms of every repeat, bytes read (text + query, "
                          "each once), bytes / time, and the ratio to align's kernels ms on the same batch")
+    ap.add_argument("--clip", action="store_true",
+                    help="also run Verifier.clip (match 1, penalty 2) and Verifier.annotate on the batch's results: the clipping "
+                         "pass's kernels ms of every repeat, the columns walked, and the ratios to annotate's and to align's "
+                         "kernels ms on the same batch")
     ap.add_argument("--decoys", type=float, default=0.0, metavar="F",
                     help="this share of the alignments takes its text window from an unrelated place (a wrong locus)")
     ap.add_argument("--long", action="store_true", help="Verifier.align_long on reads beyond 65 536 bases (see above)")
@@ -189,6 +194,24 @@ def main():
                     "annotate_over_align": min(a_ms) / min(all_ms), "xcigar_entries": int(len(xc)), "ref_bases": int(len(rb)),
                     "checks": {"nm_is_minus_score": bool(np.array_equal(nm.astype(np.int64), -score.astype(np.int64)))}}
 
+    clip = None
+    if args.clip:
+        c_ms, c_wall, a_ms = [], [], []
+        for _ in range(args.repeat):
+            v.annotate(reads, start, tl, rc, qs, ql, begin, off, cg)
+            a_ms.append(v.annotate_stats()["ms_kernels"])
+            t0 = time.perf_counter()
+            got = v.clip(reads, start, tl, rc, qs, ql, begin, off, cg)
+            c_wall.append(time.perf_counter() - t0)
+            c_ms.append(v.clip_stats()["ms_kernels"])
+        by_op = lambda ops: int((got["xcigar"] >> 4)[np.isin(got["xcigar"] & 15, ops)].sum())     # entry lengths of these ops
+        clip = {"ms_kernels_clip": c_ms, "ms_kernels_annotate": a_ms, "ms_kernels_align": all_ms, "wall_s_clip": c_wall,
+                "columns": v.clip_stats()["columns"], "spread": (max(c_ms) - min(c_ms)) / min(c_ms),
+                "clip_over_annotate": min(c_ms) / min(a_ms), "clip_over_align": min(c_ms) / min(all_ms),
+                "xcigar_entries": int(len(got["xcigar"])), "clipped_bases": int(got["clip_left"].sum() + got["clip_right"].sum()),
+                "checks": {"queries_are_covered": bool(by_op([4, 7, 8, 1]) == int(ql[np.diff(off.astype(np.int64)) > 0].sum())),
+                           "scores_add_up": bool(int(got["score"].sum()) == by_op([7]) - 2 * int(got["nm"].sum()))}}
+
     ns = min(args.cpu_sample, args.reads)
     same, cpu = None, None
     if ns > 0:                                         # (--cpu-sample 0: no oracle in the process at all -- bench.py's leg)
@@ -207,6 +230,7 @@ def main():
         "cpu_baseline": cpu,
         "bounded": bounded,
         "annotate": annotate,
+        "clip": clip,
         "checks": {"sample_identical_to_oracle": same},
     }))
 
