@@ -147,6 +147,12 @@ struct bmf_ctx {
     int32_t *d_k2i = nullptr;
     uint32_t *d_zeros = nullptr;
     uint32_t *d_qgram_ok = nullptr;  // bitmap over 4^q q-grams
+    // Pair table of the plain vote (bmf_pair_rows_kernel), built at index load when build_pair_table's conditions hold:
+    // (4^(q+1) + 1) x pitch, the last row all ones.  The lists then hold ceil(G/2) of its row ids per sample
+    // (dp.pair, dp.E) and the vote kernel streams it instead of d_rows: half the row bytes, the same outputs.
+    uint8_t *d_pair = nullptr;
+    uint64_t pair_rows = 0;          // rows of d_pair, the all-ones row included
+    uint32_t list_cap = 0;           // ids per (window, orientation) a batch's list buffer is sized for: the G-rows form
     // constants
     uint8_t *d_lut = nullptr;
     uint16_t *d_pos_table = nullptr;
@@ -209,6 +215,8 @@ struct bmf_ctx {
 };
 
 extern "C" {
+
+static void set_entries_per_sample(bmf_ctx *c, uint32_t E, bool pair);
 
 int bmf_abi_version(void) { return BMF_ABI_VERSION; }
 const char *bmf_last_error(void) { return g_err; }
@@ -310,8 +318,8 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
     d.max_cand = p.max_candidates;
     d.read_len = p.read_len;
     d.max_kmers = p.read_len - p.k + 1;
-    // S*G row ids, rounded up to the ring depth, plus one ring of padding (all-ones rows)
-    d.list_len = (d.S * d.G + (uint32_t)c->depth - 1u) / (uint32_t)c->depth * (uint32_t)c->depth + (uint32_t)c->depth;
+    set_entries_per_sample(c, d.G, false);
+    c->list_cap = d.list_len;
     d.n_chunks = n_chunks;
     d.pitch = (row_bytes + 127u) & ~127u;
     d.ones_row = 0;
@@ -408,7 +416,25 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
     return BMF_OK;
 }
 
+// E list entries per sample: G rows of the index, or (pair) ceil(G/2) rows of the pair table.  list_len = S*E ids,
+// rounded up to the ring depth, plus one ring of padding (all-ones rows); never more than the G-rows form's.
+static void set_entries_per_sample(bmf_ctx *c, uint32_t E, bool pair) {
+    bmf::DevParams &d = c->dp;
+    const uint32_t depth = (uint32_t)c->depth;
+    d.E = E;
+    d.pair = pair ? 1u : 0u;
+    d.list_len = (d.S * E + depth - 1u) / depth * depth + depth;
+}
+
+static void free_pair_table(bmf_ctx *c) {
+    (void)hipFree(c->d_pair);
+    c->d_pair = nullptr;
+    c->pair_rows = 0;
+    set_entries_per_sample(c, c->dp.G, false);
+}
+
 static void free_index(bmf_ctx *c) {
+    free_pair_table(c);
     (void)hipFree(c->d_rows);
     (void)hipFree(c->d_k2i);
     (void)hipFree(c->d_zeros);
@@ -603,6 +629,50 @@ static int select_pruned_variant(bmf_ctx *c) {
     return BMF_OK;
 }
 
+// The pair table for the index just loaded (the contexts without BMF_FLAG_EARLY_EXIT: the pruning kernels read the
+// index itself).  Decided once per load, here, so that no batch pays for it: BMF_FLAG_PLAIN_ROWS or BMF_DERIVED=0
+// keep the index rows; so do short rows (below), a table larger than BMF_DERIVED_MAX_MB MiB (default 24 576) or than half of the
+// device's free memory, and a failed allocation -- the card is shared, and the plain path gives the same outputs.
+static int build_pair_table(bmf_ctx *c) {
+    free_pair_table(c);
+    const bmf::DevParams &d = c->dp;
+    if ((c->p.flags & (BMF_FLAG_EARLY_EXIT | BMF_FLAG_PLAIN_ROWS)) || d.G < 2 || c->p.q > 14) return BMF_OK;
+    const char *env_derived = getenv("BMF_DERIVED");
+    if (env_derived && !strcmp(env_derived, "0")) return BMF_OK;
+    // The table trades memory for HBM bytes.  On short rows (NB <= 2 048: at most 16 chunks, the threshold below which
+    // select_pruned_variant keeps the plain kernel too) the vote is bound by latency, not by bytes, and the whole index
+    // sits in the caches: four times the index in HBM would buy nothing there, so such an index keeps its rows.
+    // BMF_DERIVED=1 builds the table all the same (tests, experiments).
+    if (d.n_chunks <= 16u && !(env_derived && !strcmp(env_derived, "1"))) return BMF_OK;
+    uint64_t max_mb = 24576;
+    if (const char *env = getenv("BMF_DERIVED_MAX_MB")) max_mb = strtoull(env, nullptr, 10);
+    const uint64_t n_high = 1ull << (2 * c->p.q), n_pair = 4 * n_high;
+    if (n_pair + 1 >= 0x7FFFFFFFull || (n_pair + 1) > (max_mb << 20) / d.pitch) return BMF_OK;
+    const size_t bytes = (size_t)(n_pair + 1) * d.pitch;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 2) {
+        (void)hipGetLastError();
+        return BMF_OK;
+    }
+    if (hipMalloc(reinterpret_cast<void **>(&c->d_pair), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_pair = nullptr;
+        return BMF_OK;
+    }
+    hipLaunchKernelGGL(bmf::bmf_pair_rows_kernel, dim3((unsigned)std::min<uint64_t>(n_high, 1u << 20)), dim3(bmf::kWave), 0, c->stream,
+                       c->d_rows, c->d_k2i, d.n_kmers, (uint32_t)n_high, d.qbits, d.pitch, d.nb, c->d_pair);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_pair + (size_t)n_pair * d.pitch, 0xFF, d.pitch, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        free_pair_table(c);
+        return fail(BMF_ERR_HIP, "building the pair table failed: %s", hipGetErrorString(e));
+    }
+    c->pair_rows = n_pair + 1;
+    set_entries_per_sample(c, (d.G + 1u) / 2u, true);
+    return BMF_OK;
+}
+
 static void release_batch(bmf_batch *b) {
     b->bases.release(); b->quals.release(); b->scan_tmp.release(); b->win_start.release(); b->win_len.release();
     b->lists.release(); b->list_n.release(); b->rows_anded.release(); b->counts.release(); b->buckets.release();
@@ -720,7 +790,8 @@ static int upload_finish(bmf_ctx *c) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->loaded = true;
-    return select_pruned_variant(c);
+    const int rc = select_pruned_variant(c);
+    return rc != BMF_OK ? rc : build_pair_table(c);
 }
 
 int bmf_load_index(bmf_ctx *c, const uint8_t *rows, uint64_t n_rows, const int32_t *kmer_to_index,
@@ -841,7 +912,8 @@ int bmf_build_index(bmf_ctx *c, const uint8_t *genome, uint64_t n_bases, const u
         return fail(BMF_ERR_HIP, "bmf_build_index: %s", hipGetErrorString(e));
     }
     c->loaded = true;
-    return select_pruned_variant(c);
+    const int rc = select_pruned_variant(c);
+    return rc != BMF_OK ? rc : build_pair_table(c);
 }
 
 int bmf_index_download(bmf_ctx *c, uint8_t *rows_out, uint64_t *n_rows_out) {
@@ -996,7 +1068,7 @@ static hipError_t batch_reserve(bmf_ctx *c, bmf_batch *b, size_t n, size_t n_byt
     }
     ok(b->win_start.need(n));
     ok(b->win_len.need(n));
-    ok(b->lists.need(2 * n * c->dp.list_len));
+    ok(b->lists.need(2 * n * c->list_cap));   // (the G-rows form: a reload may change the form under a live batch)
     ok(b->list_n.need(n));
     ok(b->rows_anded.need(n));
     ok(b->counts.need(2 * n));
@@ -1153,11 +1225,11 @@ static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
             c->guard_pending = true;
         }
     } else if (c->n_slices == 1) {
-        hipLaunchKernelGGL(c->vote, dim3(2 * n_windows), dim3(bmf::kWave), 0, c->stream, c->dp, c->d_rows, b->lists.p,
-                           b->list_n.p, b->counts.p, b->buckets.p, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(c->vote, dim3(2 * n_windows), dim3(bmf::kWave), 0, c->stream, c->dp, c->dp.pair ? c->d_pair : c->d_rows,
+                           b->lists.p, b->list_n.p, b->counts.p, b->buckets.p, (uint32_t *)nullptr);
     } else {
-        hipLaunchKernelGGL(c->vote, dim3(2 * n_windows, c->n_slices), dim3(bmf::kWave), 0, c->stream, c->dp, c->d_rows,
-                           b->lists.p, b->list_n.p, b->slice_cnt.p, b->slice_ids.p, b->slice_min.p);
+        hipLaunchKernelGGL(c->vote, dim3(2 * n_windows, c->n_slices), dim3(bmf::kWave), 0, c->stream, c->dp,
+                           c->dp.pair ? c->d_pair : c->d_rows, b->lists.p, b->list_n.p, b->slice_cnt.p, b->slice_ids.p, b->slice_min.p);
         hipLaunchKernelGGL(bmf::bmf_merge_slices_kernel, dim3((2 * n_windows + 255) / 256), dim3(256), 0, c->stream, c->dp,
                            2 * n_windows, c->n_slices, b->slice_min.p, b->slice_cnt.p, b->slice_ids.p, b->counts.p,
                            b->buckets.p);
@@ -1776,6 +1848,25 @@ int bmf_info(bmf_ctx *c, uint32_t *row_pitch_bytes, uint32_t *chunks_per_lane, u
     if (chunks_per_lane) *chunks_per_lane = (uint32_t)c->cpl;
     if (planes) *planes = (uint32_t)c->planes;
     if (rows_in_flight) *rows_in_flight = (uint32_t)c->depth;
+    return BMF_OK;
+}
+
+int bmf_derived_info(bmf_ctx *c, uint32_t *span, uint64_t *n_rows, uint64_t *bytes) {
+    if (!c) return fail(BMF_ERR_ARG, "bmf_derived_info: null context");
+    if (span) *span = c->dp.pair ? 2u : 1u;
+    if (n_rows) *n_rows = c->pair_rows;
+    if (bytes) *bytes = c->pair_rows * c->dp.pitch;
+    return BMF_OK;
+}
+
+int bmf_derived_row(bmf_ctx *c, uint64_t gram, uint8_t *out_row_bytes) {
+    if (!c || !out_row_bytes) return fail(BMF_ERR_ARG, "bmf_derived_row: null argument");
+    if (!c->loaded || !c->d_pair) return fail(BMF_ERR_STATE, "no pair table: the context reads the index rows");
+    if (gram >= c->pair_rows) return fail(BMF_ERR_ARG, "row %llu is outside the pair table (%llu rows)", (unsigned long long)gram,
+                                          (unsigned long long)c->pair_rows);
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out_row_bytes, c->d_pair + (size_t)gram * c->dp.pitch, (c->p.num_buckets + 7u) >> 3, hipMemcpyDeviceToHost));
     return BMF_OK;
 }
 

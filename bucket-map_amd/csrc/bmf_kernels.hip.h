@@ -4,8 +4,9 @@
 //   bmf_sample_kernel : one wave per window (persistent workgroups).  k-mer hashes, quality window sums, distinguishability +
 //                       quality filter, ordered compaction, deterministic sampling, q-gram -> row-id
 //                       lists for both orientations (reference: q_gram_mapper.h:431-469).
-//   bmf_vote_kernel   : one wave per (window, orientation).  Streams the S*G index rows of the list
-//                       through a DEPTH-deep register ring of 16-byte-per-lane loads, ANDs the G rows
+//   bmf_vote_kernel   : one wave per (window, orientation).  Streams the S*E rows of the list (E = G index rows
+//                       per sample, or ceil(G/2) rows of the pair table, bmf_pair_rows_kernel)
+//                       through a DEPTH-deep register ring of 16-byte-per-lane loads, ANDs the E rows
 //                       of each sample, keeps the per-bucket miss count bit-sliced in VGPRs, then
 //                       finds the minimum and emits the ascending bucket ids
 //                       (reference: q_gram_mapper.h:380-412 + fault_tolerate_filter :59-102).
@@ -36,7 +37,7 @@ struct DevParams {
     uint32_t max_cand;
     uint32_t read_len;
     uint32_t max_kmers;  // read_len - k + 1
-    uint32_t list_len;   // row ids per (window, orientation): S*G rounded up to the ring depth, + depth (padding)
+    uint32_t list_len;   // row ids per (window, orientation): S*E rounded up to the ring depth, + depth (padding)
     uint32_t n_chunks;   // ceil(ceil(NB/8)/16) : 16-byte chunks per row that hold buckets
     uint32_t pitch;      // bytes between rows in HBM (multiple of 128)
     uint32_t ones_row;   // id of the all-ones row appended after the index (for un-indexed q-grams)
@@ -46,6 +47,8 @@ struct DevParams {
     uint32_t max_live;   // two-pass variant: live chunks (= lanes) an item may bring to the recount kernel (16 or 32)
     uint32_t item_base;  // two-pass variant: first (window, orientation) item of this launch (the batch goes out in slices)
     uint32_t row_order;  // entry i of a sample's G row ids is the row of q-gram (row_order >> 4i) & 15: a permutation of 0..G-1
+    uint32_t E;          // list entries per sample: G row ids, or ceil(G/2) pair-row ids when `pair` is set
+    uint32_t pair;       // the lists hold rows of the pair table (bmf_pair_rows_kernel): ids of (q+1)-grams; its all-ones row is 4^(q+1)
 };
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
@@ -179,6 +182,38 @@ __global__ void bmf_qgram_ok_kernel(const int32_t *k2i, uint64_t n_kmers, const 
         }
     }
     bitmap[w] = bits;
+}
+
+// Pair table of the plain vote: row x, x a (q+1)-gram, is R(x & qbits) & R(x >> 2) -- the AND of the rows of the two
+// q-grams x contains, R(g) being g's index row or, for a q-gram that is not indexed, all ones (the sample kernel's
+// rule).  A sample's G rows are then the AND of ceil(G/2) rows of this table: half the row bytes per read.  Bits
+// >= NB stay 0 as in the index itself.  One wave per value of x >> 2: it writes the four rows that share that q-gram,
+// 16 bytes per lane, 1 KiB contiguous per wave and load.  n_high = 4^q; `pitch` is a multiple of 128.
+__global__ __launch_bounds__(kWave) void bmf_pair_rows_kernel(const uint8_t *__restrict__ rows, const int32_t *__restrict__ k2i,
+                                                             uint32_t n_kmers, uint32_t n_high, uint32_t qbits, uint32_t pitch,
+                                                             uint32_t nb, uint8_t *__restrict__ pair) {
+    const uint32_t lane = threadIdx.x, n_chunks = pitch >> 4;
+    for (uint32_t hi = blockIdx.x; hi < n_high; hi += gridDim.x) {
+        const int32_t ih = hi < n_kmers ? k2i[hi] : -1;
+        // the four q-grams x & qbits of x = 4 hi .. 4 hi + 3 are neighbours in k2i (n_kmers is 4^q, or 0: nothing indexed)
+        const uint32_t lo0 = (hi * 4u) & qbits;
+        const int4 il = lo0 + 3u < n_kmers ? *reinterpret_cast<const int4 *>(k2i + lo0) : make_int4(-1, -1, -1, -1);
+        for (uint32_t c = lane; c < n_chunks; c += kWave) {
+            const uint32_t b0 = c * 128u;
+            auto word = [&](uint32_t b) { return b >= nb ? 0u : (nb - b >= 32u ? 0xFFFFFFFFu : (1u << (nb - b)) - 1u); };
+            const uint4 ones = make_uint4(word(b0), word(b0 + 32u), word(b0 + 64u), word(b0 + 96u));   // all ones, cut at NB
+            auto row = [&](int32_t i) { return i >= 0 ? *reinterpret_cast<const uint4 *>(rows + (size_t)i * pitch + 16u * c) : ones; };
+            const uint4 h = row(ih);
+            auto put = [&](uint32_t d, int32_t i) {
+                const uint4 l = row(i);
+                *reinterpret_cast<uint4 *>(pair + ((size_t)hi * 4u + d) * pitch + 16u * c) = make_uint4(h.x & l.x, h.y & l.y, h.z & l.z, h.w & l.w);
+            };
+            put(0, il.x);
+            put(1, il.y);
+            put(2, il.z);
+            put(3, il.w);
+        }
+    }
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -369,19 +404,31 @@ __global__ __launch_bounds__(1024, 8) void bmf_sample_kernel(   // 8 waves per S
                 const uint32_t g1 = (h >> (2 * gi)) & P.qbits, g2 = (hr >> (2 * gi)) & P.qbits;
                 const int32_t i1 = g1 < P.n_kmers ? k2i[g1] : -1;   // index_of_kmer, q_gram_mapper.h:374-377
                 const int32_t i2 = g2 < P.n_kmers ? k2i[g2] : -1;
-                list_fwd[s * P.G + g] = i1 >= 0 ? (uint32_t)i1 : P.ones_row;
-                list_rc[s * P.G + g] = i2 >= 0 ? (uint32_t)i2 : P.ones_row;
-                cnt += (i1 >= 0) + (i2 >= 0);
+                if (!P.pair) {
+                    list_fwd[s * P.G + g] = i1 >= 0 ? (uint32_t)i1 : P.ones_row;
+                    list_rc[s * P.G + g] = i2 >= 0 ? (uint32_t)i2 : P.ones_row;
+                }
+                cnt += (i1 >= 0) + (i2 >= 0);   // the rows the reference ANDs, whatever table the vote reads
+            }
+            if (P.pair) {
+                // pair table: entry t is the (q+1)-gram that holds q-grams g and g + 1, g = min(2t, G - 2) -- for an odd
+                // G the last pair overlaps the one before it, and AND is idempotent
+                for (uint32_t t = 0; t < P.E; t++) {
+                    const uint32_t g = min(2u * t, P.G - 2u);
+                    list_fwd[s * P.E + t] = (h >> (2u * g)) & (4u * P.qbits + 3u);
+                    list_rc[s * P.E + t] = (hr >> (2u * g)) & (4u * P.qbits + 3u);
+                }
             }
         }
         // pad both lists with the all-ones row (see bmf_vote_kernel)
-        for (uint32_t t = P.S * P.G + lane; t < P.list_len; t += kWave) {
-            list_fwd[t] = P.ones_row;
-            list_rc[t] = P.ones_row;
+        const uint32_t pad_row = P.pair ? 4u * P.qbits + 4u : P.ones_row;
+        for (uint32_t t = P.S * P.E + lane; t < P.list_len; t += kWave) {
+            list_fwd[t] = pad_row;
+            list_rc[t] = pad_row;
         }
         cnt = wave_sum(cnt);
         if (lane == 0) {
-            list_n[w] = P.S * P.G;
+            list_n[w] = P.S * P.E;
             rows_anded[w] = cnt;
         }
     }
@@ -640,7 +687,7 @@ __global__ __launch_bounds__(kWave) void bmf_vote_kernel(DevParams P, const uint
 #pragma unroll
             for (int j = 0; j < CPL; j++)
                 if (!PRUNE || act[j]) ring[d][j] = load_chunk(rp + coff[j]);
-            if (++g == P.G) {
+            if (++g == P.E) {
                 g = 0;
                 count_misses<CPL, PLANES>(bf, cnt);
                 ++samples_done;

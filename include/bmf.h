@@ -69,6 +69,15 @@ typedef struct bmf_params {
  * are identical; only the number of row bytes actually read (not the algorithmic row count) drops. */
 #define BMF_FLAG_EARLY_EXIT 1u
 
+/* Keep the plain vote on the index rows themselves.  Without this flag (and without BMF_FLAG_EARLY_EXIT) a context
+ * tabulates, when an index is loaded, the AND of the rows of every two overlapping q-grams -- one row per (q+1)-gram,
+ * 4^(q+1) rows of the index's pitch beside the index -- and the vote kernel then reads ceil((k-q+1)/2) rows per
+ * sample instead of k-q+1: the same outputs from half the row bytes.  The table is skipped (and the index rows are
+ * read as with this flag) when k == q, when BMF_DERIVED=0 is set, when the rows are short (NB <= 2 048: the vote is
+ * bound by latency there, not by bytes; BMF_DERIVED=1 builds the table all the same), when it would exceed BMF_DERIVED_MAX_MB MiB
+ * (default 24 576) or half of the device's free memory, or when its allocation fails. */
+#define BMF_FLAG_PLAIN_ROWS 2u
+
 typedef struct bmf_ctx bmf_ctx;
 typedef struct bmf_batch bmf_batch;
 
@@ -183,6 +192,13 @@ int  bmf_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
 /* Introspection for DESIGN.md / bench: bytes per padded row in HBM, kernel variant chosen. */
 int  bmf_info(bmf_ctx *ctx, uint32_t *row_pitch_bytes, uint32_t *chunks_per_lane, uint32_t *planes,
               uint32_t *rows_in_flight);
+/* The pair table of the plain vote (BMF_FLAG_PLAIN_ROWS): span = q-gram rows one list entry stands for -- 2 with the
+ * table, 1 without --, n_rows = rows of the table (4^(q+1) and one all-ones row; 0 without), bytes = its size in HBM. */
+int  bmf_derived_info(bmf_ctx *ctx, uint32_t *span, uint64_t *n_rows, uint64_t *bytes);
+/* Copies row `gram` of the pair table -- the AND of the rows of q-grams gram & (4^q - 1) and gram >> 2, an all-ones
+ * row standing for a q-gram that is not indexed -- to out_row_bytes, ceil(NB/8) bytes in the .qgram layout.
+ * BMF_ERR_STATE when the context has no table. */
+int  bmf_derived_row(bmf_ctx *ctx, uint64_t gram, uint8_t *out_row_bytes);
 /* BMF_FLAG_EARLY_EXIT only: index rows per sample the first pass of the two-pass pruning kernel streams
  * for the loaded index; 0 = the single-pass pruning kernel (or no pruning) serves it. */
 int  bmf_pass1_rows(bmf_ctx *ctx, uint32_t *out);
