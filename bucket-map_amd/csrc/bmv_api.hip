@@ -3,6 +3,7 @@
 // that the traceback bits of one chunk fit the scratch budget, offsets of the packed CIGAR output
 // (bm_scan.hip.h's exclusive sum).
 #include "bmv_annotate.hip.h"
+#include "bmv_best.hip.h"
 #include "bmv_clip.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_screen.hip.h"
@@ -54,6 +55,19 @@ extern template __global__ void bmv_annotate_kernel<true>(AnnotateJob);
 extern template __global__ void bmv_clip_range_kernel<kAnnotateWaves>(ClipJob);
 extern template __global__ void bmv_clip_emit_kernel<false>(ClipJob);
 extern template __global__ void bmv_clip_emit_kernel<true>(ClipJob);
+
+// (bmv_best.hip)
+extern template __global__ void bmv_best_lane_kernel<1>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<2>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<3>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<4>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<5>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<6>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<7>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<8>(BestJob);
+extern template __global__ void bmv_best_wave_kernel<1>(BestJob);
+extern template __global__ void bmv_best_wave_kernel<2>(BestJob);
+extern template __global__ void bmv_best_wave_kernel<4>(BestJob);
 
 // CIGAR entries of one chunk, reversed into reading order at their final offsets.
 __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t ops_stride,
@@ -222,6 +236,16 @@ struct bmv_ctx {
     std::vector<uint8_t> h_cl_ref_bases;
     float ms_clip = 0.f;
     uint64_t n_clip_columns = 0;
+    // bmv_align_best: the distance round's and the pick's buffers (the batch's views go through the aligners' own), the
+    // host results of bmv_best and what bmv_last_best_stats reports
+    DevBuf<uint32_t> bs_bound, bs_list, bs_d, bs_end, bs_full, bs_group_offset, bs_margin, bs_winner, bs_need, bs_need_at,
+        bs_realign, bs_edits, bs_out_end;
+    DevBuf<unsigned long long> bs_count;
+    uint32_t n_best = 0, n_best_groups = 0;
+    std::vector<uint32_t> h_bs_winner, h_bs_edits, h_bs_end;
+    uint32_t bs_n_seed = 0, bs_n_distance = 0, bs_n_beyond = 0, bs_n_undecided = 0, bs_n_realigned = 0;
+    uint64_t bs_cells = 0;
+    float ms_distance = 0.f, ms_pick = 0.f;
 };
 
 // bmv_load_genome(_records) after their argument checks: the genome is the n_records records back to back (n_bases in all)
@@ -298,6 +322,9 @@ void bmv_destroy(bmv_ctx *c) {
     c->long_slots.release(); c->long_tiles.release();
     c->max_edits.release(); c->keep.release(); c->keep_at.release(); c->survivors.release(); c->screen_list.release();
     c->screen_count.release();
+    c->bs_bound.release(); c->bs_list.release(); c->bs_d.release(); c->bs_end.release(); c->bs_full.release();
+    c->bs_group_offset.release(); c->bs_margin.release(); c->bs_winner.release(); c->bs_need.release(); c->bs_need_at.release();
+    c->bs_realign.release(); c->bs_edits.release(); c->bs_out_end.release(); c->bs_count.release();
     c->an_begin.release(); c->an_cigar.release(); c->an_nm.release(); c->an_pos.release(); c->an_ref_len.release();
     c->an_n_xcigar.release(); c->an_n_ref.release(); c->an_xcigar.release(); c->an_cigar_offset.release();
     c->an_xcigar_offset.release(); c->an_ref_offset.release(); c->an_ref_bases.release();
@@ -1089,6 +1116,350 @@ int bmv_last_bounded_stats(bmv_ctx *c, uint32_t *n_rejected, uint64_t *screen_ce
     if (n_rejected) *n_rejected = c->n_rejected;
     if (screen_cells) *screen_cells = c->screen_cells;
     if (ms_screen) *ms_screen = c->ms_screen;
+    return BMV_OK;
+}
+
+// The best alignment of each group (include/bmv.h, bmv_best.hip.h).  Four rounds: the seeds -- one alignment per group, the
+// hinted one -- in full by bmv_align_long; every other alignment through the distance kernels under k = seed's edits +
+// margin, and what they leave undecided in full as well; the pick on the device; the winners that have no full alignment
+// yet in full.  Every full alignment is bmv_align_long's on a batch of its own, so what the winners carry is what that call
+// gives them.
+static int best_sub_batch(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                          const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                          const std::vector<uint32_t> &which, std::vector<int32_t> &score, std::vector<uint32_t> &begin,
+                          std::vector<uint32_t> &r_len, std::vector<std::vector<uint32_t>> &cigar, float *ms) {
+    const size_t ns = which.size();
+    if (ns == 0) return BMV_OK;
+    std::vector<uint64_t> ts(ns), qs(ns);
+    std::vector<uint32_t> tl(ns), ql(ns);
+    std::vector<uint8_t> trc(ns);
+    for (size_t s = 0; s < ns; s++) {
+        const uint32_t a = which[s];
+        ts[s] = text_start[a];
+        tl[s] = text_len[a];
+        trc[s] = text_rc[a];
+        qs[s] = query_start[a];
+        ql[s] = query_len[a];
+    }
+    uint64_t tot = 0;
+    if (int rc = bmv_align_long(c, reads, n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), (uint32_t)ns, &tot)) return rc;
+    for (size_t s = 0; s < ns; s++) {
+        const uint32_t a = which[s];
+        score[a] = c->h_score[s];
+        begin[a] = c->h_begin[s];
+        cigar[a].assign(c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s], c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s + 1]);
+        uint32_t r = 0;                                         // text columns the alignment spans: its M and D lengths
+        for (uint32_t e : cigar[a])
+            if ((e & 15u) != BMV_OP_I) r += e >> 4;
+        r_len[a] = r;
+    }
+    *ms += c->ms_kernels;
+    return BMV_OK;
+}
+
+int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                   const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
+                   const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                   uint64_t *total_cigar) {
+    if (!c || !total_cigar || !group_offset) return fail(BMV_ERR_ARG, "bmv_align_best: null argument");
+    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_align_best before bmv_load_genome");
+    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || (n_read_bytes && !reads)))
+        return fail(BMV_ERR_ARG, "bmv_align_best: null argument");
+    if (n_groups && !margin) return fail(BMV_ERR_ARG, "bmv_align_best: null argument");
+    if (group_offset[0] != 0u) return fail(BMV_ERR_ARG, "bmv_align_best: group_offset[0] is %u, not 0", group_offset[0]);
+    for (uint32_t g = 0; g < n_groups; g++) {
+        if (group_offset[g + 1] < group_offset[g] || group_offset[g + 1] > n)
+            return fail(BMV_ERR_ARG, "group %u: group_offset runs from %u to %u (not monotone, or beyond the %u alignments)", g,
+                        group_offset[g], group_offset[g + 1], n);
+        const uint32_t size = group_offset[g + 1] - group_offset[g];
+        if (hint && size && hint[g] >= size) return fail(BMV_ERR_ARG, "group %u: hint %u, the group has %u alignments", g, hint[g], size);
+    }
+    if (group_offset[n_groups] != n)
+        return fail(BMV_ERR_ARG, "group %u: group_offset ends at %u, the batch has %u alignments", n_groups ? n_groups - 1u : 0u,
+                    group_offset[n_groups], n);
+    const uint32_t long_from = getenv("BMV_LONG_FROM") ? (uint32_t)strtoul(getenv("BMV_LONG_FROM"), nullptr, 10) : 0u;
+    uint64_t cells = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
+        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
+            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
+        cells += (uint64_t)query_len[a] * text_len[a];
+    }
+
+    // what full alignments leave, per alignment of the batch
+    std::vector<int32_t> f_score(n, BMV_REJECTED);
+    std::vector<uint32_t> f_begin(n, 0), f_rlen(n, 0), full(n, 0u);
+    std::vector<std::vector<uint32_t>> f_cigar(n);
+    float ms_total = 0.f;
+    c->bs_n_seed = c->bs_n_distance = c->bs_n_beyond = c->bs_n_undecided = c->bs_n_realigned = 0;
+    c->bs_cells = 0;
+    c->ms_distance = c->ms_pick = 0.f;
+
+    // 1. the seeds
+    std::vector<uint32_t> seeds, seed_of(n_groups, bmv::kBestBeyond);
+    for (uint32_t g = 0; g < n_groups; g++) {
+        if (group_offset[g + 1] == group_offset[g]) continue;
+        seed_of[g] = group_offset[g] + (hint ? hint[g] : 0u);
+        seeds.push_back(seed_of[g]);
+    }
+    if (int rc = best_sub_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, seeds, f_score, f_begin,
+                                f_rlen, f_cigar, &ms_total))
+        return rc;
+    for (uint32_t a : seeds) full[a] = 1u;
+    c->bs_n_seed = (uint32_t)seeds.size();
+
+    std::vector<uint32_t> h_d(n, bmv::kBestUndecided), h_end(n, 0u), h_winner(n_groups, bmv::kBestBeyond), h_edits(n, bmv::kBestBeyond),
+        h_out_end(n, 0u);
+    for (uint32_t a : seeds) {
+        h_d[a] = (uint32_t)(-(int64_t)f_score[a]);
+        h_end[a] = f_begin[a] + f_rlen[a];
+    }
+    if (seeds.size() == n) {
+        // every group is its seed alone: nothing to decide
+        for (uint32_t g = 0; g < n_groups; g++) h_winner[g] = seed_of[g];
+        h_edits = h_d;
+        h_out_end = h_end;
+    } else {
+        // 2. the distance round: everything but the seeds, under k = min(seed's edits + margin, query length)
+        constexpr uint32_t kWaveCw[] = {1, 2, 4};               // bmv_best_wave_kernel's variants
+        std::vector<uint32_t> bound(n, 0u), lane_list, wave_list[3], undecided;
+        uint32_t lane_words = 1;
+        for (uint32_t g = 0; g < n_groups; g++) {
+            for (uint32_t a = group_offset[g]; a < group_offset[g + 1]; a++) {
+                if (a == seed_of[g]) continue;
+                const uint32_t m = query_len[a];
+                const uint32_t k = (uint32_t)std::min<uint64_t>((uint64_t)h_d[seed_of[g]] + margin[g], m);
+                bound[a] = k;
+                const bool beyond = m > c->p.max_query_len || text_len[a] > c->p.max_text_len || (long_from && m >= long_from);
+                const uint32_t words = (m + 63u) / 64u;
+                if (beyond || m == 0u || text_len[a] == 0u) {   // (an empty side: the aligner's own conventions)
+                    undecided.push_back(a);
+                } else if (words <= kLaneWords) {
+                    lane_list.push_back(a);
+                    lane_words = std::max(lane_words, words);
+                } else {
+                    // the band of a wrong locus is about 2 k rows (bmv_align_bounded): the smallest variant that holds it
+                    const uint64_t band = std::min<uint64_t>(words, ((uint64_t)k * 9u / 4u + 128u) / 64u + 2u);
+                    uint32_t v = 0;
+                    while (v + 1u < 3u && band > 64u * kWaveCw[v]) v++;
+                    wave_list[v].push_back(a);
+                }
+            }
+        }
+        const size_t n_listed = lane_list.size() + wave_list[0].size() + wave_list[1].size() + wave_list[2].size();
+        c->bs_n_distance = (uint32_t)n_listed;
+        HIP_TRY(hipSetDevice(c->p.device));
+        HIP_TRY(c->bs_d.need_exact(n));
+        HIP_TRY(c->bs_end.need_exact(n));
+        if (n_listed) {
+            HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
+            HIP_TRY(c->text_start.need_exact(n));
+            HIP_TRY(c->text_len.need_exact(n));
+            HIP_TRY(c->text_rc.need_exact(n));
+            HIP_TRY(c->query_start.need_exact(n));
+            HIP_TRY(c->query_len.need_exact(n));
+            HIP_TRY(c->bs_bound.need_exact(n));
+            HIP_TRY(c->bs_list.need_exact(n_listed));
+            HIP_TRY(c->bs_count.need_exact(1));
+            if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->bs_bound.p, bound.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            std::vector<uint32_t> list;
+            list.reserve(n_listed);
+            list.insert(list.end(), lane_list.begin(), lane_list.end());
+            for (const auto &w : wave_list) list.insert(list.end(), w.begin(), w.end());
+            HIP_TRY(hipMemcpyAsync(c->bs_list.p, list.data(), n_listed * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(c->bs_count.p, 0, sizeof(unsigned long long), c->stream));
+            bmv::BestJob j{};
+            j.genome = c->genome.p;
+            j.reads = c->reads.p;
+            j.lut = c->lut.p;
+            j.text_start = c->text_start.p;
+            j.text_len = c->text_len.p;
+            j.text_rc = c->text_rc.p;
+            j.query_start = c->query_start.p;
+            j.query_len = c->query_len.p;
+            j.bound = c->bs_bound.p;
+            j.d = c->bs_d.p;
+            j.end = c->bs_end.p;
+            j.cells = c->bs_count.p;
+            using best_fn = void (*)(bmv::BestJob);
+            static const best_fn per_lane[kLaneWords + 1] = {nullptr,
+                                                             bmv::bmv_best_lane_kernel<1>, bmv::bmv_best_lane_kernel<2>,
+                                                             bmv::bmv_best_lane_kernel<3>, bmv::bmv_best_lane_kernel<4>,
+                                                             bmv::bmv_best_lane_kernel<5>, bmv::bmv_best_lane_kernel<6>,
+                                                             bmv::bmv_best_lane_kernel<7>, bmv::bmv_best_lane_kernel<8>};
+            static const best_fn per_wave[3] = {bmv::bmv_best_wave_kernel<1>, bmv::bmv_best_wave_kernel<2>, bmv::bmv_best_wave_kernel<4>};
+            HIP_TRY(hipEventRecord(c->ev0, c->stream));
+            size_t at = 0;
+            if (!lane_list.empty()) {
+                j.list = c->bs_list.p;
+                j.count = (uint32_t)lane_list.size();
+                hipLaunchKernelGGL(per_lane[lane_words], dim3((j.count + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, j);
+                HIP_TRY(hipGetLastError());
+                at += lane_list.size();
+            }
+            for (uint32_t v = 0; v < 3u; v++) {
+                if (wave_list[v].empty()) continue;
+                j.list = c->bs_list.p + at;
+                j.count = (uint32_t)wave_list[v].size();
+                hipLaunchKernelGGL(per_wave[v], dim3(j.count), dim3(bmv::kWave), 0, c->stream, j);
+                HIP_TRY(hipGetLastError());
+                at += wave_list[v].size();
+            }
+            HIP_TRY(hipEventRecord(c->ev1, c->stream));
+            unsigned long long steps = 0;
+            HIP_TRY(hipMemcpyAsync(h_d.data(), c->bs_d.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h_end.data(), c->bs_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&steps, c->bs_count.p, sizeof steps, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(hipEventElapsedTime(&c->ms_distance, c->ev0, c->ev1));
+            c->bs_cells = 64u * (uint64_t)steps;
+            for (uint32_t a : list) {
+                if (h_d[a] == bmv::kBestUndecided) {
+                    undecided.push_back(a);
+                    c->bs_n_undecided++;
+                } else if (h_d[a] == bmv::kBestBeyond) {
+                    c->bs_n_beyond++;
+                }
+            }
+            ms_total += c->ms_distance;
+            if (getenv("BMV_LOG_CLASSES"))
+                fprintf(stderr, "[bmv] best: %zu seeds; distance round %zu per lane, %zu / %zu / %zu per wave at 1 / 2 / 4 words a lane; %u beyond, %u undecided, %.2f ms\n",
+                        seeds.size(), lane_list.size(), wave_list[0].size(), wave_list[1].size(), wave_list[2].size(), c->bs_n_beyond,
+                        c->bs_n_undecided, c->ms_distance);
+        }
+        // what the kernels did not take or gave up on: in full, which gives d and end as well
+        std::sort(undecided.begin(), undecided.end());
+        if (int rc = best_sub_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, undecided, f_score,
+                                    f_begin, f_rlen, f_cigar, &ms_total))
+            return rc;
+        for (uint32_t a : undecided) {
+            full[a] = 1u;
+            h_d[a] = (uint32_t)(-(int64_t)f_score[a]);
+            h_end[a] = f_begin[a] + f_rlen[a];
+        }
+
+        // 3. the pick
+        HIP_TRY(hipSetDevice(c->p.device));
+        HIP_TRY(c->bs_full.need_exact(n));
+        HIP_TRY(c->bs_group_offset.need_exact((size_t)n_groups + 1u));
+        HIP_TRY(c->bs_margin.need_exact(n_groups));
+        HIP_TRY(c->bs_winner.need_exact(n_groups));
+        HIP_TRY(c->bs_need.need_exact(n_groups));
+        HIP_TRY(c->bs_need_at.need_exact((size_t)n_groups + 1u));
+        HIP_TRY(c->bs_realign.need_exact(n_groups));
+        HIP_TRY(c->bs_edits.need_exact(n));
+        HIP_TRY(c->bs_out_end.need_exact(n));
+        HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n_groups) * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_full.p, full.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_group_offset.p, group_offset, ((size_t)n_groups + 1u) * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_margin.p, margin, (size_t)n_groups * 4, hipMemcpyHostToDevice, c->stream));
+        bmv::PickJob pj{};
+        pj.d = c->bs_d.p;
+        pj.end = c->bs_end.p;
+        pj.full = c->bs_full.p;
+        pj.group_offset = c->bs_group_offset.p;
+        pj.margin = c->bs_margin.p;
+        pj.n_groups = n_groups;
+        pj.winner = c->bs_winner.p;
+        pj.need = c->bs_need.p;
+        pj.out_edits = c->bs_edits.p;
+        pj.out_end = c->bs_out_end.p;
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        hipLaunchKernelGGL(bmv::bmv_best_pick_kernel, dim3((n_groups + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, pj);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->bs_need.p, c->bs_need_at.p, n_groups, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
+        hipLaunchKernelGGL(bmv::bmv_best_compact_kernel, dim3((n_groups + 255u) / 256u), dim3(256), 0, c->stream, c->bs_need.p,
+                           c->bs_need_at.p, c->bs_winner.p, n_groups, c->bs_realign.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        uint32_t n_realign = 0;
+        HIP_TRY(hipMemcpyAsync(&n_realign, c->bs_need_at.p + n_groups, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_winner.data(), c->bs_winner.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_edits.data(), c->bs_edits.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_out_end.data(), c->bs_out_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipEventElapsedTime(&c->ms_pick, c->ev0, c->ev1));
+        ms_total += c->ms_pick;
+        if (n_realign > n_groups) return fail(BMV_ERR_STATE, "bmv_align_best: the pick lists %u winners for %u groups", n_realign, n_groups);
+        std::vector<uint32_t> realign(n_realign);
+        if (n_realign) HIP_TRY(hipMemcpy(realign.data(), c->bs_realign.p, (size_t)n_realign * 4, hipMemcpyDeviceToHost));
+        for (uint32_t a : realign)
+            if (a >= n) return fail(BMV_ERR_STATE, "bmv_align_best: the pick lists alignment %u of %u", a, n);
+
+        // 4. the winners that have no full alignment yet
+        if (int rc = best_sub_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, realign, f_score, f_begin,
+                                    f_rlen, f_cigar, &ms_total))
+            return rc;
+        c->bs_n_realigned = n_realign;
+        for (uint32_t a : realign) {
+            // the distance round and the aligner are two computations of one quantity
+            if ((uint32_t)(-(int64_t)f_score[a]) != h_d[a] || f_begin[a] + f_rlen[a] != h_end[a])
+                return fail(BMV_ERR_STATE, "bmv_align_best: alignment %u has %u edits ending at %u by the distance round, %lld ending at %u in full",
+                            a, h_d[a], h_end[a], -(long long)f_score[a], f_begin[a] + f_rlen[a]);
+        }
+    }
+
+    // the winners in batch order, everything else rejected
+    std::vector<int32_t> score(n, BMV_REJECTED);
+    std::vector<uint32_t> begin(n, 0), cig;
+    std::vector<uint64_t> offset((size_t)n + 1, 0);
+    std::vector<uint8_t> wins(n, 0);
+    for (uint32_t g = 0; g < n_groups; g++)
+        if (h_winner[g] != bmv::kBestBeyond) wins[h_winner[g]] = 1;
+    for (uint32_t a = 0; a < n; a++) {
+        offset[a] = cig.size();
+        if (!wins[a]) continue;
+        score[a] = f_score[a];
+        begin[a] = f_begin[a];
+        cig.insert(cig.end(), f_cigar[a].begin(), f_cigar[a].end());
+    }
+    offset[n] = cig.size();
+    c->n_last = n;
+    c->n_cells = cells;
+    c->ms_kernels = ms_total;
+    c->h_score = std::move(score);
+    c->h_begin = std::move(begin);
+    c->h_offset = std::move(offset);
+    c->h_cigar = std::move(cig);
+    c->n_best = n;
+    c->n_best_groups = n_groups;
+    c->h_bs_winner = std::move(h_winner);
+    c->h_bs_edits = std::move(h_edits);
+    c->h_bs_end = std::move(h_out_end);
+    *total_cigar = c->h_cigar.size();
+    return BMV_OK;
+}
+
+int bmv_best(bmv_ctx *c, uint32_t *out_winner, uint32_t *out_edits, uint32_t *out_end) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_best: null context");
+    if (out_winner && c->n_best_groups) memcpy(out_winner, c->h_bs_winner.data(), (size_t)c->n_best_groups * 4);
+    if (out_edits && c->n_best) memcpy(out_edits, c->h_bs_edits.data(), (size_t)c->n_best * 4);
+    if (out_end && c->n_best) memcpy(out_end, c->h_bs_end.data(), (size_t)c->n_best * 4);
+    return BMV_OK;
+}
+
+int bmv_last_best_stats(bmv_ctx *c, uint32_t *n_seed, uint32_t *n_distance, uint32_t *n_beyond, uint32_t *n_undecided,
+                        uint32_t *n_realigned, uint64_t *distance_cells, float *ms_distance, float *ms_pick) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_best_stats: null context");
+    if (n_seed) *n_seed = c->bs_n_seed;
+    if (n_distance) *n_distance = c->bs_n_distance;
+    if (n_beyond) *n_beyond = c->bs_n_beyond;
+    if (n_undecided) *n_undecided = c->bs_n_undecided;
+    if (n_realigned) *n_realigned = c->bs_n_realigned;
+    if (distance_cells) *distance_cells = c->bs_cells;
+    if (ms_distance) *ms_distance = c->ms_distance;
+    if (ms_pick) *ms_pick = c->ms_pick;
     return BMV_OK;
 }
 

@@ -13,6 +13,7 @@
 // drops an exact hit at bucket offset 0, results are appended per read in bucket order.
 #pragma once
 
+#include "best_mapq.h"
 #include "bm_genome.h"
 #include "mapper.h"
 #include "sam_tags.h"
@@ -151,6 +152,63 @@ public:
         (void)begin; (void)cigar_offset; (void)cigar; (void)n; (void)match; (void)penalty; (void)out;
         throw std::runtime_error("--clip: this build's alignment verifier has no clipping pass");
     }
+    // The best alignment of every group (bmv_align_best's contract, include/bmv.h): group g owns the alignments
+    // group_offset[g] .. group_offset[g + 1] - 1; with d = -score and end = begin + the M and D lengths, winner[g] is the lowest
+    // index with the group's smallest d (kBeyond for an empty group) and alone keeps its score, begin and CIGAR -- every other
+    // alignment comes back with score kRejected, begin 0 and no entries; edits / end carry d / end of every alignment with
+    // d <= best + margin[g], kBeyond / 0 elsewhere.  hint[g] (may be null) is the index inside the group to try first; the
+    // result does not depend on it.  This default aligns everything and selects afterwards; the GPU verifier aligns one
+    // alignment per group in full and decides the rest score-only.
+    static constexpr uint32_t kBeyond = UINT32_MAX;
+    virtual void best(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                      const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
+                      const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                      std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
+                      std::vector<uint32_t> &cigar, std::vector<uint32_t> &winner, std::vector<uint32_t> &edits,
+                      std::vector<uint32_t> &end) {
+        (void)hint;
+        align(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, score, begin, cigar_offset, cigar);
+        std::vector<uint32_t> d(n), e(n);
+        for (uint32_t a = 0; a < n; a++) {
+            uint32_t r = 0;
+            for (uint64_t x = cigar_offset[a]; x < cigar_offset[a + 1]; x++)
+                if ((cigar[x] & 15u) != 1u) r += cigar[x] >> 4;
+            d[a] = static_cast<uint32_t>(-static_cast<int64_t>(score[a]));
+            e[a] = begin[a] + r;
+        }
+        winner.assign(n_groups, kBeyond);
+        edits.assign(n, kBeyond);
+        end.assign(n, 0);
+        std::vector<uint8_t> wins(n, 0);
+        for (uint32_t g = 0; g < n_groups; g++) {
+            const uint32_t a0 = group_offset[g], a1 = group_offset[g + 1];
+            if (a0 == a1) continue;
+            uint32_t w = a0;
+            for (uint32_t a = a0 + 1; a < a1; a++)
+                if (d[a] < d[w]) w = a;
+            winner[g] = w;
+            wins[w] = 1;
+            const uint64_t reach = static_cast<uint64_t>(d[w]) + margin[g];
+            for (uint32_t a = a0; a < a1; a++) {
+                if (d[a] > reach) continue;
+                edits[a] = d[a];
+                end[a] = e[a];
+            }
+        }
+        uint64_t at = 0;
+        for (uint32_t a = 0; a < n; a++) {
+            const uint64_t from = cigar_offset[a], to = cigar_offset[a + 1];
+            cigar_offset[a] = at;
+            if (!wins[a]) {
+                score[a] = kRejected;
+                begin[a] = 0;
+                continue;
+            }
+            for (uint64_t x = from; x < to; x++) cigar[at++] = cigar[x];
+        }
+        cigar_offset[n] = at;
+        cigar.resize(at);
+    }
 };
 
 // SAM text as seqan3::sam_file_output lays it out: records are appended to one buffer with
@@ -258,6 +316,7 @@ private:
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
     uint32_t _clip_match = 1, _clip_penalty = 2;
+    float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
     const Genome *genome_ = nullptr;
     std::vector<Bucket> buckets_;
     std::vector<uint64_t> bstart_;               // bucket views into the records laid back to back
@@ -458,6 +517,9 @@ public:
     void set_annotate(bool on) { _annotate = on; }
     // --clip: the --annotate layout, the written alignments through the verifier's clipping pass instead (POS, CIGAR, NM and MD
     // of the kept part, S entries, AS:i); an alignment of which nothing is kept writes no record
+    // --best: every read's candidates go through the verifier as one group (alignment_verifier::best), the read gets ONE record,
+    // its best alignment's, with MAPQ and X0 from best_mapq.h; margin = max(1, (uint32_t)(rate x read length))
+    void set_best(float margin_rate) { _best_margin = margin_rate; }
     void set_clip(uint32_t match, uint32_t penalty) {
         _clip = _annotate = true;
         _clip_match = match;
@@ -763,6 +825,7 @@ private:
             std::vector<uint8_t> bases;
             std::vector<uint64_t> text_start, query_start, cigar_offset;
             std::vector<uint32_t> text_len, query_len, begin, cigar, max_edits;
+            std::vector<uint32_t> group_offset{0}, margin, hint, winner, edits, end;    // --best: a group per read
             std::vector<uint8_t> text_rc;
             std::vector<int32_t> score;
             std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
@@ -778,13 +841,23 @@ private:
         blocks[0].first_read = read_id;
         std::thread worker;
         const bool bounded = _max_edit_rate >= 0.f;             // --max-edit-rate: rejected alignments leave no record
+        const bool best = _best_margin >= 0.f;                  // --best: neither do the alignments that did not win
         auto is_written = [&](const Block &b, size_t a) {       // :570-573, and the edit bound
             const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
-            return !(bounded && b.score[a] == alignment_verifier::kRejected) && !(map_qual < quality_threshold);
+            return !((bounded || best) && b.score[a] == alignment_verifier::kRejected) && !(map_qual < quality_threshold);
         };
         auto align = [&](Block &b) {                            // on the worker thread
             try {
-                if (!b.text_start.empty() && bounded)
+                if (!b.text_start.empty() && best) {
+                    _v->best(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
+                             b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.group_offset.data(),
+                             static_cast<uint32_t>(b.margin.size()), b.margin.data(), b.hint.data(), b.score, b.begin, b.cigar_offset,
+                             b.cigar, b.winner, b.edits, b.end);
+                    // --max-edit-rate on top: a winner beyond its bound leaves no record
+                    for (size_t a = 0; bounded && a < b.score.size(); a++)
+                        if (b.score[a] != alignment_verifier::kRejected && -static_cast<int64_t>(b.score[a]) > static_cast<int64_t>(b.max_edits[a]))
+                            b.score[a] = alignment_verifier::kRejected;
+                } else if (!b.text_start.empty() && bounded)
                     _v->align_bounded(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                                       b.query_start.data(), b.query_len.data(), b.max_edits.data(),
                                       static_cast<uint32_t>(b.text_start.size()), b.score, b.begin, b.cigar_offset, b.cigar);
@@ -820,24 +893,33 @@ private:
         };
         // BM_DUMP_ALIGNMENTS=<file> (tests): every alignment the verifier returned, kept or not, one line each --
         // read, text start in the concatenated genome, text length, strand, query length, score, begin, CIGAR
+        // (--best: the winners only)
         std::ofstream dump;
         if (const char *e = std::getenv("BM_DUMP_ALIGNMENTS")) dump.open(e);
         auto write = [&](Block &b) {
             if (b.failed) std::rethrow_exception(b.failed);
             size_t a = 0;
-            std::string cg, tags, rc_seq, rc_qual;
+            std::string cg, tags, rc_seq, rc_qual, best_tag;
             for (size_t r = 0; r < b.reads.size(); r++) {
                 rc_seq.clear();                                 // (--annotate: made for the read's first flag-16 record)
+                best_quality bq{0u, 0u};                        // --best: the MAPQ and X0 of the read's one record
+                if (best && b.group_offset[r + 1] > b.group_offset[r]) {
+                    const uint32_t a0 = b.group_offset[r];
+                    bq = best_mapq(b.winner[r] - a0, b.edits.data() + a0, b.end.data() + a0, b.text_start.data() + a0,
+                                   b.text_len.data() + a0, b.text_rc.data() + a0, b.group_offset[r + 1] - a0, b.margin[r]);
+                    best_tag = "X0:i:";
+                    sam_tags::number(best_tag, bq.x0);
+                }
                 for (auto &[bucket_id, offset, segment_offset, votes, is_original] : locate_res[b.first_read + r]) {
                     (void)segment_offset; (void)votes;
-                    if (dump.is_open()) {
+                    if (dump.is_open() && !(best && b.winner[r] != a)) {
                         dump << b.first_read + r << ' ' << b.text_start[a] << ' ' << b.text_len[a] << ' ' << int(b.text_rc[a]) << ' '
                              << b.query_len[a] << ' ' << b.score[a] << ' ' << b.begin[a] << ' ';
                         for (uint64_t x = b.cigar_offset[a]; x < b.cigar_offset[a + 1]; x++) dump << (b.cigar[x] >> 4) << "MID"[b.cigar[x] & 15u];
                         dump << (b.cigar_offset[a] == b.cigar_offset[a + 1] ? "*\n" : "\n");
                     }
                     const unsigned int wrapped = 60u + static_cast<unsigned int>(b.score[a]);        // :570
-                    const size_t map_qual = wrapped;
+                    const size_t map_qual = best ? bq.mapq : wrapped;
                     if (is_written(b, a) && _clip && b.ann.score[b.ann_slot[a]] == 0) {
                         // --clip: the kept range is empty (a kept column scores at least `match`): no record
                     } else if (is_written(b, a) && _annotate) {
@@ -857,6 +939,7 @@ private:
                             tags += "\tAS:i:";
                             sam_tags::number(tags, static_cast<uint64_t>(b.ann.score[s]));
                         }
+                        if (best) tags += "\t" + best_tag;
                         if (!is_original && rc_seq.empty()) {
                             sam_tags::append_revcomp(rc_seq, b.reads[r].seq);
                             rc_qual.assign(b.reads[r].qual.rbegin(), b.reads[r].qual.rend());
@@ -874,7 +957,8 @@ private:
                         }
                         if (cg.empty()) cg = "*";
                         sam.record(b.reads[r].id, is_original ? 0 : 16, h.bucket_name[bucket_id], ref_offset + 1,
-                                   static_cast<uint8_t>(map_qual), cg, b.reads[r].seq, b.reads[r].qual);
+                                   static_cast<uint8_t>(map_qual), cg, b.reads[r].seq, b.reads[r].qual,
+                                   best ? std::string_view(best_tag) : std::string_view());
                         mapped_locations++;
                     }
                     a++;
@@ -883,6 +967,7 @@ private:
             b.reads.clear(); b.bases.clear();
             b.text_start.clear(); b.text_len.clear(); b.text_rc.clear(); b.query_start.clear(); b.query_len.clear();
             b.max_edits.clear();
+            b.group_offset.assign(1, 0); b.margin.clear(); b.hint.clear();
         };
         // the block just filled goes to the verifier as soon as the one before has left it; that one's records are written
         // while the verifier works
@@ -919,6 +1004,21 @@ private:
                     b.query_start.push_back(b.reads.back().start);
                     b.query_len.push_back(static_cast<uint32_t>(len));
                     if (bounded) b.max_edits.push_back(static_cast<uint32_t>(std::min(_max_edit_rate * static_cast<float>(len), 4e9f)));
+                }
+                if (best) {
+                    // the read's group: the hint is the candidate with the most locator votes, the first of them
+                    uint32_t at = 0, most = 0, k = 0;
+                    for (auto &[bucket_id, offset, segment_offset, votes, is_original] : locate_res[read_id]) {
+                        (void)bucket_id; (void)offset; (void)segment_offset; (void)is_original;
+                        if (k == 0 || votes > most) {
+                            most = votes;
+                            at = k;
+                        }
+                        k++;
+                    }
+                    b.group_offset.push_back(static_cast<uint32_t>(b.text_start.size()));
+                    b.margin.push_back(std::max(1u, static_cast<uint32_t>(std::min(_best_margin * static_cast<float>(len), 4e9f))));
+                    b.hint.push_back(at);
                 }
                 read_id++;
                 if (b.reads.size() >= block_reads || b.bases.size() >= block_bases) flush();

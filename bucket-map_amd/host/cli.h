@@ -36,6 +36,10 @@ struct cmd_arguments {
     bool annotate = false;        // --annotate (bucketmap_align): records on the forward strand with =/X CIGAR, NM and MD
     bool clip = false;            // --clip (bucketmap_align): --annotate's records with low-identity ends soft-clipped (S) and AS
     unsigned int clip_match = 1, clip_penalty = 2;   // --clip-scores M,P (implies --clip): bmv_clip's scores, 1..1024 each
+    bool best = false;            // --best (bucketmap_align): one record per read, its best alignment's, with a MAPQ that tells a
+                                  // unique hit from a repeat and an X0 tag
+    float best_margin = 0.05f;    // --best-margin R (implies --best): alignments within max(1, R * read length) edits of the best
+                                  // count towards MAPQ and X0
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -155,6 +159,13 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             if (!(a.max_edit_rate >= 0.f)) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number >= 0.");
         }
         else if (opt == "--annotate") a.annotate = true;
+        else if (opt == "--best") a.best = true;
+        else if (opt == "--best-margin") {
+            const std::string s = value();
+            a.best_margin = as_float(s);
+            if (!(a.best_margin >= 0.f)) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number >= 0.");
+            a.best = true;
+        }
         else if (opt == "--clip") a.clip = true;
         else if (opt == "--clip-scores") {
             const std::string s = value();

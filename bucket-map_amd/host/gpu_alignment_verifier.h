@@ -64,6 +64,89 @@ public:
         run(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, max_edits, n, score, begin, cigar_offset, cigar);
     }
 
+    // bmv_align_best per device: the batch is cut at GROUP borders into ranges of roughly equal cell count, the per-alignment
+    // results are stitched as run() stitches them, the winners rebased to batch indices
+    void best(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+              const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n, const uint32_t *group_offset,
+              uint32_t n_groups, const uint32_t *margin, const uint32_t *hint, std::vector<int32_t> &score,
+              std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset, std::vector<uint32_t> &cigar,
+              std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end) override {
+        const size_t D = ctx_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        score.assign(n, 0);
+        begin.assign(n, 0);
+        cigar_offset.assign(static_cast<size_t>(n) + 1, 0);
+        winner.assign(n_groups, kBeyond);
+        edits.assign(n, kBeyond);
+        end.assign(n, 0);
+        const std::vector<uint32_t> cut = cut_by_cost(n_groups, D, [&](uint32_t g) {
+            uint64_t cells = 1;
+            for (uint32_t a = group_offset[g]; a < group_offset[g + 1]; a++) cells += static_cast<uint64_t>(query_len[a]) * text_len[a];
+            return cells;
+        });
+        std::vector<uint64_t> total(D, 0), cells(D, 0), dist_cells(D, 0);
+        std::vector<float> ms(D, 0.f);
+        std::vector<std::array<uint32_t, 5>> counts(D, std::array<uint32_t, 5>{});
+        for_each_device(D, [&](size_t d) {
+            const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
+            if (ng == 0) return;
+            const uint32_t a0 = group_offset[g0], m = group_offset[g0 + ng] - a0;
+            if (D == 1) {
+                check(bmv_align_best(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset,
+                                     n_groups, margin, hint, &total[0]), "the GPU alignment verifier failed: ");
+            } else {
+                uint64_t lo = ~0ull, hi = 0;
+                for (uint32_t a = a0; a < a0 + m; a++) {
+                    lo = std::min(lo, query_start[a]);
+                    hi = std::max(hi, query_start[a] + query_len[a]);
+                }
+                if (m == 0) lo = 0;
+                std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
+                for (uint64_t &s : rebased) s -= lo;
+                std::vector<uint32_t> off(group_offset + g0, group_offset + g0 + ng + 1);
+                for (uint32_t &o : off) o -= a0;
+                check(bmv_align_best(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
+                                     query_len + a0, m, off.data(), ng, margin + g0, hint ? hint + g0 : nullptr, &total[d]),
+                      "the GPU alignment verifier failed: ");
+            }
+            bmv_last_stats(ctx_[d], &ms[d], &cells[d]);
+            bmv_last_best_stats(ctx_[d], &counts[d][0], &counts[d][1], &counts[d][2], &counts[d][3], &counts[d][4], &dist_cells[d], nullptr,
+                                nullptr);
+        });
+        std::vector<uint64_t> at(D + 1, 0);
+        for (size_t d = 0; d < D; d++) at[d + 1] = at[d] + total[d];
+        cigar.assign(at[D], 0);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
+            if (ng == 0) return;
+            const uint32_t a0 = group_offset[g0], m = group_offset[g0 + ng] - a0;
+            std::vector<uint64_t> off(static_cast<size_t>(m) + 1);
+            check(bmv_results(ctx_[d], score.data() + a0, begin.data() + a0, off.data(), cigar.data() + at[d]),
+                  "reading the verifier's results failed: ");
+            check(bmv_best(ctx_[d], winner.data() + g0, edits.data() + a0, end.data() + a0), "reading the verifier's results failed: ");
+            for (uint32_t a = 0; a < m; a++) cigar_offset[a0 + a] = at[d] + off[a];
+            for (uint32_t g = g0; g < g0 + ng; g++)
+                if (winner[g] != kBeyond) winner[g] += a0;
+        });
+        // (ranges are contiguous and in order: an empty range's alignments do not exist, so every offset is set but the last)
+        cigar_offset[n] = at[D];
+        float slowest = 0;
+        uint64_t all_cells = 0, all_dist = 0;
+        std::array<uint64_t, 5> all{};
+        for (size_t d = 0; d < D; d++) {
+            slowest = std::max(slowest, ms[d]);
+            all_cells += cells[d];
+            all_dist += dist_cells[d];
+            for (size_t k = 0; k < 5; k++) all[k] += counts[d][k];
+        }
+        const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::cerr << "[BENCHMARK]\tGPU alignment verification, best per read: " << n << " alignments in " << n_groups << " groups, "
+                  << all_cells << " cells; " << all[0] << " seeds, " << all[1] << " through the distance round (" << all_dist
+                  << " cells, " << all[2] << " beyond, " << all[3] << " undecided), " << all[4] << " realigned; kernels " << slowest
+                  << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of " << call_ms
+                  << " ms in the call.\n";
+    }
+
     // bmv_annotate per device: the batch is cut exactly as run() cuts it and the packed arrays are stitched the same way
     void annotate(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
                   const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,

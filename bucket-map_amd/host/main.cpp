@@ -131,6 +131,7 @@ int main(int argc, char **argv) {
         loc.set_max_edit_rate(args.max_edit_rate);
         loc.set_annotate(args.annotate);
         if (args.clip) loc.set_clip(args.clip_match, args.clip_penalty);
+        if (args.best) loc.set_best(args.best_margin);
 #endif
         run_indexer();
         loc.initialize(genome, cwd, args.index_indicator);                                    // main.cpp:221

@@ -9,6 +9,7 @@ from . import lib as _bmf_lib
 
 BMV_OK = 0
 REJECTED = -(2 ** 31)     # BMV_REJECTED: the score of an alignment beyond its edit bound (align_bounded)
+BEYOND = 2 ** 32 - 1      # BMV_BEYOND: no winner (an empty group) / edits beyond best + margin (align_best)
 
 
 class BmvError(RuntimeError):
@@ -33,6 +34,11 @@ SYMBOLS = {
     "bmv_align_long": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u64p]),
     "bmv_align_bounded": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, C.c_uint32, _u64p]),
     "bmv_last_bounded_stats": (C.c_int, [C.c_void_p, _u32p, _u64p, C.POINTER(C.c_float)]),
+    "bmv_align_best": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u32p, C.c_uint32,
+                                 _u32p, _u32p, _u64p]),
+    "bmv_best": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p]),
+    "bmv_last_best_stats": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float)]),
     "bmv_results": (C.c_int, [C.c_void_p, _i32p, _u32p, _u64p, _u32p]),
     "bmv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
     "bmv_annotate": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32,
@@ -101,6 +107,57 @@ def md_string(xcigar, ref_bases) -> str:
     return "".join(out) + str(run)
 
 
+def select_best(d, end, group_offset, margin):
+    """The contract of bmv_align_best in plain numpy, from every alignment's distance d[a] and end column end[a] (begin + M
+    and D lengths of its CIGAR): returns (winner u32[n_groups], edits u32[n], end u32[n]).  winner[g] is the lowest batch
+    index with the group's smallest distance (BEYOND for an empty group); edits / end are d / end where d <= best + margin[g]
+    and BEYOND / 0 elsewhere."""
+    d, end = np.asarray(d, np.int64), np.asarray(end, np.int64)
+    off, margin = np.asarray(group_offset, np.int64), np.asarray(margin, np.int64)
+    n_groups = len(off) - 1
+    if len(margin) != n_groups or len(d) != len(end):
+        raise ValueError("one margin per group, one end per distance")
+    if n_groups < 0 or off[0] != 0 or off[-1] != len(d) or (np.diff(off) < 0).any():
+        raise ValueError("group_offset must run from 0 to the number of alignments without decreasing")
+    winner = np.full(n_groups, BEYOND, np.uint32)
+    edits, out_end = np.full(len(d), BEYOND, np.uint32), np.zeros(len(d), np.uint32)
+    for g in range(n_groups):
+        a0, a1 = int(off[g]), int(off[g + 1])
+        if a0 == a1:
+            continue
+        best = int(d[a0:a1].min())
+        winner[g] = a0 + int(np.argmax(d[a0:a1] == best))
+        within = d[a0:a1] <= best + int(margin[g])
+        edits[a0:a1][within] = d[a0:a1][within]
+        out_end[a0:a1][within] = end[a0:a1][within]
+    return winner, edits, out_end
+
+
+def best_mapq(winner, edits, end, text_start, text_len, text_rc, margin) -> tuple:
+    """MAPQ and X0 of one group's winner (host/best_mapq.h; a definition by choice).  winner: its index in the
+    group's arrays; edits / end: the group's slice of align_best's outputs; text_start / text_len / text_rc: the group's
+    windows; margin: the group's M.  The other alignments within the margin (edits != BEYOND) count unless they lie at the
+    winner's own locus -- the same strand and the same genome coordinate of the end: text_start + end forward,
+    text_start + text_len - end reverse (overlapping windows find one alignment twice).  With e1 the winner's edits and e2
+    the smallest among the others: none -> 60; e2 = e1 -> 0; else (e2 - e1) * 60 // (M + 1).  X0: distinct loci at e1, the
+    winner's included.  Returns (mapq, x0)."""
+    def locus(a):
+        rc = int(text_rc[a]) != 0
+        at = int(text_start[a]) + int(text_len[a]) - int(end[a]) if rc else int(text_start[a]) + int(end[a])
+        return (rc, at)
+    e1, home = int(edits[winner]), locus(winner)
+    others = {}
+    for a in range(len(edits)):
+        if a == winner or int(edits[a]) == BEYOND or locus(a) == home:
+            continue
+        others[locus(a)] = min(int(edits[a]), others.get(locus(a), BEYOND))
+    x0 = 1 + sum(1 for e in others.values() if e == e1)
+    if not others:
+        return 60, x0
+    e2 = min(others.values())
+    return (0 if e2 == e1 else min(60, (e2 - e1) * 60 // (int(margin) + 1))), x0
+
+
 class Verifier:
     """align_pairwise of the BM_ALIGN branch (bucket_locator.h:520-528,569-576) for batches, on one GPU."""
 
@@ -135,6 +192,51 @@ class Verifier:
         rej, cells, ms = C.c_uint32(), C.c_uint64(), C.c_float()
         _check(lib().bmv_last_bounded_stats(self._h, C.byref(rej), C.byref(cells), C.byref(ms)))
         return {"n_rejected": rej.value, "screen_cells": cells.value, "ms_screen": ms.value}
+
+    def align_best(self, reads, text_start, text_len, text_rc, query_start, query_len, group_offset, margin, hint=None) -> dict:
+        """bmv_align_best: of every group of alignments (group g owns group_offset[g] .. group_offset[g + 1] - 1) only the
+        best is aligned in full.  Returns a dict: score, begin, cigar_offset, cigar as align_long returns them for the winners
+        and REJECTED / 0 / no entries for everything else; winner u32[n_groups] (BEYOND for an empty group); edits u32[n] and
+        end u32[n], the distance and end column of every alignment within best + margin[g] (BEYOND / 0 elsewhere).  The
+        result does not depend on hint (the index inside each group to try first)."""
+        r = np.ascontiguousarray(reads, np.uint8)
+        ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
+        trc = np.ascontiguousarray(text_rc, np.uint8)
+        qs, ql = np.ascontiguousarray(query_start, np.uint64), np.ascontiguousarray(query_len, np.uint32)
+        off, mg = np.ascontiguousarray(group_offset, np.uint32), np.ascontiguousarray(margin, np.uint32)
+        n, n_groups = len(ts), len(off) - 1
+        if n_groups < 0 or len(mg) != n_groups:
+            raise ValueError("group_offset holds n_groups + 1 entries, margin n_groups")
+        if not (len(tl) == len(trc) == len(qs) == len(ql) == n):
+            raise ValueError("one entry per alignment in every array")
+        hp = None
+        if hint is not None:
+            hn = np.ascontiguousarray(hint, np.uint32)
+            if len(hn) != n_groups:
+                raise ValueError("hint must hold one index per group")
+            hp = _p(hn, _u32p)
+        total = C.c_uint64()
+        _check(lib().bmv_align_best(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
+                                    _p(ql, _u32p), n, _p(off, _u32p), n_groups, _p(mg, _u32p), hp, C.byref(total)))
+        score, begin = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        co = np.zeros(n + 1, np.uint64)
+        cg = np.zeros(max(total.value, 1), np.uint32)
+        _check(lib().bmv_results(self._h, _p(score, _i32p), _p(begin, _u32p), _p(co, _u64p), _p(cg, _u32p)))
+        winner = np.zeros(max(n_groups, 1), np.uint32)
+        edits, end = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        _check(lib().bmv_best(self._h, _p(winner, _u32p), _p(edits, _u32p), _p(end, _u32p)))
+        return {"score": score, "begin": begin, "cigar_offset": co, "cigar": cg[: total.value], "winner": winner[:n_groups],
+                "edits": edits[:n], "end": end[:n]}
+
+    def best_stats(self) -> dict:
+        """Of the last align_best: seeds aligned in full, alignments in the distance round, of these proven beyond the bound
+        and given up on, winners aligned in full after the pick, cells of the distance round, kernel ms of both."""
+        u = [C.c_uint32() for _ in range(5)]
+        cells, ms_d, ms_p = C.c_uint64(), C.c_float(), C.c_float()
+        _check(lib().bmv_last_best_stats(self._h, *(C.byref(x) for x in u), C.byref(cells), C.byref(ms_d), C.byref(ms_p)))
+        names = ("n_seed", "n_distance", "n_beyond", "n_undecided", "n_realigned")
+        return {**{k: x.value for k, x in zip(names, u)}, "distance_cells": cells.value, "ms_distance": ms_d.value,
+                "ms_pick": ms_p.value}
 
     def _align(self, fn, reads, text_start, text_len, text_rc, query_start, query_len, max_edits=None):
         r = np.ascontiguousarray(reads, np.uint8)

@@ -104,7 +104,43 @@ int  bmv_align_bounded(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes
  * the whole call). */
 int  bmv_last_bounded_stats(bmv_ctx *ctx, uint32_t *n_rejected, uint64_t *screen_cells, float *ms_screen);
 
-/* Results of the last bmv_align, bmv_align_long or bmv_align_bounded:
+/* The best alignment of each GROUP of a batch: one full alignment per group instead of one per alignment.  A group is the set of
+ * candidate alignments of one read; group g owns the alignments group_offset[g] .. group_offset[g + 1] - 1 of the batch
+ * (n_groups + 1 entries, non-decreasing, [0] = 0, [n_groups] = n).  The contract is on the outputs, exact, and independent of hint:
+ *   d[a]                alignment a's semi-global edit distance: -score of bmv_align_long
+ *   end[a]              begin + R of the result bmv_align_long gives it (R: its M and D lengths): the exclusive end column in
+ *                       the text as the aligner saw it -- tie rule (1) above
+ *   best[g]             the minimum of d over the group
+ *   out_winner[g]       the LOWEST batch index a of the group with d[a] = best[g]; BMV_BEYOND for an empty group
+ *   bmv_results         the winner carries exactly bmv_align_long's score, begin and CIGAR; every other alignment has score
+ *                       BMV_REJECTED, begin 0 and no CIGAR entries; *total_cigar counts the winners' entries
+ *   out_edits[a], out_end[a]   d[a] and end[a] whenever d[a] <= best[g] + margin[g] (the sum in 64 bits, capped at query_len[a]:
+ *                       no distance is larger), else BMV_BEYOND and 0.  The winner is always within the margin.
+ * hint[g] (or NULL: 0) is the index INSIDE group g of the alignment to try first -- the caller's guess at the winner; it decides
+ * how much work the call is, never what it returns.  Argument checks and limits are bmv_align_long's; in addition group_offset
+ * must be as above and hint[g] smaller than the group's size (ignored for an empty group): BMV_ERR_ARG, the message names the
+ * group, nothing ran and the context stays usable.  The call leaves untouched what bmv_annotations, bmv_clipped and their stats
+ * calls return.
+ * How (bmv_best.hip.h): the hinted alignment of every group is aligned in full by bmv_align_long (a group of one is finished
+ * there); every other one goes through score-only kernels -- bmv_align_bounded's screen made to decide: under
+ * k = min(hinted edits + margin, query_len) they give the exact (d, end), or the proof that d > k, or give up when the band
+ * outgrows a wave, and what they give up on (and what lies beyond the context's limits) is aligned in full; a segmented pass
+ * picks the winners; the winners that were not aligned yet are aligned in full. */
+#define BMV_BEYOND UINT32_MAX
+int  bmv_align_best(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                    const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                    uint32_t n, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                    uint64_t *total_cigar);
+/* Of the last bmv_align_best: out_winner n_groups entries, out_edits and out_end n entries; any pointer may be NULL. */
+int  bmv_best(bmv_ctx *ctx, uint32_t *out_winner, uint32_t *out_edits, uint32_t *out_end);
+/* Of the last bmv_align_best: the alignments aligned in full as seeds, those that entered the distance round, of these the ones
+ * proven beyond k and the ones given up on, the winners aligned in full after the pick, 64 x the (64-row word, text column)
+ * steps of the distance round (as screen_cells), and the kernel ms of the distance round and of the pick (parts of
+ * bmv_last_stats' ms_kernels, which covers the whole call).  Any pointer may be NULL. */
+int  bmv_last_best_stats(bmv_ctx *ctx, uint32_t *n_seed, uint32_t *n_distance, uint32_t *n_beyond, uint32_t *n_undecided,
+                         uint32_t *n_realigned, uint64_t *distance_cells, float *ms_distance, float *ms_pick);
+
+/* Results of the last bmv_align, bmv_align_long, bmv_align_bounded or bmv_align_best:
  *   out_score[a]        alignment.score() = -(edit distance)                       (bucket_locator.h:570)
  *   out_begin[a]        alignment.sequence1_begin_position(), 0-based in the text  (:576)
  *   out_cigar_offset    n + 1 entries; alignment a owns out_cigar[offset[a] .. offset[a+1])

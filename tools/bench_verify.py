@@ -6,6 +6,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py --long [--long-reads 1000] [--long-len 100000]
     python tools/bench_verify.py --annotate [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --clip [--reads 20000 --len 10000 --indel-rate 0.1]
+    python tools/bench_verify.py --best [--groups 20000 --len 10000 --text-len 11001] [--groups 200000 --len 300 --text-len 307]
 
 Prints one JSON line: alignments/s and cell updates/s of the device kernels (HIP events inside bmv_align),
 the wall time of the call (host buffers in, results out), and the CPU restatement (oracle, full DP matrix,
@@ -83,8 +84,114 @@ def long_main(args):
         np.array([len(q)], np.uint32), f"one {len(q)} x {n} alignment, ONT-like errors", {"query_len": len(q), "text_len": n})
 
 
+def best_main(args):
+    """Verifier.align_best on groups of five candidates: the true locus (ONT-like errors from 1 000 bases on, else
+    substitutions at --sub), two near copies of it -- planted in the genome, diverged by substitutions worth 0.5 x to 3 x the
+    margin -- and two unrelated windows, in random order.  Run with hint = the true locus and with hint = a wrong candidate,
+    beside Verifier.align and Verifier.align_bounded (rates 0.15 and 0.1) on the same batch; one JSON line."""
+    from bucket_map_amd import verify
+
+    rng = np.random.default_rng(20250903)
+    G, m, n = args.groups, args.len, args.text_len or args.len + 1 + int(np.float32(args.indel_rate) * np.float32(args.len))
+    margin = max(1, int(np.float32(args.margin_rate) * np.float32(m)))
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    # the genome: per group its true window and two diverged copies of it, back to back
+    genome = bases[rng.integers(0, 4, (G, 3, n), dtype=np.uint8)]
+    for c in (1, 2):
+        genome[:, c, :] = genome[:, 0, :]
+        for g0 in range(0, G, 2048):
+            part = genome[g0: g0 + 2048, c, :]
+            rate = rng.uniform(0.5, 3.0, (len(part), 1)) * margin / m
+            hit = rng.random(part.shape) < rate
+            part[hit] = bases[(np.searchsorted(bases, part[hit]) + rng.integers(1, 4, int(hit.sum()))) % 4]
+    genome = genome.reshape(-1)
+    lead = (n - m) // 2
+    parts = []
+    for g in range(G):
+        src = genome[g * 3 * n + lead: g * 3 * n + lead + m + m // 8]
+        if m >= 1000:
+            parts.append(_ont(rng, src)[:m])
+        else:
+            q = src[:m].copy()
+            hit = rng.random(m) < args.sub
+            q[hit] = bases[rng.integers(0, 4, int(hit.sum()))]
+            parts.append(q)
+    ql_g = np.array([len(p) for p in parts], np.uint32)
+    qs_g = np.concatenate([[0], np.cumsum(ql_g[:-1], dtype=np.uint64)]).astype(np.uint64)
+    reads = np.concatenate(parts)
+    del parts
+    order = np.argsort(rng.random((G, 5)), axis=1)                 # member k of group g is candidate order[g, k]; 0 = true
+    own = (np.arange(G, dtype=np.uint64) * 3 * n)[:, None]
+    cand = np.concatenate([own + np.arange(3, dtype=np.uint64)[None, :] * n,
+                           rng.integers(0, len(genome) - n, (G, 2)).astype(np.uint64)], axis=1)
+    ts = np.take_along_axis(cand, order, axis=1).reshape(-1)
+    tl = np.full(5 * G, n, np.uint32)
+    rc = np.zeros(5 * G, np.uint8)
+    qs, ql = np.repeat(qs_g, 5), np.repeat(ql_g, 5)
+    off = (np.arange(G + 1, dtype=np.uint32) * 5)
+    true_at = np.argmin(order, axis=1).astype(np.uint32)
+    wrong_at = np.argmax(order, axis=1).astype(np.uint32)          # an unrelated window
+    mg = np.full(G, margin, np.uint32)
+
+    v = verify.Verifier()
+    v.load_genome(genome)
+    batch = (reads, ts, tl, rc, qs, ql)
+    a_ms, a_wall = [], []
+    for _ in range(args.repeat):
+        t0 = time.perf_counter()
+        score, begin, co, cg = v.align(*batch)
+        a_wall.append(time.perf_counter() - t0)
+        a_ms.append(v.stats()["ms_kernels"])
+    cells = v.stats()["cells"]
+    ref_cols = np.where((cg & 15) != 1, cg >> 4, 0).astype(np.int64)
+    run_sum = np.concatenate([[0], np.cumsum(ref_cols)])
+    d = -score.astype(np.int64)
+    end = begin.astype(np.int64) + run_sum[co[1:].astype(np.int64)] - run_sum[co[:-1].astype(np.int64)]
+    del cg
+    bounded = {}
+    for rate in (0.15, 0.1):
+        b_ms, b_screen = [], []
+        for _ in range(args.repeat):
+            v.align_bounded(*batch, (np.float32(rate) * ql.astype(np.float32)).astype(np.uint32))
+            b_ms.append(v.stats()["ms_kernels"])
+            b_screen.append(v.bounded_stats()["ms_screen"])
+        bst = v.bounded_stats()
+        bounded[str(rate)] = {"ms_kernels": b_ms, "ms_screen": b_screen, "rejected_share": bst["n_rejected"] / (5 * G),
+                              "screen_cells_share": bst["screen_cells"] / max(cells, 1)}
+    want = verify.select_best(d, end, off, mg)
+    runs = {}
+    for name, hint in (("hint_true", true_at), ("hint_wrong", wrong_at)):
+        ms, wall, dist, pick = [], [], [], []
+        for _ in range(args.repeat):
+            t0 = time.perf_counter()
+            got = v.align_best(*batch, off, mg, hint)
+            wall.append(time.perf_counter() - t0)
+            ms.append(v.stats()["ms_kernels"])
+            st = v.best_stats()
+            dist.append(st["ms_distance"])
+            pick.append(st["ms_pick"])
+        wins = got["winner"]
+        ok = bool(np.array_equal(wins, want[0]) and np.array_equal(got["edits"], want[1]) and np.array_equal(got["end"], want[2])
+                  and np.array_equal(got["score"][wins], score[wins]) and np.array_equal(got["begin"][wins], begin[wins]))
+        runs[name] = {"ms_kernels": ms, "ms_distance": dist, "ms_pick": pick,
+                      "ms_full_alignments": [a - b - c for a, b, c in zip(ms, dist, pick)], "wall_s": wall,
+                      **{k: st[k] for k in ("n_seed", "n_distance", "n_beyond", "n_undecided", "n_realigned", "distance_cells")},
+                      "distance_cells_share": st["distance_cells"] / max(cells, 1),
+                      "full_alignments_per_group": (st["n_seed"] + st["n_undecided"] + st["n_realigned"]) / G,
+                      "best_over_align": min(ms) / min(a_ms), "checks": {"identical_to_align_plus_select_best": ok}}
+    print(json.dumps({
+        "metric": "bmv_align_best kernels ms (hint = true locus)", "value": min(runs["hint_true"]["ms_kernels"]), "unit": "ms",
+        "config": {"groups": G, "candidates": 5, "query_len": m, "text_len": n, "margin": margin},
+        "cells": cells, "true_locus_wins": float((want[0] == off[:-1] + true_at).mean()), "mean_edits_true": float(d[off[:-1] + true_at].mean()),
+        "align": {"ms_kernels": a_ms, "wall_s": a_wall}, "align_bounded": bounded, "align_best": runs}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--best", action="store_true", help="Verifier.align_best on groups of five candidates (see best_main)")
+    ap.add_argument("--groups", type=int, default=20_000)
+    ap.add_argument("--text-len", type=int, default=0, help="--best: the window's length (default: as the tool computes it)")
+    ap.add_argument("--margin-rate", type=float, default=0.05, help="--best: margin = max(1, rate x query length)")
     ap.add_argument("--reads", type=int, default=1_000_000)
     ap.add_argument("--len", type=int, default=300)
     ap.add_argument("--indel-rate", type=float, default=0.02)
@@ -114,6 +221,8 @@ def main():
     from bucket_map_amd import verify
     if args.long:
         return long_main(args)
+    if args.best:
+        return best_main(args)
 
     rng = np.random.default_rng(20240003)
     m = args.len
