@@ -119,10 +119,25 @@ inline hipError_t upload_pageable_records(void *dst, const uint8_t *const *rec, 
 // Grow-only buffers: a context or batch that is used again keeps its allocations.  need(n) leaves headroom (batches of a
 // file differ a little in size), need_exact(n) takes what is asked; either holds at least one element.  DevBuf lives in
 // device memory; PinnedBuf is page-locked host memory, staging for asynchronous copies.  `cap` counts elements.
+// A buffer owns its memory: it frees it when it goes (so a context's `delete` releases every buffer it holds, with the
+// context's device current), moves and does not copy.  None may have static storage: it would free after the runtime is gone.
 template <typename T, bool kPinned>
 struct GrowBuf {
     T *p = nullptr;
     size_t cap = 0;
+    GrowBuf() = default;
+    ~GrowBuf() { release(); }
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    GrowBuf(GrowBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    GrowBuf &operator=(GrowBuf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
     hipError_t need(size_t n) {
         const size_t bytes = n * sizeof(T);
         return grow(n, kPinned ? bytes + bytes / 8 + 64 : ((n ? n : 1) + n / 8) * sizeof(T));

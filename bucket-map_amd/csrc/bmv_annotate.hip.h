@@ -163,4 +163,8 @@ __global__ __launch_bounds__(64 * kAnnotateWaves) void bmv_annotate_kernel(Annot
     }
 }
 
+// instantiated in bmv_annotate.hip
+extern template __global__ void bmv_annotate_kernel<false>(AnnotateJob);
+extern template __global__ void bmv_annotate_kernel<true>(AnnotateJob);
+
 }  // namespace bmv

@@ -2,72 +2,28 @@
 // Host side only: validation, choice of the kernel shape for the longest query of the batch, chunking so
 // that the traceback bits of one chunk fit the scratch budget, offsets of the packed CIGAR output
 // (bm_scan.hip.h's exclusive sum).
+// The steps every entry point shares -- checking and uploading a batch's views, a sub-batch through bmv_align_long, the
+// band lists of the screen and the distance round, CIGARs to the host, the two passes of annotate and clip -- are the
+// helpers in front of `extern "C"`; the kernels a step launches are instantiated in the files their headers name.
+#include "../../include/bmv.h"
+
+#include "bm_hip_util.h"
+#include "bm_scan.hip.h"
 #include "bmv_annotate.hip.h"
 #include "bmv_best.hip.h"
 #include "bmv_clip.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_screen.hip.h"
 
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
 namespace bmv {
-// instantiated in bmv_variants.hip
-extern template __global__ void bmv_align_kernel<4, 5, false>(Job);
-extern template __global__ void bmv_align_kernel<4, 6, false>(Job);
-extern template __global__ void bmv_align_kernel<4, 7, false>(Job);
-extern template __global__ void bmv_align_kernel<4, 8, false>(Job);
-extern template __global__ void bmv_align_kernel<8, 4, false>(Job);
-extern template __global__ void bmv_align_kernel<8, 5, false>(Job);
-extern template __global__ void bmv_align_kernel<8, 6, false>(Job);
-extern template __global__ void bmv_align_kernel<8, 7, false>(Job);
-extern template __global__ void bmv_align_kernel<8, 8, false>(Job);
-extern template __global__ void bmv_align_kernel<4, 6, true>(Job);
-extern template __global__ void bmv_align_kernel<4, 8, true>(Job);
-extern template __global__ void bmv_align_lane_kernel<1>(Job);
-extern template __global__ void bmv_align_lane_kernel<2>(Job);
-extern template __global__ void bmv_align_lane_kernel<3>(Job);
-extern template __global__ void bmv_align_lane_kernel<4>(Job);
-extern template __global__ void bmv_align_lane_kernel<5>(Job);
-extern template __global__ void bmv_align_lane_kernel<6>(Job);
-extern template __global__ void bmv_align_lane_kernel<7>(Job);
-extern template __global__ void bmv_align_lane_kernel<8>(Job);
-// instantiated in bmv_long.hip
-extern template __global__ void bmv_long_prep_kernel<kLongCw>(LongJob, uint32_t);
-extern template __global__ void bmv_long_tile_kernel<kLongCw>(LongJob);
-extern template __global__ void bmv_long_traceback_kernel<kLongCw>(LongJob);
-
-// instantiated in bmv_screen.hip
-extern template __global__ void bmv_screen_lane_kernel<1>(ScreenJob);
-extern template __global__ void bmv_screen_lane_kernel<2>(ScreenJob);
-extern template __global__ void bmv_screen_lane_kernel<3>(ScreenJob);
-extern template __global__ void bmv_screen_lane_kernel<4>(ScreenJob);
-extern template __global__ void bmv_screen_lane_kernel<5>(ScreenJob);
-extern template __global__ void bmv_screen_lane_kernel<6>(ScreenJob);
-extern template __global__ void bmv_screen_lane_kernel<7>(ScreenJob);
-extern template __global__ void bmv_screen_lane_kernel<8>(ScreenJob);
-extern template __global__ void bmv_screen_wave_kernel<1>(ScreenJob);
-extern template __global__ void bmv_screen_wave_kernel<2>(ScreenJob);
-extern template __global__ void bmv_screen_wave_kernel<4>(ScreenJob);
-
-// instantiated in bmv_annotate.hip
-extern template __global__ void bmv_annotate_kernel<false>(AnnotateJob);
-extern template __global__ void bmv_annotate_kernel<true>(AnnotateJob);
-
-// instantiated in bmv_clip.hip
-extern template __global__ void bmv_clip_range_kernel<kAnnotateWaves>(ClipJob);
-extern template __global__ void bmv_clip_emit_kernel<false>(ClipJob);
-extern template __global__ void bmv_clip_emit_kernel<true>(ClipJob);
-
-// (bmv_best.hip)
-extern template __global__ void bmv_best_lane_kernel<1>(BestJob);
-extern template __global__ void bmv_best_lane_kernel<2>(BestJob);
-extern template __global__ void bmv_best_lane_kernel<3>(BestJob);
-extern template __global__ void bmv_best_lane_kernel<4>(BestJob);
-extern template __global__ void bmv_best_lane_kernel<5>(BestJob);
-extern template __global__ void bmv_best_lane_kernel<6>(BestJob);
-extern template __global__ void bmv_best_lane_kernel<7>(BestJob);
-extern template __global__ void bmv_best_lane_kernel<8>(BestJob);
-extern template __global__ void bmv_best_wave_kernel<1>(BestJob);
-extern template __global__ void bmv_best_wave_kernel<2>(BestJob);
-extern template __global__ void bmv_best_wave_kernel<4>(BestJob);
 
 // CIGAR entries of one chunk, reversed into reading order at their final offsets.
 __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t ops_stride,
@@ -82,18 +38,6 @@ __global__ void bmv_gather_kernel(const uint32_t *__restrict__ ops_rev, uint32_t
 }
 
 }  // namespace bmv
-#include "bm_hip_util.h"
-
-#include "../../include/bmv.h"
-
-#include "bm_scan.hip.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
 
 #define HIP_TRY(expr) BM_HIP_TRY(expr, BMV_ERR_HIP)
 
@@ -183,10 +127,26 @@ Shape pick_shape(uint32_t words, uint32_t max_n) {
     return {g, 1, bmv::bmv_align_kernel<16, 1, false>, false};
 }
 
+// What the two-pass emit of bmv_annotate and bmv_clip writes on the device ...
+struct EmitDev {
+    DevBuf<uint32_t> nm, pos, ref_len, n_xcigar, n_ref, xcigar;
+    DevBuf<uint64_t> xcigar_offset, ref_offset;
+    DevBuf<uint8_t> ref_bases;
+};
+// ... and what it leaves on the host, with the call's stats
+struct EmitHost {
+    std::vector<uint32_t> nm, pos, ref_len, xcigar;
+    std::vector<uint64_t> xcigar_offset, ref_offset;
+    std::vector<uint8_t> ref_bases;
+    float ms = 0.f;
+    uint64_t n_columns = 0;
+};
+
 }  // namespace
 
 constexpr uint32_t kSideStreams = 4;
 
+// Every device buffer is a DevBuf: `delete` frees them all, bmv_destroy handles only what has an order.
 struct bmv_ctx {
     bmv_params p{};
     hipStream_t stream = nullptr;
@@ -215,27 +175,19 @@ struct bmv_ctx {
     uint32_t n_rejected = 0;
     uint64_t screen_cells = 0;
     float ms_screen = 0.f;
-    // bmv_annotate: its own device buffers and host results (bmv_results / bmv_last_stats keep what the last align left)
-    DevBuf<uint32_t> an_begin, an_cigar, an_nm, an_pos, an_ref_len, an_n_xcigar, an_n_ref, an_xcigar;
-    DevBuf<uint64_t> an_cigar_offset, an_xcigar_offset, an_ref_offset;
-    DevBuf<uint8_t> an_ref_bases;
-    std::vector<uint32_t> h_an_nm, h_an_pos, h_an_ref_len, h_an_xcigar;
-    std::vector<uint64_t> h_an_xcigar_offset, h_an_ref_offset;
-    std::vector<uint8_t> h_an_ref_bases;
-    float ms_annotate = 0.f;
-    uint64_t n_columns = 0;
-    // bmv_clip: the inputs go through bmv_annotate's device buffers (its results are on the host by then), the outputs and
-    // the host results are its own (bmv_annotations keeps what the last bmv_annotate left)
+    // bmv_annotate and bmv_clip: the inputs beyond the views, and the emit's outputs -- one set on the device (a call's
+    // results are on the host when it returns), one per call on the host (bmv_results / bmv_last_stats keep what the last
+    // align left, bmv_annotations what the last bmv_annotate left)
+    DevBuf<uint32_t> an_begin, an_cigar;
+    DevBuf<uint64_t> an_cigar_offset;
+    EmitDev emit;
+    EmitHost h_an, h_cl;
+    // bmv_clip: what it writes beside the emit's outputs
     DevBuf<int64_t> cl_score;
-    DevBuf<uint64_t> cl_l, cl_r, cl_xcigar_offset, cl_ref_offset;
-    DevBuf<uint32_t> cl_pos0, cl_left, cl_right, cl_nm, cl_pos, cl_ref_len, cl_n_xcigar, cl_n_ref, cl_xcigar;
-    DevBuf<uint8_t> cl_ref_bases;
+    DevBuf<uint64_t> cl_l, cl_r;
+    DevBuf<uint32_t> cl_pos0, cl_left, cl_right;
     std::vector<int64_t> h_cl_score;
-    std::vector<uint32_t> h_cl_left, h_cl_right, h_cl_nm, h_cl_pos, h_cl_ref_len, h_cl_xcigar;
-    std::vector<uint64_t> h_cl_xcigar_offset, h_cl_ref_offset;
-    std::vector<uint8_t> h_cl_ref_bases;
-    float ms_clip = 0.f;
-    uint64_t n_clip_columns = 0;
+    std::vector<uint32_t> h_cl_left, h_cl_right;
     // bmv_align_best: the distance round's and the pick's buffers (the batch's views go through the aligners' own), the
     // host results of bmv_best and what bmv_last_best_stats reports
     DevBuf<uint32_t> bs_bound, bs_list, bs_d, bs_end, bs_full, bs_group_offset, bs_margin, bs_winner, bs_need, bs_need_at,
@@ -248,8 +200,683 @@ struct bmv_ctx {
     float ms_distance = 0.f, ms_pick = 0.f;
 };
 
+namespace {
+
+// Grow with headroom: the longest read differs a little from call to call, and a reallocation is a free, an
+// allocation and a synchronisation of the device each time (the calls themselves are cheap: 0.2-0.5 ms for 45 GiB,
+// tools/malloc_probe.py).
+size_t with_headroom(size_t need, size_t have) { return need <= have ? have : need + need / 4; }
+
+// experiment / test knob: every query of at least this many bases takes the long path (0: off)
+uint32_t long_from() { return getenv("BMV_LONG_FROM") ? (uint32_t)strtoul(getenv("BMV_LONG_FROM"), nullptr, 10) : 0u; }
+
+// an alignment bmv_align does not take: beyond the context's limits, or from BMV_LONG_FROM on
+bool goes_long(const bmv_ctx *c, uint32_t m, uint32_t text_len, uint32_t from) {
+    return m > c->p.max_query_len || text_len > c->p.max_text_len || (from && m >= from);
+}
+
+// every buffer to at least n elements
+template <typename... B>
+hipError_t need_exact_all(size_t n, B &...buf) {
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? buf.need_exact(n) : e), ...);
+    return e;
+}
+
+template <typename T, typename V>
+void copy_out(T *dst, const V &src) {
+    if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof src[0]);
+}
+
+// ---- the host view of a batch: the eight arguments every entry point takes ----
+struct Views {
+    const uint8_t *reads;
+    uint64_t n_read_bytes;
+    const uint64_t *text_start;
+    const uint32_t *text_len;
+    const uint8_t *text_rc;
+    const uint64_t *query_start;
+    const uint32_t *query_len;
+    uint32_t n;
+};
+
+// The null and state checks of the call `who`, in the order every entry point makes them.  outputs_ok: the pointers the call
+// needs whatever n is; extras_ok: its per-alignment arrays beyond the views.
+int check_view_args(const bmv_ctx *c, const char *who, const Views &v, bool outputs_ok, bool extras_ok) {
+    if (!c || !outputs_ok) return fail(BMV_ERR_ARG, "%s: null argument", who);
+    if (!c->loaded) return fail(BMV_ERR_STATE, "%s before bmv_load_genome", who);
+    if (v.n && (!v.text_start || !v.text_len || !v.text_rc || !v.query_start || !v.query_len || !extras_ok || (v.n_read_bytes && !v.reads)))
+        return fail(BMV_ERR_ARG, "%s: null argument", who);
+    return BMV_OK;
+}
+
+// alignment a: its query inside the read buffer, its text inside the genome
+int check_view(const bmv_ctx *c, const Views &v, uint32_t a) {
+    if (v.query_start[a] > v.n_read_bytes || v.query_len[a] > v.n_read_bytes - v.query_start[a])
+        return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
+    if (v.text_start[a] > c->n_genome || v.text_len[a] > c->n_genome - v.text_start[a])
+        return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
+    return BMV_OK;
+}
+
+// ... of every alignment, with the batch's cell count; within_limits: the context's limits hold too (bmv_align)
+int check_view_ranges(const bmv_ctx *c, const Views &v, bool within_limits, uint64_t *cells) {
+    *cells = 0;
+    for (uint32_t a = 0; a < v.n; a++) {
+        if (within_limits && v.query_len[a] > c->p.max_query_len)
+            return fail(BMV_ERR_ARG, "alignment %u: query of %u bases, max_query_len is %u", a, v.query_len[a], c->p.max_query_len);
+        if (within_limits && v.text_len[a] > c->p.max_text_len)
+            return fail(BMV_ERR_ARG, "alignment %u: text of %u bases, max_text_len is %u", a, v.text_len[a], c->p.max_text_len);
+        if (const int rc = check_view(c, v, a)) return rc;
+        *cells += (uint64_t)v.query_len[a] * v.text_len[a];
+    }
+    return BMV_OK;
+}
+
+int check_views(const bmv_ctx *c, const char *who, const Views &v, bool outputs_ok, bool extras_ok, bool within_limits, uint64_t *cells) {
+    if (const int rc = check_view_args(c, who, v, outputs_ok, extras_ok)) return rc;
+    return check_view_ranges(c, v, within_limits, cells);
+}
+
+// The checked batch (n > 0) on its way to the device, on the context's stream (the context's device is current).
+int upload_views(bmv_ctx *c, const Views &v) {
+    const size_t n = v.n;
+    HIP_TRY(c->reads.need_exact((size_t)v.n_read_bytes + 64u));   // (slack: an empty query is still fetched from)
+    HIP_TRY(need_exact_all(n, c->text_start, c->text_len, c->text_rc, c->query_start, c->query_len));
+    if (v.n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, v.reads, (size_t)v.n_read_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_start.p, v.text_start, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_len.p, v.text_len, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->text_rc.p, v.text_rc, n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->query_start.p, v.query_start, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->query_len.p, v.query_len, n * 4, hipMemcpyHostToDevice, c->stream));
+    return BMV_OK;
+}
+
+// the uploaded batch as a kernel sees it: the input pointers the job structs share (AnnotateJob reads no lut; LongJob has the
+// two lengths in its slots)
+template <typename J>
+void fill_views(const bmv_ctx *c, J &j) {
+    j.genome = c->genome.p;
+    j.reads = c->reads.p;
+    j.text_start = c->text_start.p;
+    j.text_rc = c->text_rc.p;
+    j.query_start = c->query_start.p;
+    if constexpr (!std::is_same_v<J, bmv::AnnotateJob>) j.lut = c->lut.p;
+    if constexpr (!std::is_same_v<J, bmv::LongJob>) {
+        j.text_len = c->text_len.p;
+        j.query_len = c->query_len.p;
+    }
+}
+
+// ---- a sub-batch in full ----
+// What bmv_align_long left for the alignments `which` of a batch, taken as a batch of their own: slot s is alignment which[s].
+struct SubResults {
+    std::vector<int32_t> score;
+    std::vector<uint32_t> begin, cigar;
+    std::vector<uint64_t> offset;          // size() + 1 entries
+    float ms = 0.f;
+    uint64_t len(size_t s) const { return offset[s + 1] - offset[s]; }
+};
+
+// The alignments `which` of v through bmv_align_long -- which is bmv_align itself for everything within the context's
+// limits --, exactly what that call does with them on their own; the context's results move to `out`.
+int align_sub_batch(bmv_ctx *c, const Views &v, const std::vector<uint32_t> &which, SubResults &out) {
+    const size_t ns = which.size();
+    std::vector<uint64_t> ts(ns), qs(ns);
+    std::vector<uint32_t> tl(ns), ql(ns);
+    std::vector<uint8_t> trc(ns);
+    for (size_t s = 0; s < ns; s++) {
+        const uint32_t a = which[s];
+        ts[s] = v.text_start[a];
+        tl[s] = v.text_len[a];
+        trc[s] = v.text_rc[a];
+        qs[s] = v.query_start[a];
+        ql[s] = v.query_len[a];
+    }
+    uint64_t tot = 0;
+    if (int rc = bmv_align_long(c, v.reads, v.n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), (uint32_t)ns, &tot)) return rc;
+    out.score = std::move(c->h_score);
+    out.begin = std::move(c->h_begin);
+    out.cigar = std::move(c->h_cigar);
+    out.offset = std::move(c->h_offset);
+    out.ms = c->ms_kernels;
+    return BMV_OK;
+}
+
+// The results of a call in batch order -> the context, where bmv_results and bmv_last_stats read them: alignment a's CIGAR is
+// the len[a] entries of pool from at[a].
+void pack_cigars(bmv_ctx *c, uint32_t n, const std::vector<uint32_t> &pool, const std::vector<uint64_t> &at, const std::vector<uint64_t> &len) {
+    c->h_offset.assign((size_t)n + 1, 0);
+    uint64_t total = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        c->h_offset[a] = total;
+        total += len[a];
+    }
+    c->h_offset[n] = total;
+    c->h_cigar.resize(total);
+    for (uint32_t a = 0; a < n; a++) std::copy_n(pool.data() + at[a], len[a], c->h_cigar.data() + c->h_offset[a]);
+}
+
+void store_results(bmv_ctx *c, uint32_t n, uint64_t cells, float ms, std::vector<int32_t> &score, std::vector<uint32_t> &begin,
+                   const std::vector<uint32_t> &pool, const std::vector<uint64_t> &at, const std::vector<uint64_t> &len, uint64_t *total_cigar) {
+    c->n_last = n;
+    c->n_cells = cells;
+    c->ms_kernels = ms;
+    c->h_score = std::move(score);
+    c->h_begin = std::move(begin);
+    pack_cigars(c, n, pool, at, len);
+    *total_cigar = c->h_cigar.size();
+}
+
+// what full alignments leave, per alignment of a bmv_align_best batch
+struct BestFull {
+    std::vector<int32_t> score;
+    std::vector<uint32_t> begin, r_len, pool;   // r_len: text columns the alignment spans, its M and D lengths
+    std::vector<uint64_t> cig_at, cig_len;      // its CIGAR in pool
+    float ms = 0.f;
+    explicit BestFull(uint32_t n) : score(n, BMV_REJECTED), begin(n, 0), r_len(n, 0), cig_at(n, 0), cig_len(n, 0) {}
+    uint32_t edits(uint32_t a) const { return (uint32_t)(-(int64_t)score[a]); }
+    uint32_t end(uint32_t a) const { return begin[a] + r_len[a]; }
+};
+
+// the alignments `which` in full, into f
+int best_sub_batch(bmv_ctx *c, const Views &v, const std::vector<uint32_t> &which, BestFull &f) {
+    if (which.empty()) return BMV_OK;
+    SubResults sub;
+    if (int rc = align_sub_batch(c, v, which, sub)) return rc;
+    for (size_t s = 0; s < which.size(); s++) {
+        const uint32_t a = which[s];
+        f.score[a] = sub.score[s];
+        f.begin[a] = sub.begin[s];
+        f.cig_at[a] = f.pool.size() + sub.offset[s];
+        f.cig_len[a] = sub.len(s);
+        uint32_t r = 0;
+        for (uint64_t x = sub.offset[s]; x < sub.offset[s + 1]; x++)
+            if ((sub.cigar[x] & 15u) != BMV_OP_I) r += sub.cigar[x] >> 4;
+        f.r_len[a] = r;
+    }
+    f.pool.insert(f.pool.end(), sub.cigar.begin(), sub.cigar.end());
+    f.ms += sub.ms;
+    return BMV_OK;
+}
+
+// ---- the bands of the score-only kernels (the screen of bmv_align_bounded, the distance round of bmv_align_best) ----
+// Both come as one kernel per lane for queries of up to kLaneWords words and as a wave per alignment in three variants of
+// kWaveCw words a lane.  A wrong locus keeps about 2 k rows within a bound of k edits (random bases: D grows by about half
+// a row's worth per row): a longer query goes to the smallest variant whose 64 lanes hold that band, or the whole query.
+constexpr uint32_t kWaveCw[3] = {1, 2, 4};
+
+// -1: the lane kernel; else the wave kernel's variant
+int band_class(uint32_t m, uint32_t k) {
+    const uint32_t words = (m + 63u) / 64u;
+    if (words <= kLaneWords) return -1;
+    const uint64_t band = std::min<uint64_t>(words, ((uint64_t)k * 9u / 4u + 128u) / 64u + 2u);
+    int v = 0;
+    while (v + 1 < 3 && band > 64u * kWaveCw[v]) v++;
+    return v;
+}
+
+struct BandLists {
+    std::vector<uint32_t> lane, wave[3];
+    std::vector<uint32_t> all;              // the lane list, then the wave lists: what the device gets (upload_band_lists)
+    uint32_t lane_words = 1;                // the longest query of the lane list
+    void add(uint32_t a, uint32_t m, uint32_t k) {
+        const int v = band_class(m, k);
+        (v < 0 ? lane : wave[v]).push_back(a);
+        if (v < 0) lane_words = std::max(lane_words, (m + 63u) / 64u);
+    }
+    size_t size() const { return lane.size() + wave[0].size() + wave[1].size() + wave[2].size(); }
+};
+
+int upload_band_lists(bmv_ctx *c, BandLists &b, uint32_t *d_list) {
+    b.all.reserve(b.size());
+    b.all.insert(b.all.end(), b.lane.begin(), b.lane.end());
+    for (const auto &w : b.wave) b.all.insert(b.all.end(), w.begin(), w.end());
+    HIP_TRY(hipMemcpyAsync(d_list, b.all.data(), b.all.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return BMV_OK;
+}
+
+// One lane kernel and up to three wave kernels over the segments of the uploaded list, between the context's two events.
+template <typename J>
+int launch_bands(bmv_ctx *c, const BandLists &b, const uint32_t *d_list, void (*const *per_lane)(J), void (*const *per_wave)(J), J j) {
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    size_t at = 0;
+    if (!b.lane.empty()) {
+        j.list = d_list;
+        j.count = (uint32_t)b.lane.size();
+        hipLaunchKernelGGL(per_lane[b.lane_words], dim3((j.count + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        at += b.lane.size();
+    }
+    for (uint32_t v = 0; v < 3u; v++) {
+        if (b.wave[v].empty()) continue;
+        j.list = d_list + at;
+        j.count = (uint32_t)b.wave[v].size();
+        hipLaunchKernelGGL(per_wave[v], dim3(j.count), dim3(bmv::kWave), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        at += b.wave[v].size();
+    }
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    return BMV_OK;
+}
+
+// ---- CIGARs to the host ----
+// `count` slots from slot0 of nops / offsets, their reversed entries at ops_rev with ops_stride words a slot
+struct GatherPiece {
+    const uint32_t *ops_rev;
+    uint32_t ops_stride, slot0, count;
+};
+
+// CIGARs of `slots` slots (launch order, the pieces' back to back) -> the host, through one exclusive sum and one gather per
+// piece: h_nops gets their lengths, h_packed their entries in slot order.
+int collect_cigars(bmv_ctx *c, const std::vector<GatherPiece> &pieces, uint32_t slots, std::vector<uint32_t> &h_nops, std::vector<uint32_t> &h_packed) {
+    HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(slots) * sizeof(uint32_t)));
+    HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->nops.p, c->offsets.p, slots, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
+    uint32_t total = 0;                                         // the scan writes slots + 1 values: the last is the total
+    HIP_TRY(hipMemcpyAsync(&total, c->offsets.p + slots, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(c->packed.need_exact(with_headroom(total, c->packed.cap)));
+    for (const GatherPiece &pc : pieces) {
+        hipLaunchKernelGGL(bmv::bmv_gather_kernel, dim3((pc.count + 31u) / 32u), dim3(256), 0, c->stream, pc.ops_rev, pc.ops_stride,
+                           c->nops.p + pc.slot0, c->offsets.p + pc.slot0, pc.count, c->packed.p);
+        HIP_TRY(hipGetLastError());
+    }
+    h_nops.resize(slots);
+    h_packed.resize(total);
+    HIP_TRY(hipMemcpyAsync(h_nops.data(), c->nops.p, (size_t)slots * 4, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(h_packed.data(), c->packed.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BMV_OK;
+}
+
+// ---- bmv_align: classes, plans, pieces, rounds ----
+// Length classes.  The kernel's shape -- lanes per alignment, words per lane -- is fixed per launch by the longest query
+// it holds, and a 5-kbp read run in the shape of a 30-kbp one costs six times what it should: the batch is cut into
+// classes of similar query length (in 64-row words; everything up to 8 words -- 512 bases, one alignment per lane -- is
+// one class, so a short-read batch stays one launch; then up to 16 words), each class is a launch series of its own over an index list, and the
+// results find their way back through that list.
+constexpr uint32_t kClassUpTo[] = {kLaneWords, 16, 20, 24, 32, 40, 48, 64, 80, 96, 128, 160, 192, 256, 320, 384, 512, 640, 768, 1024};
+constexpr uint32_t kClasses = sizeof kClassUpTo / sizeof kClassUpTo[0];
+
+struct ClassOrder {
+    uint32_t lo[kClasses + 1] = {0};        // class k is order[lo[k] .. lo[k + 1])
+    uint32_t n_classes = 0;                 // of them, not empty
+    std::vector<uint32_t> order;            // the batch by class, file order within a class
+};
+
+ClassOrder partition_classes(const uint32_t *query_len, uint32_t n) {
+    const bool classes_off = getenv("BMV_ONE_CLASS") != nullptr;    // experiment knob: the whole batch in the longest query's shape
+    auto class_of = [&](uint32_t m) {
+        const uint32_t words = classes_off ? 0u : (m + 63u) / 64u;
+        uint32_t k = 0;
+        while (k + 1u < kClasses && words > kClassUpTo[k]) k++;
+        return k;
+    };
+    ClassOrder co;
+    for (uint32_t a = 0; a < n; a++) co.lo[class_of(query_len[a]) + 1u]++;
+    for (uint32_t k = 0; k < kClasses; k++) {
+        co.n_classes += co.lo[k + 1] ? 1u : 0u;
+        co.lo[k + 1] += co.lo[k];
+    }
+    co.order.resize(n);
+    uint32_t at[kClasses];
+    for (uint32_t k = 0; k < kClasses; k++) at[k] = co.lo[k];
+    for (uint32_t a = 0; a < n; a++) co.order[at[class_of(query_len[a])]++] = a;      // stable: file order within a class
+    return co;
+}
+
+// A batch of one length class (or of a few neighbouring ones: 10-kbp reads with indels straddle a class boundary) gains
+// nothing from more alignments in flight than fill the card, and fresh device memory is not free (the first call that
+// grew the scratch to 90 GB spent 2 s in hipMalloc): only a batch that really mixes lengths -- three classes or more,
+// the longest query at least twice the shortest class's -- may use more than 48 GiB.
+size_t scratch_budget(const bmv_ctx *c, const uint32_t *query_len, uint32_t n, uint32_t n_classes) {
+    uint32_t lo_m = 0xFFFFFFFFu, hi_m = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        lo_m = std::min(lo_m, std::max(query_len[a], 1024u));
+        hi_m = std::max(hi_m, query_len[a]);
+    }
+    if (n_classes >= 3 && hi_m >= 2u * lo_m) return c->scratch_bytes;
+    return std::min<size_t>(c->scratch_bytes, (size_t)48 << 30);
+}
+
+// what a class needs: its kernel, the scratch of one alignment slot, how many slots a launch may hold
+struct Plan {
+    uint32_t lo, members, max_m, trace_words, gpw, n_blocks, ops_stride, lds_stride;
+    Shape sh;
+    uint64_t trace_stride, chunk;
+    size_t lds;
+    uint64_t per_slot() const { return trace_stride / gpw * 8u + (uint64_t)ops_stride * 4u; }   // bytes of scratch
+};
+
+// the plan of the class order[lo .. lo + members)
+int plan_class(const Views &v, const std::vector<uint32_t> &order, uint32_t lo, uint32_t members, size_t budget, Plan &pl) {
+    pl = Plan{};
+    pl.lo = lo;
+    pl.members = members;
+    uint32_t max_m = 0, max_n = 0;
+    for (uint32_t s0 = pl.lo; s0 < pl.lo + pl.members; s0++) {
+        max_m = std::max(max_m, v.query_len[order[s0]]);
+        max_n = std::max(max_n, v.text_len[order[s0]]);
+    }
+    pl.max_m = max_m;
+    // kernel shape for the longest query of the class; scratch per alignment slot
+    const uint32_t words = (max_m + 63u) / 64u;
+    pl.sh = pick_shape(words ? words : 1u, max_n);
+    pl.trace_words = std::max(std::max(words, 1u), pl.sh.group * (uint32_t)pl.sh.cw);   // (more than the words only for strips)
+    pl.gpw = 64u / pl.sh.group;
+    // checkpoints every 16 columns: (Pv, Mv) per word, plus one 32-bit word of horizontal deltas per word and block
+    pl.n_blocks = (max_n + pl.sh.group + 15u) / 16u + 1u;     // blocks of 16 STEPS: the group's last lane is group - 1 steps behind
+    const uint64_t n_entries = (uint64_t)pl.n_blocks * pl.gpw * pl.trace_words;
+    pl.trace_stride = n_entries * 2u + (n_entries + 1u) / 2u;               // 64-bit words per wave
+    pl.trace_stride += 2u * pl.trace_words * pl.gpw;                        // ... and the query's bit planes, for the traceback
+    pl.ops_stride = max_m + max_n + 1u;
+    pl.lds_stride = (max_n + 15u) / 16u * 4u + 4u;                          // the text as a 2-bit stream
+    if (pl.sh.per_lane) pl.lds_stride = (max_n + 63u) / 64u * 16u + 8u;     // ... as two bit planes, 64 columns at a time
+    pl.lds = 256 + (size_t)pl.gpw * pl.lds_stride;
+    if (pl.lds > 160 * 1024) return fail(BMV_ERR_UNSUPPORTED, "text windows of %u bases need %zu B of LDS", max_n, pl.lds);
+    if (pl.lds > 48 * 1024) HIP_TRY(bmhip::raise_dynamic_lds(reinterpret_cast<const void *>(pl.sh.fn), pl.lds));
+    uint64_t chunk = std::max<uint64_t>(pl.gpw, budget / pl.per_slot());
+    chunk = std::min<uint64_t>(chunk, (uint64_t)pl.gpw << 25);   // one wave per gpw alignments: waves * 64 threads < 2^32
+    chunk = std::min<uint64_t>(chunk / pl.gpw * pl.gpw, (uint64_t)pl.members);
+    if (chunk == 0) chunk = pl.members;
+    // pieces of equal size: 40 000 alignments under a limit of 31 000 are 2 x 20 000, not 31 000 + 9 000 (a piece's
+    // last waves run on a card that is emptying, whatever its size)
+    const uint64_t n_pieces = (pl.members + chunk - 1u) / chunk;
+    const uint64_t even = ((pl.members + n_pieces - 1u) / n_pieces + pl.gpw - 1u) / pl.gpw * pl.gpw;
+    pl.chunk = std::min(chunk, even);
+    return BMV_OK;
+}
+
+// a launch: `count` members of a class from `first`, and the scratch they take
+struct Todo {
+    const Plan *pl;
+    uint64_t first;         // within the class
+    uint32_t count;
+    size_t trace_words, ops_words;
+};
+
+// Rounds.  A launch's scratch (checkpoints + reversed CIGAR entries) is what bounds how many alignments are in flight:
+// 19 MB per 30-kbp alignment.  A class of long reads is few waves that each run for tens of milliseconds, so one class
+// at a time leaves most of the card idle (measured on 40 000 alignments of 1 .. 30 kbp: 19.8 T cell updates/s against
+// 37-41 T for uniform batches).  Every class is therefore cut into pieces of at most a THIRD of the scratch budget (when
+// there is more than one class), the pieces -- longest reads first -- are packed into rounds that fit the budget
+// together, and the pieces of a round run side by side on a few streams; their CIGARs are collected once per round.
+// BMV_SERIAL_CLASSES=1: one piece per round (the old behaviour), for comparison.
+std::vector<Todo> cut_pieces(const std::vector<Plan> &plans, size_t budget, bool serial) {
+    std::vector<Todo> todo;
+    for (size_t i = plans.size(); i-- > 0;) {                   // the longest first: they take the longest
+        const Plan &pl = plans[i];
+        uint64_t chunk = pl.chunk;
+        if (plans.size() > 1 && !serial) {
+            const uint64_t third = std::max<uint64_t>(pl.gpw, budget / 3u / pl.per_slot()) / pl.gpw * pl.gpw;
+            chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(third, pl.gpw));
+            const uint64_t n_pieces = (pl.members + chunk - 1u) / chunk;
+            chunk = std::min<uint64_t>(chunk, ((pl.members + n_pieces - 1u) / n_pieces + pl.gpw - 1u) / pl.gpw * pl.gpw);
+        }
+        for (uint64_t first = 0; first < pl.members; first += chunk) {
+            const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, pl.members - first);
+            todo.push_back({&pl, first, count, (size_t)((count + pl.gpw - 1u) / pl.gpw * pl.trace_stride), (size_t)count * pl.ops_stride});
+        }
+    }
+    return todo;
+}
+
+// the pieces of the round that begins at todo[at]: as many as fit the budget (at least one); returns where it ends
+size_t round_end(const std::vector<Todo> &todo, size_t at, size_t budget, bool serial) {
+    size_t end = at, sum_trace = 0, sum_ops = 0;
+    while (end < todo.size() &&
+           (end == at || (!serial && (sum_trace + todo[end].trace_words) * 8u + (sum_ops + todo[end].ops_words) * 4u <= budget))) {
+        sum_trace += todo[end].trace_words;
+        sum_ops += todo[end].ops_words;
+        end++;
+    }
+    return end;
+}
+
+int launch_piece(bmv_ctx *c, const Todo &t, hipStream_t stream, uint64_t *trace, uint32_t *ops_rev, uint32_t *nops, uint32_t stop_after) {
+    const Plan &pl = *t.pl;
+    bmv::Job j{};
+    fill_views(c, j);
+    j.order = c->order.p + pl.lo + t.first;
+    j.count = t.count;
+    j.trace = trace;
+    j.trace_stride = pl.trace_stride;
+    j.trace_words = pl.trace_words;
+    j.trace_blocks = pl.n_blocks;
+    j.group = pl.sh.group;
+    j.ops_rev = ops_rev;
+    j.ops_stride = pl.ops_stride;
+    j.text_lds_stride = pl.lds_stride;
+    j.out_score = c->out_score.p;
+    j.out_begin = c->out_begin.p;
+    j.out_nops = nops;
+    j.stop_after = stop_after;
+    hipLaunchKernelGGL(pl.sh.fn, dim3((t.count + pl.gpw - 1u) / pl.gpw), dim3(bmv::kWave), pl.lds, stream, j);
+    HIP_TRY(hipGetLastError());
+    return BMV_OK;
+}
+
+// Where the CIGARs of the rounds go.  One class: order is the identity and they arrive in place, in c->h_cigar with their
+// offsets in c->h_offset.  Else they are kept aside in launch order until every length is known (pack_cigars).
+struct CigarStash {
+    bool in_place;
+    std::vector<uint32_t> pool;
+    std::vector<uint64_t> at, len;          // per alignment of the batch
+    std::vector<uint32_t> h_nops, h_packed; // a round's, as collect_cigars leaves them
+};
+
+// The round todo[at .. end): the pieces launched side by side (alone: on the context's stream), their CIGARs collected into
+// `stash`, the round's time added to c->ms_kernels.
+int run_round(bmv_ctx *c, const std::vector<Todo> &todo, size_t at, size_t end, const std::vector<uint32_t> &order, uint32_t stop_after,
+              CigarStash &stash) {
+    size_t sum_trace = 0, sum_ops = 0, slots = 0;
+    for (size_t i = at; i < end; i++) {
+        sum_trace += todo[i].trace_words;
+        sum_ops += todo[i].ops_words;
+        slots += todo[i].count;
+    }
+    HIP_TRY(c->trace.need_exact(with_headroom(sum_trace, c->trace.cap)));
+    HIP_TRY(c->ops_rev.need_exact(with_headroom(sum_ops, c->ops_rev.cap)));
+    HIP_TRY(c->nops.need_exact(with_headroom(slots, c->nops.cap)));
+    HIP_TRY(c->offsets.need_exact(with_headroom(slots + 1, c->offsets.cap)));
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));             // the uploads above / the round before
+    std::vector<GatherPiece> pieces;
+    size_t trace_at = 0, ops_at = 0;
+    uint32_t slot_at = 0;
+    const bool alone = end - at == 1;
+    for (size_t i = at; i < end; i++) {
+        const Todo &t = todo[i];
+        hipStream_t st = alone ? c->stream : c->side[(i - at) % kSideStreams];
+        if (!alone) HIP_TRY(hipStreamWaitEvent(st, c->ev0, 0));
+        if (int rc = launch_piece(c, t, st, c->trace.p + trace_at, c->ops_rev.p + ops_at, c->nops.p + slot_at, stop_after)) return rc;
+        pieces.push_back({c->ops_rev.p + ops_at, t.pl->ops_stride, slot_at, t.count});
+        trace_at += t.trace_words;
+        ops_at += t.ops_words;
+        slot_at += t.count;
+    }
+    if (!alone)
+        for (uint32_t k = 0; k < kSideStreams; k++) {       // the main stream goes on when all of them are done
+            HIP_TRY(hipEventRecord(c->side_done[k], c->side[k]));
+            HIP_TRY(hipStreamWaitEvent(c->stream, c->side_done[k], 0));
+        }
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    if (int rc = collect_cigars(c, pieces, slot_at, stash.h_nops, stash.h_packed)) return rc;
+    std::vector<uint32_t> &dst = stash.in_place ? c->h_cigar : stash.pool;
+    uint64_t cig_at = dst.size();
+    for (size_t i = at; i < end; i++) {                         // in slot order, and the slots are theirs back to back
+        const Todo &t = todo[i];
+        for (uint32_t s0 = 0; s0 < t.count; s0++) {
+            const uint32_t len = stash.h_nops[pieces[i - at].slot0 + s0];
+            if (stash.in_place) {
+                c->h_offset[t.first + s0] = cig_at;
+            } else {
+                const uint32_t a = order[t.pl->lo + t.first + s0];
+                stash.len[a] = len;
+                stash.at[a] = cig_at;
+            }
+            cig_at += len;
+        }
+    }
+    dst.insert(dst.end(), stash.h_packed.begin(), stash.h_packed.end());
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->ms_kernels += ms;
+    if (getenv("BMV_LOG_CLASSES")) {
+        fprintf(stderr, "[bmv] round of %zu piece(s), %.2f ms:", end - at, ms);
+        for (size_t i = at; i < end; i++)
+            fprintf(stderr, " [up to %u bases: %u of %u alignments, %u lanes x %d words]", todo[i].pl->max_m, todo[i].count,
+                    todo[i].pl->members, todo[i].pl->sh.group, todo[i].pl->sh.cw);
+        fprintf(stderr, "\n");
+    }
+    return BMV_OK;
+}
+
+// ---- bmv_annotate and bmv_clip ----
+// The annotation pass (include/bmv.h, bmv_annotate.hip.h) and the clipping pass (bmv_clip.hip.h) take the same batch.
+// Everything a kernel relies on is checked here first -- the views, the CIGAR alphabet, that every CIGAR consumes exactly
+// its query and stays inside its window -- so that the kernels index without bounds checks.  `who`: the call, for the message.
+int check_annotate_batch(bmv_ctx *c, const char *who, const Views &v, const uint32_t *begin, const uint64_t *cigar_offset,
+                         const uint32_t *cigar, uint64_t *out_columns) {
+    uint64_t columns = 0;
+    for (uint32_t a = 0; a < v.n; a++) {
+        if (const int rc = check_view(c, v, a)) return rc;
+        if (cigar_offset[a + 1] < cigar_offset[a] || cigar_offset[a + 1] - cigar_offset[a] > 0xFFFFFFFFull - v.query_len[a])
+            return fail(BMV_ERR_ARG, "alignment %u: CIGAR offsets %llu .. %llu", a, (unsigned long long)cigar_offset[a],
+                        (unsigned long long)cigar_offset[a + 1]);
+        if (cigar_offset[a + 1] > cigar_offset[a] && !cigar) return fail(BMV_ERR_ARG, "%s: null argument", who);
+        if (cigar_offset[a + 1] == cigar_offset[a]) continue;   // an empty CIGAR: zeros and no entries, whatever the views hold
+        uint64_t in_query = 0, in_text = 0, cols = 0;
+        uint32_t before = 0xFFFFFFFFu;
+        for (uint64_t x = cigar_offset[a]; x < cigar_offset[a + 1]; x++) {
+            const uint32_t op = cigar[x] & 15u, len = cigar[x] >> 4;
+            const unsigned long long k = (unsigned long long)(x - cigar_offset[a]);
+            if (op > BMV_OP_D) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entry %llu has op code %u (M, I and D are taken)", a, k, op);
+            if (len == 0) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entry %llu has length 0", a, k);
+            if (op == before) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entries %llu and %llu share an op", a, k - 1u, k);
+            before = op;
+            if (op != BMV_OP_D) in_query += len;
+            if (op != BMV_OP_I) in_text += len;
+            cols += len;
+        }
+        if (in_query != v.query_len[a])
+            return fail(BMV_ERR_ARG, "alignment %u: the CIGAR consumes %llu query bases, the query has %u", a,
+                        (unsigned long long)in_query, v.query_len[a]);
+        if ((uint64_t)begin[a] + in_text > v.text_len[a])
+            return fail(BMV_ERR_ARG, "alignment %u: begin %u + %llu reference bases run past the window of %u", a, begin[a],
+                        (unsigned long long)in_text, v.text_len[a]);
+        columns += cols;
+    }
+    *out_columns = columns;
+    return BMV_OK;
+}
+
+// The checked batch (n > 0) on its way to the device, on the context's stream; j receives the input pointers.  `rebased` is
+// the caller's: the copy out of it may still be under way on return.
+int upload_annotate_batch(bmv_ctx *c, const Views &v, const uint32_t *begin, const uint64_t *cigar_offset, const uint32_t *cigar,
+                          std::vector<uint64_t> &rebased, bmv::AnnotateJob &j) {
+    const size_t n = v.n;
+    const uint64_t cig0 = cigar_offset[0], n_cigar = cigar_offset[n] - cig0;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(c->an_begin.need_exact(n));
+    HIP_TRY(c->an_cigar_offset.need_exact(n + 1u));
+    HIP_TRY(c->an_cigar.need((size_t)n_cigar));
+    HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n) * sizeof(uint64_t)));
+    if (const int rc = upload_views(c, v)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->an_begin.p, begin, n * 4, hipMemcpyHostToDevice, c->stream));
+    rebased.assign(cigar_offset, cigar_offset + n + 1u);                            // the device holds cigar[cig0 ..) only
+    for (uint64_t &o : rebased) o -= cig0;
+    HIP_TRY(hipMemcpyAsync(c->an_cigar_offset.p, rebased.data(), (n + 1u) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_cigar) HIP_TRY(hipMemcpyAsync(c->an_cigar.p, cigar + cig0, (size_t)n_cigar * 4, hipMemcpyHostToDevice, c->stream));
+    fill_views(c, j);
+    j.begin = c->an_begin.p;
+    j.cigar_offset = c->an_cigar_offset.p;
+    j.cigar = c->an_cigar.p;
+    j.count = v.n;
+    return BMV_OK;
+}
+
+// what a call of either leaves before anything runs: n alignments of zeros and no entries
+void reset_emit(EmitHost &h, uint32_t n, uint64_t columns) {
+    h.nm.assign(n, 0);
+    h.pos.assign(n, 0);
+    h.ref_len.assign(n, 0);
+    h.xcigar_offset.assign((size_t)n + 1, 0);
+    h.ref_offset.assign((size_t)n + 1, 0);
+    h.xcigar.clear();
+    h.ref_bases.clear();
+    h.ms = 0.f;
+    h.n_columns = columns;
+}
+
+// The two passes over an uploaded batch (j's inputs are filled): count pass -> two 64-bit exclusive sums -> the offsets to the
+// host -> the outputs sized -> write pass -> download into h.  `count` and `write` launch the caller's kernels on the
+// context's stream once j's outputs of that pass are set; `more` queues the caller's own downloads in front of the common
+// ones.  who / passes: for the log line.
+template <typename Count, typename Write, typename More>
+int two_pass_emit(bmv_ctx *c, const char *who, const char *passes, bmv::AnnotateJob &j, EmitHost &h, Count count, Write write, More more,
+                  uint64_t *total_xcigar, uint64_t *total_ref_bases) {
+    const size_t n = j.count;
+    EmitDev &d = c->emit;
+    HIP_TRY(need_exact_all(n, d.nm, d.pos, d.ref_len, d.n_xcigar, d.n_ref));
+    HIP_TRY(need_exact_all(n + 1u, d.xcigar_offset, d.ref_offset));
+    j.nm = d.nm.p;
+    j.pos = d.pos.p;
+    j.ref_len = d.ref_len.p;
+    j.n_xcigar = d.n_xcigar.p;
+    j.n_ref = d.n_ref.p;
+    uint64_t *scan_tmp = reinterpret_cast<uint64_t *>(c->scan_tmp.p);
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(count());
+    HIP_TRY(bmscan::exclusive_sum<uint64_t>(d.n_xcigar.p, d.xcigar_offset.p, n, scan_tmp, c->stream));
+    HIP_TRY(bmscan::exclusive_sum<uint64_t>(d.n_ref.p, d.ref_offset.p, n, scan_tmp, c->stream));
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.xcigar_offset.data(), d.xcigar_offset.p, (n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.ref_offset.data(), d.ref_offset.p, (n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms_count = 0.f, ms_write = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_count, c->ev0, c->ev1));
+    const uint64_t n_x = h.xcigar_offset[n], n_r = h.ref_offset[n];
+    HIP_TRY(d.xcigar.need_exact(with_headroom((size_t)n_x, d.xcigar.cap)));
+    HIP_TRY(d.ref_bases.need_exact(with_headroom((size_t)n_r, d.ref_bases.cap)));
+    j.xcigar_offset = d.xcigar_offset.p;
+    j.ref_offset = d.ref_offset.p;
+    j.xcigar = d.xcigar.p;
+    j.ref_bases = d.ref_bases.p;
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(write());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    h.xcigar.resize((size_t)n_x);
+    h.ref_bases.resize((size_t)n_r);
+    HIP_TRY(more());
+    HIP_TRY(hipMemcpyAsync(h.nm.data(), d.nm.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.pos.data(), d.pos.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.ref_len.data(), d.ref_len.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_x) HIP_TRY(hipMemcpyAsync(h.xcigar.data(), d.xcigar.p, (size_t)n_x * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_r) HIP_TRY(hipMemcpyAsync(h.ref_bases.data(), d.ref_bases.p, (size_t)n_r, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&ms_write, c->ev0, c->ev1));
+    h.ms = ms_count + ms_write;
+    if (getenv("BMV_LOG_CLASSES"))
+        fprintf(stderr, "[bmv] %s: %zu alignments, %s and scans %.3f ms, write pass %.3f ms\n", who, n, passes, ms_count, ms_write);
+    *total_xcigar = n_x;
+    *total_ref_bases = n_r;
+    return BMV_OK;
+}
+
+// what bmv_annotations and bmv_clipped share
+void copy_emit(const EmitHost &h, uint32_t *out_nm, uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset,
+               uint32_t *out_xcigar, uint64_t *out_ref_offset, uint8_t *out_ref_bases) {
+    copy_out(out_nm, h.nm);
+    copy_out(out_pos, h.pos);
+    copy_out(out_ref_len, h.ref_len);
+    copy_out(out_xcigar_offset, h.xcigar_offset);
+    copy_out(out_xcigar, h.xcigar);
+    copy_out(out_ref_offset, h.ref_offset);
+    copy_out(out_ref_bases, h.ref_bases);
+}
+
 // bmv_load_genome(_records) after their argument checks: the genome is the n_records records back to back (n_bases in all)
-static int load_genome(bmv_ctx *c, const uint8_t *const *rec, const uint64_t *rec_len, uint32_t n_records, uint64_t n_bases) {
+int load_genome(bmv_ctx *c, const uint8_t *const *rec, const uint64_t *rec_len, uint32_t n_records, uint64_t n_bases) {
     HIP_TRY(hipSetDevice(c->p.device));
     HIP_TRY(c->genome.need_exact((size_t)n_bases + 64u));       // (slack: an empty text window at the very end is still fetched from)
     HIP_TRY(bmhip::upload_pageable_records(c->genome.p, rec, rec_len, n_records));
@@ -257,6 +884,8 @@ static int load_genome(bmv_ctx *c, const uint8_t *const *rec, const uint64_t *re
     c->loaded = true;
     return BMV_OK;
 }
+
+}  // namespace
 
 extern "C" {
 
@@ -304,6 +933,8 @@ int bmv_create(const bmv_params *params, bmv_ctx **out) {
     return BMV_OK;
 }
 
+// What has an order: the device, the streams drained before anything of theirs goes, the buffers (`delete`: every DevBuf of
+// the context frees itself) while the device is still the context's.
 void bmv_destroy(bmv_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->p.device);
@@ -315,22 +946,6 @@ void bmv_destroy(bmv_ctx *c) {
         }
         if (c->side_done[k]) (void)hipEventDestroy(c->side_done[k]);
     }
-    c->genome.release(); c->lut.release(); c->reads.release(); c->text_rc.release(); c->scan_tmp.release();
-    c->text_start.release(); c->query_start.release(); c->trace.release();
-    c->text_len.release(); c->query_len.release(); c->ops_rev.release(); c->nops.release(); c->offsets.release();
-    c->packed.release(); c->out_begin.release(); c->out_score.release(); c->order.release();
-    c->long_slots.release(); c->long_tiles.release();
-    c->max_edits.release(); c->keep.release(); c->keep_at.release(); c->survivors.release(); c->screen_list.release();
-    c->screen_count.release();
-    c->bs_bound.release(); c->bs_list.release(); c->bs_d.release(); c->bs_end.release(); c->bs_full.release();
-    c->bs_group_offset.release(); c->bs_margin.release(); c->bs_winner.release(); c->bs_need.release(); c->bs_need_at.release();
-    c->bs_realign.release(); c->bs_edits.release(); c->bs_out_end.release(); c->bs_count.release();
-    c->an_begin.release(); c->an_cigar.release(); c->an_nm.release(); c->an_pos.release(); c->an_ref_len.release();
-    c->an_n_xcigar.release(); c->an_n_ref.release(); c->an_xcigar.release(); c->an_cigar_offset.release();
-    c->an_xcigar_offset.release(); c->an_ref_offset.release(); c->an_ref_bases.release();
-    c->cl_score.release(); c->cl_l.release(); c->cl_r.release(); c->cl_xcigar_offset.release(); c->cl_ref_offset.release();
-    c->cl_pos0.release(); c->cl_left.release(); c->cl_right.release(); c->cl_nm.release(); c->cl_pos.release();
-    c->cl_ref_len.release(); c->cl_n_xcigar.release(); c->cl_n_ref.release(); c->cl_xcigar.release(); c->cl_ref_bases.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -352,25 +967,14 @@ int bmv_load_genome_records(bmv_ctx *c, const uint8_t *const *rec, const uint64_
     return load_genome(c, rec, rec_len, n_records, n_bases);
 }
 
+// The batch by length class (partition_classes), a plan per class (plan_class), the plans cut into pieces (cut_pieces) and
+// the pieces packed into rounds (round_end, run_round).
 int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
               const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
               uint32_t n, uint64_t *total_cigar) {
-    if (!c || !total_cigar) return fail(BMV_ERR_ARG, "bmv_align: null argument");
-    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_align before bmv_load_genome");
-    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || (n_read_bytes && !reads)))
-        return fail(BMV_ERR_ARG, "bmv_align: null argument");
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
     uint64_t cells = 0;
-    for (uint32_t a = 0; a < n; a++) {
-        if (query_len[a] > c->p.max_query_len)
-            return fail(BMV_ERR_ARG, "alignment %u: query of %u bases, max_query_len is %u", a, query_len[a], c->p.max_query_len);
-        if (text_len[a] > c->p.max_text_len)
-            return fail(BMV_ERR_ARG, "alignment %u: text of %u bases, max_text_len is %u", a, text_len[a], c->p.max_text_len);
-        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
-        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
-        cells += (uint64_t)query_len[a] * text_len[a];
-    }
+    if (const int rc = check_views(c, "bmv_align", v, total_cigar != nullptr, true, true, &cells)) return rc;
     c->n_last = n;
     c->n_cells = cells;
     c->ms_kernels = 0.f;
@@ -382,286 +986,33 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
     if (n == 0) return BMV_OK;
 
     HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));   // (slack: so is an empty query)
-    HIP_TRY(c->text_start.need_exact(n));
-    HIP_TRY(c->text_len.need_exact(n));
-    HIP_TRY(c->text_rc.need_exact(n));
-    HIP_TRY(c->query_start.need_exact(n));
-    HIP_TRY(c->query_len.need_exact(n));
-    HIP_TRY(c->out_score.need_exact(n));
-    HIP_TRY(c->out_begin.need_exact(n));
-    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-
-    // Length classes.  The kernel's shape -- lanes per alignment, words per lane -- is fixed per launch by the longest query
-    // it holds, and a 5-kbp read run in the shape of a 30-kbp one costs six times what it should: the batch is cut into
-    // classes of similar query length (in 64-row words; everything up to 8 words -- 512 bases, one alignment per lane -- is
-    // one class, so a short-read batch stays one launch; then up to 16 words), each class is a launch series of its own over an index list, and the
-    // results find their way back through that list.
-    static const uint32_t kClassUpTo[] = {kLaneWords, 16, 20, 24, 32, 40, 48, 64, 80, 96, 128, 160, 192, 256, 320, 384, 512, 640, 768, 1024};
-    constexpr uint32_t kClasses = sizeof kClassUpTo / sizeof kClassUpTo[0];
-    const bool classes_off = getenv("BMV_ONE_CLASS") != nullptr;    // experiment knob: the whole batch in the longest query's shape
-    auto class_of = [&](uint32_t m) {
-        const uint32_t words = classes_off ? 0u : (m + 63u) / 64u;
-        uint32_t k = 0;
-        while (k + 1u < kClasses && words > kClassUpTo[k]) k++;
-        return k;
-    };
-    uint32_t class_lo[kClasses + 1] = {0};
-    for (uint32_t a = 0; a < n; a++) class_lo[class_of(query_len[a]) + 1u]++;
-    uint32_t n_classes = 0;
-    for (uint32_t k = 0; k < kClasses; k++) {
-        n_classes += class_lo[k + 1] ? 1u : 0u;
-        class_lo[k + 1] += class_lo[k];
+    HIP_TRY(need_exact_all(n, c->out_score, c->out_begin, c->order));
+    if (const int rc = upload_views(c, v)) return rc;
+    const ClassOrder co = partition_classes(query_len, n);
+    HIP_TRY(hipMemcpyAsync(c->order.p, co.order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    CigarStash stash;
+    stash.in_place = co.n_classes == 1;                         // then order is the identity and the CIGARs arrive in place
+    if (!stash.in_place) {
+        stash.len.assign(n, 0);
+        stash.at.assign(n, 0);
     }
-    std::vector<uint32_t> order(n);
-    {
-        uint32_t at[kClasses];
-        for (uint32_t k = 0; k < kClasses; k++) at[k] = class_lo[k];
-        for (uint32_t a = 0; a < n; a++) order[at[class_of(query_len[a])]++] = a;      // stable: file order within a class
-    }
-    const bool one_class = n_classes == 1;                      // then order is the identity and the CIGARs arrive in place
-    HIP_TRY(c->order.need_exact(n));
-    HIP_TRY(hipMemcpyAsync(c->order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    std::vector<uint32_t> h_nops, h_packed, cigar_len, stash;
-    std::vector<uint64_t> stash_at;
-    if (!one_class) {
-        cigar_len.assign(n, 0);
-        stash_at.assign(n, 0);
-    }
-    // Grow these with headroom: the longest read differs a little from call to call, and a reallocation is a free, an
-    // allocation and a synchronisation of the device each time (the calls themselves are cheap: 0.2-0.5 ms for 45 GiB,
-    // tools/malloc_probe.py).
-    auto with_headroom = [](size_t need, size_t have) { return need <= have ? have : need + need / 4; };
-
-    // what each class needs, then one allocation for the largest of them
-    struct Plan {
-        uint32_t lo, members, max_m, trace_words, gpw, n_blocks, ops_stride, lds_stride;
-        Shape sh;
-        uint64_t trace_stride, chunk;
-        size_t lds;
-    };
+    const size_t budget = scratch_budget(c, query_len, n, co.n_classes);
     std::vector<Plan> plans;
-    size_t need_trace = 0, need_ops = 0, need_slots = 0;
-    // A batch of one length class (or of a few neighbouring ones: 10-kbp reads with indels straddle a class boundary) gains
-    // nothing from more alignments in flight than fill the card, and fresh device memory is not free (the first call that
-    // grew the scratch to 90 GB spent 2 s in hipMalloc): only a batch that really mixes lengths -- three classes or more,
-    // the longest query at least twice the shortest class's -- may use more than 48 GiB.
-    size_t budget = std::min<size_t>(c->scratch_bytes, (size_t)48 << 30);
-    {
-        uint32_t lo_m = 0xFFFFFFFFu, hi_m = 0;
-        for (uint32_t a = 0; a < n; a++) {
-            lo_m = std::min(lo_m, std::max(query_len[a], 1024u));
-            hi_m = std::max(hi_m, query_len[a]);
-        }
-        if (n_classes >= 3 && hi_m >= 2u * lo_m) budget = c->scratch_bytes;
-    }
     for (uint32_t k = 0; k < kClasses; k++) {
-        Plan pl{};
-        pl.lo = class_lo[k];
-        pl.members = class_lo[k + 1] - pl.lo;
-        if (pl.members == 0) continue;
-        uint32_t max_m = 0, max_n = 0;
-        for (uint32_t s0 = pl.lo; s0 < pl.lo + pl.members; s0++) {
-            max_m = std::max(max_m, query_len[order[s0]]);
-            max_n = std::max(max_n, text_len[order[s0]]);
-        }
-        pl.max_m = max_m;
-        // kernel shape for the longest query of the class; scratch per alignment slot
-        const uint32_t words = (max_m + 63u) / 64u;
-        pl.sh = pick_shape(words ? words : 1u, max_n);
-        pl.trace_words = std::max(std::max(words, 1u), pl.sh.group * (uint32_t)pl.sh.cw);   // (more than the words only for strips)
-        pl.gpw = 64u / pl.sh.group;
-        // checkpoints every 16 columns: (Pv, Mv) per word, plus one 32-bit word of horizontal deltas per word and block
-        pl.n_blocks = (max_n + pl.sh.group + 15u) / 16u + 1u;     // blocks of 16 STEPS: the group's last lane is group - 1 steps behind
-        const uint64_t n_entries = (uint64_t)pl.n_blocks * pl.gpw * pl.trace_words;
-        pl.trace_stride = n_entries * 2u + (n_entries + 1u) / 2u;               // 64-bit words per wave
-        pl.trace_stride += 2u * pl.trace_words * pl.gpw;                        // ... and the query's bit planes, for the traceback
-        pl.ops_stride = max_m + max_n + 1u;
-        pl.lds_stride = (max_n + 15u) / 16u * 4u + 4u;                          // the text as a 2-bit stream
-        if (pl.sh.per_lane) pl.lds_stride = (max_n + 63u) / 64u * 16u + 8u;     // ... as two bit planes, 64 columns at a time
-        pl.lds = 256 + (size_t)pl.gpw * pl.lds_stride;
-        if (pl.lds > 160 * 1024) return fail(BMV_ERR_UNSUPPORTED, "text windows of %u bases need %zu B of LDS", max_n, pl.lds);
-        if (pl.lds > 48 * 1024) HIP_TRY(bmhip::raise_dynamic_lds(reinterpret_cast<const void *>(pl.sh.fn), pl.lds));
-        const uint64_t per_slot = pl.trace_stride / pl.gpw * 8u + (uint64_t)pl.ops_stride * 4u;
-        uint64_t chunk = std::max<uint64_t>(pl.gpw, budget / per_slot);
-        chunk = std::min<uint64_t>(chunk, (uint64_t)pl.gpw << 25);   // one wave per gpw alignments: waves * 64 threads < 2^32
-        chunk = std::min<uint64_t>(chunk / pl.gpw * pl.gpw, (uint64_t)pl.members);
-        if (chunk == 0) chunk = pl.members;
-        // pieces of equal size: 40 000 alignments under a limit of 31 000 are 2 x 20 000, not 31 000 + 9 000 (a piece's
-        // last waves run on a card that is emptying, whatever its size)
-        const uint64_t n_pieces = (pl.members + chunk - 1u) / chunk;
-        const uint64_t even = ((pl.members + n_pieces - 1u) / n_pieces + pl.gpw - 1u) / pl.gpw * pl.gpw;
-        pl.chunk = std::min(chunk, even);
-        need_trace = std::max(need_trace, (size_t)((pl.chunk + pl.gpw - 1u) / pl.gpw * pl.trace_stride));
-        need_ops = std::max(need_ops, (size_t)(pl.chunk * pl.ops_stride));
-        need_slots = std::max(need_slots, (size_t)pl.chunk);
+        if (co.lo[k + 1] == co.lo[k]) continue;
+        Plan pl;
+        if (const int rc = plan_class(v, co.order, co.lo[k], co.lo[k + 1] - co.lo[k], budget, pl)) return rc;
         plans.push_back(pl);
     }
     const uint32_t stop_after = getenv("BMV_STOP_AFTER") ? (uint32_t)atoi(getenv("BMV_STOP_AFTER")) : 0u;   // phase timing
-    auto launch = [&](const Plan &pl, uint64_t first, uint32_t count, hipStream_t stream, uint64_t *trace, uint32_t *ops_rev,
-                      uint32_t *nops) {
-        bmv::Job j{};
-        j.genome = c->genome.p;
-        j.reads = c->reads.p;
-        j.lut = c->lut.p;
-        j.text_start = c->text_start.p;
-        j.text_len = c->text_len.p;
-        j.text_rc = c->text_rc.p;
-        j.query_start = c->query_start.p;
-        j.query_len = c->query_len.p;
-        j.order = c->order.p + pl.lo + first;
-        j.count = count;
-        j.trace = trace;
-        j.trace_stride = pl.trace_stride;
-        j.trace_words = pl.trace_words;
-        j.trace_blocks = pl.n_blocks;
-        j.group = pl.sh.group;
-        j.ops_rev = ops_rev;
-        j.ops_stride = pl.ops_stride;
-        j.text_lds_stride = pl.lds_stride;
-        j.out_score = c->out_score.p;
-        j.out_begin = c->out_begin.p;
-        j.out_nops = nops;
-        j.stop_after = stop_after;
-        hipLaunchKernelGGL(pl.sh.fn, dim3((count + pl.gpw - 1u) / pl.gpw), dim3(bmv::kWave), pl.lds, stream, j);
-        return hipGetLastError();
-    };
-    // CIGARs of `count` slots (launch order) -> the host, through one exclusive sum and one gather per ops_stride
-    struct Piece {
-        const Plan *pl;
-        uint64_t first;         // within the class
-        uint32_t count, slot0;  // slots [slot0, slot0 + count) of nops / offsets
-        uint32_t *ops_rev;
-    };
-    auto collect = [&](const std::vector<Piece> &pieces, uint32_t slots) -> int {
-        HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(slots) * sizeof(uint32_t)));
-        HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->nops.p, c->offsets.p, slots, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
-        uint32_t total = 0;                                     // the scan writes slots + 1 values: the last is the total
-        HIP_TRY(hipMemcpyAsync(&total, c->offsets.p + slots, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->packed.need_exact(with_headroom(total, c->packed.cap)));
-        for (const Piece &pc : pieces) {
-            hipLaunchKernelGGL(bmv::bmv_gather_kernel, dim3((pc.count + 31u) / 32u), dim3(256), 0, c->stream, pc.ops_rev,
-                               pc.pl->ops_stride, c->nops.p + pc.slot0, c->offsets.p + pc.slot0, pc.count, c->packed.p);
-            HIP_TRY(hipGetLastError());
-        }
-        h_nops.resize(slots);
-        h_packed.resize(total);
-        HIP_TRY(hipMemcpyAsync(h_nops.data(), c->nops.p, (size_t)slots * 4, hipMemcpyDeviceToHost, c->stream));
-        if (total) HIP_TRY(hipMemcpyAsync(h_packed.data(), c->packed.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::vector<uint32_t> &dst = one_class ? c->h_cigar : stash;
-        uint64_t at = dst.size();
-        for (const Piece &pc : pieces) {                        // in slot order, and the slots are theirs back to back
-            for (uint32_t s0 = 0; s0 < pc.count; s0++) {
-                const uint32_t len = h_nops[pc.slot0 + s0];
-                if (one_class) {                                // order is the identity: the CIGARs arrive in place
-                    c->h_offset[pc.first + s0] = at;
-                } else {                                        // kept aside in launch order until every length is known
-                    const uint32_t a = order[pc.pl->lo + pc.first + s0];
-                    cigar_len[a] = len;
-                    stash_at[a] = at;
-                }
-                at += len;
-            }
-        }
-        dst.insert(dst.end(), h_packed.begin(), h_packed.end());
-        return BMV_OK;
-    };
-
-    // Rounds.  A launch's scratch (checkpoints + reversed CIGAR entries) is what bounds how many alignments are in flight:
-    // 19 MB per 30-kbp alignment.  A class of long reads is few waves that each run for tens of milliseconds, so one class
-    // at a time leaves most of the card idle (measured on 40 000 alignments of 1 .. 30 kbp: 19.8 T cell updates/s against
-    // 37-41 T for uniform batches).  Every class is therefore cut into pieces of at most a THIRD of the scratch budget (when
-    // there is more than one class), the pieces -- longest reads first -- are packed into rounds that fit the budget
-    // together, and the pieces of a round run side by side on a few streams; their CIGARs are collected once per round.
-    // BMV_SERIAL_CLASSES=1: one piece per round (the old behaviour), for comparison.
-    struct Todo {
-        const Plan *pl;
-        uint64_t first;
-        uint32_t count;
-        size_t trace_words, ops_words;
-    };
-    std::vector<Todo> todo;
     const bool serial = getenv("BMV_SERIAL_CLASSES") != nullptr;
-    for (size_t i = plans.size(); i-- > 0;) {                   // the longest first: they take the longest
-        const Plan &pl = plans[i];
-        const uint64_t per_slot = pl.trace_stride / pl.gpw * 8u + (uint64_t)pl.ops_stride * 4u;
-        uint64_t chunk = pl.chunk;
-        if (plans.size() > 1 && !serial) {
-            const uint64_t third = std::max<uint64_t>(pl.gpw, budget / 3u / per_slot) / pl.gpw * pl.gpw;
-            chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(third, pl.gpw));
-            const uint64_t n_pieces = (pl.members + chunk - 1u) / chunk;
-            chunk = std::min<uint64_t>(chunk, ((pl.members + n_pieces - 1u) / n_pieces + pl.gpw - 1u) / pl.gpw * pl.gpw);
-        }
-        for (uint64_t first = 0; first < pl.members; first += chunk) {
-            const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, pl.members - first);
-            todo.push_back({&pl, first, count, (size_t)((count + pl.gpw - 1u) / pl.gpw * pl.trace_stride), (size_t)count * pl.ops_stride});
-        }
-    }
+    const std::vector<Todo> todo = cut_pieces(plans, budget, serial);
     for (size_t at = 0; at < todo.size();) {
-        // the pieces of this round: as many as fit the budget (at least one)
-        size_t end = at, sum_trace = 0, sum_ops = 0, slots = 0;
-        while (end < todo.size() && (end == at || (!serial && (sum_trace + todo[end].trace_words) * 8u + (sum_ops + todo[end].ops_words) * 4u <=
-                                                                   budget))) {
-            sum_trace += todo[end].trace_words;
-            sum_ops += todo[end].ops_words;
-            slots += todo[end].count;
-            end++;
-        }
-        HIP_TRY(c->trace.need_exact(with_headroom(sum_trace, c->trace.cap)));
-        HIP_TRY(c->ops_rev.need_exact(with_headroom(sum_ops, c->ops_rev.cap)));
-        HIP_TRY(c->nops.need_exact(with_headroom(slots, c->nops.cap)));
-        HIP_TRY(c->offsets.need_exact(with_headroom(slots + 1, c->offsets.cap)));
-        HIP_TRY(hipEventRecord(c->ev0, c->stream));             // the uploads above / the round before
-        std::vector<Piece> pieces;
-        size_t trace_at = 0, ops_at = 0;
-        uint32_t slot_at = 0;
-        const bool alone = end - at == 1;
-        for (size_t i = at; i < end; i++) {
-            const Todo &t = todo[i];
-            hipStream_t st = alone ? c->stream : c->side[(i - at) % kSideStreams];
-            if (!alone) HIP_TRY(hipStreamWaitEvent(st, c->ev0, 0));
-            HIP_TRY(launch(*t.pl, t.first, t.count, st, c->trace.p + trace_at, c->ops_rev.p + ops_at, c->nops.p + slot_at));
-            pieces.push_back({t.pl, t.first, t.count, slot_at, c->ops_rev.p + ops_at});
-            trace_at += t.trace_words;
-            ops_at += t.ops_words;
-            slot_at += t.count;
-        }
-        if (!alone)
-            for (uint32_t k = 0; k < kSideStreams; k++) {       // the main stream goes on when all of them are done
-                HIP_TRY(hipEventRecord(c->side_done[k], c->side[k]));
-                HIP_TRY(hipStreamWaitEvent(c->stream, c->side_done[k], 0));
-            }
-        HIP_TRY(hipEventRecord(c->ev1, c->stream));
-        if (int rc = collect(pieces, slot_at)) return rc;
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->ms_kernels += ms;
-        if (getenv("BMV_LOG_CLASSES")) {
-            fprintf(stderr, "[bmv] round of %zu piece(s), %.2f ms:", end - at, ms);
-            for (size_t i = at; i < end; i++)
-                fprintf(stderr, " [up to %u bases: %u of %u alignments, %u lanes x %d words]", todo[i].pl->max_m, todo[i].count,
-                        todo[i].pl->members, todo[i].pl->sh.group, todo[i].pl->sh.cw);
-            fprintf(stderr, "\n");
-        }
+        const size_t end = round_end(todo, at, budget, serial);
+        if (const int rc = run_round(c, todo, at, end, co.order, stop_after, stash)) return rc;
         at = end;
     }
-    if (!one_class) {
-        uint64_t at = 0;
-        for (uint32_t a = 0; a < n; a++) {
-            c->h_offset[a] = at;
-            at += cigar_len[a];
-        }
-        c->h_cigar.resize(at);
-        for (uint32_t a = 0; a < n; a++)
-            std::copy_n(stash.data() + stash_at[a], cigar_len[a], c->h_cigar.data() + c->h_offset[a]);
-    }
+    if (!stash.in_place) pack_cigars(c, n, stash.pool, stash.at, stash.len);
     c->h_offset[n] = c->h_cigar.size();
     HIP_TRY(hipMemcpy(c->h_score.data(), c->out_score.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(c->h_begin.data(), c->out_begin.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -676,23 +1027,12 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
 int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
                    const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
                    uint32_t n, uint64_t *total_cigar) {
-    if (!c || !total_cigar) return fail(BMV_ERR_ARG, "bmv_align_long: null argument");
-    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_align_long before bmv_load_genome");
-    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || (n_read_bytes && !reads)))
-        return fail(BMV_ERR_ARG, "bmv_align_long: null argument");
-    // experiment / test knob: every query of at least this many bases takes the long path (0: off)
-    const uint32_t long_from = getenv("BMV_LONG_FROM") ? (uint32_t)strtoul(getenv("BMV_LONG_FROM"), nullptr, 10) : 0u;
-    std::vector<uint32_t> shorts, longs;
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
     uint64_t cells = 0;
-    for (uint32_t a = 0; a < n; a++) {
-        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
-        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
-        cells += (uint64_t)query_len[a] * text_len[a];
-        const bool beyond = query_len[a] > c->p.max_query_len || text_len[a] > c->p.max_text_len || (long_from && query_len[a] >= long_from);
-        (beyond ? longs : shorts).push_back(a);
-    }
+    if (const int rc = check_views(c, "bmv_align_long", v, total_cigar != nullptr, true, false, &cells)) return rc;
+    const uint32_t from = long_from();
+    std::vector<uint32_t> shorts, longs;
+    for (uint32_t a = 0; a < n; a++) (goes_long(c, query_len[a], text_len[a], from) ? longs : shorts).push_back(a);
     if (longs.empty())                                          // nothing beyond the limits: bmv_align's own path
         return bmv_align(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, total_cigar);
 
@@ -740,43 +1080,23 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
     std::vector<uint32_t> pool;                                 // CIGAR entries, alignment by alignment in any order
     float ms_total = 0.f;
     if (!shorts.empty()) {                                      // exactly what bmv_align does with them on their own
-        const size_t ns = shorts.size();
-        std::vector<uint64_t> ts(ns), qs(ns);
-        std::vector<uint32_t> tl(ns), ql(ns);
-        std::vector<uint8_t> trc(ns);
-        for (size_t k = 0; k < ns; k++) {
+        SubResults sub;
+        if (int rc = align_sub_batch(c, v, shorts, sub)) return rc;
+        for (size_t k = 0; k < shorts.size(); k++) {
             const uint32_t a = shorts[k];
-            ts[k] = text_start[a];
-            tl[k] = text_len[a];
-            trc[k] = text_rc[a];
-            qs[k] = query_start[a];
-            ql[k] = query_len[a];
+            score[a] = sub.score[k];
+            begin[a] = sub.begin[k];
+            cig_at[a] = sub.offset[k];
+            cig_len[a] = sub.len(k);
         }
-        uint64_t tot = 0;
-        if (int rc = bmv_align(c, reads, n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), (uint32_t)ns, &tot)) return rc;
-        for (size_t k = 0; k < ns; k++) {
-            const uint32_t a = shorts[k];
-            score[a] = c->h_score[k];
-            begin[a] = c->h_begin[k];
-            cig_at[a] = c->h_offset[k];
-            cig_len[a] = c->h_offset[k + 1] - c->h_offset[k];
-        }
-        pool = c->h_cigar;
-        ms_total += c->ms_kernels;
+        pool = std::move(sub.cigar);
+        ms_total += sub.ms;
     }
     for (uint32_t a : empty_query) begin[a] = text_len[a];      // H[0][j] = 0 everywhere: the last column
 
     HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
-    HIP_TRY(c->text_start.need_exact(n));
-    HIP_TRY(c->text_rc.need_exact(n));
-    HIP_TRY(c->query_start.need_exact(n));
-    HIP_TRY(c->out_score.need_exact(n));
-    HIP_TRY(c->out_begin.need_exact(n));
-    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(need_exact_all(n, c->out_score, c->out_begin));
+    if (const int rc = upload_views(c, v)) return rc;
     std::vector<bmv::LongSlot> slots;
     std::vector<uint32_t> tiles, h_nops, h_packed;
     std::vector<uint64_t> tile_at;
@@ -845,12 +1165,7 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
         HIP_TRY(hipMemcpyAsync(c->long_slots.p, slots.data(), slots.size() * sizeof(bmv::LongSlot), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->long_tiles.p, tiles.data(), tiles.size() * 4u, hipMemcpyHostToDevice, c->stream));
         bmv::LongJob j{};
-        j.genome = c->genome.p;
-        j.reads = c->reads.p;
-        j.lut = c->lut.p;
-        j.text_start = c->text_start.p;
-        j.text_rc = c->text_rc.p;
-        j.query_start = c->query_start.p;
+        fill_views(c, j);
         j.slots = reinterpret_cast<const bmv::LongSlot *>(c->long_slots.p);
         j.count = count;
         j.scratch = reinterpret_cast<uint8_t *>(c->trace.p);
@@ -876,26 +1191,12 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
                            c->stream, j);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ev1, c->stream));
-        // CIGARs of the piece -> the host: one exclusive sum, one gather
-        HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(count) * sizeof(uint32_t)));
-        HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->nops.p, c->offsets.p, count, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
-        uint32_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, c->offsets.p + count, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->packed.need_exact(total));
-        hipLaunchKernelGGL(bmv::bmv_gather_kernel, dim3((count + 31u) / 32u), dim3(256), 0, c->stream, c->ops_rev.p, (uint32_t)ops_stride,
-                           c->nops.p, c->offsets.p, count, c->packed.p);
-        HIP_TRY(hipGetLastError());
-        h_nops.resize(count);
-        h_packed.resize(total);
-        HIP_TRY(hipMemcpyAsync(h_nops.data(), c->nops.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-        if (total) HIP_TRY(hipMemcpyAsync(h_packed.data(), c->packed.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        uint64_t from = pool.size();
+        if (int rc = collect_cigars(c, {{c->ops_rev.p, (uint32_t)ops_stride, 0u, count}}, count, h_nops, h_packed)) return rc;
+        uint64_t from_at = pool.size();
         for (uint32_t q = 0; q < count; q++) {
-            cig_at[slots[q].a] = from;
+            cig_at[slots[q].a] = from_at;
             cig_len[slots[q].a] = h_nops[q];
-            from += h_nops[q];
+            from_at += h_nops[q];
         }
         pool.insert(pool.end(), h_packed.begin(), h_packed.end());
         float ms = 0.f;
@@ -911,22 +1212,7 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
         score[l.s.a] = h_score[l.s.a];
         begin[l.s.a] = h_begin[l.s.a];
     }
-    // the results in batch order, as bmv_align leaves them
-    c->n_last = n;
-    c->n_cells = cells;
-    c->ms_kernels = ms_total;
-    c->h_score = std::move(score);
-    c->h_begin = std::move(begin);
-    c->h_offset.assign((size_t)n + 1, 0);
-    c->h_cigar.resize(pool.size());
-    uint64_t at = 0;
-    for (uint32_t a = 0; a < n; a++) {
-        c->h_offset[a] = at;
-        std::copy_n(pool.data() + cig_at[a], cig_len[a], c->h_cigar.data() + at);
-        at += cig_len[a];
-    }
-    c->h_offset[n] = at;
-    *total_cigar = at;
+    store_results(c, n, cells, ms_total, score, begin, pool, cig_at, cig_len, total_cigar);   // as bmv_align leaves them
     return BMV_OK;
 }
 
@@ -939,36 +1225,15 @@ int bmv_align_long(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
 int bmv_align_bounded(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
                       const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
                       const uint32_t *max_edits, uint32_t n, uint64_t *total_cigar) {
-    if (!c || !total_cigar) return fail(BMV_ERR_ARG, "bmv_align_bounded: null argument");
-    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_align_bounded before bmv_load_genome");
-    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || !max_edits || (n_read_bytes && !reads)))
-        return fail(BMV_ERR_ARG, "bmv_align_bounded: null argument");
-    const uint32_t long_from = getenv("BMV_LONG_FROM") ? (uint32_t)strtoul(getenv("BMV_LONG_FROM"), nullptr, 10) : 0u;
-    constexpr uint32_t kWaveCw[] = {1, 2, 4};                   // bmv_screen_wave_kernel's variants
-    std::vector<uint32_t> lane_list, wave_list[3];
-    uint32_t lane_words = 1;
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
     uint64_t cells = 0;
+    if (const int rc = check_views(c, "bmv_align_bounded", v, total_cigar != nullptr, max_edits != nullptr, false, &cells)) return rc;
+    const uint32_t from = long_from();
+    BandLists screened;
     for (uint32_t a = 0; a < n; a++) {
-        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
-        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
-        cells += (uint64_t)query_len[a] * text_len[a];
         const uint32_t m = query_len[a], k = max_edits[a];
-        const bool beyond = m > c->p.max_query_len || text_len[a] > c->p.max_text_len || (long_from && m >= long_from);
-        if (beyond || k >= m) continue;                         // not screened: the bound is applied to the score
-        const uint32_t words = (m + 63u) / 64u;
-        if (words <= kLaneWords) {
-            lane_list.push_back(a);
-            lane_words = std::max(lane_words, words);
-        } else {
-            // a wrong locus keeps about 2 k rows within the bound (random bases: D grows by about half a row's worth per
-            // row): the smallest variant whose 64 lanes hold that, or the whole query
-            const uint64_t band = std::min<uint64_t>(words, ((uint64_t)k * 9u / 4u + 128u) / 64u + 2u);
-            uint32_t v = 0;
-            while (v + 1u < 3u && band > 64u * kWaveCw[v]) v++;
-            wave_list[v].push_back(a);
-        }
+        if (goes_long(c, m, text_len[a], from) || k >= m) continue;     // not screened: the bound is applied to the score
+        screened.add(a, m, k);
     }
     c->n_rejected = 0;
     c->screen_cells = 0;
@@ -976,48 +1241,25 @@ int bmv_align_bounded(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, c
     if (n == 0) return bmv_align_long(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, total_cigar);
 
     std::vector<uint32_t> survivors;
-    const size_t n_screened = lane_list.size() + wave_list[0].size() + wave_list[1].size() + wave_list[2].size();
+    const size_t n_screened = screened.size();
     if (n_screened == 0) {
         survivors.resize(n);
         for (uint32_t a = 0; a < n; a++) survivors[a] = a;
     } else {
         HIP_TRY(hipSetDevice(c->p.device));
-        HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
-        HIP_TRY(c->text_start.need_exact(n));
-        HIP_TRY(c->text_len.need_exact(n));
-        HIP_TRY(c->text_rc.need_exact(n));
-        HIP_TRY(c->query_start.need_exact(n));
-        HIP_TRY(c->query_len.need_exact(n));
-        HIP_TRY(c->max_edits.need_exact(n));
-        HIP_TRY(c->keep.need_exact(n));
-        HIP_TRY(c->keep_at.need_exact((size_t)n + 1u));
-        HIP_TRY(c->survivors.need_exact(n));
+        HIP_TRY(need_exact_all(n, c->max_edits, c->keep, c->survivors));
+        HIP_TRY(need_exact_all((size_t)n + 1u, c->keep_at));
         HIP_TRY(c->screen_list.need_exact(n_screened));
         HIP_TRY(c->screen_count.need_exact(1));
         HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n) * sizeof(uint32_t)));
-        if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        if (const int rc = upload_views(c, v)) return rc;
         HIP_TRY(hipMemcpyAsync(c->max_edits.p, max_edits, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        std::vector<uint32_t> ones(n, 1u), list;
-        list.reserve(n_screened);
-        list.insert(list.end(), lane_list.begin(), lane_list.end());
-        for (const auto &w : wave_list) list.insert(list.end(), w.begin(), w.end());
+        std::vector<uint32_t> ones(n, 1u);
         HIP_TRY(hipMemcpyAsync(c->keep.p, ones.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->screen_list.p, list.data(), n_screened * 4, hipMemcpyHostToDevice, c->stream));
+        if (const int rc = upload_band_lists(c, screened, c->screen_list.p)) return rc;
         HIP_TRY(hipMemsetAsync(c->screen_count.p, 0, sizeof(unsigned long long), c->stream));
         bmv::ScreenJob j{};
-        j.genome = c->genome.p;
-        j.reads = c->reads.p;
-        j.lut = c->lut.p;
-        j.text_start = c->text_start.p;
-        j.text_len = c->text_len.p;
-        j.text_rc = c->text_rc.p;
-        j.query_start = c->query_start.p;
-        j.query_len = c->query_len.p;
+        fill_views(c, j);
         j.max_edits = c->max_edits.p;
         j.keep = c->keep.p;
         j.cells = c->screen_count.p;
@@ -1028,24 +1270,7 @@ int bmv_align_bounded(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, c
                                                            bmv::bmv_screen_lane_kernel<5>, bmv::bmv_screen_lane_kernel<6>,
                                                            bmv::bmv_screen_lane_kernel<7>, bmv::bmv_screen_lane_kernel<8>};
         static const screen_fn per_wave[3] = {bmv::bmv_screen_wave_kernel<1>, bmv::bmv_screen_wave_kernel<2>, bmv::bmv_screen_wave_kernel<4>};
-        HIP_TRY(hipEventRecord(c->ev0, c->stream));
-        size_t at = 0;
-        if (!lane_list.empty()) {
-            j.list = c->screen_list.p;
-            j.count = (uint32_t)lane_list.size();
-            hipLaunchKernelGGL(per_lane[lane_words], dim3((j.count + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, j);
-            HIP_TRY(hipGetLastError());
-            at += lane_list.size();
-        }
-        for (uint32_t v = 0; v < 3u; v++) {
-            if (wave_list[v].empty()) continue;
-            j.list = c->screen_list.p + at;
-            j.count = (uint32_t)wave_list[v].size();
-            hipLaunchKernelGGL(per_wave[v], dim3(j.count), dim3(bmv::kWave), 0, c->stream, j);
-            HIP_TRY(hipGetLastError());
-            at += wave_list[v].size();
-        }
-        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        if (const int rc = launch_bands(c, screened, c->screen_list.p, per_lane, per_wave, j)) return rc;
         // the survivors' indices, compacted on the device
         HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->keep.p, c->keep_at.p, n, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
         hipLaunchKernelGGL(bmv::bmv_screen_compact_kernel, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->keep.p, c->keep_at.p, n,
@@ -1062,52 +1287,28 @@ int bmv_align_bounded(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, c
         c->screen_cells = 64u * (uint64_t)steps;
         if (getenv("BMV_LOG_CLASSES"))
             fprintf(stderr, "[bmv] screen: %zu per lane, %zu / %zu / %zu per wave at 1 / 2 / 4 words a lane; %u of %u let through, %.2f ms\n",
-                    lane_list.size(), wave_list[0].size(), wave_list[1].size(), wave_list[2].size(), n_keep, n, c->ms_screen);
+                    screened.lane.size(), screened.wave[0].size(), screened.wave[1].size(), screened.wave[2].size(), n_keep, n, c->ms_screen);
     }
 
     // the survivors as a batch of their own, in batch order
-    const size_t ns = survivors.size();
-    std::vector<uint64_t> ts(ns), qs(ns);
-    std::vector<uint32_t> tl(ns), ql(ns);
-    std::vector<uint8_t> trc(ns);
-    for (size_t s = 0; s < ns; s++) {
-        const uint32_t a = survivors[s];
-        ts[s] = text_start[a];
-        tl[s] = text_len[a];
-        trc[s] = text_rc[a];
-        qs[s] = query_start[a];
-        ql[s] = query_len[a];
-    }
-    uint64_t tot = 0;
-    const float ms_screen = c->ms_screen;
-    if (int rc = bmv_align_long(c, reads, n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), (uint32_t)ns, &tot)) return rc;
+    SubResults sub;
+    if (int rc = align_sub_batch(c, v, survivors, sub)) return rc;
     // back to batch order; the bound applied to what was let through
     std::vector<int32_t> score(n, BMV_REJECTED);
-    std::vector<uint32_t> begin(n, 0), cig;
-    std::vector<uint64_t> offset((size_t)n + 1, 0);
-    cig.reserve(c->h_cigar.size());
-    std::vector<uint32_t> slot_of(n, 0xFFFFFFFFu);
-    for (size_t s = 0; s < ns; s++) slot_of[survivors[s]] = (uint32_t)s;
+    std::vector<uint32_t> begin(n, 0);
+    std::vector<uint64_t> cig_at(n, 0), cig_len(n, 0);
     uint32_t accepted = 0;
-    for (uint32_t a = 0; a < n; a++) {
-        offset[a] = cig.size();
-        const uint32_t s = slot_of[a];
-        if (s == 0xFFFFFFFFu || -(int64_t)c->h_score[s] > (int64_t)max_edits[a]) continue;   // rejected: an empty CIGAR
-        score[a] = c->h_score[s];
-        begin[a] = c->h_begin[s];
-        cig.insert(cig.end(), c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s], c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s + 1]);
+    for (size_t s = 0; s < survivors.size(); s++) {
+        const uint32_t a = survivors[s];
+        if (-(int64_t)sub.score[s] > (int64_t)max_edits[a]) continue;   // rejected: an empty CIGAR
+        score[a] = sub.score[s];
+        begin[a] = sub.begin[s];
+        cig_at[a] = sub.offset[s];
+        cig_len[a] = sub.len(s);
         accepted++;
     }
-    offset[n] = cig.size();
-    c->n_last = n;
-    c->n_cells = cells;
-    c->ms_kernels += ms_screen;
+    store_results(c, n, cells, sub.ms + c->ms_screen, score, begin, sub.cigar, cig_at, cig_len, total_cigar);
     c->n_rejected = n - accepted;
-    c->h_score = std::move(score);
-    c->h_begin = std::move(begin);
-    c->h_offset = std::move(offset);
-    c->h_cigar = std::move(cig);
-    *total_cigar = c->h_cigar.size();
     return BMV_OK;
 }
 
@@ -1124,47 +1325,12 @@ int bmv_last_bounded_stats(bmv_ctx *c, uint32_t *n_rejected, uint64_t *screen_ce
 // margin, and what they leave undecided in full as well; the pick on the device; the winners that have no full alignment
 // yet in full.  Every full alignment is bmv_align_long's on a batch of its own, so what the winners carry is what that call
 // gives them.
-static int best_sub_batch(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
-                          const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
-                          const std::vector<uint32_t> &which, std::vector<int32_t> &score, std::vector<uint32_t> &begin,
-                          std::vector<uint32_t> &r_len, std::vector<std::vector<uint32_t>> &cigar, float *ms) {
-    const size_t ns = which.size();
-    if (ns == 0) return BMV_OK;
-    std::vector<uint64_t> ts(ns), qs(ns);
-    std::vector<uint32_t> tl(ns), ql(ns);
-    std::vector<uint8_t> trc(ns);
-    for (size_t s = 0; s < ns; s++) {
-        const uint32_t a = which[s];
-        ts[s] = text_start[a];
-        tl[s] = text_len[a];
-        trc[s] = text_rc[a];
-        qs[s] = query_start[a];
-        ql[s] = query_len[a];
-    }
-    uint64_t tot = 0;
-    if (int rc = bmv_align_long(c, reads, n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), (uint32_t)ns, &tot)) return rc;
-    for (size_t s = 0; s < ns; s++) {
-        const uint32_t a = which[s];
-        score[a] = c->h_score[s];
-        begin[a] = c->h_begin[s];
-        cigar[a].assign(c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s], c->h_cigar.begin() + (ptrdiff_t)c->h_offset[s + 1]);
-        uint32_t r = 0;                                         // text columns the alignment spans: its M and D lengths
-        for (uint32_t e : cigar[a])
-            if ((e & 15u) != BMV_OP_I) r += e >> 4;
-        r_len[a] = r;
-    }
-    *ms += c->ms_kernels;
-    return BMV_OK;
-}
-
 int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
                    const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
                    const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
                    uint64_t *total_cigar) {
-    if (!c || !total_cigar || !group_offset) return fail(BMV_ERR_ARG, "bmv_align_best: null argument");
-    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_align_best before bmv_load_genome");
-    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || (n_read_bytes && !reads)))
-        return fail(BMV_ERR_ARG, "bmv_align_best: null argument");
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_align_best", v, total_cigar && group_offset, true)) return rc;
     if (n_groups && !margin) return fail(BMV_ERR_ARG, "bmv_align_best: null argument");
     if (group_offset[0] != 0u) return fail(BMV_ERR_ARG, "bmv_align_best: group_offset[0] is %u, not 0", group_offset[0]);
     for (uint32_t g = 0; g < n_groups; g++) {
@@ -1177,21 +1343,12 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
     if (group_offset[n_groups] != n)
         return fail(BMV_ERR_ARG, "group %u: group_offset ends at %u, the batch has %u alignments", n_groups ? n_groups - 1u : 0u,
                     group_offset[n_groups], n);
-    const uint32_t long_from = getenv("BMV_LONG_FROM") ? (uint32_t)strtoul(getenv("BMV_LONG_FROM"), nullptr, 10) : 0u;
     uint64_t cells = 0;
-    for (uint32_t a = 0; a < n; a++) {
-        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
-        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
-        cells += (uint64_t)query_len[a] * text_len[a];
-    }
+    if (const int rc = check_view_ranges(c, v, false, &cells)) return rc;
+    const uint32_t from = long_from();
 
-    // what full alignments leave, per alignment of the batch
-    std::vector<int32_t> f_score(n, BMV_REJECTED);
-    std::vector<uint32_t> f_begin(n, 0), f_rlen(n, 0), full(n, 0u);
-    std::vector<std::vector<uint32_t>> f_cigar(n);
-    float ms_total = 0.f;
+    BestFull f(n);
+    std::vector<uint32_t> full(n, 0u);
     c->bs_n_seed = c->bs_n_distance = c->bs_n_beyond = c->bs_n_undecided = c->bs_n_realigned = 0;
     c->bs_cells = 0;
     c->ms_distance = c->ms_pick = 0.f;
@@ -1203,17 +1360,15 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
         seed_of[g] = group_offset[g] + (hint ? hint[g] : 0u);
         seeds.push_back(seed_of[g]);
     }
-    if (int rc = best_sub_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, seeds, f_score, f_begin,
-                                f_rlen, f_cigar, &ms_total))
-        return rc;
+    if (int rc = best_sub_batch(c, v, seeds, f)) return rc;
     for (uint32_t a : seeds) full[a] = 1u;
     c->bs_n_seed = (uint32_t)seeds.size();
 
     std::vector<uint32_t> h_d(n, bmv::kBestUndecided), h_end(n, 0u), h_winner(n_groups, bmv::kBestBeyond), h_edits(n, bmv::kBestBeyond),
         h_out_end(n, 0u);
     for (uint32_t a : seeds) {
-        h_d[a] = (uint32_t)(-(int64_t)f_score[a]);
-        h_end[a] = f_begin[a] + f_rlen[a];
+        h_d[a] = f.edits(a);
+        h_end[a] = f.end(a);
     }
     if (seeds.size() == n) {
         // every group is its seed alone: nothing to decide
@@ -1222,70 +1377,36 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
         h_out_end = h_end;
     } else {
         // 2. the distance round: everything but the seeds, under k = min(seed's edits + margin, query length)
-        constexpr uint32_t kWaveCw[] = {1, 2, 4};               // bmv_best_wave_kernel's variants
-        std::vector<uint32_t> bound(n, 0u), lane_list, wave_list[3], undecided;
-        uint32_t lane_words = 1;
+        std::vector<uint32_t> bound(n, 0u), undecided;
+        BandLists listed;
         for (uint32_t g = 0; g < n_groups; g++) {
             for (uint32_t a = group_offset[g]; a < group_offset[g + 1]; a++) {
                 if (a == seed_of[g]) continue;
                 const uint32_t m = query_len[a];
                 const uint32_t k = (uint32_t)std::min<uint64_t>((uint64_t)h_d[seed_of[g]] + margin[g], m);
                 bound[a] = k;
-                const bool beyond = m > c->p.max_query_len || text_len[a] > c->p.max_text_len || (long_from && m >= long_from);
-                const uint32_t words = (m + 63u) / 64u;
-                if (beyond || m == 0u || text_len[a] == 0u) {   // (an empty side: the aligner's own conventions)
+                if (goes_long(c, m, text_len[a], from) || m == 0u || text_len[a] == 0u)   // (an empty side: the aligner's own conventions)
                     undecided.push_back(a);
-                } else if (words <= kLaneWords) {
-                    lane_list.push_back(a);
-                    lane_words = std::max(lane_words, words);
-                } else {
-                    // the band of a wrong locus is about 2 k rows (bmv_align_bounded): the smallest variant that holds it
-                    const uint64_t band = std::min<uint64_t>(words, ((uint64_t)k * 9u / 4u + 128u) / 64u + 2u);
-                    uint32_t v = 0;
-                    while (v + 1u < 3u && band > 64u * kWaveCw[v]) v++;
-                    wave_list[v].push_back(a);
-                }
+                else
+                    listed.add(a, m, k);
             }
         }
-        const size_t n_listed = lane_list.size() + wave_list[0].size() + wave_list[1].size() + wave_list[2].size();
+        const size_t n_listed = listed.size();
         c->bs_n_distance = (uint32_t)n_listed;
         HIP_TRY(hipSetDevice(c->p.device));
-        HIP_TRY(c->bs_d.need_exact(n));
-        HIP_TRY(c->bs_end.need_exact(n));
+        HIP_TRY(need_exact_all(n, c->bs_d, c->bs_end));
         if (n_listed) {
-            HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
-            HIP_TRY(c->text_start.need_exact(n));
-            HIP_TRY(c->text_len.need_exact(n));
-            HIP_TRY(c->text_rc.need_exact(n));
-            HIP_TRY(c->query_start.need_exact(n));
-            HIP_TRY(c->query_len.need_exact(n));
             HIP_TRY(c->bs_bound.need_exact(n));
             HIP_TRY(c->bs_list.need_exact(n_listed));
             HIP_TRY(c->bs_count.need_exact(1));
-            if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            if (const int rc = upload_views(c, v)) return rc;
             HIP_TRY(hipMemcpyAsync(c->bs_bound.p, bound.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-            std::vector<uint32_t> list;
-            list.reserve(n_listed);
-            list.insert(list.end(), lane_list.begin(), lane_list.end());
-            for (const auto &w : wave_list) list.insert(list.end(), w.begin(), w.end());
-            HIP_TRY(hipMemcpyAsync(c->bs_list.p, list.data(), n_listed * 4, hipMemcpyHostToDevice, c->stream));
+            if (const int rc = upload_band_lists(c, listed, c->bs_list.p)) return rc;
             HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemsetAsync(c->bs_count.p, 0, sizeof(unsigned long long), c->stream));
             bmv::BestJob j{};
-            j.genome = c->genome.p;
-            j.reads = c->reads.p;
-            j.lut = c->lut.p;
-            j.text_start = c->text_start.p;
-            j.text_len = c->text_len.p;
-            j.text_rc = c->text_rc.p;
-            j.query_start = c->query_start.p;
-            j.query_len = c->query_len.p;
+            fill_views(c, j);
             j.bound = c->bs_bound.p;
             j.d = c->bs_d.p;
             j.end = c->bs_end.p;
@@ -1297,24 +1418,7 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
                                                              bmv::bmv_best_lane_kernel<5>, bmv::bmv_best_lane_kernel<6>,
                                                              bmv::bmv_best_lane_kernel<7>, bmv::bmv_best_lane_kernel<8>};
             static const best_fn per_wave[3] = {bmv::bmv_best_wave_kernel<1>, bmv::bmv_best_wave_kernel<2>, bmv::bmv_best_wave_kernel<4>};
-            HIP_TRY(hipEventRecord(c->ev0, c->stream));
-            size_t at = 0;
-            if (!lane_list.empty()) {
-                j.list = c->bs_list.p;
-                j.count = (uint32_t)lane_list.size();
-                hipLaunchKernelGGL(per_lane[lane_words], dim3((j.count + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, j);
-                HIP_TRY(hipGetLastError());
-                at += lane_list.size();
-            }
-            for (uint32_t v = 0; v < 3u; v++) {
-                if (wave_list[v].empty()) continue;
-                j.list = c->bs_list.p + at;
-                j.count = (uint32_t)wave_list[v].size();
-                hipLaunchKernelGGL(per_wave[v], dim3(j.count), dim3(bmv::kWave), 0, c->stream, j);
-                HIP_TRY(hipGetLastError());
-                at += wave_list[v].size();
-            }
-            HIP_TRY(hipEventRecord(c->ev1, c->stream));
+            if (const int rc = launch_bands(c, listed, c->bs_list.p, per_lane, per_wave, j)) return rc;
             unsigned long long steps = 0;
             HIP_TRY(hipMemcpyAsync(h_d.data(), c->bs_d.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipMemcpyAsync(h_end.data(), c->bs_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1322,7 +1426,7 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
             HIP_TRY(hipStreamSynchronize(c->stream));
             HIP_TRY(hipEventElapsedTime(&c->ms_distance, c->ev0, c->ev1));
             c->bs_cells = 64u * (uint64_t)steps;
-            for (uint32_t a : list) {
+            for (uint32_t a : listed.all) {
                 if (h_d[a] == bmv::kBestUndecided) {
                     undecided.push_back(a);
                     c->bs_n_undecided++;
@@ -1330,34 +1434,26 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
                     c->bs_n_beyond++;
                 }
             }
-            ms_total += c->ms_distance;
+            f.ms += c->ms_distance;
             if (getenv("BMV_LOG_CLASSES"))
                 fprintf(stderr, "[bmv] best: %zu seeds; distance round %zu per lane, %zu / %zu / %zu per wave at 1 / 2 / 4 words a lane; %u beyond, %u undecided, %.2f ms\n",
-                        seeds.size(), lane_list.size(), wave_list[0].size(), wave_list[1].size(), wave_list[2].size(), c->bs_n_beyond,
+                        seeds.size(), listed.lane.size(), listed.wave[0].size(), listed.wave[1].size(), listed.wave[2].size(), c->bs_n_beyond,
                         c->bs_n_undecided, c->ms_distance);
         }
         // what the kernels did not take or gave up on: in full, which gives d and end as well
         std::sort(undecided.begin(), undecided.end());
-        if (int rc = best_sub_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, undecided, f_score,
-                                    f_begin, f_rlen, f_cigar, &ms_total))
-            return rc;
+        if (int rc = best_sub_batch(c, v, undecided, f)) return rc;
         for (uint32_t a : undecided) {
             full[a] = 1u;
-            h_d[a] = (uint32_t)(-(int64_t)f_score[a]);
-            h_end[a] = f_begin[a] + f_rlen[a];
+            h_d[a] = f.edits(a);
+            h_end[a] = f.end(a);
         }
 
         // 3. the pick
         HIP_TRY(hipSetDevice(c->p.device));
-        HIP_TRY(c->bs_full.need_exact(n));
-        HIP_TRY(c->bs_group_offset.need_exact((size_t)n_groups + 1u));
-        HIP_TRY(c->bs_margin.need_exact(n_groups));
-        HIP_TRY(c->bs_winner.need_exact(n_groups));
-        HIP_TRY(c->bs_need.need_exact(n_groups));
-        HIP_TRY(c->bs_need_at.need_exact((size_t)n_groups + 1u));
-        HIP_TRY(c->bs_realign.need_exact(n_groups));
-        HIP_TRY(c->bs_edits.need_exact(n));
-        HIP_TRY(c->bs_out_end.need_exact(n));
+        HIP_TRY(need_exact_all(n, c->bs_full, c->bs_edits, c->bs_out_end));
+        HIP_TRY(need_exact_all(n_groups, c->bs_margin, c->bs_winner, c->bs_need, c->bs_realign));
+        HIP_TRY(need_exact_all((size_t)n_groups + 1u, c->bs_group_offset, c->bs_need_at));
         HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n_groups) * sizeof(uint32_t)));
         HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -1390,7 +1486,7 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
         HIP_TRY(hipMemcpyAsync(h_out_end.data(), c->bs_out_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipEventElapsedTime(&c->ms_pick, c->ev0, c->ev1));
-        ms_total += c->ms_pick;
+        f.ms += c->ms_pick;
         if (n_realign > n_groups) return fail(BMV_ERR_STATE, "bmv_align_best: the pick lists %u winners for %u groups", n_realign, n_groups);
         std::vector<uint32_t> realign(n_realign);
         if (n_realign) HIP_TRY(hipMemcpy(realign.data(), c->bs_realign.p, (size_t)n_realign * 4, hipMemcpyDeviceToHost));
@@ -1398,46 +1494,32 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
             if (a >= n) return fail(BMV_ERR_STATE, "bmv_align_best: the pick lists alignment %u of %u", a, n);
 
         // 4. the winners that have no full alignment yet
-        if (int rc = best_sub_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, realign, f_score, f_begin,
-                                    f_rlen, f_cigar, &ms_total))
-            return rc;
+        if (int rc = best_sub_batch(c, v, realign, f)) return rc;
         c->bs_n_realigned = n_realign;
         for (uint32_t a : realign) {
             // the distance round and the aligner are two computations of one quantity
-            if ((uint32_t)(-(int64_t)f_score[a]) != h_d[a] || f_begin[a] + f_rlen[a] != h_end[a])
+            if (f.edits(a) != h_d[a] || f.end(a) != h_end[a])
                 return fail(BMV_ERR_STATE, "bmv_align_best: alignment %u has %u edits ending at %u by the distance round, %lld ending at %u in full",
-                            a, h_d[a], h_end[a], -(long long)f_score[a], f_begin[a] + f_rlen[a]);
+                            a, h_d[a], h_end[a], -(long long)f.score[a], f.end(a));
         }
     }
 
     // the winners in batch order, everything else rejected
-    std::vector<int32_t> score(n, BMV_REJECTED);
-    std::vector<uint32_t> begin(n, 0), cig;
-    std::vector<uint64_t> offset((size_t)n + 1, 0);
     std::vector<uint8_t> wins(n, 0);
     for (uint32_t g = 0; g < n_groups; g++)
         if (h_winner[g] != bmv::kBestBeyond) wins[h_winner[g]] = 1;
     for (uint32_t a = 0; a < n; a++) {
-        offset[a] = cig.size();
-        if (!wins[a]) continue;
-        score[a] = f_score[a];
-        begin[a] = f_begin[a];
-        cig.insert(cig.end(), f_cigar[a].begin(), f_cigar[a].end());
+        if (wins[a]) continue;
+        f.score[a] = BMV_REJECTED;
+        f.begin[a] = 0;
+        f.cig_len[a] = 0;
     }
-    offset[n] = cig.size();
-    c->n_last = n;
-    c->n_cells = cells;
-    c->ms_kernels = ms_total;
-    c->h_score = std::move(score);
-    c->h_begin = std::move(begin);
-    c->h_offset = std::move(offset);
-    c->h_cigar = std::move(cig);
+    store_results(c, n, cells, f.ms, f.score, f.begin, f.pool, f.cig_at, f.cig_len, total_cigar);
     c->n_best = n;
     c->n_best_groups = n_groups;
     c->h_bs_winner = std::move(h_winner);
     c->h_bs_edits = std::move(h_edits);
     c->h_bs_end = std::move(h_out_end);
-    *total_cigar = c->h_cigar.size();
     return BMV_OK;
 }
 
@@ -1463,201 +1545,52 @@ int bmv_last_best_stats(bmv_ctx *c, uint32_t *n_seed, uint32_t *n_distance, uint
     return BMV_OK;
 }
 
-// The annotation pass (include/bmv.h, bmv_annotate.hip.h) and the clipping pass (bmv_clip.hip.h) take the same batch.
-// Everything a kernel relies on is checked here first -- the views, the CIGAR alphabet, that every CIGAR consumes exactly
-// its query and stays inside its window -- so that the kernels index without bounds checks.  `who`: the call, for the message.
-static int check_annotate_batch(bmv_ctx *c, const char *who, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
-                                const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
-                                const uint32_t *query_len, const uint32_t *begin, const uint64_t *cigar_offset,
-                                const uint32_t *cigar, uint32_t n, uint64_t *out_columns) {
-    if (!c->loaded) return fail(BMV_ERR_STATE, "%s before bmv_load_genome", who);
-    if (n && (!text_start || !text_len || !text_rc || !query_start || !query_len || !begin || !cigar_offset || (n_read_bytes && !reads)))
-        return fail(BMV_ERR_ARG, "%s: null argument", who);
-    uint64_t columns = 0;
-    for (uint32_t a = 0; a < n; a++) {
-        if (query_start[a] > n_read_bytes || query_len[a] > n_read_bytes - query_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: query lies outside the read buffer", a);
-        if (text_start[a] > c->n_genome || text_len[a] > c->n_genome - text_start[a])
-            return fail(BMV_ERR_ARG, "alignment %u: text lies outside the genome", a);
-        if (cigar_offset[a + 1] < cigar_offset[a] || cigar_offset[a + 1] - cigar_offset[a] > 0xFFFFFFFFull - query_len[a])
-            return fail(BMV_ERR_ARG, "alignment %u: CIGAR offsets %llu .. %llu", a, (unsigned long long)cigar_offset[a],
-                        (unsigned long long)cigar_offset[a + 1]);
-        if (cigar_offset[a + 1] > cigar_offset[a] && !cigar) return fail(BMV_ERR_ARG, "%s: null argument", who);
-        if (cigar_offset[a + 1] == cigar_offset[a]) continue;   // an empty CIGAR: zeros and no entries, whatever the views hold
-        uint64_t in_query = 0, in_text = 0, cols = 0;
-        uint32_t before = 0xFFFFFFFFu;
-        for (uint64_t x = cigar_offset[a]; x < cigar_offset[a + 1]; x++) {
-            const uint32_t op = cigar[x] & 15u, len = cigar[x] >> 4;
-            const unsigned long long k = (unsigned long long)(x - cigar_offset[a]);
-            if (op > BMV_OP_D) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entry %llu has op code %u (M, I and D are taken)", a, k, op);
-            if (len == 0) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entry %llu has length 0", a, k);
-            if (op == before) return fail(BMV_ERR_ARG, "alignment %u: CIGAR entries %llu and %llu share an op", a, k - 1u, k);
-            before = op;
-            if (op != BMV_OP_D) in_query += len;
-            if (op != BMV_OP_I) in_text += len;
-            cols += len;
-        }
-        if (in_query != query_len[a])
-            return fail(BMV_ERR_ARG, "alignment %u: the CIGAR consumes %llu query bases, the query has %u", a,
-                        (unsigned long long)in_query, query_len[a]);
-        if ((uint64_t)begin[a] + in_text > text_len[a])
-            return fail(BMV_ERR_ARG, "alignment %u: begin %u + %llu reference bases run past the window of %u", a, begin[a],
-                        (unsigned long long)in_text, text_len[a]);
-        columns += cols;
-    }
-    *out_columns = columns;
-    return BMV_OK;
-}
-
-// The checked batch (n > 0) on its way to the device, on the context's stream; j receives the input pointers.  `rebased` is
-// the caller's: the copy out of it may still be under way on return.
-static int upload_annotate_batch(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
-                                 const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start,
-                                 const uint32_t *query_len, const uint32_t *begin, const uint64_t *cigar_offset,
-                                 const uint32_t *cigar, uint32_t n, std::vector<uint64_t> &rebased, bmv::AnnotateJob &j) {
-    const uint64_t cig0 = cigar_offset[0], n_cigar = cigar_offset[n] - cig0;
-    HIP_TRY(hipSetDevice(c->p.device));
-    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
-    HIP_TRY(c->text_start.need_exact(n));
-    HIP_TRY(c->text_len.need_exact(n));
-    HIP_TRY(c->text_rc.need_exact(n));
-    HIP_TRY(c->query_start.need_exact(n));
-    HIP_TRY(c->query_len.need_exact(n));
-    HIP_TRY(c->an_begin.need_exact(n));
-    HIP_TRY(c->an_cigar_offset.need_exact((size_t)n + 1u));
-    HIP_TRY(c->an_cigar.need((size_t)n_cigar));
-    HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n) * sizeof(uint64_t)));
-    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_start.p, text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_len.p, text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->query_start.p, query_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->query_len.p, query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->an_begin.p, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    rebased.assign(cigar_offset, cigar_offset + (size_t)n + 1u);                    // the device holds cigar[cig0 ..) only
-    for (uint64_t &o : rebased) o -= cig0;
-    HIP_TRY(hipMemcpyAsync(c->an_cigar_offset.p, rebased.data(), ((size_t)n + 1u) * 8, hipMemcpyHostToDevice, c->stream));
-    if (n_cigar) HIP_TRY(hipMemcpyAsync(c->an_cigar.p, cigar + cig0, (size_t)n_cigar * 4, hipMemcpyHostToDevice, c->stream));
-    j.genome = c->genome.p;
-    j.reads = c->reads.p;
-    j.text_start = c->text_start.p;
-    j.text_len = c->text_len.p;
-    j.text_rc = c->text_rc.p;
-    j.query_start = c->query_start.p;
-    j.query_len = c->query_len.p;
-    j.begin = c->an_begin.p;
-    j.cigar_offset = c->an_cigar_offset.p;
-    j.cigar = c->an_cigar.p;
-    j.count = n;
-    return BMV_OK;
-}
-
-// bmv_annotate: upload, the count pass, two exclusive sums, the write pass, download.
+// bmv_annotate: upload, the count pass, two exclusive sums, the write pass, download (two_pass_emit).
 int bmv_annotate(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
                  const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
                  const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint64_t *total_xcigar, uint64_t *total_ref_bases) {
-    if (!c || !total_xcigar || !total_ref_bases) return fail(BMV_ERR_ARG, "bmv_annotate: null argument");
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_annotate", v, total_xcigar && total_ref_bases, begin && cigar_offset)) return rc;
     uint64_t columns = 0;
-    if (const int rc = check_annotate_batch(c, "bmv_annotate", reads, n_read_bytes, text_start, text_len, text_rc, query_start,
-                                            query_len, begin, cigar_offset, cigar, n, &columns))
-        return rc;
-    c->h_an_nm.assign(n, 0);
-    c->h_an_pos.assign(n, 0);
-    c->h_an_ref_len.assign(n, 0);
-    c->h_an_xcigar_offset.assign((size_t)n + 1, 0);
-    c->h_an_ref_offset.assign((size_t)n + 1, 0);
-    c->h_an_xcigar.clear();
-    c->h_an_ref_bases.clear();
-    c->ms_annotate = 0.f;
-    c->n_columns = columns;
+    if (const int rc = check_annotate_batch(c, "bmv_annotate", v, begin, cigar_offset, cigar, &columns)) return rc;
+    reset_emit(c->h_an, n, columns);
     *total_xcigar = 0;
     *total_ref_bases = 0;
     if (n == 0) return BMV_OK;
 
     bmv::AnnotateJob j{};
     std::vector<uint64_t> rebased;
-    if (const int rc = upload_annotate_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin,
-                                             cigar_offset, cigar, n, rebased, j))
-        return rc;
-    HIP_TRY(c->an_nm.need_exact(n));
-    HIP_TRY(c->an_pos.need_exact(n));
-    HIP_TRY(c->an_ref_len.need_exact(n));
-    HIP_TRY(c->an_n_xcigar.need_exact(n));
-    HIP_TRY(c->an_n_ref.need_exact(n));
-    HIP_TRY(c->an_xcigar_offset.need_exact((size_t)n + 1u));
-    HIP_TRY(c->an_ref_offset.need_exact((size_t)n + 1u));
-    j.nm = c->an_nm.p;
-    j.pos = c->an_pos.p;
-    j.ref_len = c->an_ref_len.p;
-    j.n_xcigar = c->an_n_xcigar.p;
-    j.n_ref = c->an_n_ref.p;
+    if (const int rc = upload_annotate_batch(c, v, begin, cigar_offset, cigar, rebased, j)) return rc;
     const dim3 grid((n + bmv::kAnnotateWaves - 1u) / bmv::kAnnotateWaves), block(64u * bmv::kAnnotateWaves);
-    uint64_t *scan_tmp = reinterpret_cast<uint64_t *>(c->scan_tmp.p);
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(bmv::bmv_annotate_kernel<false>, grid, block, 0, c->stream, j);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->an_n_xcigar.p, c->an_xcigar_offset.p, n, scan_tmp, c->stream));
-    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->an_n_ref.p, c->an_ref_offset.p, n, scan_tmp, c->stream));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_an_xcigar_offset.data(), c->an_xcigar_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_an_ref_offset.data(), c->an_ref_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms_count = 0.f, ms_write = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_count, c->ev0, c->ev1));
-    const uint64_t n_x = c->h_an_xcigar_offset[n], n_r = c->h_an_ref_offset[n];
-    auto with_headroom = [](size_t need, size_t have) { return need <= have ? have : need + need / 4; };
-    HIP_TRY(c->an_xcigar.need_exact(with_headroom((size_t)n_x, c->an_xcigar.cap)));
-    HIP_TRY(c->an_ref_bases.need_exact(with_headroom((size_t)n_r, c->an_ref_bases.cap)));
-    j.xcigar_offset = c->an_xcigar_offset.p;
-    j.ref_offset = c->an_ref_offset.p;
-    j.xcigar = c->an_xcigar.p;
-    j.ref_bases = c->an_ref_bases.p;
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(bmv::bmv_annotate_kernel<true>, grid, block, 0, c->stream, j);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    c->h_an_xcigar.resize((size_t)n_x);
-    c->h_an_ref_bases.resize((size_t)n_r);
-    HIP_TRY(hipMemcpyAsync(c->h_an_nm.data(), c->an_nm.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_an_pos.data(), c->an_pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_an_ref_len.data(), c->an_ref_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (n_x) HIP_TRY(hipMemcpyAsync(c->h_an_xcigar.data(), c->an_xcigar.p, (size_t)n_x * 4, hipMemcpyDeviceToHost, c->stream));
-    if (n_r) HIP_TRY(hipMemcpyAsync(c->h_an_ref_bases.data(), c->an_ref_bases.p, (size_t)n_r, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&ms_write, c->ev0, c->ev1));
-    c->ms_annotate = ms_count + ms_write;
-    if (getenv("BMV_LOG_CLASSES"))
-        fprintf(stderr, "[bmv] annotate: %u alignments, count pass and scans %.3f ms, write pass %.3f ms\n", n, ms_count, ms_write);
-    *total_xcigar = n_x;
-    *total_ref_bases = n_r;
-    return BMV_OK;
+    return two_pass_emit(
+        c, "annotate", "count pass", j, c->h_an,
+        [&] {
+            hipLaunchKernelGGL(bmv::bmv_annotate_kernel<false>, grid, block, 0, c->stream, j);
+            return hipGetLastError();
+        },
+        [&] {
+            hipLaunchKernelGGL(bmv::bmv_annotate_kernel<true>, grid, block, 0, c->stream, j);
+            return hipGetLastError();
+        },
+        [] { return hipSuccess; }, total_xcigar, total_ref_bases);
 }
 
 int bmv_annotations(bmv_ctx *c, uint32_t *out_nm, uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset,
                     uint32_t *out_xcigar, uint64_t *out_ref_offset, uint8_t *out_ref_bases) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_annotations: null context");
-    auto copy = [](auto *dst, const auto &src) {
-        if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof src[0]);
-    };
-    copy(out_nm, c->h_an_nm);
-    copy(out_pos, c->h_an_pos);
-    copy(out_ref_len, c->h_an_ref_len);
-    copy(out_xcigar_offset, c->h_an_xcigar_offset);
-    copy(out_xcigar, c->h_an_xcigar);
-    copy(out_ref_offset, c->h_an_ref_offset);
-    copy(out_ref_bases, c->h_an_ref_bases);
+    copy_emit(c->h_an, out_nm, out_pos, out_ref_len, out_xcigar_offset, out_xcigar, out_ref_offset, out_ref_bases);
     return BMV_OK;
 }
 
 int bmv_last_annotate_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_last_annotate_stats: null context");
-    if (ms_kernels) *ms_kernels = c->ms_annotate;
-    if (n_columns) *n_columns = c->n_columns;
+    if (ms_kernels) *ms_kernels = c->h_an.ms;
+    if (n_columns) *n_columns = c->h_an.n_columns;
     return BMV_OK;
 }
 
-// The clipping pass (include/bmv.h, bmv_clip.hip.h): bmv_annotate's checks and upload, then the range pass, the count pass,
-// two exclusive sums, the write pass, download -- into results of its own.
+// The clipping pass (include/bmv.h, bmv_clip.hip.h): bmv_annotate's checks and upload, then the range pass in front of the
+// count pass, two exclusive sums, the write pass, download (two_pass_emit) -- into results of its own.
 int bmv_clip(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
              const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
              const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t penalty,
@@ -1665,44 +1598,22 @@ int bmv_clip(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint
     if (!c || !total_xcigar || !total_ref_bases) return fail(BMV_ERR_ARG, "bmv_clip: null argument");
     if (match < 1u || match > 1024u || penalty < 1u || penalty > 1024u)
         return fail(BMV_ERR_ARG, "bmv_clip: match and penalty must be in 1..1024 (got %u and %u)", match, penalty);
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_clip", v, true, begin && cigar_offset)) return rc;
     uint64_t columns = 0;
-    if (const int rc = check_annotate_batch(c, "bmv_clip", reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len,
-                                            begin, cigar_offset, cigar, n, &columns))
-        return rc;
+    if (const int rc = check_annotate_batch(c, "bmv_clip", v, begin, cigar_offset, cigar, &columns)) return rc;
     c->h_cl_score.assign(n, 0);
     c->h_cl_left.assign(n, 0);
     c->h_cl_right.assign(n, 0);
-    c->h_cl_nm.assign(n, 0);
-    c->h_cl_pos.assign(n, 0);
-    c->h_cl_ref_len.assign(n, 0);
-    c->h_cl_xcigar_offset.assign((size_t)n + 1, 0);
-    c->h_cl_ref_offset.assign((size_t)n + 1, 0);
-    c->h_cl_xcigar.clear();
-    c->h_cl_ref_bases.clear();
-    c->ms_clip = 0.f;
-    c->n_clip_columns = columns;
+    reset_emit(c->h_cl, n, columns);
     *total_xcigar = 0;
     *total_ref_bases = 0;
     if (n == 0) return BMV_OK;
 
     bmv::ClipJob j{};
     std::vector<uint64_t> rebased;
-    if (const int rc = upload_annotate_batch(c, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin,
-                                             cigar_offset, cigar, n, rebased, j.a))
-        return rc;
-    HIP_TRY(c->cl_score.need_exact(n));
-    HIP_TRY(c->cl_l.need_exact(n));
-    HIP_TRY(c->cl_r.need_exact(n));
-    HIP_TRY(c->cl_pos0.need_exact(n));
-    HIP_TRY(c->cl_left.need_exact(n));
-    HIP_TRY(c->cl_right.need_exact(n));
-    HIP_TRY(c->cl_nm.need_exact(n));
-    HIP_TRY(c->cl_pos.need_exact(n));
-    HIP_TRY(c->cl_ref_len.need_exact(n));
-    HIP_TRY(c->cl_n_xcigar.need_exact(n));
-    HIP_TRY(c->cl_n_ref.need_exact(n));
-    HIP_TRY(c->cl_xcigar_offset.need_exact((size_t)n + 1u));
-    HIP_TRY(c->cl_ref_offset.need_exact((size_t)n + 1u));
+    if (const int rc = upload_annotate_batch(c, v, begin, cigar_offset, cigar, rebased, j.a)) return rc;
+    HIP_TRY(need_exact_all(n, c->cl_score, c->cl_l, c->cl_r, c->cl_pos0, c->cl_left, c->cl_right));
     j.match = match;
     j.penalty = penalty;
     j.score = c->cl_score.p;
@@ -1711,91 +1622,51 @@ int bmv_clip(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint
     j.pos0 = c->cl_pos0.p;
     j.clip_left = c->cl_left.p;
     j.clip_right = c->cl_right.p;
-    j.a.nm = c->cl_nm.p;
-    j.a.pos = c->cl_pos.p;
-    j.a.ref_len = c->cl_ref_len.p;
-    j.a.n_xcigar = c->cl_n_xcigar.p;
-    j.a.n_ref = c->cl_n_ref.p;
     const dim3 grid((n + bmv::kAnnotateWaves - 1u) / bmv::kAnnotateWaves), block(64u * bmv::kAnnotateWaves);
-    uint64_t *scan_tmp = reinterpret_cast<uint64_t *>(c->scan_tmp.p);
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(bmv::bmv_clip_range_kernel<bmv::kAnnotateWaves>, grid, block, 0, c->stream, j);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<false>, grid, block, 0, c->stream, j);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->cl_n_xcigar.p, c->cl_xcigar_offset.p, n, scan_tmp, c->stream));
-    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->cl_n_ref.p, c->cl_ref_offset.p, n, scan_tmp, c->stream));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_cl_xcigar_offset.data(), c->cl_xcigar_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_cl_ref_offset.data(), c->cl_ref_offset.p, ((size_t)n + 1u) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms_count = 0.f, ms_write = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_count, c->ev0, c->ev1));
-    const uint64_t n_x = c->h_cl_xcigar_offset[n], n_r = c->h_cl_ref_offset[n];
-    auto with_headroom = [](size_t need, size_t have) { return need <= have ? have : need + need / 4; };
-    HIP_TRY(c->cl_xcigar.need_exact(with_headroom((size_t)n_x, c->cl_xcigar.cap)));
-    HIP_TRY(c->cl_ref_bases.need_exact(with_headroom((size_t)n_r, c->cl_ref_bases.cap)));
-    j.a.xcigar_offset = c->cl_xcigar_offset.p;
-    j.a.ref_offset = c->cl_ref_offset.p;
-    j.a.xcigar = c->cl_xcigar.p;
-    j.a.ref_bases = c->cl_ref_bases.p;
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<true>, grid, block, 0, c->stream, j);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    c->h_cl_xcigar.resize((size_t)n_x);
-    c->h_cl_ref_bases.resize((size_t)n_r);
-    HIP_TRY(hipMemcpyAsync(c->h_cl_score.data(), c->cl_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_cl_left.data(), c->cl_left.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_cl_right.data(), c->cl_right.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_cl_nm.data(), c->cl_nm.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_cl_pos.data(), c->cl_pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_cl_ref_len.data(), c->cl_ref_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (n_x) HIP_TRY(hipMemcpyAsync(c->h_cl_xcigar.data(), c->cl_xcigar.p, (size_t)n_x * 4, hipMemcpyDeviceToHost, c->stream));
-    if (n_r) HIP_TRY(hipMemcpyAsync(c->h_cl_ref_bases.data(), c->cl_ref_bases.p, (size_t)n_r, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&ms_write, c->ev0, c->ev1));
-    c->ms_clip = ms_count + ms_write;
-    if (getenv("BMV_LOG_CLASSES"))
-        fprintf(stderr, "[bmv] clip: %u alignments, range and count passes and scans %.3f ms, write pass %.3f ms\n", n, ms_count, ms_write);
-    *total_xcigar = n_x;
-    *total_ref_bases = n_r;
-    return BMV_OK;
+    return two_pass_emit(
+        c, "clip", "range and count passes", j.a, c->h_cl,
+        [&] {
+            hipLaunchKernelGGL(bmv::bmv_clip_range_kernel<bmv::kAnnotateWaves>, grid, block, 0, c->stream, j);
+            if (const hipError_t e = hipGetLastError()) return e;
+            hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<false>, grid, block, 0, c->stream, j);
+            return hipGetLastError();
+        },
+        [&] {
+            hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<true>, grid, block, 0, c->stream, j);
+            return hipGetLastError();
+        },
+        [&] {
+            if (const hipError_t e = hipMemcpyAsync(c->h_cl_score.data(), c->cl_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream)) return e;
+            if (const hipError_t e = hipMemcpyAsync(c->h_cl_left.data(), c->cl_left.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)) return e;
+            return hipMemcpyAsync(c->h_cl_right.data(), c->cl_right.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
+        },
+        total_xcigar, total_ref_bases);
 }
 
 int bmv_clipped(bmv_ctx *c, int64_t *out_score, uint32_t *out_clip_left, uint32_t *out_clip_right, uint32_t *out_nm,
                 uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset, uint32_t *out_xcigar,
                 uint64_t *out_ref_offset, uint8_t *out_ref_bases) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_clipped: null context");
-    auto copy = [](auto *dst, const auto &src) {
-        if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof src[0]);
-    };
-    copy(out_score, c->h_cl_score);
-    copy(out_clip_left, c->h_cl_left);
-    copy(out_clip_right, c->h_cl_right);
-    copy(out_nm, c->h_cl_nm);
-    copy(out_pos, c->h_cl_pos);
-    copy(out_ref_len, c->h_cl_ref_len);
-    copy(out_xcigar_offset, c->h_cl_xcigar_offset);
-    copy(out_xcigar, c->h_cl_xcigar);
-    copy(out_ref_offset, c->h_cl_ref_offset);
-    copy(out_ref_bases, c->h_cl_ref_bases);
+    copy_out(out_score, c->h_cl_score);
+    copy_out(out_clip_left, c->h_cl_left);
+    copy_out(out_clip_right, c->h_cl_right);
+    copy_emit(c->h_cl, out_nm, out_pos, out_ref_len, out_xcigar_offset, out_xcigar, out_ref_offset, out_ref_bases);
     return BMV_OK;
 }
 
 int bmv_last_clip_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_last_clip_stats: null context");
-    if (ms_kernels) *ms_kernels = c->ms_clip;
-    if (n_columns) *n_columns = c->n_clip_columns;
+    if (ms_kernels) *ms_kernels = c->h_cl.ms;
+    if (n_columns) *n_columns = c->h_cl.n_columns;
     return BMV_OK;
 }
 
 int bmv_results(bmv_ctx *c, int32_t *out_score, uint32_t *out_begin, uint64_t *out_cigar_offset, uint32_t *out_cigar) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_results: null context");
-    if (out_score) memcpy(out_score, c->h_score.data(), c->h_score.size() * sizeof(int32_t));
-    if (out_begin) memcpy(out_begin, c->h_begin.data(), c->h_begin.size() * sizeof(uint32_t));
-    if (out_cigar_offset) memcpy(out_cigar_offset, c->h_offset.data(), c->h_offset.size() * sizeof(uint64_t));
-    if (out_cigar && !c->h_cigar.empty()) memcpy(out_cigar, c->h_cigar.data(), c->h_cigar.size() * sizeof(uint32_t));
+    copy_out(out_score, c->h_score);
+    copy_out(out_begin, c->h_begin);
+    copy_out(out_cigar_offset, c->h_offset);
+    copy_out(out_cigar, c->h_cigar);
     return BMV_OK;
 }
 

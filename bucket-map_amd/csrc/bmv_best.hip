@@ -1,5 +1,5 @@
 // bmv_best.hip -- the distance and pick kernels of bmv_align_best (bmv_best.hip.h), instantiated in a translation unit of
-// their own (declared `extern template` in bmv_api.hip), like bmv_screen.hip.
+// their own (declared `extern template` in bmv_best.hip.h), like bmv_screen.hip.
 #include "bmv_best.hip.h"
 
 namespace bmv {

@@ -416,4 +416,17 @@ __global__ void bmv_best_pick_kernel(PickJob P);
 __global__ void bmv_best_compact_kernel(const uint32_t *__restrict__ need, const uint32_t *__restrict__ where,
                                         const uint32_t *__restrict__ winner, uint32_t n_groups, uint32_t *__restrict__ out);
 
+// instantiated in bmv_best.hip
+extern template __global__ void bmv_best_lane_kernel<1>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<2>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<3>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<4>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<5>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<6>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<7>(BestJob);
+extern template __global__ void bmv_best_lane_kernel<8>(BestJob);
+extern template __global__ void bmv_best_wave_kernel<1>(BestJob);
+extern template __global__ void bmv_best_wave_kernel<2>(BestJob);
+extern template __global__ void bmv_best_wave_kernel<4>(BestJob);
+
 }  // namespace bmv

@@ -1,5 +1,5 @@
 // bmv_clip.hip -- the soft-clipping kernels of bmv_clip (bmv_clip.hip.h), in a translation unit of their own (declared
-// `extern` in bmv_api.hip), like bmv_annotate.hip: no other kernel's device code is recompiled beside them.
+// `extern` in bmv_clip.hip.h), like bmv_annotate.hip: no other kernel's device code is recompiled beside them.
 #include "bmv_clip.hip.h"
 
 namespace bmv {

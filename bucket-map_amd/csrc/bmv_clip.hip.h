@@ -291,4 +291,9 @@ __global__ __launch_bounds__(64 * kAnnotateWaves) void bmv_clip_emit_kernel(Clip
     }
 }
 
+// instantiated in bmv_clip.hip
+extern template __global__ void bmv_clip_range_kernel<kAnnotateWaves>(ClipJob);
+extern template __global__ void bmv_clip_emit_kernel<false>(ClipJob);
+extern template __global__ void bmv_clip_emit_kernel<true>(ClipJob);
+
 }  // namespace bmv

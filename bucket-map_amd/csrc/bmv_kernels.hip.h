@@ -816,4 +816,26 @@ __global__ __launch_bounds__(kWave) void bmv_align_lane_kernel(Job J) {
     J.out_nops[slot] = n_rev;
 }
 
+// Instantiated in bmv_variants.hip, bmv_variants2.hip and bmv_variants3.hip, one compiler run each; every other combination is
+// instantiated where it is used (bmv_api.hip: groups of up to 4 words a lane, and the lone lane).
+extern template __global__ void bmv_align_kernel<4, 5, false>(Job);
+extern template __global__ void bmv_align_kernel<4, 6, false>(Job);
+extern template __global__ void bmv_align_kernel<4, 7, false>(Job);
+extern template __global__ void bmv_align_kernel<4, 8, false>(Job);
+extern template __global__ void bmv_align_kernel<8, 4, false>(Job);
+extern template __global__ void bmv_align_kernel<8, 5, false>(Job);
+extern template __global__ void bmv_align_kernel<8, 6, false>(Job);
+extern template __global__ void bmv_align_kernel<8, 7, false>(Job);
+extern template __global__ void bmv_align_kernel<8, 8, false>(Job);
+extern template __global__ void bmv_align_kernel<4, 6, true>(Job);
+extern template __global__ void bmv_align_kernel<4, 8, true>(Job);
+extern template __global__ void bmv_align_lane_kernel<1>(Job);
+extern template __global__ void bmv_align_lane_kernel<2>(Job);
+extern template __global__ void bmv_align_lane_kernel<3>(Job);
+extern template __global__ void bmv_align_lane_kernel<4>(Job);
+extern template __global__ void bmv_align_lane_kernel<5>(Job);
+extern template __global__ void bmv_align_lane_kernel<6>(Job);
+extern template __global__ void bmv_align_lane_kernel<7>(Job);
+extern template __global__ void bmv_align_lane_kernel<8>(Job);
+
 }  // namespace bmv

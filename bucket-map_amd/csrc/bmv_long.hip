@@ -1,5 +1,5 @@
 // bmv_long.hip -- the kernels of bmv_align_long (bmv_long.hip.h), instantiated in a translation unit of their own
-// (declared `extern template` in bmv_api.hip), like bmv_variants*.hip: compile time stays bounded.
+// (declared `extern template` in bmv_long.hip.h), like bmv_variants*.hip: compile time stays bounded.
 #include "bmv_long.hip.h"
 
 namespace bmv {

@@ -384,4 +384,9 @@ __global__ __launch_bounds__(kWave) void bmv_long_traceback_kernel(LongJob J) {
     J.out_nops[slot] = n_rev;
 }
 
+// instantiated in bmv_long.hip
+extern template __global__ void bmv_long_prep_kernel<kLongCw>(LongJob, uint32_t);
+extern template __global__ void bmv_long_tile_kernel<kLongCw>(LongJob);
+extern template __global__ void bmv_long_traceback_kernel<kLongCw>(LongJob);
+
 }  // namespace bmv

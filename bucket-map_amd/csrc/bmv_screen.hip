@@ -1,5 +1,5 @@
 // bmv_screen.hip -- the score-only screen kernels of bmv_align_bounded (bmv_screen.hip.h), instantiated in a translation
-// unit of their own (declared `extern template` in bmv_api.hip), like bmv_long.hip.
+// unit of their own (declared `extern template` in bmv_screen.hip.h), like bmv_long.hip.
 #include "bmv_screen.hip.h"
 
 namespace bmv {

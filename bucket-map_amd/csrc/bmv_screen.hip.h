@@ -360,4 +360,17 @@ __global__ __launch_bounds__(kWave) void bmv_screen_wave_kernel(ScreenJob J) {
 __global__ void bmv_screen_compact_kernel(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ where, uint32_t n,
                                           uint32_t *__restrict__ out);
 
+// instantiated in bmv_screen.hip
+extern template __global__ void bmv_screen_lane_kernel<1>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<2>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<3>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<4>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<5>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<6>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<7>(ScreenJob);
+extern template __global__ void bmv_screen_lane_kernel<8>(ScreenJob);
+extern template __global__ void bmv_screen_wave_kernel<1>(ScreenJob);
+extern template __global__ void bmv_screen_wave_kernel<2>(ScreenJob);
+extern template __global__ void bmv_screen_wave_kernel<4>(ScreenJob);
+
 }  // namespace bmv

@@ -1,5 +1,5 @@
 // bmv_variants.hip -- the group kernel with 5 to 8 words per lane in groups of 8 lanes and more, and the two strip kernels, instantiated in a translation unit of
-// their own (declared `extern template` in bmv_api.hip): the alignment kernels in one compiler run took more than five minutes;
+// their own (declared `extern template` in bmv_kernels.hip.h): the alignment kernels in one compiler run took more than five minutes;
 // side by side the slowest takes under two.
 #include "bmv_kernels.hip.h"
 

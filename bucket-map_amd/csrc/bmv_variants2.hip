@@ -1,5 +1,5 @@
 // bmv_variants2.hip -- the group kernel with 4 to 8 words per lane in groups of 2..7 lanes, instantiated in a translation unit of
-// their own (declared `extern template` in bmv_api.hip): the alignment kernels in one compiler run took more than five minutes;
+// their own (declared `extern template` in bmv_kernels.hip.h): the alignment kernels in one compiler run took more than five minutes;
 // side by side the slowest takes under two.
 #include "bmv_kernels.hip.h"
 

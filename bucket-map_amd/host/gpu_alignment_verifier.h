@@ -13,6 +13,9 @@
 #include "bucket_locator.h"
 #include "device_pool.h"
 
+#include <sstream>
+#include <string>
+
 namespace bm {
 
 class gpu_alignment_verifier : public alignment_verifier {
@@ -73,6 +76,7 @@ public:
               std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end) override {
         const size_t D = ctx_.size();
         const auto t0 = std::chrono::steady_clock::now();
+        const batch all{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
         score.assign(n, 0);
         begin.assign(n, 0);
         cigar_offset.assign(static_cast<size_t>(n) + 1, 0);
@@ -90,31 +94,21 @@ public:
         for_each_device(D, [&](size_t d) {
             const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
             if (ng == 0) return;
-            const uint32_t a0 = group_offset[g0], m = group_offset[g0 + ng] - a0;
-            if (D == 1) {
-                check(bmv_align_best(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset,
-                                     n_groups, margin, hint, &total[0]), "the GPU alignment verifier failed: ");
-            } else {
-                uint64_t lo = ~0ull, hi = 0;
-                for (uint32_t a = a0; a < a0 + m; a++) {
-                    lo = std::min(lo, query_start[a]);
-                    hi = std::max(hi, query_start[a] + query_len[a]);
-                }
-                if (m == 0) lo = 0;
-                std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
-                for (uint64_t &s : rebased) s -= lo;
-                std::vector<uint32_t> off(group_offset + g0, group_offset + g0 + ng + 1);
+            const uint32_t a0 = group_offset[g0];
+            const share s = slice(all, a0, group_offset[g0 + ng] - a0);
+            std::vector<uint32_t> off;                          // the range's groups, counted from its first alignment
+            if (D > 1) {
+                off.assign(group_offset + g0, group_offset + g0 + ng + 1);
                 for (uint32_t &o : off) o -= a0;
-                check(bmv_align_best(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
-                                     query_len + a0, m, off.data(), ng, margin + g0, hint ? hint + g0 : nullptr, &total[d]),
-                      "the GPU alignment verifier failed: ");
             }
+            check(bmv_align_best(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, s.n,
+                                 D > 1 ? off.data() : group_offset, ng, margin + g0, hint ? hint + g0 : nullptr, &total[d]),
+                  "the GPU alignment verifier failed: ");
             bmv_last_stats(ctx_[d], &ms[d], &cells[d]);
             bmv_last_best_stats(ctx_[d], &counts[d][0], &counts[d][1], &counts[d][2], &counts[d][3], &counts[d][4], &dist_cells[d], nullptr,
                                 nullptr);
         });
-        std::vector<uint64_t> at(D + 1, 0);
-        for (size_t d = 0; d < D; d++) at[d + 1] = at[d] + total[d];
+        const std::vector<uint64_t> at = starts(total);
         cigar.assign(at[D], 0);
         for_each_device(D, [&](size_t d) {
             const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
@@ -124,50 +118,113 @@ public:
             check(bmv_results(ctx_[d], score.data() + a0, begin.data() + a0, off.data(), cigar.data() + at[d]),
                   "reading the verifier's results failed: ");
             check(bmv_best(ctx_[d], winner.data() + g0, edits.data() + a0, end.data() + a0), "reading the verifier's results failed: ");
-            for (uint32_t a = 0; a < m; a++) cigar_offset[a0 + a] = at[d] + off[a];
+            stitch(cigar_offset, a0, m, off, at[d]);
             for (uint32_t g = g0; g < g0 + ng; g++)
                 if (winner[g] != kBeyond) winner[g] += a0;
         });
         // (ranges are contiguous and in order: an empty range's alignments do not exist, so every offset is set but the last)
         cigar_offset[n] = at[D];
-        float slowest = 0;
-        uint64_t all_cells = 0, all_dist = 0;
-        std::array<uint64_t, 5> all{};
-        for (size_t d = 0; d < D; d++) {
-            slowest = std::max(slowest, ms[d]);
-            all_cells += cells[d];
-            all_dist += dist_cells[d];
-            for (size_t k = 0; k < 5; k++) all[k] += counts[d][k];
-        }
-        const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::array<uint64_t, 5> all_counts{};
+        for (size_t d = 0; d < D; d++)
+            for (size_t k = 0; k < 5; k++) all_counts[k] += counts[d][k];
         std::cerr << "[BENCHMARK]\tGPU alignment verification, best per read: " << n << " alignments in " << n_groups << " groups, "
-                  << all_cells << " cells; " << all[0] << " seeds, " << all[1] << " through the distance round (" << all_dist
-                  << " cells, " << all[2] << " beyond, " << all[3] << " undecided), " << all[4] << " realigned; kernels " << slowest
-                  << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of " << call_ms
-                  << " ms in the call.\n";
+                  << sum(cells) << " cells; " << all_counts[0] << " seeds, " << all_counts[1] << " through the distance round ("
+                  << sum(dist_cells) << " cells, " << all_counts[2] << " beyond, " << all_counts[3] << " undecided), " << all_counts[4]
+                  << " realigned; " << timing(ms, t0);
     }
 
     // bmv_annotate per device: the batch is cut exactly as run() cuts it and the packed arrays are stitched the same way
     void annotate(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
                   const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
                   const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, annotation &out) override {
-        post_pass(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, n, out, nullptr, 0, 0);
+        post_pass({reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n}, begin, cigar_offset, cigar, out, nullptr, 0, 0);
     }
     // bmv_clip per device: the same cut, the same stitching, with the score and the two clips per alignment
     void clip(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
               const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
               const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t penalty, clipping &out) override {
-        post_pass(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, n, out, &out,
-                  match, penalty);
+        post_pass({reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n}, begin, cigar_offset, cigar, out, &out, match,
+                  penalty);
     }
 
 private:
+    // the views of a batch, as every call of the ABI takes them
+    struct batch {
+        const uint8_t *reads;
+        uint64_t n_read_bytes;
+        const uint64_t *text_start;
+        const uint32_t *text_len;
+        const uint8_t *text_rc;
+        const uint64_t *query_start;
+        const uint32_t *query_len;
+        uint32_t n;
+    };
+    // What one device is handed of a batch: the alignments a0 .. a0 + n.  Arrays the share does not hold (edit bounds, begins,
+    // CIGAR offsets) go with it as `array + a0`.
+    struct share : batch {
+        uint32_t a0 = 0;
+        std::vector<uint64_t> rebased;      // several devices: what query_start points to, counted from the share's first read byte
+        share() = default;
+        share(share &&) = default;          // (a move keeps the vector's storage; a copy would leave query_start behind)
+    };
+    // One device: the whole batch as it came, no copies (a0 = 0, n = the batch's).  Several: only the span lo .. hi of the read
+    // buffer the share's queries cover, query_start rebased to it, every pointer advanced by a0.
+    share slice(const batch &b, uint32_t a0, uint32_t m) const {
+        share s;
+        static_cast<batch &>(s) = b;
+        if (ctx_.size() == 1) return s;
+        uint64_t lo = ~0ull, hi = 0;
+        for (uint32_t a = a0; a < a0 + m; a++) {
+            lo = std::min(lo, b.query_start[a]);
+            hi = std::max(hi, b.query_start[a] + b.query_len[a]);
+        }
+        if (m == 0) lo = 0;
+        s.rebased.assign(b.query_start + a0, b.query_start + a0 + m);
+        for (uint64_t &q : s.rebased) q -= lo;
+        s.reads = b.reads + lo;
+        s.n_read_bytes = hi - lo;
+        s.text_start = b.text_start + a0;
+        s.text_len = b.text_len + a0;
+        s.text_rc = b.text_rc + a0;
+        s.query_start = s.rebased.data();
+        s.query_len = b.query_len + a0;
+        s.n = m;
+        s.a0 = a0;
+        return s;
+    }
+    // Packed arrays of the ranges back to back, in range order: where each range's entries begin (and, last, how many there are) ...
+    static std::vector<uint64_t> starts(const std::vector<uint64_t> &total) {
+        std::vector<uint64_t> at(total.size() + 1, 0);
+        for (size_t d = 0; d < total.size(); d++) at[d + 1] = at[d] + total[d];
+        return at;
+    }
+    // ... and the offsets of a range's m alignments from a0 on, which count from its own first entry, rebased by `at`
+    static void stitch(std::vector<uint64_t> &offset, uint32_t a0, uint32_t m, const std::vector<uint64_t> &of_range, uint64_t at) {
+        for (uint32_t a = 0; a < m; a++) offset[a0 + a] = at + of_range[a];
+    }
+    template <typename T>
+    static uint64_t sum(const std::vector<T> &per_device) {
+        uint64_t all = 0;
+        for (const T &x : per_device) all += x;
+        return all;
+    }
+    // the end of every [BENCHMARK] line: the kernels' time on the slowest device, of the call's
+    static std::string timing(const std::vector<float> &ms, std::chrono::steady_clock::time_point t0) {
+        const size_t D = ms.size();
+        float slowest = 0;
+        for (const float x : ms) slowest = std::max(slowest, x);
+        const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::ostringstream out;
+        out << "kernels " << slowest << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of "
+            << call_ms << " ms in the call.\n";
+        return out.str();
+    }
+
     // clipped == nullptr: bmv_annotate; else bmv_clip under (match, penalty), `clipped` being `out` itself
-    void post_pass(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
-                   const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
-                   const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, annotation &out, clipping *clipped,
-                   uint32_t match, uint32_t penalty) {
+    void post_pass(const batch &all, const uint32_t *begin, const uint64_t *cigar_offset, const uint32_t *cigar, annotation &out,
+                   clipping *clipped, uint32_t match, uint32_t penalty) {
         const size_t D = ctx_.size();
+        const uint32_t n = all.n;
         const auto t0 = std::chrono::steady_clock::now();
         const char *failed = clipped ? "the GPU clipping pass failed: " : "the GPU annotation pass failed: ";
         out.nm.assign(n, 0);
@@ -181,42 +238,23 @@ private:
             clipped->clip_right.assign(n, 0);
         }
         const std::vector<uint32_t> cut =
-            cut_by_cost(n, D, [&](uint32_t a) { return static_cast<uint64_t>(query_len[a]) * text_len[a] + 1u; });
+            cut_by_cost(n, D, [&](uint32_t a) { return static_cast<uint64_t>(all.query_len[a]) * all.text_len[a] + 1u; });
         std::vector<uint64_t> n_x(D, 0), n_r(D, 0), columns(D, 0);
         std::vector<float> ms(D, 0.f);
-        auto pass = [&](size_t d, const uint8_t *rd, uint64_t n_rd, const uint64_t *ts, const uint32_t *tl, const uint8_t *trc,
-                        const uint64_t *qs, const uint32_t *ql, const uint32_t *bg, const uint64_t *co, uint32_t m) {
-            if (clipped)
-                check(bmv_clip(ctx_[d], rd, n_rd, ts, tl, trc, qs, ql, bg, co, cigar, m, match, penalty, &n_x[d], &n_r[d]), failed);
-            else
-                check(bmv_annotate(ctx_[d], rd, n_rd, ts, tl, trc, qs, ql, bg, co, cigar, m, &n_x[d], &n_r[d]), failed);
-        };
         for_each_device(D, [&](size_t d) {
-            const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
-            if (m == 0) return;
-            if (D == 1) {
-                pass(0, reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, n);
-            } else {
-                uint64_t lo = ~0ull, hi = 0;
-                for (uint32_t a = a0; a < a0 + m; a++) {
-                    lo = std::min(lo, query_start[a]);
-                    hi = std::max(hi, query_start[a] + query_len[a]);
-                }
-                std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
-                for (uint64_t &s : rebased) s -= lo;
-                pass(d, reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(), query_len + a0, begin + a0,
-                     cigar_offset + a0, m);
-            }
-            if (clipped)
+            if (cut[d + 1] == cut[d]) return;
+            const share s = slice(all, cut[d], cut[d + 1] - cut[d]);
+            if (clipped) {
+                check(bmv_clip(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len,
+                               begin + s.a0, cigar_offset + s.a0, cigar, s.n, match, penalty, &n_x[d], &n_r[d]), failed);
                 bmv_last_clip_stats(ctx_[d], &ms[d], &columns[d]);
-            else
+            } else {
+                check(bmv_annotate(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len,
+                                   begin + s.a0, cigar_offset + s.a0, cigar, s.n, &n_x[d], &n_r[d]), failed);
                 bmv_last_annotate_stats(ctx_[d], &ms[d], &columns[d]);
+            }
         });
-        std::vector<uint64_t> at_x(D + 1, 0), at_r(D + 1, 0);
-        for (size_t d = 0; d < D; d++) {
-            at_x[d + 1] = at_x[d] + n_x[d];
-            at_r[d + 1] = at_r[d] + n_r[d];
-        }
+        const std::vector<uint64_t> at_x = starts(n_x), at_r = starts(n_r);
         out.xcigar.assign(at_x[D], 0);
         out.ref_bases.assign(at_r[D], 0);
         for_each_device(D, [&](size_t d) {
@@ -232,24 +270,13 @@ private:
                 check(bmv_annotations(ctx_[d], out.nm.data() + a0, out.pos.data() + a0, out.ref_len.data() + a0, xo.data(),
                                       out.xcigar.data() + at_x[d], ro.data(), out.ref_bases.data() + at_r[d]),
                       "reading the annotations failed: ");
-            for (uint32_t a = 0; a < m; a++) {
-                out.xcigar_offset[a0 + a] = at_x[d] + xo[a];
-                out.ref_offset[a0 + a] = at_r[d] + ro[a];
-            }
+            stitch(out.xcigar_offset, a0, m, xo, at_x[d]);
+            stitch(out.ref_offset, a0, m, ro, at_r[d]);
         });
         out.xcigar_offset[n] = at_x[D];
         out.ref_offset[n] = at_r[D];
-        float slowest = 0;
-        uint64_t all_columns = 0;
-        for (size_t d = 0; d < D; d++) {
-            slowest = std::max(slowest, ms[d]);
-            all_columns += columns[d];
-        }
-        const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        std::cerr << "[BENCHMARK]\tGPU alignment " << (clipped ? "clipping: " : "annotation: ") << n << " alignments, " << all_columns
-                  << " columns; kernels " << slowest
-                  << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of " << call_ms
-                  << " ms in the call.\n";
+        std::cerr << "[BENCHMARK]\tGPU alignment " << (clipped ? "clipping: " : "annotation: ") << n << " alignments, " << sum(columns)
+                  << " columns; " << timing(ms, t0);
     }
 
     // max_edits == nullptr: bmv_align / bmv_align_long, exactly as before
@@ -259,6 +286,7 @@ private:
              std::vector<uint32_t> &cigar) {
         const size_t D = ctx_.size();
         const auto t0 = std::chrono::steady_clock::now();
+        const batch all{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
         score.assign(n, 0);
         begin.assign(n, 0);
         cigar_offset.assign(static_cast<size_t>(n) + 1, 0);
@@ -273,34 +301,19 @@ private:
             if (m == 0) return;
             bool beyond = false;                                // a candidate bmv_align cannot take: the share goes long
             for (uint32_t a = a0; a < a0 + m; a++) beyond = beyond || query_len[a] > kMaxQuery || text_len[a] > kMaxText;
-            const auto align_fn = beyond ? bmv_align_long : bmv_align;
-            if (D == 1 && max_edits) {
-                check(bmv_align_bounded(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, max_edits, n,
-                                        &total[0]), "the GPU alignment verifier failed: ");
-            } else if (D == 1) {
-                check(align_fn(ctx_[0], reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, &total[0]),
+            const share s = slice(all, a0, m);
+            if (max_edits)
+                check(bmv_align_bounded(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len,
+                                        max_edits + s.a0, s.n, &total[d]), "the GPU alignment verifier failed: ");
+            else
+                check((beyond ? bmv_align_long : bmv_align)(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc,
+                                                            s.query_start, s.query_len, s.n, &total[d]),
                       "the GPU alignment verifier failed: ");
-            } else {
-                uint64_t lo = ~0ull, hi = 0;
-                for (uint32_t a = a0; a < a0 + m; a++) {
-                    lo = std::min(lo, query_start[a]);
-                    hi = std::max(hi, query_start[a] + query_len[a]);
-                }
-                std::vector<uint64_t> rebased(query_start + a0, query_start + a0 + m);
-                for (uint64_t &s : rebased) s -= lo;
-                if (max_edits)
-                    check(bmv_align_bounded(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
-                                            query_len + a0, max_edits + a0, m, &total[d]), "the GPU alignment verifier failed: ");
-                else
-                    check(align_fn(ctx_[d], reads + lo, hi - lo, text_start + a0, text_len + a0, text_rc + a0, rebased.data(),
-                                   query_len + a0, m, &total[d]), "the GPU alignment verifier failed: ");
-            }
             bmv_last_stats(ctx_[d], &ms[d], &cells[d]);
             if (max_edits) bmv_last_bounded_stats(ctx_[d], &rejected[d], &screened[d], nullptr);
         });
         // CIGARs of the ranges back to back, in range order; a range's offsets count from its own first entry
-        std::vector<uint64_t> at(D + 1, 0);
-        for (size_t d = 0; d < D; d++) at[d + 1] = at[d] + total[d];
+        const std::vector<uint64_t> at = starts(total);
         cigar.assign(at[D], 0);
         for_each_device(D, [&](size_t d) {
             const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
@@ -308,24 +321,13 @@ private:
             std::vector<uint64_t> off(static_cast<size_t>(m) + 1);
             check(bmv_results(ctx_[d], score.data() + a0, begin.data() + a0, off.data(), cigar.data() + at[d]),
                   "reading the verifier's results failed: ");
-            for (uint32_t a = 0; a < m; a++) cigar_offset[a0 + a] = at[d] + off[a];
+            stitch(cigar_offset, a0, m, off, at[d]);
         });
         cigar_offset[n] = at[D];
-        float slowest = 0;
-        uint64_t all_cells = 0, all_rejected = 0, all_screened = 0;
-        for (size_t d = 0; d < D; d++) {
-            slowest = std::max(slowest, ms[d]);
-            all_cells += cells[d];
-            all_rejected += rejected[d];
-            all_screened += screened[d];
-        }
-        const float call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        std::cerr << "[BENCHMARK]\tGPU alignment verification: " << n << " alignments, " << all_cells << " cells"
-                  << (max_edits ? ", " + std::to_string(all_rejected) + " rejected by the edit bound after " + std::to_string(all_screened) +
+        std::cerr << "[BENCHMARK]\tGPU alignment verification: " << n << " alignments, " << sum(cells) << " cells"
+                  << (max_edits ? ", " + std::to_string(sum(rejected)) + " rejected by the edit bound after " + std::to_string(sum(screened)) +
                                       " screen cells" : std::string())
-                  << "; kernels " << slowest
-                  << " ms" << (D > 1 ? " on the slowest of " + std::to_string(D) + " devices," : "") << " of " << call_ms
-                  << " ms in the call.\n";
+                  << "; " << timing(ms, t0);
     }
 };
 

@@ -389,6 +389,136 @@ def test_refusals_leave_the_context_usable():
     v.close()
 
 
+def _small_batch(rng, genome, n, m=100, width=110):
+    """n reads of m bases with a few substitutions, either strand, one window each."""
+    reads, ts, rc = [], [], []
+    for _ in range(n):
+        start, r = int(rng.integers(0, len(genome) - width)), int(rng.integers(0, 2))
+        src = genome[start + 1: start + 1 + m]
+        reads.append(_mutate(rng, _revcomp(src) if r else src, 0.03, 0, 0))
+        ts.append(start)
+        rc.append(r)
+    return (np.concatenate(reads), np.array(ts, np.uint64), np.full(n, width, np.uint32), np.array(rc, np.uint8),
+            np.arange(n, dtype=np.uint64) * m, np.full(n, m, np.uint32))
+
+
+def _flat(res):
+    return list(res.values()) if isinstance(res, dict) else list(res)
+
+
+@pytest.mark.gpu
+def test_view_refusals_through_every_entry_point():
+    """A query or a text that leaves its buffer is refused by all six calls that take a batch, with the alignment's index
+    and the same words; the context then does a good batch as a fresh one does (and align as the oracle does)."""
+    from bucket_map_amd import verify
+    from oracle import oracle_c as oc
+    rng = np.random.default_rng(82)
+    genome = rng.choice(list(b"ACGT"), 2000).astype(np.uint8)
+    good = _small_batch(rng, genome, 3)
+    n_read_bytes, n_genome = len(good[0]), len(genome)
+    s_ref, b_ref, o_ref, c_ref = oc.align_batch(genome, *good)
+    off, margin, bound = np.array([0, 2, 3], np.uint32), np.array([5, 5], np.uint32), np.full(3, 10, np.uint32)
+    calls = {
+        "align": lambda v, b: v.align(*b),
+        "align_long": lambda v, b: v.align_long(*b),
+        "align_bounded": lambda v, b: v.align_bounded(*b, bound),
+        "align_best": lambda v, b: v.align_best(*b, off, margin),
+        "annotate": lambda v, b: v.annotate(*b, b_ref, o_ref, c_ref),
+        "clip": lambda v, b: v.clip(*b, b_ref, o_ref, c_ref),
+    }
+
+    def with_(k, value):                                       # alignment 1's entry of array k replaced
+        b = [x.copy() for x in good]
+        b[k][1] = value
+        return b
+
+    bad = {
+        "a query one byte past the read buffer": (with_(4, n_read_bytes + 1 - 100), "query lies outside the read buffer"),
+        "query_start beyond the read buffer": (with_(4, n_read_bytes + 1), "query lies outside the read buffer"),
+        "a text one base past the genome": (with_(1, n_genome - 110 + 1), "text lies outside the genome"),
+        "text_start beyond the genome": (with_(1, n_genome + 1), "text lies outside the genome"),
+    }
+    v = verify.Verifier()
+    v.load_genome(genome)
+    for name, call in calls.items():
+        for what, (batch, words) in bad.items():
+            with pytest.raises(verify.BmvError) as e:
+                call(v, batch)
+            assert e.value.code == 1 and "alignment 1:" in str(e.value) and words in str(e.value), (name, what, str(e.value))
+    got = v.align(*good)
+    assert all(np.array_equal(x, y) for x, y in zip(got, (s_ref, b_ref, o_ref, c_ref))), "align after the refusals"
+    fresh = verify.Verifier()
+    fresh.load_genome(genome)
+    for name, call in calls.items():
+        assert all(np.array_equal(x, y) for x, y in zip(_flat(call(v, good)), _flat(call(fresh, good)))), name
+    v.close()
+    fresh.close()
+
+
+@pytest.mark.gpu
+def test_results_survive_other_calls_and_buffers_survive_size_changes():
+    """One context: align (n = 3), annotate of those, clip of another batch (n = 70: a second block in the grids and the
+    scans), align_best (n = 5 in two groups), annotate (n = 3) again.  After every call each of bmv_results, bmv_annotations,
+    bmv_clipped and bmv_best returns what its own last call left -- which is what a fresh context leaves for that call (align:
+    the oracle) -- and the last annotate equals the first."""
+    import ctypes as C
+
+    from bucket_map_amd import verify
+    from oracle import oracle_c as oc
+    rng = np.random.default_rng(83)
+    genome = rng.choice(list(b"ACGT"), 20_000).astype(np.uint8)
+    three, seventy, five = _small_batch(rng, genome, 3), _small_batch(rng, genome, 70, 300, 310), _small_batch(rng, genome, 5)
+    five = (five[0], *five[1:4], np.array([0, 0, 0, 100, 100], np.uint64), five[5])            # two reads: 3 + 2 candidates
+    off, margin = np.array([0, 3, 5], np.uint32), np.array([4, 4], np.uint32)
+    r3, r70 = oc.align_batch(genome, *three), oc.align_batch(genome, *seventy)
+    L = verify.lib()
+    p = lambda x: x.ctypes.data_as(C.POINTER({"int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "int64": C.c_int64,
+                                             "uint8": C.c_uint8}[x.dtype.name]))
+    accessor = {"results": L.bmv_results, "annotations": L.bmv_annotations, "clipped": L.bmv_clipped, "best": L.bmv_best}
+    last = {}                                                  # accessor -> the arrays its own last call should have left
+
+    def fresh(call):
+        w = verify.Verifier()
+        w.load_genome(genome)
+        out = call(w)
+        w.close()
+        return out
+
+    def check(step):
+        for name, want in last.items():
+            got = [np.zeros(max(len(x), 1), x.dtype) for x in want]
+            assert accessor[name](v._h, *(p(x) for x in got)) == 0
+            assert all(np.array_equal(g[: len(x)], x) for g, x in zip(got, want)), f"after {step}: bmv_{name} changed"
+
+    v = verify.Verifier()
+    v.load_genome(genome)
+    got = v.align(*three)
+    assert all(np.array_equal(x, y) for x, y in zip(got, r3))
+    last["results"] = list(r3)
+    check("align")
+    first = v.annotate(*three, *r3[1:])
+    want = fresh(lambda w: w.annotate(*three, *r3[1:]))
+    assert all(np.array_equal(x, y) for x, y in zip(first, want))
+    last["annotations"] = list(want)
+    check("annotate")
+    got = v.clip(*seventy, *r70[1:])
+    want = fresh(lambda w: w.clip(*seventy, *r70[1:]))
+    assert all(np.array_equal(got[k], want[k]) for k in want)
+    last["clipped"] = [want[k] for k in ("score", "clip_left", "clip_right", "nm", "pos", "ref_len", "xcigar_offset", "xcigar",
+                                         "ref_offset", "ref_bases")]
+    check("clip")
+    got = v.align_best(*five, off, margin)
+    want = fresh(lambda w: w.align_best(*five, off, margin))
+    assert all(np.array_equal(got[k], want[k]) for k in want)
+    last["results"] = [want[k] for k in ("score", "begin", "cigar_offset", "cigar")]
+    last["best"] = [want[k] for k in ("winner", "edits", "end")]
+    check("align_best")
+    again = v.annotate(*three, *r3[1:])
+    assert all(np.array_equal(x, y) for x, y in zip(again, first)), "the second annotate differs from the first"
+    check("the second annotate")
+    v.close()
+
+
 GPU_TOOL = os.path.join(ROOT, "bucket-map_amd", "bucketmap_align")
 ORACLE_TOOL = os.path.join(ROOT, "tests", "cpp", "bucketmap_align_oracle")
 
