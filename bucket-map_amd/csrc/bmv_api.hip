@@ -13,6 +13,7 @@
 #include "bmv_best.hip.h"
 #include "bmv_clip.hip.h"
 #include "bmv_long.hip.h"
+#include "bmv_pair.hip.h"
 #include "bmv_screen.hip.h"
 
 #include <stdio.h>
@@ -198,6 +199,16 @@ struct bmv_ctx {
     uint32_t bs_n_seed = 0, bs_n_distance = 0, bs_n_beyond = 0, bs_n_undecided = 0, bs_n_realigned = 0;
     uint64_t bs_cells = 0;
     float ms_distance = 0.f, ms_pick = 0.f;
+    // bmv_pair and bmv_align_paired: the pair kernel's buffers beyond the views and bmv_align_best's (edits, end and the group
+    // offsets are that call's), the host results of bmv_pairs and what bmv_last_pair_stats reports
+    DevBuf<uint32_t> pr_contig, pr_pick, pr_winner;
+    DevBuf<uint8_t> pr_proper;
+    DevBuf<uint64_t> pr_s1, pr_s2;
+    std::vector<uint32_t> h_pr_pick, h_pr_winner;
+    std::vector<uint8_t> h_pr_proper;
+    std::vector<uint64_t> h_pr_s1, h_pr_s2;
+    float ms_pair = 0.f;
+    uint64_t pr_combinations = 0;
 };
 
 namespace {
@@ -885,6 +896,307 @@ int load_genome(bmv_ctx *c, const uint8_t *const *rec, const uint64_t *rec_len, 
     return BMV_OK;
 }
 
+// ---- bmv_align_best and bmv_align_paired ----
+// group_offset as both take it, and the hints
+int check_groups(const char *who, const uint32_t *group_offset, uint32_t n_groups, uint32_t n, const uint32_t *hint) {
+    if (group_offset[0] != 0u) return fail(BMV_ERR_ARG, "%s: group_offset[0] is %u, not 0", who, group_offset[0]);
+    for (uint32_t g = 0; g < n_groups; g++) {
+        if (group_offset[g + 1] < group_offset[g] || group_offset[g + 1] > n)
+            return fail(BMV_ERR_ARG, "group %u: group_offset runs from %u to %u (not monotone, or beyond the %u alignments)", g,
+                        group_offset[g], group_offset[g + 1], n);
+        const uint32_t size = group_offset[g + 1] - group_offset[g];
+        if (hint && size && hint[g] >= size) return fail(BMV_ERR_ARG, "group %u: hint %u, the group has %u alignments", g, hint[g], size);
+    }
+    if (group_offset[n_groups] != n)
+        return fail(BMV_ERR_ARG, "group %u: group_offset ends at %u, the batch has %u alignments", n_groups ? n_groups - 1u : 0u,
+                    group_offset[n_groups], n);
+    return BMV_OK;
+}
+
+// what the first three rounds leave on the host
+struct BestRounds {
+    BestFull f;
+    std::vector<uint32_t> full;                 // per alignment: != 0 when f holds its full alignment
+    std::vector<uint32_t> d, end;               // per alignment: the distance round's (d, end), exact for every d that matters
+    std::vector<uint32_t> winner, edits, out_end, realign;      // the pick's outputs; realign: the winners without a full alignment
+    bool on_device = false;                     // bs_edits / bs_out_end / bs_group_offset hold edits / out_end / the offsets
+    BestRounds(uint32_t n, uint32_t n_groups)
+        : f(n), full(n, 0u), d(n, bmv::kBestUndecided), end(n, 0u), winner(n_groups, bmv::kBestBeyond), edits(n, bmv::kBestBeyond),
+          out_end(n, 0u) {}
+};
+
+// The rounds bmv_align_best and bmv_align_paired share, on a checked batch: the seeds -- one alignment per group, the hinted
+// one -- in full by bmv_align_long; every other alignment through the distance kernels under k = seed's edits + margin, and
+// what they leave undecided in full as well; the pick on the device, which restricts (d, end) to d <= best + margin.
+int best_rounds(bmv_ctx *c, const char *who, const Views &v, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin,
+                const uint32_t *hint, BestRounds &r) {
+    const uint32_t n = v.n;
+    const uint32_t *text_len = v.text_len, *query_len = v.query_len;
+    const uint32_t from = long_from();
+    BestFull &f = r.f;
+    std::vector<uint32_t> &full = r.full, &h_d = r.d, &h_end = r.end, &h_winner = r.winner, &h_edits = r.edits, &h_out_end = r.out_end;
+    c->bs_n_seed = c->bs_n_distance = c->bs_n_beyond = c->bs_n_undecided = c->bs_n_realigned = 0;
+    c->bs_cells = 0;
+    c->ms_distance = c->ms_pick = 0.f;
+
+    // 1. the seeds
+    std::vector<uint32_t> seeds, seed_of(n_groups, bmv::kBestBeyond);
+    for (uint32_t g = 0; g < n_groups; g++) {
+        if (group_offset[g + 1] == group_offset[g]) continue;
+        seed_of[g] = group_offset[g] + (hint ? hint[g] : 0u);
+        seeds.push_back(seed_of[g]);
+    }
+    if (int rc = best_sub_batch(c, v, seeds, f)) return rc;
+    for (uint32_t a : seeds) full[a] = 1u;
+    c->bs_n_seed = (uint32_t)seeds.size();
+
+    for (uint32_t a : seeds) {
+        h_d[a] = f.edits(a);
+        h_end[a] = f.end(a);
+    }
+    if (seeds.size() == n) {
+        // every group is its seed alone: nothing to decide
+        for (uint32_t g = 0; g < n_groups; g++) h_winner[g] = seed_of[g];
+        h_edits = h_d;
+        h_out_end = h_end;
+        return BMV_OK;
+    }
+    // 2. the distance round: everything but the seeds, under k = min(seed's edits + margin, query length)
+    std::vector<uint32_t> bound(n, 0u), undecided;
+    BandLists listed;
+    for (uint32_t g = 0; g < n_groups; g++) {
+        for (uint32_t a = group_offset[g]; a < group_offset[g + 1]; a++) {
+            if (a == seed_of[g]) continue;
+            const uint32_t m = query_len[a];
+            const uint32_t k = (uint32_t)std::min<uint64_t>((uint64_t)h_d[seed_of[g]] + margin[g], m);
+            bound[a] = k;
+            if (goes_long(c, m, text_len[a], from) || m == 0u || text_len[a] == 0u)   // (an empty side: the aligner's own conventions)
+                undecided.push_back(a);
+            else
+                listed.add(a, m, k);
+        }
+    }
+    const size_t n_listed = listed.size();
+    c->bs_n_distance = (uint32_t)n_listed;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(need_exact_all(n, c->bs_d, c->bs_end));
+    if (n_listed) {
+        HIP_TRY(c->bs_bound.need_exact(n));
+        HIP_TRY(c->bs_list.need_exact(n_listed));
+        HIP_TRY(c->bs_count.need_exact(1));
+        if (const int rc = upload_views(c, v)) return rc;
+        HIP_TRY(hipMemcpyAsync(c->bs_bound.p, bound.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        if (const int rc = upload_band_lists(c, listed, c->bs_list.p)) return rc;
+        HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(c->bs_count.p, 0, sizeof(unsigned long long), c->stream));
+        bmv::BestJob j{};
+        fill_views(c, j);
+        j.bound = c->bs_bound.p;
+        j.d = c->bs_d.p;
+        j.end = c->bs_end.p;
+        j.cells = c->bs_count.p;
+        using best_fn = void (*)(bmv::BestJob);
+        static const best_fn per_lane[kLaneWords + 1] = {nullptr,
+                                                         bmv::bmv_best_lane_kernel<1>, bmv::bmv_best_lane_kernel<2>,
+                                                         bmv::bmv_best_lane_kernel<3>, bmv::bmv_best_lane_kernel<4>,
+                                                         bmv::bmv_best_lane_kernel<5>, bmv::bmv_best_lane_kernel<6>,
+                                                         bmv::bmv_best_lane_kernel<7>, bmv::bmv_best_lane_kernel<8>};
+        static const best_fn per_wave[3] = {bmv::bmv_best_wave_kernel<1>, bmv::bmv_best_wave_kernel<2>, bmv::bmv_best_wave_kernel<4>};
+        if (const int rc = launch_bands(c, listed, c->bs_list.p, per_lane, per_wave, j)) return rc;
+        unsigned long long steps = 0;
+        HIP_TRY(hipMemcpyAsync(h_d.data(), c->bs_d.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_end.data(), c->bs_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&steps, c->bs_count.p, sizeof steps, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipEventElapsedTime(&c->ms_distance, c->ev0, c->ev1));
+        c->bs_cells = 64u * (uint64_t)steps;
+        for (uint32_t a : listed.all) {
+            if (h_d[a] == bmv::kBestUndecided) {
+                undecided.push_back(a);
+                c->bs_n_undecided++;
+            } else if (h_d[a] == bmv::kBestBeyond) {
+                c->bs_n_beyond++;
+            }
+        }
+        f.ms += c->ms_distance;
+        if (getenv("BMV_LOG_CLASSES"))
+            fprintf(stderr, "[bmv] best: %zu seeds; distance round %zu per lane, %zu / %zu / %zu per wave at 1 / 2 / 4 words a lane; %u beyond, %u undecided, %.2f ms\n",
+                    seeds.size(), listed.lane.size(), listed.wave[0].size(), listed.wave[1].size(), listed.wave[2].size(), c->bs_n_beyond,
+                    c->bs_n_undecided, c->ms_distance);
+    }
+    // what the kernels did not take or gave up on: in full, which gives d and end as well
+    std::sort(undecided.begin(), undecided.end());
+    if (int rc = best_sub_batch(c, v, undecided, f)) return rc;
+    for (uint32_t a : undecided) {
+        full[a] = 1u;
+        h_d[a] = f.edits(a);
+        h_end[a] = f.end(a);
+    }
+
+    // 3. the pick
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(need_exact_all(n, c->bs_full, c->bs_edits, c->bs_out_end));
+    HIP_TRY(need_exact_all(n_groups, c->bs_margin, c->bs_winner, c->bs_need, c->bs_realign));
+    HIP_TRY(need_exact_all((size_t)n_groups + 1u, c->bs_group_offset, c->bs_need_at));
+    HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n_groups) * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->bs_full.p, full.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->bs_group_offset.p, group_offset, ((size_t)n_groups + 1u) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->bs_margin.p, margin, (size_t)n_groups * 4, hipMemcpyHostToDevice, c->stream));
+    bmv::PickJob pj{};
+    pj.d = c->bs_d.p;
+    pj.end = c->bs_end.p;
+    pj.full = c->bs_full.p;
+    pj.group_offset = c->bs_group_offset.p;
+    pj.margin = c->bs_margin.p;
+    pj.n_groups = n_groups;
+    pj.winner = c->bs_winner.p;
+    pj.need = c->bs_need.p;
+    pj.out_edits = c->bs_edits.p;
+    pj.out_end = c->bs_out_end.p;
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_best_pick_kernel, dim3((n_groups + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, pj);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->bs_need.p, c->bs_need_at.p, n_groups, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
+    hipLaunchKernelGGL(bmv::bmv_best_compact_kernel, dim3((n_groups + 255u) / 256u), dim3(256), 0, c->stream, c->bs_need.p,
+                       c->bs_need_at.p, c->bs_winner.p, n_groups, c->bs_realign.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    uint32_t n_realign = 0;
+    HIP_TRY(hipMemcpyAsync(&n_realign, c->bs_need_at.p + n_groups, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h_winner.data(), c->bs_winner.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h_edits.data(), c->bs_edits.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h_out_end.data(), c->bs_out_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&c->ms_pick, c->ev0, c->ev1));
+    f.ms += c->ms_pick;
+    if (n_realign > n_groups) return fail(BMV_ERR_STATE, "%s: the pick lists %u winners for %u groups", who, n_realign, n_groups);
+    std::vector<uint32_t> &realign = r.realign;
+    realign.resize(n_realign);
+    if (n_realign) HIP_TRY(hipMemcpy(realign.data(), c->bs_realign.p, (size_t)n_realign * 4, hipMemcpyDeviceToHost));
+    for (uint32_t a : realign)
+        if (a >= n) return fail(BMV_ERR_STATE, "%s: the pick lists alignment %u of %u", who, a, n);
+    r.on_device = true;
+    return BMV_OK;
+}
+
+// The last round of both: the alignments `which` -- chosen by a pick, without a full alignment so far -- in full; the distance
+// round and the aligner are two computations of one quantity.
+int best_realign(bmv_ctx *c, const char *who, const Views &v, const std::vector<uint32_t> &which, BestRounds &r) {
+    if (int rc = best_sub_batch(c, v, which, r.f)) return rc;
+    c->bs_n_realigned = (uint32_t)which.size();
+    for (uint32_t a : which) {
+        r.full[a] = 1u;
+        if (r.f.edits(a) != r.d[a] || r.f.end(a) != r.end[a])
+            return fail(BMV_ERR_STATE, "%s: alignment %u has %u edits ending at %u by the distance round, %lld ending at %u in full", who, a,
+                        r.d[a], r.end[a], -(long long)r.f.score[a], r.f.end(a));
+    }
+    return BMV_OK;
+}
+
+// The alignments with keep[a] != 0 in batch order, everything else rejected -> the context, with what bmv_best returns.
+void store_best(bmv_ctx *c, uint32_t n, uint32_t n_groups, uint64_t cells, const std::vector<uint8_t> &keep, BestRounds &r,
+                uint64_t *total_cigar) {
+    BestFull &f = r.f;
+    for (uint32_t a = 0; a < n; a++) {
+        if (keep[a]) continue;
+        f.score[a] = BMV_REJECTED;
+        f.begin[a] = 0;
+        f.cig_len[a] = 0;
+    }
+    store_results(c, n, cells, f.ms, f.score, f.begin, f.pool, f.cig_at, f.cig_len, total_cigar);
+    c->n_best = n;
+    c->n_best_groups = n_groups;
+    c->h_bs_winner = std::move(r.winner);
+    c->h_bs_edits = std::move(r.edits);
+    c->h_bs_end = std::move(r.out_end);
+}
+
+// ---- bmv_pair ----
+// what the pair kernel takes beyond (edits, end): views without reads, the contigs, the groups, the fragment range
+struct PairArgs {
+    const uint64_t *text_start;
+    const uint32_t *text_len;
+    const uint8_t *text_rc;
+    const uint32_t *query_len, *contig;
+    uint32_t n;
+    const uint32_t *group_offset;
+    uint32_t n_groups, min_frag, max_frag;
+};
+
+int check_pair_args(const char *who, const PairArgs &a) {
+    if (a.n_groups & 1u) return fail(BMV_ERR_ARG, "%s: %u groups, the mates of pair p are the groups 2p and 2p + 1", who, a.n_groups);
+    if (a.min_frag > a.max_frag) return fail(BMV_ERR_ARG, "%s: min_frag %u is larger than max_frag %u", who, a.min_frag, a.max_frag);
+    for (uint32_t x = 0; x < a.n; x++)
+        if (a.text_start[x] >> 62) return fail(BMV_ERR_ARG, "alignment %u: text_start %llu does not fit the signed coordinates", x, (unsigned long long)a.text_start[x]);
+    return BMV_OK;
+}
+
+// The pair kernel over checked arguments, with edits and end where they lie on the device (offsets_there: bs_group_offset holds
+// the offsets already); the results to the host, where bmv_pairs reads them.
+int run_pair(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint32_t *d_end, bool offsets_there) {
+    const uint32_t n = a.n, n_groups = a.n_groups, n_pairs = a.n_groups / 2u;
+    c->h_pr_pick.assign(n_groups, BMV_BEYOND);
+    c->h_pr_winner.assign(n_groups, BMV_BEYOND);
+    c->h_pr_proper.assign(n_pairs, 0);
+    c->h_pr_s1.assign(n_pairs, BMV_PAIR_NONE);
+    c->h_pr_s2.assign(n_pairs, BMV_PAIR_NONE);
+    c->ms_pair = 0.f;
+    c->pr_combinations = 0;
+    if (n_pairs == 0) return BMV_OK;
+    for (uint32_t p = 0; p < n_pairs; p++)
+        c->pr_combinations += (uint64_t)(a.group_offset[2u * p + 1u] - a.group_offset[2u * p]) * (a.group_offset[2u * p + 2u] - a.group_offset[2u * p + 1u]);
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(need_exact_all(n, c->text_start, c->text_len, c->text_rc, c->query_len));
+    HIP_TRY(need_exact_all(n_groups, c->pr_pick, c->pr_winner));
+    HIP_TRY(need_exact_all(n_pairs, c->pr_proper, c->pr_s1, c->pr_s2));
+    HIP_TRY(c->bs_group_offset.need_exact((size_t)n_groups + 1u));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(c->text_start.p, a.text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->text_len.p, a.text_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->text_rc.p, a.text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->query_len.p, a.query_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        if (a.contig) {
+            HIP_TRY(c->pr_contig.need_exact(n));
+            HIP_TRY(hipMemcpyAsync(c->pr_contig.p, a.contig, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    if (!offsets_there)
+        HIP_TRY(hipMemcpyAsync(c->bs_group_offset.p, a.group_offset, ((size_t)n_groups + 1u) * 4, hipMemcpyHostToDevice, c->stream));
+    bmv::PairJob j{};
+    j.text_start = c->text_start.p;
+    j.text_len = c->text_len.p;
+    j.text_rc = c->text_rc.p;
+    j.query_len = c->query_len.p;
+    j.edits = d_edits;
+    j.end = d_end;
+    j.contig = (n && a.contig) ? c->pr_contig.p : nullptr;
+    j.group_offset = c->bs_group_offset.p;
+    j.n_pairs = n_pairs;
+    j.min_frag = (int64_t)a.min_frag;
+    j.max_frag = (int64_t)a.max_frag;
+    j.pick = c->pr_pick.p;
+    j.winner = c->pr_winner.p;
+    j.proper = c->pr_proper.p;
+    j.s1 = c->pr_s1.p;
+    j.s2 = c->pr_s2.p;
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_pair_kernel, dim3((n_pairs + bmv::kPairWaves - 1u) / bmv::kPairWaves), dim3(bmv::kPairWaves * bmv::kWave), 0,
+                       c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_pr_pick.data(), c->pr_pick.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_pr_winner.data(), c->pr_winner.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_pr_proper.data(), c->pr_proper.p, (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_pr_s1.data(), c->pr_s1.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_pr_s2.data(), c->pr_s2.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&c->ms_pair, c->ev0, c->ev1));
+    return BMV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1320,11 +1632,9 @@ int bmv_last_bounded_stats(bmv_ctx *c, uint32_t *n_rejected, uint64_t *screen_ce
     return BMV_OK;
 }
 
-// The best alignment of each group (include/bmv.h, bmv_best.hip.h).  Four rounds: the seeds -- one alignment per group, the
-// hinted one -- in full by bmv_align_long; every other alignment through the distance kernels under k = seed's edits +
-// margin, and what they leave undecided in full as well; the pick on the device; the winners that have no full alignment
-// yet in full.  Every full alignment is bmv_align_long's on a batch of its own, so what the winners carry is what that call
-// gives them.
+// The best alignment of each group (include/bmv.h, bmv_best.hip.h).  Four rounds: best_rounds' three, then the winners that
+// have no full alignment yet in full.  Every full alignment is bmv_align_long's on a batch of its own, so what the winners carry
+// is what that call gives them.
 int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
                    const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
                    const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
@@ -1332,194 +1642,98 @@ int bmv_align_best(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, cons
     const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
     if (const int rc = check_view_args(c, "bmv_align_best", v, total_cigar && group_offset, true)) return rc;
     if (n_groups && !margin) return fail(BMV_ERR_ARG, "bmv_align_best: null argument");
-    if (group_offset[0] != 0u) return fail(BMV_ERR_ARG, "bmv_align_best: group_offset[0] is %u, not 0", group_offset[0]);
-    for (uint32_t g = 0; g < n_groups; g++) {
-        if (group_offset[g + 1] < group_offset[g] || group_offset[g + 1] > n)
-            return fail(BMV_ERR_ARG, "group %u: group_offset runs from %u to %u (not monotone, or beyond the %u alignments)", g,
-                        group_offset[g], group_offset[g + 1], n);
-        const uint32_t size = group_offset[g + 1] - group_offset[g];
-        if (hint && size && hint[g] >= size) return fail(BMV_ERR_ARG, "group %u: hint %u, the group has %u alignments", g, hint[g], size);
-    }
-    if (group_offset[n_groups] != n)
-        return fail(BMV_ERR_ARG, "group %u: group_offset ends at %u, the batch has %u alignments", n_groups ? n_groups - 1u : 0u,
-                    group_offset[n_groups], n);
+    if (const int rc = check_groups("bmv_align_best", group_offset, n_groups, n, hint)) return rc;
     uint64_t cells = 0;
     if (const int rc = check_view_ranges(c, v, false, &cells)) return rc;
-    const uint32_t from = long_from();
 
-    BestFull f(n);
-    std::vector<uint32_t> full(n, 0u);
-    c->bs_n_seed = c->bs_n_distance = c->bs_n_beyond = c->bs_n_undecided = c->bs_n_realigned = 0;
-    c->bs_cells = 0;
-    c->ms_distance = c->ms_pick = 0.f;
-
-    // 1. the seeds
-    std::vector<uint32_t> seeds, seed_of(n_groups, bmv::kBestBeyond);
-    for (uint32_t g = 0; g < n_groups; g++) {
-        if (group_offset[g + 1] == group_offset[g]) continue;
-        seed_of[g] = group_offset[g] + (hint ? hint[g] : 0u);
-        seeds.push_back(seed_of[g]);
-    }
-    if (int rc = best_sub_batch(c, v, seeds, f)) return rc;
-    for (uint32_t a : seeds) full[a] = 1u;
-    c->bs_n_seed = (uint32_t)seeds.size();
-
-    std::vector<uint32_t> h_d(n, bmv::kBestUndecided), h_end(n, 0u), h_winner(n_groups, bmv::kBestBeyond), h_edits(n, bmv::kBestBeyond),
-        h_out_end(n, 0u);
-    for (uint32_t a : seeds) {
-        h_d[a] = f.edits(a);
-        h_end[a] = f.end(a);
-    }
-    if (seeds.size() == n) {
-        // every group is its seed alone: nothing to decide
-        for (uint32_t g = 0; g < n_groups; g++) h_winner[g] = seed_of[g];
-        h_edits = h_d;
-        h_out_end = h_end;
-    } else {
-        // 2. the distance round: everything but the seeds, under k = min(seed's edits + margin, query length)
-        std::vector<uint32_t> bound(n, 0u), undecided;
-        BandLists listed;
-        for (uint32_t g = 0; g < n_groups; g++) {
-            for (uint32_t a = group_offset[g]; a < group_offset[g + 1]; a++) {
-                if (a == seed_of[g]) continue;
-                const uint32_t m = query_len[a];
-                const uint32_t k = (uint32_t)std::min<uint64_t>((uint64_t)h_d[seed_of[g]] + margin[g], m);
-                bound[a] = k;
-                if (goes_long(c, m, text_len[a], from) || m == 0u || text_len[a] == 0u)   // (an empty side: the aligner's own conventions)
-                    undecided.push_back(a);
-                else
-                    listed.add(a, m, k);
-            }
-        }
-        const size_t n_listed = listed.size();
-        c->bs_n_distance = (uint32_t)n_listed;
-        HIP_TRY(hipSetDevice(c->p.device));
-        HIP_TRY(need_exact_all(n, c->bs_d, c->bs_end));
-        if (n_listed) {
-            HIP_TRY(c->bs_bound.need_exact(n));
-            HIP_TRY(c->bs_list.need_exact(n_listed));
-            HIP_TRY(c->bs_count.need_exact(1));
-            if (const int rc = upload_views(c, v)) return rc;
-            HIP_TRY(hipMemcpyAsync(c->bs_bound.p, bound.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-            if (const int rc = upload_band_lists(c, listed, c->bs_list.p)) return rc;
-            HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemsetAsync(c->bs_count.p, 0, sizeof(unsigned long long), c->stream));
-            bmv::BestJob j{};
-            fill_views(c, j);
-            j.bound = c->bs_bound.p;
-            j.d = c->bs_d.p;
-            j.end = c->bs_end.p;
-            j.cells = c->bs_count.p;
-            using best_fn = void (*)(bmv::BestJob);
-            static const best_fn per_lane[kLaneWords + 1] = {nullptr,
-                                                             bmv::bmv_best_lane_kernel<1>, bmv::bmv_best_lane_kernel<2>,
-                                                             bmv::bmv_best_lane_kernel<3>, bmv::bmv_best_lane_kernel<4>,
-                                                             bmv::bmv_best_lane_kernel<5>, bmv::bmv_best_lane_kernel<6>,
-                                                             bmv::bmv_best_lane_kernel<7>, bmv::bmv_best_lane_kernel<8>};
-            static const best_fn per_wave[3] = {bmv::bmv_best_wave_kernel<1>, bmv::bmv_best_wave_kernel<2>, bmv::bmv_best_wave_kernel<4>};
-            if (const int rc = launch_bands(c, listed, c->bs_list.p, per_lane, per_wave, j)) return rc;
-            unsigned long long steps = 0;
-            HIP_TRY(hipMemcpyAsync(h_d.data(), c->bs_d.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(h_end.data(), c->bs_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(&steps, c->bs_count.p, sizeof steps, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipEventElapsedTime(&c->ms_distance, c->ev0, c->ev1));
-            c->bs_cells = 64u * (uint64_t)steps;
-            for (uint32_t a : listed.all) {
-                if (h_d[a] == bmv::kBestUndecided) {
-                    undecided.push_back(a);
-                    c->bs_n_undecided++;
-                } else if (h_d[a] == bmv::kBestBeyond) {
-                    c->bs_n_beyond++;
-                }
-            }
-            f.ms += c->ms_distance;
-            if (getenv("BMV_LOG_CLASSES"))
-                fprintf(stderr, "[bmv] best: %zu seeds; distance round %zu per lane, %zu / %zu / %zu per wave at 1 / 2 / 4 words a lane; %u beyond, %u undecided, %.2f ms\n",
-                        seeds.size(), listed.lane.size(), listed.wave[0].size(), listed.wave[1].size(), listed.wave[2].size(), c->bs_n_beyond,
-                        c->bs_n_undecided, c->ms_distance);
-        }
-        // what the kernels did not take or gave up on: in full, which gives d and end as well
-        std::sort(undecided.begin(), undecided.end());
-        if (int rc = best_sub_batch(c, v, undecided, f)) return rc;
-        for (uint32_t a : undecided) {
-            full[a] = 1u;
-            h_d[a] = f.edits(a);
-            h_end[a] = f.end(a);
-        }
-
-        // 3. the pick
-        HIP_TRY(hipSetDevice(c->p.device));
-        HIP_TRY(need_exact_all(n, c->bs_full, c->bs_edits, c->bs_out_end));
-        HIP_TRY(need_exact_all(n_groups, c->bs_margin, c->bs_winner, c->bs_need, c->bs_realign));
-        HIP_TRY(need_exact_all((size_t)n_groups + 1u, c->bs_group_offset, c->bs_need_at));
-        HIP_TRY(c->scan_tmp.need_exact(bmscan::tmp_elems(n_groups) * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpyAsync(c->bs_d.p, h_d.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->bs_end.p, h_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->bs_full.p, full.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->bs_group_offset.p, group_offset, ((size_t)n_groups + 1u) * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->bs_margin.p, margin, (size_t)n_groups * 4, hipMemcpyHostToDevice, c->stream));
-        bmv::PickJob pj{};
-        pj.d = c->bs_d.p;
-        pj.end = c->bs_end.p;
-        pj.full = c->bs_full.p;
-        pj.group_offset = c->bs_group_offset.p;
-        pj.margin = c->bs_margin.p;
-        pj.n_groups = n_groups;
-        pj.winner = c->bs_winner.p;
-        pj.need = c->bs_need.p;
-        pj.out_edits = c->bs_edits.p;
-        pj.out_end = c->bs_out_end.p;
-        HIP_TRY(hipEventRecord(c->ev0, c->stream));
-        hipLaunchKernelGGL(bmv::bmv_best_pick_kernel, dim3((n_groups + bmv::kWave - 1u) / bmv::kWave), dim3(bmv::kWave), 0, c->stream, pj);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(bmscan::exclusive_sum<uint32_t>(c->bs_need.p, c->bs_need_at.p, n_groups, reinterpret_cast<uint32_t *>(c->scan_tmp.p), c->stream));
-        hipLaunchKernelGGL(bmv::bmv_best_compact_kernel, dim3((n_groups + 255u) / 256u), dim3(256), 0, c->stream, c->bs_need.p,
-                           c->bs_need_at.p, c->bs_winner.p, n_groups, c->bs_realign.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev1, c->stream));
-        uint32_t n_realign = 0;
-        HIP_TRY(hipMemcpyAsync(&n_realign, c->bs_need_at.p + n_groups, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(h_winner.data(), c->bs_winner.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(h_edits.data(), c->bs_edits.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(h_out_end.data(), c->bs_out_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipEventElapsedTime(&c->ms_pick, c->ev0, c->ev1));
-        f.ms += c->ms_pick;
-        if (n_realign > n_groups) return fail(BMV_ERR_STATE, "bmv_align_best: the pick lists %u winners for %u groups", n_realign, n_groups);
-        std::vector<uint32_t> realign(n_realign);
-        if (n_realign) HIP_TRY(hipMemcpy(realign.data(), c->bs_realign.p, (size_t)n_realign * 4, hipMemcpyDeviceToHost));
-        for (uint32_t a : realign)
-            if (a >= n) return fail(BMV_ERR_STATE, "bmv_align_best: the pick lists alignment %u of %u", a, n);
-
-        // 4. the winners that have no full alignment yet
-        if (int rc = best_sub_batch(c, v, realign, f)) return rc;
-        c->bs_n_realigned = n_realign;
-        for (uint32_t a : realign) {
-            // the distance round and the aligner are two computations of one quantity
-            if (f.edits(a) != h_d[a] || f.end(a) != h_end[a])
-                return fail(BMV_ERR_STATE, "bmv_align_best: alignment %u has %u edits ending at %u by the distance round, %lld ending at %u in full",
-                            a, h_d[a], h_end[a], -(long long)f.score[a], f.end(a));
-        }
-    }
+    BestRounds r(n, n_groups);
+    if (const int rc = best_rounds(c, "bmv_align_best", v, group_offset, n_groups, margin, hint, r)) return rc;
+    // 4. the winners that have no full alignment yet
+    if (const int rc = best_realign(c, "bmv_align_best", v, r.realign, r)) return rc;
 
     // the winners in batch order, everything else rejected
     std::vector<uint8_t> wins(n, 0);
     for (uint32_t g = 0; g < n_groups; g++)
-        if (h_winner[g] != bmv::kBestBeyond) wins[h_winner[g]] = 1;
-    for (uint32_t a = 0; a < n; a++) {
-        if (wins[a]) continue;
-        f.score[a] = BMV_REJECTED;
-        f.begin[a] = 0;
-        f.cig_len[a] = 0;
+        if (r.winner[g] != bmv::kBestBeyond) wins[r.winner[g]] = 1;
+    store_best(c, n, n_groups, cells, wins, r, total_cigar);
+    return BMV_OK;
+}
+
+// The pair-aware pick alone (include/bmv.h, bmv_pair.hip.h): edits and end go to the device, the kernel runs, bmv_pairs reads.
+int bmv_pair(bmv_ctx *c, const uint64_t *text_start, const uint32_t *text_len, const uint8_t *text_rc, const uint32_t *query_len,
+             const uint32_t *edits, const uint32_t *end, const uint32_t *contig, uint32_t n, const uint32_t *group_offset,
+             uint32_t n_groups, uint32_t min_frag, uint32_t max_frag) {
+    if (!c || !group_offset || (n && (!text_start || !text_len || !text_rc || !query_len || !edits || !end)))
+        return fail(BMV_ERR_ARG, "bmv_pair: null argument");
+    if (const int rc = check_groups("bmv_pair", group_offset, n_groups, n, nullptr)) return rc;
+    const PairArgs a{text_start, text_len, text_rc, query_len, contig, n, group_offset, n_groups, min_frag, max_frag};
+    if (const int rc = check_pair_args("bmv_pair", a)) return rc;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(need_exact_all(n, c->bs_edits, c->bs_out_end));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(c->bs_edits.p, edits, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_out_end.p, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     }
-    store_results(c, n, cells, f.ms, f.score, f.begin, f.pool, f.cig_at, f.cig_len, total_cigar);
-    c->n_best = n;
-    c->n_best_groups = n_groups;
-    c->h_bs_winner = std::move(h_winner);
-    c->h_bs_edits = std::move(h_edits);
-    c->h_bs_end = std::move(h_out_end);
+    return run_pair(c, a, c->bs_edits.p, c->bs_out_end.p, false);
+}
+
+int bmv_pairs(bmv_ctx *c, uint32_t *out_pick, uint8_t *out_proper, uint64_t *out_s1, uint64_t *out_s2, uint32_t *out_winner) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_pairs: null context");
+    copy_out(out_pick, c->h_pr_pick);
+    copy_out(out_proper, c->h_pr_proper);
+    copy_out(out_s1, c->h_pr_s1);
+    copy_out(out_s2, c->h_pr_s2);
+    copy_out(out_winner, c->h_pr_winner);
+    return BMV_OK;
+}
+
+int bmv_last_pair_stats(bmv_ctx *c, float *ms_pair, uint64_t *n_combinations) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_pair_stats: null context");
+    if (ms_pair) *ms_pair = c->ms_pair;
+    if (n_combinations) *n_combinations = c->pr_combinations;
+    return BMV_OK;
+}
+
+// bmv_align_best for pairs (include/bmv.h): best_rounds' three rounds leave (edits, end) within best + margin on the device --
+// whatever the hints were --, the pair kernel picks over them there, and the picks that have no full alignment yet get one.
+int bmv_align_paired(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                     const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
+                     const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                     const uint32_t *contig, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar) {
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_align_paired", v, total_cigar && group_offset, true)) return rc;
+    if (n_groups && !margin) return fail(BMV_ERR_ARG, "bmv_align_paired: null argument");
+    if (const int rc = check_groups("bmv_align_paired", group_offset, n_groups, n, hint)) return rc;
+    const PairArgs a{text_start, text_len, text_rc, query_len, contig, n, group_offset, n_groups, min_frag, max_frag};
+    if (const int rc = check_pair_args("bmv_align_paired", a)) return rc;
+    uint64_t cells = 0;
+    if (const int rc = check_view_ranges(c, v, false, &cells)) return rc;
+
+    // 1. and 2.
+    BestRounds r(n, n_groups);
+    if (const int rc = best_rounds(c, "bmv_align_paired", v, group_offset, n_groups, margin, hint, r)) return rc;
+    // 3. the pair kernel (every group its seed alone: the host holds the distances, nothing went to the device)
+    if (!r.on_device && n) {
+        HIP_TRY(hipSetDevice(c->p.device));
+        HIP_TRY(need_exact_all(n, c->bs_edits, c->bs_out_end));
+        HIP_TRY(hipMemcpyAsync(c->bs_edits.p, r.edits.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_out_end.p, r.out_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if (const int rc = run_pair(c, a, c->bs_edits.p, c->bs_out_end.p, r.on_device)) return rc;
+    r.f.ms += c->ms_pair;
+    // 4. the picks that have no full alignment yet
+    std::vector<uint8_t> picked(n, 0);
+    std::vector<uint32_t> realign;
+    for (uint32_t g = 0; g < n_groups; g++) {
+        const uint32_t x = c->h_pr_pick[g];
+        if (x == BMV_BEYOND) continue;
+        if (x < group_offset[g] || x >= group_offset[g + 1] || r.edits[x] == bmv::kBestBeyond)
+            return fail(BMV_ERR_STATE, "bmv_align_paired: the pair kernel picked alignment %u for group %u", x, g);
+        picked[x] = 1;
+        if (!r.full[x]) realign.push_back(x);
+    }
+    if (const int rc = best_realign(c, "bmv_align_paired", v, realign, r)) return rc;
+    store_best(c, n, n_groups, cells, picked, r, total_cigar);
     return BMV_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "best_mapq.h"
 #include "bm_genome.h"
 #include "mapper.h"
+#include "pair_mapq.h"
 #include "sam_tags.h"
 
 #include <algorithm>
@@ -133,7 +134,8 @@ public:
     }
     // What a SAM record needs beyond that (bmv_annotate's contract, include/bmv.h): forward-strand pos, =/X/I/D entries, NM
     // and the reference bases under X and D columns, for alignments given with their begin and M/I/D CIGAR.  The GPU
-    // verifier's pass; a verifier without one says so.
+    // verifier's pass; for a verifier without one (can_annotate() false) the locator annotates on the host.
+    virtual bool can_annotate() const { return false; }
     virtual void annotate(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
                           const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
                           const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, annotation &out) {
@@ -209,6 +211,70 @@ public:
         cigar_offset[n] = at;
         cigar.resize(at);
     }
+    // The same for pairs (bmv_align_paired's contract, include/bmv.h): the groups 2p and 2p + 1 are the candidates of the two
+    // mates of pair p (n_groups is even); winner, edits and end as best() returns them; pick[g] is the alignment of group g that
+    // select_pair (pair_mapq.h) picks over those edits and ends -- the group's own winner where the pair has no proper
+    // combination -- and alone keeps its score, begin and CIGAR; proper, s1 and s2 per pair.  contig[a] (may be null: one
+    // contig) is the reference sequence alignment a lies on.  This default aligns everything and picks on the host; the GPU
+    // verifier aligns in full only the seeds and the picks.
+    virtual void paired(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                        const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
+                        const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                        const uint32_t *contig, uint32_t min_frag, uint32_t max_frag, std::vector<int32_t> &score,
+                        std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset, std::vector<uint32_t> &cigar,
+                        std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end,
+                        std::vector<uint32_t> &pick, std::vector<uint8_t> &proper, std::vector<uint64_t> &s1, std::vector<uint64_t> &s2) {
+        (void)hint;
+        if (n_groups & 1u) throw std::runtime_error("paired: an odd number of groups");
+        align(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, score, begin, cigar_offset, cigar);
+        winner.assign(n_groups, kBeyond);
+        edits.assign(n, kBeyond);
+        end.assign(n, 0);
+        for (uint32_t g = 0; g < n_groups; g++) {
+            const uint32_t a0 = group_offset[g], a1 = group_offset[g + 1];
+            uint64_t best_d = UINT64_MAX;
+            for (uint32_t a = a0; a < a1; a++) best_d = std::min<uint64_t>(best_d, static_cast<uint64_t>(-static_cast<int64_t>(score[a])));
+            for (uint32_t a = a0; a < a1; a++) {
+                const uint64_t d = static_cast<uint64_t>(-static_cast<int64_t>(score[a]));
+                if (d == best_d && winner[g] == kBeyond) winner[g] = a;
+                if (d > best_d + margin[g]) continue;
+                uint32_t r = 0;
+                for (uint64_t x = cigar_offset[a]; x < cigar_offset[a + 1]; x++)
+                    if ((cigar[x] & 15u) != 1u) r += cigar[x] >> 4;
+                edits[a] = static_cast<uint32_t>(d);
+                end[a] = begin[a] + r;
+            }
+        }
+        pick.assign(n_groups, kBeyond);
+        proper.assign(n_groups / 2u, 0);
+        s1.assign(n_groups / 2u, kPairNone);
+        s2.assign(n_groups / 2u, kPairNone);
+        std::vector<uint8_t> keep(n, 0);
+        for (uint32_t p = 0; p < n_groups / 2u; p++) {
+            const pair_pick pp = select_pair(text_start, text_len, text_rc, query_len, edits.data(), end.data(), contig, group_offset[2 * p],
+                                             group_offset[2 * p + 1], group_offset[2 * p + 2], min_frag, max_frag);
+            for (uint32_t k = 0; k < 2u; k++) {
+                pick[2 * p + k] = pp.pick[k];
+                if (pp.pick[k] != kBeyond) keep[pp.pick[k]] = 1;
+            }
+            proper[p] = pp.proper ? 1 : 0;
+            s1[p] = pp.s1;
+            s2[p] = pp.s2;
+        }
+        uint64_t at = 0;
+        for (uint32_t a = 0; a < n; a++) {
+            const uint64_t from = cigar_offset[a], to = cigar_offset[a + 1];
+            cigar_offset[a] = at;
+            if (!keep[a]) {
+                score[a] = kRejected;
+                begin[a] = 0;
+                continue;
+            }
+            for (uint64_t x = from; x < to; x++) cigar[at++] = cigar[x];
+        }
+        cigar_offset[n] = at;
+        cigar.resize(at);
+    }
 };
 
 // SAM text as seqan3::sam_file_output lays it out: records are appended to one buffer with
@@ -273,16 +339,21 @@ public:
             buf_ += '\n';
         }
     }
-    // QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL [tags: "NM:i:3\tMD:Z:..." -- appended after a tab when not empty]
+    // QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL [tags: "NM:i:3\tMD:Z:..." -- appended after a tab when not empty];
+    // RNEXT PNEXT TLEN are * 0 0 for every record but those of --paired
     static void format(std::string &buf, std::string_view qname, unsigned flag, std::string_view rname, uint64_t pos, unsigned mapq,
-                       std::string_view cigar, std::string_view seq, std::string_view qual, std::string_view tags = {}) {
+                       std::string_view cigar, std::string_view seq, std::string_view qual, std::string_view tags = {},
+                       std::string_view rnext = "*", uint64_t pnext = 0, int64_t tlen = 0) {
         buf.append(qname); buf += '\t';
         number(buf, flag); buf += '\t';
         buf.append(rname); buf += '\t';
         number(buf, pos); buf += '\t';
         number(buf, mapq); buf += '\t';
-        buf.append(cigar);
-        buf += "\t*\t0\t0\t";
+        buf.append(cigar); buf += '\t';
+        buf.append(rnext); buf += '\t';
+        number(buf, pnext); buf += '\t';
+        if (tlen < 0) buf += '-';
+        number(buf, tlen < 0 ? static_cast<uint64_t>(-tlen) : static_cast<uint64_t>(tlen)); buf += '\t';
         buf.append(seq); buf += '\t';
         buf.append(qual);
         if (!tags.empty()) {
@@ -292,8 +363,9 @@ public:
         buf += '\n';
     }
     void record(std::string_view qname, unsigned flag, std::string_view rname, uint64_t pos, unsigned mapq, std::string_view cigar,
-                std::string_view seq, std::string_view qual, std::string_view tags = {}) {
-        format(buf_, qname, flag, rname, pos, mapq, cigar, seq, qual, tags);
+                std::string_view seq, std::string_view qual, std::string_view tags = {}, std::string_view rnext = "*", uint64_t pnext = 0,
+                int64_t tlen = 0) {
+        format(buf_, qname, flag, rname, pos, mapq, cigar, seq, qual, tags, rnext, pnext, tlen);
         if (buf_.size() > (4u << 20)) flush();
     }
     // records formatted elsewhere (format(): a few threads, each a block of reads), appended in order
@@ -317,6 +389,9 @@ private:
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
     uint32_t _clip_match = 1, _clip_penalty = 2;
     float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
+    bool _paired = false;                        // --paired: records 2p and 2p + 1 of the FASTQ file are mates, placed together
+    uint32_t _min_frag = 1, _max_frag = 1000;    // --frag-range: what a proper pair spans, leftmost to rightmost base
+    std::vector<uint8_t> flat_genome_;           // --annotate with a verifier that cannot annotate: the records back to back
     const Genome *genome_ = nullptr;
     std::vector<Bucket> buckets_;
     std::vector<uint64_t> bstart_;               // bucket views into the records laid back to back
@@ -520,6 +595,15 @@ public:
     // --best: every read's candidates go through the verifier as one group (alignment_verifier::best), the read gets ONE record,
     // its best alignment's, with MAPQ and X0 from best_mapq.h; margin = max(1, (uint32_t)(rate x read length))
     void set_best(float margin_rate) { _best_margin = margin_rate; }
+    // --paired: the FASTQ file is interleaved; the two mates' candidates go through the verifier together
+    // (alignment_verifier::paired) and each mate gets the record of its PICK, with the pair's flags, RNEXT, PNEXT and TLEN and
+    // the MAPQ and X0 of pair_mapq.h.  Implies --best (the caller sets its margin) and --annotate.
+    void set_paired(uint32_t min_frag, uint32_t max_frag) {
+        _paired = _annotate = true;
+        if (_best_margin < 0.f) _best_margin = 0.05f;
+        _min_frag = min_frag;
+        _max_frag = max_frag;
+    }
     void set_clip(uint32_t match, uint32_t penalty) {
         _clip = _annotate = true;
         _clip_match = match;
@@ -826,6 +910,9 @@ private:
             std::vector<uint64_t> text_start, query_start, cigar_offset;
             std::vector<uint32_t> text_len, query_len, begin, cigar, max_edits;
             std::vector<uint32_t> group_offset{0}, margin, hint, winner, edits, end;    // --best: a group per read
+            std::vector<uint32_t> contig, pick;                 // --paired: per alignment its @SQ entry; per read its pick
+            std::vector<uint8_t> proper;                        // ... and per pair (reads 2p, 2p + 1 of the block)
+            std::vector<uint64_t> s1, s2;
             std::vector<uint8_t> text_rc;
             std::vector<int32_t> score;
             std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
@@ -842,13 +929,34 @@ private:
         std::thread worker;
         const bool bounded = _max_edit_rate >= 0.f;             // --max-edit-rate: rejected alignments leave no record
         const bool best = _best_margin >= 0.f;                  // --best: neither do the alignments that did not win
+        const bool paired = _paired;                            // --paired: --best with the pick of the pair in the winner's place
+        std::vector<uint32_t> bucket_ref;                       // per bucket the index of its @SQ entry (runs of equal names)
+        if (paired) {
+            if (locate_res.size() % 2u)
+                throw std::runtime_error(sequence_file + " holds " + std::to_string(locate_res.size()) +
+                                         " records, an odd number: --paired takes one interleaved FASTQ file, records 2p and 2p + 1 being mates");
+            for (size_t bk = 0; bk < h.bucket_name.size(); bk++)
+                bucket_ref.push_back(bk == 0 ? 0u : bucket_ref[bk - 1] + (h.bucket_name[bk] == h.bucket_name[bk - 1] ? 0u : 1u));
+        }
+        // --annotate with a verifier that has no annotation pass (the oracle-backed test tools): sam_tags::annotate_on_host
+        const bool annotate_here = _annotate && !_clip && !_v->can_annotate();
+        if (annotate_here && flat_genome_.empty())
+            for (const auto &seq : genome_->seqs) flat_genome_.insert(flat_genome_.end(), seq.begin(), seq.end());
         auto is_written = [&](const Block &b, size_t a) {       // :570-573, and the edit bound
             const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
             return !((bounded || best) && b.score[a] == alignment_verifier::kRejected) && !(map_qual < quality_threshold);
         };
         auto align = [&](Block &b) {                            // on the worker thread
             try {
-                if (!b.text_start.empty() && best) {
+                if (!b.text_start.empty() && paired) {
+                    _v->paired(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
+                               b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.group_offset.data(),
+                               static_cast<uint32_t>(b.margin.size()), b.margin.data(), b.hint.data(), b.contig.data(), _min_frag, _max_frag,
+                               b.score, b.begin, b.cigar_offset, b.cigar, b.winner, b.edits, b.end, b.pick, b.proper, b.s1, b.s2);
+                    for (size_t a = 0; bounded && a < b.score.size(); a++)
+                        if (b.score[a] != alignment_verifier::kRejected && -static_cast<int64_t>(b.score[a]) > static_cast<int64_t>(b.max_edits[a]))
+                            b.score[a] = alignment_verifier::kRejected;
+                } else if (!b.text_start.empty() && best) {
                     _v->best(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                              b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.group_offset.data(),
                              static_cast<uint32_t>(b.margin.size()), b.margin.data(), b.hint.data(), b.score, b.begin, b.cigar_offset,
@@ -883,6 +991,9 @@ private:
                     if (_clip)
                         _v->clip(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
                                  co.data(), cg.data(), static_cast<uint32_t>(ts.size()), _clip_match, _clip_penalty, b.ann);
+                    else if (annotate_here)
+                        sam_tags::annotate_on_host(flat_genome_.data(), b.bases.data(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(),
+                                                   bg.data(), co.data(), cg.data(), static_cast<uint32_t>(ts.size()), b.ann);
                     else
                         _v->annotate(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
                                      co.data(), cg.data(), static_cast<uint32_t>(ts.size()), b.ann);
@@ -896,6 +1007,28 @@ private:
         // (--best: the winners only)
         std::ofstream dump;
         if (const char *e = std::getenv("BM_DUMP_ALIGNMENTS")) dump.open(e);
+        // --paired: the one record read r of the block may get -- its pick's, when it passes what a --best record passes
+        struct mate_record {
+            bool has = false, rc = false;
+            unsigned int bucket = 0;
+            uint64_t pos = 0;                                   // 1-based, as written
+            uint32_t ref_len = 0;
+        };
+        auto mate_of = [&](const Block &b, size_t r) {
+            mate_record m;
+            const uint32_t a0 = b.group_offset[r];
+            if (b.group_offset[r + 1] == a0 || b.pick[r] == alignment_verifier::kBeyond) return m;
+            const uint32_t a = b.pick[r];
+            if (!is_written(b, a) || (_clip && b.ann.score[b.ann_slot[a]] == 0)) return m;
+            const locate_t &loc = locate_res[b.first_read + r][a - a0];
+            const int offset = std::get<1>(loc);
+            m.has = true;
+            m.rc = !std::get<4>(loc);
+            m.bucket = std::get<0>(loc);
+            m.pos = static_cast<uint64_t>(b.ann.pos[b.ann_slot[a]]) + h.bucket_offsets[m.bucket] + (offset < 0 ? 0 : offset) + 1u;
+            m.ref_len = b.ann.ref_len[b.ann_slot[a]];
+            return m;
+        };
         auto write = [&](Block &b) {
             if (b.failed) std::rethrow_exception(b.failed);
             size_t a = 0;
@@ -903,16 +1036,50 @@ private:
             for (size_t r = 0; r < b.reads.size(); r++) {
                 rc_seq.clear();                                 // (--annotate: made for the read's first flag-16 record)
                 best_quality bq{0u, 0u};                        // --best: the MAPQ and X0 of the read's one record
-                if (best && b.group_offset[r + 1] > b.group_offset[r]) {
+                const bool candidates = best && b.group_offset[r + 1] > b.group_offset[r];
+                const bool proper = paired && candidates && b.proper[r / 2] != 0;
+                if (proper) {
+                    const uint32_t a0 = b.group_offset[r];
+                    const size_t p = r / 2;
+                    bq = pair_mate_mapq(pair_quality(b.s1[p], b.s2[p], static_cast<uint64_t>(b.margin[2 * p]) + b.margin[2 * p + 1]),
+                                        b.pick[r] - a0, b.winner[r] - a0, b.edits.data() + a0, b.end.data() + a0, b.text_start.data() + a0,
+                                        b.text_len.data() + a0, b.text_rc.data() + a0, b.group_offset[r + 1] - a0, b.margin[r]);
+                } else if (candidates) {
                     const uint32_t a0 = b.group_offset[r];
                     bq = best_mapq(b.winner[r] - a0, b.edits.data() + a0, b.end.data() + a0, b.text_start.data() + a0,
                                    b.text_len.data() + a0, b.text_rc.data() + a0, b.group_offset[r + 1] - a0, b.margin[r]);
+                }
+                if (candidates) {
                     best_tag = "X0:i:";
                     sam_tags::number(best_tag, bq.x0);
                 }
+                // --paired: what the record says about the pair and about the mate's record
+                unsigned int pair_flags = 0;
+                std::string_view rnext = "*";
+                uint64_t pnext = 0;
+                int64_t tlen = 0;
+                if (paired && candidates) {
+                    const mate_record me = mate_of(b, r), mate = mate_of(b, r ^ 1u);
+                    pair_flags = 0x1u | (r % 2 ? 0x80u : 0x40u);
+                    if (!mate.has) {
+                        pair_flags |= 0x8u;
+                    } else {
+                        if (proper) pair_flags |= 0x2u;
+                        if (mate.rc) pair_flags |= 0x20u;
+                        const bool same = bucket_ref[me.bucket] == bucket_ref[mate.bucket];
+                        rnext = same ? std::string_view("=") : std::string_view(h.bucket_name[mate.bucket]);
+                        pnext = mate.pos;
+                        if (same && me.has) {
+                            const uint64_t lo = std::min(me.pos, mate.pos), hi = std::max(me.pos + me.ref_len, mate.pos + mate.ref_len);
+                            const bool leftmost = me.pos < mate.pos || (me.pos == mate.pos && r % 2 == 0);
+                            tlen = leftmost ? static_cast<int64_t>(hi - lo) : -static_cast<int64_t>(hi - lo);
+                        }
+                    }
+                }
+                const uint32_t chosen = !candidates ? alignment_verifier::kBeyond : paired ? b.pick[r] : b.winner[r];
                 for (auto &[bucket_id, offset, segment_offset, votes, is_original] : locate_res[b.first_read + r]) {
                     (void)segment_offset; (void)votes;
-                    if (dump.is_open() && !(best && b.winner[r] != a)) {
+                    if (dump.is_open() && !(best && chosen != a)) {
                         dump << b.first_read + r << ' ' << b.text_start[a] << ' ' << b.text_len[a] << ' ' << int(b.text_rc[a]) << ' '
                              << b.query_len[a] << ' ' << b.score[a] << ' ' << b.begin[a] << ' ';
                         for (uint64_t x = b.cigar_offset[a]; x < b.cigar_offset[a + 1]; x++) dump << (b.cigar[x] >> 4) << "MID"[b.cigar[x] & 15u];
@@ -944,8 +1111,9 @@ private:
                             sam_tags::append_revcomp(rc_seq, b.reads[r].seq);
                             rc_qual.assign(b.reads[r].qual.rbegin(), b.reads[r].qual.rend());
                         }
-                        sam.record(b.reads[r].id, is_original ? 0 : 16, h.bucket_name[bucket_id], ref_offset + 1, static_cast<uint8_t>(map_qual),
-                                   cg, is_original ? b.reads[r].seq : rc_seq, is_original ? b.reads[r].qual : rc_qual, tags);
+                        sam.record(b.reads[r].id, (is_original ? 0 : 16) | pair_flags, h.bucket_name[bucket_id], ref_offset + 1,
+                                   static_cast<uint8_t>(map_qual), cg, is_original ? b.reads[r].seq : rc_seq,
+                                   is_original ? b.reads[r].qual : rc_qual, tags, rnext, pnext, tlen);
                         mapped_locations++;
                     } else if (is_written(b, a)) {
                         const int clipped = offset < 0 ? 0 : offset;
@@ -967,7 +1135,7 @@ private:
             b.reads.clear(); b.bases.clear();
             b.text_start.clear(); b.text_len.clear(); b.text_rc.clear(); b.query_start.clear(); b.query_len.clear();
             b.max_edits.clear();
-            b.group_offset.assign(1, 0); b.margin.clear(); b.hint.clear();
+            b.group_offset.assign(1, 0); b.margin.clear(); b.hint.clear(); b.contig.clear();
         };
         // the block just filled goes to the verifier as soon as the one before has left it; that one's records are written
         // while the verifier works
@@ -990,6 +1158,15 @@ private:
                 Block &b = blocks[cur];
                 const size_t len = rec.seq.size();
                 b.reads.push_back({std::string(rec.id), std::string(), std::string(rec.qual), b.bases.size()});
+                if (paired) {
+                    // QNAME without a trailing /1 or /2; the two mates share it (blocks are cut at even counts: the first mate
+                    // is the read before in this block)
+                    std::string &id = b.reads.back().id;
+                    if (id.size() >= 2 && id[id.size() - 2] == '/' && (id.back() == '1' || id.back() == '2')) id.resize(id.size() - 2);
+                    if (read_id % 2u && id != b.reads[b.reads.size() - 2].id)
+                        throw std::runtime_error("records " + std::to_string(read_id - 1) + " and " + std::to_string(read_id) + " of " + sequence_file +
+                                                 " are not mates: their names are '" + b.reads[b.reads.size() - 2].id + "' and '" + id + "'");
+                }
                 append_dna4(b.reads.back().seq, rec.seq);
                 b.bases.insert(b.bases.end(), rec.seq.begin(), rec.seq.end());
                 for (auto &[bucket_id, offset, segment_offset, votes, is_original] : locate_res[read_id]) {
@@ -1003,6 +1180,7 @@ private:
                     b.text_rc.push_back(is_original ? 0 : 1);                                               // :563-567
                     b.query_start.push_back(b.reads.back().start);
                     b.query_len.push_back(static_cast<uint32_t>(len));
+                    if (paired) b.contig.push_back(bucket_ref[bucket_id]);
                     if (bounded) b.max_edits.push_back(static_cast<uint32_t>(std::min(_max_edit_rate * static_cast<float>(len), 4e9f)));
                 }
                 if (best) {
@@ -1021,7 +1199,7 @@ private:
                     b.hint.push_back(at);
                 }
                 read_id++;
-                if (b.reads.size() >= block_reads || b.bases.size() >= block_bases) flush();
+                if ((b.reads.size() >= block_reads || b.bases.size() >= block_bases) && !(paired && b.reads.size() % 2u)) flush();
             });
             flush();                                            // the last, possibly empty, block
             worker.join();

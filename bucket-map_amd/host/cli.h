@@ -40,6 +40,10 @@ struct cmd_arguments {
                                   // unique hit from a repeat and an X0 tag
     float best_margin = 0.05f;    // --best-margin R (implies --best): alignments within max(1, R * read length) edits of the best
                                   // count towards MAPQ and X0
+    bool paired = false;          // --paired (bucketmap_align): the FASTQ file is interleaved, records 2p and 2p + 1 are mates;
+                                  // the two are placed together and written with the pair's flags, RNEXT, PNEXT and TLEN
+                                  // (implies --best and --annotate)
+    unsigned int frag_min = 1, frag_max = 1000;      // --frag-range MIN,MAX (implies --paired): what a proper pair may span
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -167,6 +171,23 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.best = true;
         }
         else if (opt == "--clip") a.clip = true;
+#ifdef BM_ALIGN
+        else if (opt == "--paired") a.paired = true;
+        else if (opt == "--frag-range") {
+            const std::string s = value();
+            const size_t comma = s.find(',');
+            if (comma == std::string::npos) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be MIN,MAX such as 1,1000.");
+            const unsigned long lo = as_uint(s.substr(0, comma)), hi = as_uint(s.substr(comma + 1));
+            if (lo > hi || hi > 0xFFFFFFFFul)
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be two numbers MIN <= MAX below 2^32.");
+            a.frag_min = static_cast<unsigned>(lo);
+            a.frag_max = static_cast<unsigned>(hi);
+            a.paired = true;
+        }
+#else
+        else if (opt == "--paired" || opt == "--frag-range")
+            throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it cannot place mates together.");
+#endif
         else if (opt == "--clip-scores") {
             const std::string s = value();
             const size_t comma = s.find(',');
@@ -191,6 +212,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         else throw parser_error("Unknown option " + opt + ". In case this is meant to be a non-option/argument/parameter, please specify the start of non-options with '--'.");
     }
     if (!have_indicator) throw parser_error("Option -i/--index-indicator is required but not set.");
+    if (a.paired) a.best = a.annotate = true;
     return a;
 }
 

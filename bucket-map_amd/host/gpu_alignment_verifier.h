@@ -74,7 +74,44 @@ public:
               uint32_t n_groups, const uint32_t *margin, const uint32_t *hint, std::vector<int32_t> &score,
               std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset, std::vector<uint32_t> &cigar,
               std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end) override {
+        grouped(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset, n_groups, margin, hint, nullptr,
+                score, begin, cigar_offset, cigar, winner, edits, end);
+    }
+
+    // bmv_align_paired per device: the same, the batch cut at PAIR borders (the groups 2p and 2p + 1 stay on one device); the
+    // picks rebased like the winners
+    void paired(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n, const uint32_t *group_offset,
+                uint32_t n_groups, const uint32_t *margin, const uint32_t *hint, const uint32_t *contig, uint32_t min_frag,
+                uint32_t max_frag, std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
+                std::vector<uint32_t> &cigar, std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end,
+                std::vector<uint32_t> &pick, std::vector<uint8_t> &proper, std::vector<uint64_t> &s1, std::vector<uint64_t> &s2) override {
+        if (n_groups & 1u) throw std::runtime_error("paired: an odd number of groups");
+        pair_io io{contig, min_frag, max_frag, &pick, &proper, &s1, &s2};
+        grouped(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset, n_groups, margin, hint, &io, score,
+                begin, cigar_offset, cigar, winner, edits, end);
+    }
+
+    bool can_annotate() const override { return true; }
+
+private:
+    // what paired() takes and returns beyond best()
+    struct pair_io {
+        const uint32_t *contig;
+        uint32_t min_frag, max_frag;
+        std::vector<uint32_t> *pick;
+        std::vector<uint8_t> *proper;
+        std::vector<uint64_t> *s1, *s2;
+    };
+
+    // best() (pairs == nullptr) and paired(): the unit the batch is cut at is a group, or a pair of groups
+    void grouped(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                 const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n, const uint32_t *group_offset,
+                 uint32_t n_groups, const uint32_t *margin, const uint32_t *hint, const pair_io *pairs, std::vector<int32_t> &score,
+                 std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset, std::vector<uint32_t> &cigar,
+                 std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end) {
         const size_t D = ctx_.size();
+        const uint32_t unit = pairs ? 2u : 1u;
         const auto t0 = std::chrono::steady_clock::now();
         const batch all{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
         score.assign(n, 0);
@@ -83,11 +120,20 @@ public:
         winner.assign(n_groups, kBeyond);
         edits.assign(n, kBeyond);
         end.assign(n, 0);
-        const std::vector<uint32_t> cut = cut_by_cost(n_groups, D, [&](uint32_t g) {
+        if (pairs) {
+            pairs->pick->assign(n_groups, kBeyond);
+            pairs->proper->assign(n_groups / 2u, 0);
+            pairs->s1->assign(n_groups / 2u, kPairNone);
+            pairs->s2->assign(n_groups / 2u, kPairNone);
+        }
+        std::vector<uint32_t> cut = cut_by_cost(n_groups / unit, D, [&](uint32_t u) {
             uint64_t cells = 1;
-            for (uint32_t a = group_offset[g]; a < group_offset[g + 1]; a++) cells += static_cast<uint64_t>(query_len[a]) * text_len[a];
+            for (uint32_t a = group_offset[u * unit]; a < group_offset[(u + 1u) * unit]; a++) cells += static_cast<uint64_t>(query_len[a]) * text_len[a];
             return cells;
         });
+        for (uint32_t &x : cut) x *= unit;                      // in groups
+        std::vector<float> ms_pair(D, 0.f);
+        std::vector<uint64_t> combinations(D, 0);
         std::vector<uint64_t> total(D, 0), cells(D, 0), dist_cells(D, 0);
         std::vector<float> ms(D, 0.f);
         std::vector<std::array<uint32_t, 5>> counts(D, std::array<uint32_t, 5>{});
@@ -101,9 +147,16 @@ public:
                 off.assign(group_offset + g0, group_offset + g0 + ng + 1);
                 for (uint32_t &o : off) o -= a0;
             }
-            check(bmv_align_best(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, s.n,
-                                 D > 1 ? off.data() : group_offset, ng, margin + g0, hint ? hint + g0 : nullptr, &total[d]),
-                  "the GPU alignment verifier failed: ");
+            if (pairs) {
+                check(bmv_align_paired(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, s.n,
+                                       D > 1 ? off.data() : group_offset, ng, margin + g0, hint ? hint + g0 : nullptr,
+                                       pairs->contig ? pairs->contig + s.a0 : nullptr, pairs->min_frag, pairs->max_frag, &total[d]),
+                      "the GPU alignment verifier failed: ");
+                bmv_last_pair_stats(ctx_[d], &ms_pair[d], &combinations[d]);
+            } else
+                check(bmv_align_best(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, s.n,
+                                     D > 1 ? off.data() : group_offset, ng, margin + g0, hint ? hint + g0 : nullptr, &total[d]),
+                      "the GPU alignment verifier failed: ");
             bmv_last_stats(ctx_[d], &ms[d], &cells[d]);
             bmv_last_best_stats(ctx_[d], &counts[d][0], &counts[d][1], &counts[d][2], &counts[d][3], &counts[d][4], &dist_cells[d], nullptr,
                                 nullptr);
@@ -121,17 +174,31 @@ public:
             stitch(cigar_offset, a0, m, off, at[d]);
             for (uint32_t g = g0; g < g0 + ng; g++)
                 if (winner[g] != kBeyond) winner[g] += a0;
+            if (!pairs) return;
+            check(bmv_pairs(ctx_[d], pairs->pick->data() + g0, pairs->proper->data() + g0 / 2u, pairs->s1->data() + g0 / 2u,
+                            pairs->s2->data() + g0 / 2u, nullptr),
+                  "reading the verifier's results failed: ");
+            for (uint32_t g = g0; g < g0 + ng; g++)
+                if ((*pairs->pick)[g] != kBeyond) (*pairs->pick)[g] += a0;
         });
         // (ranges are contiguous and in order: an empty range's alignments do not exist, so every offset is set but the last)
         cigar_offset[n] = at[D];
         std::array<uint64_t, 5> all_counts{};
         for (size_t d = 0; d < D; d++)
             for (size_t k = 0; k < 5; k++) all_counts[k] += counts[d][k];
-        std::cerr << "[BENCHMARK]\tGPU alignment verification, best per read: " << n << " alignments in " << n_groups << " groups, "
-                  << sum(cells) << " cells; " << all_counts[0] << " seeds, " << all_counts[1] << " through the distance round ("
-                  << sum(dist_cells) << " cells, " << all_counts[2] << " beyond, " << all_counts[3] << " undecided), " << all_counts[4]
-                  << " realigned; " << timing(ms, t0);
+        std::string pair_part;
+        if (pairs) {
+            float slowest = 0;
+            for (const float x : ms_pair) slowest = std::max(slowest, x);
+            pair_part = "the pair kernel " + std::to_string(sum(combinations)) + " combinations in " + std::to_string(slowest) + " ms; ";
+        }
+        std::cerr << "[BENCHMARK]\tGPU alignment verification, " << (pairs ? "best per pair: " : "best per read: ") << n << " alignments in "
+                  << n_groups << " groups, " << sum(cells) << " cells; " << all_counts[0] << " seeds, " << all_counts[1]
+                  << " through the distance round (" << sum(dist_cells) << " cells, " << all_counts[2] << " beyond, " << all_counts[3]
+                  << " undecided), " << all_counts[4] << " realigned; " << pair_part << timing(ms, t0);
     }
+
+public:
 
     // bmv_annotate per device: the batch is cut exactly as run() cuts it and the packed arrays are stitched the same way
     void annotate(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,

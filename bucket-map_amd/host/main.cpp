@@ -1,7 +1,8 @@
 // main.cpp -- the `bucketmap` command-line tool (bucket_map/main.cpp:135-234), MI355X edition.
 // Compiled a second time with -DBM_ALIGN it is `bucketmap_align` (bucket_map/CMakeLists.txt:138): every
 // located candidate is verified by a pairwise alignment and written with MAPQ = 60 + score and a CIGAR
-// (--annotate: as forward-strand records with an =/X CIGAR, NM and MD; --clip: those with low-identity ends soft-clipped).
+// (--annotate: as forward-strand records with an =/X CIGAR, NM and MD; --clip: those with low-identity ends soft-clipped;
+// --paired: an interleaved FASTQ file, mates placed together and written as pairs).
 //
 //   bucketmap -x -i <name> --genome ref.fa                       index only (writes into the cwd)
 //   bucketmap -i <name> -q reads.fq -o out.sam --genome ref.fa    map (indexes first if needed)
@@ -132,6 +133,7 @@ int main(int argc, char **argv) {
         loc.set_annotate(args.annotate);
         if (args.clip) loc.set_clip(args.clip_match, args.clip_penalty);
         if (args.best) loc.set_best(args.best_margin);
+        if (args.paired) loc.set_paired(args.frag_min, args.frag_max);
 #endif
         run_indexer();
         loc.initialize(genome, cwd, args.index_indicator);                                    // main.cpp:221

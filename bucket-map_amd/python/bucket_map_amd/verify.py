@@ -10,6 +10,7 @@ from . import lib as _bmf_lib
 BMV_OK = 0
 REJECTED = -(2 ** 31)     # BMV_REJECTED: the score of an alignment beyond its edit bound (align_bounded)
 BEYOND = 2 ** 32 - 1      # BMV_BEYOND: no winner (an empty group) / edits beyond best + margin (align_best)
+PAIR_NONE = 2 ** 64 - 1   # BMV_PAIR_NONE: no proper combination (s1) / none at another locus (s2)
 
 
 class BmvError(RuntimeError):
@@ -39,6 +40,12 @@ SYMBOLS = {
     "bmv_best": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p]),
     "bmv_last_best_stats": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_float)]),
+    "bmv_pair": (C.c_int, [C.c_void_p, _u64p, _u32p, _u8p, _u32p, _u32p, _u32p, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32,
+                           C.c_uint32]),
+    "bmv_pairs": (C.c_int, [C.c_void_p, _u32p, _u8p, _u64p, _u64p, _u32p]),
+    "bmv_last_pair_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
+    "bmv_align_paired": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u32p, C.c_uint32,
+                                   _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p]),
     "bmv_results": (C.c_int, [C.c_void_p, _i32p, _u32p, _u64p, _u32p]),
     "bmv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
     "bmv_annotate": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32,
@@ -158,6 +165,95 @@ def best_mapq(winner, edits, end, text_start, text_len, text_rc, margin) -> tupl
     return (0 if e2 == e1 else min(60, (e2 - e1) * 60 // (int(margin) + 1))), x0
 
 
+def pair_coordinates(text_start, text_len, text_rc, query_len, end):
+    """L, R and the locus coordinate of every alignment as bmv_pair defines them (include/bmv.h), int64: forward R = text_start
+    + end and L = R - query_len; reverse L = text_start + text_len - end and R = L + query_len; the locus is R forward, L
+    reverse -- the exact one of the two."""
+    ts, tl = np.asarray(text_start).astype(np.int64), np.asarray(text_len).astype(np.int64)
+    rc, m, e = np.asarray(text_rc) != 0, np.asarray(query_len).astype(np.int64), np.asarray(end).astype(np.int64)
+    left = np.where(rc, ts + tl - e, ts + e - m)
+    right = np.where(rc, ts + tl - e + m, ts + e)
+    return left, right, np.where(rc, left, right)
+
+
+def select_pairs(text_start, text_len, text_rc, query_len, edits, end, group_offset, min_frag, max_frag, contig=None) -> dict:
+    """The contract of bmv_pair in plain numpy (include/bmv.h): the mates of pair p are the groups 2p and 2p + 1; a combination
+    of a known alignment of each (edits != BEYOND) is proper when the two lie on one contig and on different strands and, with
+    f the forward and r the reverse one, L(f) <= L(r), R(f) <= R(r) and min_frag <= R(r) - L(f) <= max_frag.  The pick minimises
+    (edits[i] + edits[j], i, j); s1 is its sum, s2 the smallest sum over the proper combinations that differ from it in the
+    locus of either mate.  Returns a dict: pick u32[n_groups] (the group's own winner -- the lowest known index with the
+    smallest edits, BEYOND when there is none -- where the pair has no proper combination), proper u8[n_pairs], s1 and s2
+    u64[n_pairs] (PAIR_NONE where undefined), winner u32[n_groups]."""
+    off = np.asarray(group_offset, np.int64)
+    ed = np.asarray(edits).astype(np.int64)
+    n, n_groups = len(ed), len(off) - 1
+    if n_groups < 0 or n_groups % 2 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise ValueError("group_offset must run from 0 to the number of alignments without decreasing, over an even number of groups")
+    if int(min_frag) > int(max_frag):
+        raise ValueError("min_frag is larger than max_frag")
+    left, right, at = pair_coordinates(text_start, text_len, text_rc, query_len, end)
+    rc = np.asarray(text_rc) != 0
+    ctg = np.zeros(n, np.int64) if contig is None else np.asarray(contig).astype(np.int64)
+    known = ed != BEYOND
+    winner = np.full(n_groups, BEYOND, np.uint32)
+    for g in range(n_groups):
+        a0, a1 = int(off[g]), int(off[g + 1])
+        if known[a0:a1].any():
+            winner[g] = a0 + int(np.argmin(np.where(known[a0:a1], ed[a0:a1], 2 ** 40)))
+    pick = winner.copy()
+    n_pairs = n_groups // 2
+    proper = np.zeros(n_pairs, np.uint8)
+    s1, s2 = np.full(n_pairs, PAIR_NONE, np.uint64), np.full(n_pairs, PAIR_NONE, np.uint64)
+    for p in range(n_pairs):
+        i, j = np.arange(off[2 * p], off[2 * p + 1]), np.arange(off[2 * p + 1], off[2 * p + 2])
+        if len(i) == 0 or len(j) == 0:
+            continue
+        I, J = i[:, None], j[None, :]
+        fwd_i = ~rc[I] & rc[J]                                   # i is the forward one (else j, where the strands differ)
+        fl, fr = np.where(fwd_i, left[I], left[J]), np.where(fwd_i, right[I], right[J])
+        rl, rr = np.where(fwd_i, left[J], left[I]), np.where(fwd_i, right[J], right[I])
+        ok = known[I] & known[J] & (ctg[I] == ctg[J]) & (rc[I] != rc[J]) & (fl <= rl) & (fr <= rr) & \
+            (rr - fl >= int(min_frag)) & (rr - fl <= int(max_frag))
+        if not ok.any():
+            continue
+        total = np.where(ok, ed[I] + ed[J], 2 ** 40)
+        k = int(np.argmin(total))                                # row-major: the lowest i, then the lowest j, of the minimum
+        bi, bj = int(i[k // len(j)]), int(j[k % len(j)])
+        pick[2 * p], pick[2 * p + 1], proper[p], s1[p] = bi, bj, 1, int(total.ravel()[k])
+        other = ok & ((rc[I] != rc[bi]) | (at[I] != at[bi]) | (rc[J] != rc[bj]) | (at[J] != at[bj]))
+        if other.any():
+            s2[p] = int(total[other].min())
+    return {"pick": pick, "proper": proper, "s1": s1, "s2": s2, "winner": winner}
+
+
+def pair_mapq(proper, s1, s2, mates) -> list:
+    """MAPQ and X0 of the two mates of one pair (host/pair_mapq.h; a definition by choice).  mates: two dicts, one
+    per mate, of the mate's own group -- pick and winner (indices INSIDE the group, as select_pairs / align_paired return them
+    minus the group's offset), edits, end, text_start, text_len, text_rc (the group's slices) and margin.  A pair that is not
+    proper: each mate gets best_mapq of its own winner.  A proper one, with M the sum of the two margins: q_pair = 60 when s2 is
+    PAIR_NONE, 0 when s2 == s1, else min(60, (s2 - s1) * 60 // (M + 1)); q_single = best_mapq's value when the pick is the
+    group's own winner, else 0; MAPQ = max(q_pair, q_single); X0 = the distinct loci of the mate's own group at the pick's
+    edits, its own included.  Returns [(mapq, x0), (mapq, x0)]."""
+    def single(m):
+        return best_mapq(m["winner"], m["edits"], m["end"], m["text_start"], m["text_len"], m["text_rc"], m["margin"])
+    if not proper:
+        return [single(m) for m in mates]
+    big_m = sum(int(m["margin"]) for m in mates)
+    s1, s2 = int(s1), int(s2)
+    q_pair = 60 if s2 == PAIR_NONE else 0 if s2 == s1 else min(60, (s2 - s1) * 60 // (big_m + 1))
+    out = []
+    for m in mates:
+        pick, e = int(m["pick"]), [int(x) for x in m["edits"]]
+        q_single = single(m)[0] if pick == int(m["winner"]) else 0
+        loci = set()
+        for a in range(len(e)):
+            if e[a] == e[pick]:
+                rc = int(m["text_rc"][a]) != 0
+                loci.add((rc, int(m["text_start"][a]) + (int(m["text_len"][a]) - int(m["end"][a]) if rc else int(m["end"][a]))))
+        out.append((max(q_pair, q_single), len(loci)))
+    return out
+
+
 class Verifier:
     """align_pairwise of the BM_ALIGN branch (bucket_locator.h:520-528,569-576) for batches, on one GPU."""
 
@@ -227,6 +323,85 @@ class Verifier:
         _check(lib().bmv_best(self._h, _p(winner, _u32p), _p(edits, _u32p), _p(end, _u32p)))
         return {"score": score, "begin": begin, "cigar_offset": co, "cigar": cg[: total.value], "winner": winner[:n_groups],
                 "edits": edits[:n], "end": end[:n]}
+
+    def _pairs(self, n_groups) -> dict:
+        pick, winner = np.zeros(max(n_groups, 1), np.uint32), np.zeros(max(n_groups, 1), np.uint32)
+        proper = np.zeros(max(n_groups // 2, 1), np.uint8)
+        s1, s2 = np.zeros(max(n_groups // 2, 1), np.uint64), np.zeros(max(n_groups // 2, 1), np.uint64)
+        _check(lib().bmv_pairs(self._h, _p(pick, _u32p), _p(proper, _u8p), _p(s1, _u64p), _p(s2, _u64p), _p(winner, _u32p)))
+        return {"pick": pick[:n_groups], "proper": proper[: n_groups // 2], "s1": s1[: n_groups // 2], "s2": s2[: n_groups // 2],
+                "winner": winner[:n_groups]}
+
+    def pair(self, text_start, text_len, text_rc, query_len, edits, end, group_offset, min_frag, max_frag, contig=None) -> dict:
+        """bmv_pair: the pair-aware pick over alignments given by numbers alone -- the views' text_start, text_len, text_rc and
+        query_len, edits and end as align_best returns them, the contig of each (None: all on one); the mates of pair p are
+        the groups 2p and 2p + 1.  Returns what select_pairs returns: pick, proper, s1, s2, winner."""
+        ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
+        trc, ql = np.ascontiguousarray(text_rc, np.uint8), np.ascontiguousarray(query_len, np.uint32)
+        ed, en = np.ascontiguousarray(edits, np.uint32), np.ascontiguousarray(end, np.uint32)
+        off = np.ascontiguousarray(group_offset, np.uint32)
+        n, n_groups = len(ts), len(off) - 1
+        if n_groups < 0 or not (len(tl) == len(trc) == len(ql) == len(ed) == len(en) == n):
+            raise ValueError("one entry per alignment in every array, n_groups + 1 in group_offset")
+        cp = None
+        if contig is not None:
+            cn = np.ascontiguousarray(contig, np.uint32)
+            if len(cn) != n:
+                raise ValueError("contig must hold one entry per alignment")
+            cp = _p(cn, _u32p)
+        _check(lib().bmv_pair(self._h, _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(ql, _u32p), _p(ed, _u32p), _p(en, _u32p), cp, n,
+                              _p(off, _u32p), n_groups, int(min_frag), int(max_frag)))
+        return self._pairs(n_groups)
+
+    def align_paired(self, reads, text_start, text_len, text_rc, query_start, query_len, group_offset, margin, min_frag, max_frag,
+                     hint=None, contig=None) -> dict:
+        """bmv_align_paired: align_best for pairs.  The groups 2p and 2p + 1 are the candidates of the two mates of pair p; of
+        every group the PICK of select_pairs -- over the distances and end columns within best + margin of each group -- is
+        aligned in full.  Returns align_best's dict (score, begin, cigar_offset, cigar for the picks, REJECTED / 0 / no entries
+        elsewhere; winner, edits, end as align_best returns them) plus pick, proper, s1 and s2.  The result does not depend on
+        hint."""
+        r = np.ascontiguousarray(reads, np.uint8)
+        ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
+        trc = np.ascontiguousarray(text_rc, np.uint8)
+        qs, ql = np.ascontiguousarray(query_start, np.uint64), np.ascontiguousarray(query_len, np.uint32)
+        off, mg = np.ascontiguousarray(group_offset, np.uint32), np.ascontiguousarray(margin, np.uint32)
+        n, n_groups = len(ts), len(off) - 1
+        if n_groups < 0 or len(mg) != n_groups:
+            raise ValueError("group_offset holds n_groups + 1 entries, margin n_groups")
+        if not (len(tl) == len(trc) == len(qs) == len(ql) == n):
+            raise ValueError("one entry per alignment in every array")
+        hp = cp = None
+        if hint is not None:
+            hn = np.ascontiguousarray(hint, np.uint32)
+            if len(hn) != n_groups:
+                raise ValueError("hint must hold one index per group")
+            hp = _p(hn, _u32p)
+        if contig is not None:
+            cn = np.ascontiguousarray(contig, np.uint32)
+            if len(cn) != n:
+                raise ValueError("contig must hold one entry per alignment")
+            cp = _p(cn, _u32p)
+        total = C.c_uint64()
+        _check(lib().bmv_align_paired(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
+                                      _p(ql, _u32p), n, _p(off, _u32p), n_groups, _p(mg, _u32p), hp, cp, int(min_frag),
+                                      int(max_frag), C.byref(total)))
+        score, begin = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        co = np.zeros(n + 1, np.uint64)
+        cg = np.zeros(max(total.value, 1), np.uint32)
+        _check(lib().bmv_results(self._h, _p(score, _i32p), _p(begin, _u32p), _p(co, _u64p), _p(cg, _u32p)))
+        winner = np.zeros(max(n_groups, 1), np.uint32)
+        edits, end = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        _check(lib().bmv_best(self._h, _p(winner, _u32p), _p(edits, _u32p), _p(end, _u32p)))
+        out = self._pairs(n_groups)
+        out.update({"score": score, "begin": begin, "cigar_offset": co, "cigar": cg[: total.value], "winner": winner[:n_groups],
+                    "edits": edits[:n], "end": end[:n]})
+        return out
+
+    def pair_stats(self) -> dict:
+        """Of the last pair or align_paired: the pair kernel's ms and the combinations it examined."""
+        ms, combos = C.c_float(), C.c_uint64()
+        _check(lib().bmv_last_pair_stats(self._h, C.byref(ms), C.byref(combos)))
+        return {"ms_pair": ms.value, "combinations": combos.value}
 
     def best_stats(self) -> dict:
         """Of the last align_best: seeds aligned in full, alignments in the distance round, of these proven beyond the bound

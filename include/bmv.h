@@ -140,7 +140,51 @@ int  bmv_best(bmv_ctx *ctx, uint32_t *out_winner, uint32_t *out_edits, uint32_t 
 int  bmv_last_best_stats(bmv_ctx *ctx, uint32_t *n_seed, uint32_t *n_distance, uint32_t *n_beyond, uint32_t *n_undecided,
                          uint32_t *n_realigned, uint64_t *distance_cells, float *ms_distance, float *ms_pick);
 
-/* Results of the last bmv_align, bmv_align_long, bmv_align_bounded or bmv_align_best:
+/* The pair-aware pick: reads that come as PAIRS (two mates sequenced from the two ends of one fragment, on opposite strands)
+ * are placed together.  A call of its own, like bmv_annotate and bmv_clip: it needs no reads and no genome, only numbers per
+ * alignment -- the views' text_start, text_len, text_rc and query_len, edits and end as bmv_best returns them (BMV_BEYOND: not
+ * known), and contig, the reference sequence an alignment lies on (NULL: all on one).  Groups as in bmv_align_best; the mates of
+ * pair p are the groups 2p and 2p + 1.  All coordinates are signed 64-bit, in the concatenated genome:
+ *   known(a)            edits[a] != BMV_BEYOND
+ *   text_rc[a] == 0     R(a) = text_start + end (exact), L(a) = R(a) - query_len (an estimate: only the end is exact)
+ *   text_rc[a] != 0     L(a) = text_start + text_len - end (exact), R(a) = L(a) + query_len (the estimate)
+ *   locus(a)            (text_rc != 0, R forward / L reverse): the coordinate host/best_mapq.h tells loci apart by
+ *   own winner of g     the lowest known index of the group with the smallest edits; BMV_BEYOND when there is none
+ *   proper (i, j)       i in group 2p, j in group 2p + 1, both known, on one contig, on different strands, and with f the forward
+ *                       and r the reverse one: L(f) <= L(r), R(f) <= R(r), min_frag <= R(r) - L(f) <= max_frag
+ *   the pick of p       the proper combination that minimises (edits[i] + edits[j], i, j) lexicographically, the sum in 64 bits
+ *   s1, s2              the pick's sum; the smallest sum over the proper combinations (i', j') with locus(i') != locus(i) or
+ *                       locus(j') != locus(j)
+ * Outputs (bmv_pairs; any pointer may be NULL): out_pick[g] the picked alignment of group g -- the group's own winner when the
+ * pair has no proper combination --, out_proper[p] 0 or 1, out_s1[p] and out_s2[p] (BMV_PAIR_NONE where undefined),
+ * out_winner[g] the own winner.
+ * Checks: group_offset as in bmv_align_best; n_groups even; min_frag <= max_frag; text_start below 2^62: BMV_ERR_ARG, nothing
+ * ran and the context stays usable.  The call leaves untouched what every other result call returns.
+ * How (bmv_pair.hip.h): a wave per pair; up to 64 candidates of the second mate in the lanes, the first mate's walked
+ * wave-uniformly, both dimensions looped; the pick and s2 are minima taken across the wave. */
+#define BMV_PAIR_NONE UINT64_MAX
+int  bmv_pair(bmv_ctx *ctx, const uint64_t *text_start, const uint32_t *text_len, const uint8_t *text_rc, const uint32_t *query_len,
+              const uint32_t *edits, const uint32_t *end, const uint32_t *contig, uint32_t n, const uint32_t *group_offset,
+              uint32_t n_groups, uint32_t min_frag, uint32_t max_frag);
+/* Of the last bmv_pair or bmv_align_paired: out_pick and out_winner n_groups entries, the others n_groups / 2. */
+int  bmv_pairs(bmv_ctx *ctx, uint32_t *out_pick, uint8_t *out_proper, uint64_t *out_s1, uint64_t *out_s2, uint32_t *out_winner);
+/* Of the last bmv_pair or bmv_align_paired: the pair kernel's time in ms and the combinations it examined (the sum over the
+ * pairs of the product of the two group sizes). */
+int  bmv_last_pair_stats(bmv_ctx *ctx, float *ms_pair, uint64_t *n_combinations);
+
+/* bmv_align_best for pairs: the same batch and groups (n_groups even), plus contig, min_frag and max_frag as bmv_pair takes them.
+ * Four rounds: bmv_align_best's seed and distance rounds; its restriction of (d, end) to d <= best + margin, which makes what
+ * follows independent of hint; the bmv_pair kernel on those arrays where they lie on the device; the full alignment of every
+ * pick that has none yet.  bmv_results: the PICKS carry exactly bmv_align_long's score, begin and CIGAR, everything else score
+ * BMV_REJECTED, begin 0 and no entries; bmv_best returns what it returns after bmv_align_best (out_winner: the own winners);
+ * bmv_pairs the pair outputs; bmv_last_best_stats as after bmv_align_best, n_realigned counting the picks aligned in the last
+ * round.  Checks are bmv_align_best's and bmv_pair's. */
+int  bmv_align_paired(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                      const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                      uint32_t n, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                      const uint32_t *contig, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar);
+
+/* Results of the last bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best or bmv_align_paired:
  *   out_score[a]        alignment.score() = -(edit distance)                       (bucket_locator.h:570)
  *   out_begin[a]        alignment.sequence1_begin_position(), 0-based in the text  (:576)
  *   out_cigar_offset    n + 1 entries; alignment a owns out_cigar[offset[a] .. offset[a+1])

@@ -7,6 +7,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py --annotate [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --clip [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --best [--groups 20000 --len 10000 --text-len 11001] [--groups 200000 --len 300 --text-len 307]
+    python tools/bench_verify.py --paired [--pairs 500000 --len 300]
 
 Prints one JSON line: alignments/s and cell updates/s of the device kernels (HIP events inside bmv_align),
 the wall time of the call (host buffers in, results out), and the CPU restatement (oracle, full DP matrix,
@@ -186,8 +187,85 @@ def best_main(args):
         "align": {"ms_kernels": a_ms, "wall_s": a_wall}, "align_bounded": bounded, "align_best": runs}), flush=True)
 
 
+def paired_main(args):
+    """Verifier.align_paired on --pairs pairs of --len-base reads, fragments of 2 x len: per mate three candidates in random
+    order -- the true window, a planted copy of the pair's whole region diverged by substitutions worth 0.5 x to 3 x the margin
+    (so the copy holds a second proper combination), and an unrelated window.  Beside it Verifier.align_best on the same batch,
+    the mates as groups of their own: ms_pair of the one next to ms_pick of the other.  The picks of the first 2 000 pairs are
+    held against verify.select_pairs.  One JSON line."""
+    from bucket_map_amd import verify
+
+    rng = np.random.default_rng(20251005)
+    P, m = args.pairs, args.len
+    n = m + 1 + int(np.float32(args.indel_rate) * np.float32(m))
+    frag, lead = 2 * m, 8
+    region = frag + 2 * lead + (n - m)
+    margin = max(1, int(np.float32(args.margin_rate) * np.float32(m)))
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    genome = bases[rng.integers(0, 4, (P, 2, region), dtype=np.uint8)]
+    genome[:, 1, :] = genome[:, 0, :]
+    for p0 in range(0, P, 4096):
+        part = genome[p0: p0 + 4096, 1, :]
+        hit = rng.random(part.shape) < rng.uniform(0.5, 3.0, (len(part), 1)) * margin / m
+        part[hit] = bases[(np.searchsorted(bases, part[hit]) + rng.integers(1, 4, int(hit.sum()))) % 4]
+    # mate 1 forward from the fragment's left end, mate 2 the reverse complement of its right end, substitutions at --sub
+    reads = np.stack([genome[:, 0, lead: lead + m], comp[genome[:, 0, lead + frag - m: lead + frag]][:, ::-1]], 1).copy()
+    hit = rng.random(reads.shape) < args.sub
+    reads[hit] = bases[rng.integers(0, 4, int(hit.sum()))]
+    reads = reads.reshape(-1)
+    genome = genome.reshape(-1)
+    at = np.array([lead - (n - m) // 2, lead + frag - m - (n - m) // 2], np.uint64)              # the two mates' windows in a region
+    own = (np.arange(P, dtype=np.uint64) * 2 * region)[:, None, None] + at[None, :, None]         # [pair, mate, 1]
+    cand = np.concatenate([own, own + np.uint64(region), rng.integers(0, len(genome) - n, (P, 2, 1)).astype(np.uint64)], axis=2)
+    order = np.argsort(rng.random((P, 2, 3)), axis=2)
+    ts = np.take_along_axis(cand, order, axis=2).reshape(-1)
+    N = 6 * P
+    tl = np.full(N, n, np.uint32)
+    rc = np.tile(np.repeat(np.array([0, 1], np.uint8), 3), P)
+    qs = np.repeat(np.arange(2 * P, dtype=np.uint64) * m, 3)
+    ql = np.full(N, m, np.uint32)
+    off = np.arange(2 * P + 1, dtype=np.uint32) * 3
+    mg = np.full(2 * P, margin, np.uint32)
+    hint = np.argmin(order, axis=2).reshape(-1).astype(np.uint32)                                 # the true window
+    v = verify.Verifier()
+    v.load_genome(genome)
+    batch = (reads, ts, tl, rc, qs, ql)
+    best, pair = {"ms_kernels": [], "ms_pick": [], "ms_distance": [], "wall_s": []}, {"ms_kernels": [], "ms_pair": [], "wall_s": []}
+    for _ in range(args.repeat):
+        t0 = time.perf_counter()
+        v.align_best(*batch, off, mg, hint)
+        best["wall_s"].append(time.perf_counter() - t0)
+        st = v.best_stats()
+        best["ms_kernels"].append(v.stats()["ms_kernels"])
+        best["ms_pick"].append(st["ms_pick"])
+        best["ms_distance"].append(st["ms_distance"])
+    for _ in range(args.repeat):
+        t0 = time.perf_counter()
+        got = v.align_paired(*batch, off, mg, 1, 1000, hint)
+        pair["wall_s"].append(time.perf_counter() - t0)
+        pair["ms_kernels"].append(v.stats()["ms_kernels"])
+        pair["ms_pair"].append(v.pair_stats()["ms_pair"])
+    st, pst = v.best_stats(), v.pair_stats()
+    k = min(P, 2000)
+    want = verify.select_pairs(ts[: 6 * k], tl[: 6 * k], rc[: 6 * k], ql[: 6 * k], got["edits"][: 6 * k], got["end"][: 6 * k],
+                               off[: 2 * k + 1], 1, 1000)
+    ok = all(np.array_equal(np.asarray(got[key])[: len(want[key])], want[key]) for key in ("pick", "proper", "s1", "s2"))
+    print(json.dumps({
+        "metric": "bmv_align_paired pair kernel ms", "value": min(pair["ms_pair"]), "unit": "ms",
+        "config": {"pairs": P, "candidates_per_mate": 3, "query_len": m, "text_len": n, "margin": margin, "frag_range": [1, 1000]},
+        "ms_pair": pair["ms_pair"], "ms_pick_of_align_best": best["ms_pick"], "combinations": pst["combinations"],
+        "proper_share": float(got["proper"].mean()), "pairs_with_a_second_combination": float((got["s2"] != verify.PAIR_NONE).mean()),
+        "pick_is_not_the_own_winner": float((got["pick"] != got["winner"]).mean()),
+        "align_best": best, "align_paired": {**pair, "n_realigned": st["n_realigned"], "n_seed": st["n_seed"]},
+        "checks": {"first_pairs_identical_to_select_pairs": bool(ok)}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--paired", action="store_true", help="Verifier.align_paired beside Verifier.align_best (see paired_main)")
+    ap.add_argument("--pairs", type=int, default=500_000)
     ap.add_argument("--best", action="store_true", help="Verifier.align_best on groups of five candidates (see best_main)")
     ap.add_argument("--groups", type=int, default=20_000)
     ap.add_argument("--text-len", type=int, default=0, help="--best: the window's length (default: as the tool computes it)")
@@ -223,6 +301,8 @@ def main():
         return long_main(args)
     if args.best:
         return best_main(args)
+    if args.paired:
+        return paired_main(args)
 
     rng = np.random.default_rng(20240003)
     m = args.len
