@@ -5,6 +5,7 @@
 // and HIP-event timing.  There is deliberately no CPU implementation of the filter in this library.
 #include "bmf_kernels.hip.h"
 #include "bmf_vote2.hip.h"
+#include "bmf_kmer_lists.hip.h"
 #include "bmi_kernels.hip.h"
 #include "bm_hip_util.h"
 #include "bm_scan.hip.h"
@@ -152,6 +153,14 @@ struct bmf_ctx {
     // (dp.pair, dp.E) and the vote kernel streams it instead of d_rows: half the row bytes, the same outputs.
     uint8_t *d_pair = nullptr;
     uint64_t pair_rows = 0;          // rows of d_pair, the all-ones row included
+    // Per-k-mer bucket-id lists (bmf_kmer_lists.hip.h), built instead of the pair table where build_kmer_lists' rule
+    // holds: the lists then hold one k-mer hash per sample (dp.pair == 2, dp.E == 1) and bmf_vote_kernel_lists serves.
+    uint64_t *d_koff = nullptr;      // 4^k + 1 offsets in 16-byte units
+    uint16_t *d_kids = nullptr;
+    uint64_t klist_kmers = 0, klist_bytes = 0;   // 4^k; bytes of offsets + lists
+    int klist_bits = 0;              // bits per hit counter of the vote kernel: 4 (S <= 15) or 8
+    size_t klist_lds = 0;
+    double klist_mean_bytes = 0.0;   // list bytes a sample meets, as the estimate found them (BMF_LOG_TUNE prints it)
     uint32_t list_cap = 0;           // ids per (window, orientation) a batch's list buffer is sized for: the G-rows form
     // constants
     uint8_t *d_lut = nullptr;
@@ -216,7 +225,7 @@ struct bmf_ctx {
 
 extern "C" {
 
-static void set_entries_per_sample(bmf_ctx *c, uint32_t E, bool pair);
+static void set_entries_per_sample(bmf_ctx *c, uint32_t E, uint32_t form);
 
 int bmf_abi_version(void) { return BMF_ABI_VERSION; }
 const char *bmf_last_error(void) { return g_err; }
@@ -318,7 +327,7 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
     d.max_cand = p.max_candidates;
     d.read_len = p.read_len;
     d.max_kmers = p.read_len - p.k + 1;
-    set_entries_per_sample(c, d.G, false);
+    set_entries_per_sample(c, d.G, 0u);
     c->list_cap = d.list_len;
     d.n_chunks = n_chunks;
     d.pitch = (row_bytes + 127u) & ~127u;
@@ -416,13 +425,14 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
     return BMF_OK;
 }
 
-// E list entries per sample: G rows of the index, or (pair) ceil(G/2) rows of the pair table.  list_len = S*E ids,
-// rounded up to the ring depth, plus one ring of padding (all-ones rows); never more than the G-rows form's.
-static void set_entries_per_sample(bmf_ctx *c, uint32_t E, bool pair) {
+// E list entries per sample: G rows of the index (form 0), ceil(G/2) rows of the pair table (1) or the k-mer itself (2).
+// list_len = S*E ids, rounded up to the ring depth, plus one ring of padding (all-ones rows); never more than the
+// G-rows form's.
+static void set_entries_per_sample(bmf_ctx *c, uint32_t E, uint32_t form) {
     bmf::DevParams &d = c->dp;
     const uint32_t depth = (uint32_t)c->depth;
     d.E = E;
-    d.pair = pair ? 1u : 0u;
+    d.pair = form;
     d.list_len = (d.S * E + depth - 1u) / depth * depth + depth;
 }
 
@@ -430,7 +440,12 @@ static void free_pair_table(bmf_ctx *c) {
     (void)hipFree(c->d_pair);
     c->d_pair = nullptr;
     c->pair_rows = 0;
-    set_entries_per_sample(c, c->dp.G, false);
+    (void)hipFree(c->d_koff);
+    (void)hipFree(c->d_kids);
+    c->d_koff = nullptr;
+    c->d_kids = nullptr;
+    c->klist_kmers = c->klist_bytes = 0;
+    set_entries_per_sample(c, c->dp.G, 0u);
 }
 
 static void free_index(bmf_ctx *c) {
@@ -629,6 +644,109 @@ static int select_pruned_variant(bmf_ctx *c) {
     return BMF_OK;
 }
 
+// The lists serve when the list a sample MEETS is on average at most 1/R of the bytes the pair vote reads for it (ceil(G/2)
+// rows).  A read's k-mers come from the genome, so it meets a k-mer in proportion to how often the k-mer occurs, and a k-mer
+// occurs in at most as many buckets as its list is long: the mean is therefore weighted by the list length itself
+// (sum of squares over sum).  On an index of uniform rows that is the plain mean; on a genome-like index the heavy k-mers
+// dominate what reads meet, and the plain mean would promise a gain that the vote does not see.
+// R >= 2 is a condition, not a tuning value: below it dense random indexes, where the lists are no shorter than the
+// rows, would get them.  Above 2 it is the break-even of LDS atomics against streamed row bytes; 4 until that has been
+// measured on the card.
+constexpr double kKmerListsRatio = 4.0;
+static bool kmer_lists_pay(double mean_list_bytes, uint32_t G, uint32_t row_bytes) {
+    return mean_list_bytes * kKmerListsRatio <= (double)((G + 1u) / 2u) * (double)row_bytes;
+}
+
+// The per-k-mer lists (bmf_kmer_lists.hip.h) for the index just loaded, considered before the pair table and under the
+// same gate.  True: they serve, and the pair table is not built.  False, with nothing left allocated: not eligible
+// (sliced rows; NB > 65 535, kPadId must be no bucket), BMF_KMER_LISTS=0, the rule above says no (BMF_KMER_LISTS=1
+// overrides the rule, never the memory limits), the exact size exceeds BMF_DERIVED_MAX_MB or half of the free device
+// memory, or an allocation or launch failed -- the pair table is then built as before.
+static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
+    const bmf::DevParams &d = c->dp;
+    const char *env = getenv("BMF_KMER_LISTS");
+    const bool forced = env && !strcmp(env, "1");
+    if ((env && !strcmp(env, "0")) || c->n_slices > 1 || d.nb > 65535u) return false;
+    const uint64_t n_k = 1ull << (2 * c->p.k), n_prefix = n_k / 4;
+    const uint32_t row_bytes = (d.nb + 7u) >> 3;
+    const int bits = d.S <= 15u ? 4 : 8;
+    const size_t lds = bmf::kmer_vote_lds_bytes(d.nb, (uint32_t)bits);
+    const void *kernel = bits == 4 ? reinterpret_cast<const void *>(bmf::bmf_vote_kernel_lists<4>)
+                                   : reinterpret_cast<const void *>(bmf::bmf_vote_kernel_lists<8>);
+    uint32_t *d_units = nullptr;
+    uint64_t *d_off = nullptr, *d_tmp = nullptr;
+    uint16_t *d_ids = nullptr;
+    auto give_up = [&]() {
+        (void)hipGetLastError();
+        (void)hipFree(d_units);
+        (void)hipFree(d_off);
+        (void)hipFree(d_tmp);
+        (void)hipFree(d_ids);
+        return false;
+    };
+    auto room = [&](uint64_t bytes) {
+        size_t free_b = 0, total_b = 0;
+        return bytes <= (max_mb << 20) && hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= free_b / 2;
+    };
+    auto count = [&](uint32_t p_first, uint32_t p_stride, uint64_t n_p, uint32_t *units) {
+        hipLaunchKernelGGL(bmf::bmf_kmer_count_kernel, dim3((unsigned)std::min<uint64_t>(n_p, 1u << 20)), dim3(bmf::kWave), 0, c->stream,
+                           c->d_rows, c->d_k2i, d.n_kmers, d.qbits, d.G, d.pitch, d.nb, d.n_chunks, p_first, p_stride,
+                           (uint32_t)(n_prefix - 1), (uint32_t)n_p, units);
+        return hipGetLastError() == hipSuccess;
+    };
+    if (lds > 48 * 1024 && bmhip::raise_dynamic_lds(kernel, lds) != hipSuccess) return give_up();
+    // 1. the estimate: a strided sample of (k-1)-prefixes -- an odd stride near n_prefix / phi, taken modulo n_prefix,
+    //    visits every prefix once and spreads over high and low bases alike
+    const uint64_t n_s = std::min<uint64_t>(n_prefix, 4096);
+    const uint32_t stride = n_s == n_prefix ? 1u : ((uint32_t)((double)n_prefix * 0.6180339887) | 1u);
+    std::vector<uint32_t> sample((size_t)n_s * 4);
+    if (dev_alloc(&d_units, sample.size()) != hipSuccess || !count(0u, stride, n_s, d_units) ||
+        hipMemcpyAsync(sample.data(), d_units, sample.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return give_up();
+    double units = 0.0, squares = 0.0;
+    for (uint32_t u : sample) {
+        units += (double)u;
+        squares += (double)u * (double)u;
+    }
+    c->klist_mean_bytes = units > 0.0 ? 16.0 * squares / units : 0.0;
+    const bool pay = kmer_lists_pay(c->klist_mean_bytes, d.G, row_bytes);
+    if (getenv("BMF_LOG_TUNE"))
+        fprintf(stderr, "bmf: k-mer lists: %.1f B per k-mer over %zu sampled (length-weighted: %.1f B met per sample), pair vote reads %u B per sample: %s\n",
+                16.0 * units / (double)sample.size(), sample.size(), c->klist_mean_bytes, (d.G + 1u) / 2u * row_bytes, pay ? "lists" : (forced ? "lists (forced)" : "pair table"));
+    if (!pay && !forced) return give_up();
+    (void)hipFree(d_units);
+    d_units = nullptr;
+    // 2. count, scan, fill
+    const uint64_t scratch = n_k * sizeof(uint32_t) + (n_k + 1 + bmscan::tmp_elems(n_k)) * sizeof(uint64_t);
+    if (n_prefix > 0x7FFFFFFFull || !room(scratch)) return give_up();
+    if (dev_alloc(&d_units, (size_t)n_k) != hipSuccess || dev_alloc(&d_off, (size_t)n_k + 1) != hipSuccess ||
+        dev_alloc(&d_tmp, bmscan::tmp_elems(n_k)) != hipSuccess || !count(0u, 1u, n_prefix, d_units) ||
+        bmscan::exclusive_sum<uint64_t>(d_units, d_off, n_k, d_tmp, c->stream) != hipSuccess)
+        return give_up();
+    uint64_t total = 0;
+    if (hipMemcpyAsync(&total, d_off + n_k, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return give_up();
+    (void)hipFree(d_units);
+    (void)hipFree(d_tmp);
+    d_units = nullptr;
+    d_tmp = nullptr;
+    const uint64_t bytes = total * 16 + (n_k + 1) * sizeof(uint64_t);
+    if (!room(bytes) || hipMalloc(reinterpret_cast<void **>(&d_ids), (size_t)std::max<uint64_t>(total, 1) * 16) != hipSuccess) return give_up();
+    hipLaunchKernelGGL(bmf::bmf_kmer_fill_kernel, dim3((unsigned)std::min<uint64_t>(n_prefix, 1u << 20)), dim3(bmf::kWave), 0, c->stream,
+                       c->d_rows, c->d_k2i, d.n_kmers, d.qbits, d.G, d.pitch, d.nb, d.n_chunks, (uint32_t)n_prefix, d_off, d_ids);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return give_up();
+    c->d_koff = d_off;
+    c->d_kids = d_ids;
+    c->klist_kmers = n_k;
+    c->klist_bytes = bytes;
+    c->klist_bits = bits;
+    c->klist_lds = lds;
+    set_entries_per_sample(c, 1u, 2u);
+    return true;
+}
+
 // The pair table for the index just loaded (the contexts without BMF_FLAG_EARLY_EXIT: the pruning kernels read the
 // index itself).  Decided once per load, here, so that no batch pays for it: BMF_FLAG_PLAIN_ROWS or BMF_DERIVED=0
 // keep the index rows; so do short rows (below), a table larger than BMF_DERIVED_MAX_MB MiB (default 24 576) or than half of the
@@ -646,6 +764,7 @@ static int build_pair_table(bmf_ctx *c) {
     if (d.n_chunks <= 16u && !(env_derived && !strcmp(env_derived, "1"))) return BMF_OK;
     uint64_t max_mb = 24576;
     if (const char *env = getenv("BMF_DERIVED_MAX_MB")) max_mb = strtoull(env, nullptr, 10);
+    if (build_kmer_lists(c, max_mb)) return BMF_OK;
     const uint64_t n_high = 1ull << (2 * c->p.q), n_pair = 4 * n_high;
     if (n_pair + 1 >= 0x7FFFFFFFull || (n_pair + 1) > (max_mb << 20) / d.pitch) return BMF_OK;
     const size_t bytes = (size_t)(n_pair + 1) * d.pitch;
@@ -669,7 +788,7 @@ static int build_pair_table(bmf_ctx *c) {
         return fail(BMF_ERR_HIP, "building the pair table failed: %s", hipGetErrorString(e));
     }
     c->pair_rows = n_pair + 1;
-    set_entries_per_sample(c, (d.G + 1u) / 2u, true);
+    set_entries_per_sample(c, (d.G + 1u) / 2u, 1u);
     return BMF_OK;
 }
 
@@ -1224,6 +1343,10 @@ static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
             c->guard_items = n_items;
             c->guard_pending = true;
         }
+    } else if (c->dp.pair == 2u) {
+        auto kv = c->klist_bits == 4 ? bmf::bmf_vote_kernel_lists<4> : bmf::bmf_vote_kernel_lists<8>;
+        hipLaunchKernelGGL(kv, dim3(2 * n_windows), dim3(bmf::kWave), c->klist_lds, c->stream, c->dp, c->d_koff,
+                           reinterpret_cast<const uint4 *>(c->d_kids), b->lists.p, b->list_n.p, b->counts.p, b->buckets.p);
     } else if (c->n_slices == 1) {
         hipLaunchKernelGGL(c->vote, dim3(2 * n_windows), dim3(bmf::kWave), 0, c->stream, c->dp, c->dp.pair ? c->d_pair : c->d_rows,
                            b->lists.p, b->list_n.p, b->counts.p, b->buckets.p, (uint32_t *)nullptr);
@@ -1853,20 +1976,40 @@ int bmf_info(bmf_ctx *c, uint32_t *row_pitch_bytes, uint32_t *chunks_per_lane, u
 
 int bmf_derived_info(bmf_ctx *c, uint32_t *span, uint64_t *n_rows, uint64_t *bytes) {
     if (!c) return fail(BMF_ERR_ARG, "bmf_derived_info: null context");
-    if (span) *span = c->dp.pair ? 2u : 1u;
-    if (n_rows) *n_rows = c->pair_rows;
-    if (bytes) *bytes = c->pair_rows * c->dp.pitch;
+    const bool lists = c->dp.pair == 2u;
+    if (span) *span = lists ? c->dp.G : (c->dp.pair ? 2u : 1u);
+    if (n_rows) *n_rows = lists ? c->klist_kmers : c->pair_rows;
+    if (bytes) *bytes = lists ? c->klist_bytes : c->pair_rows * c->dp.pitch;
+    return BMF_OK;
+}
+
+int bmf_derived_form(bmf_ctx *c, uint32_t *form) {
+    if (!c || !form) return fail(BMF_ERR_ARG, "bmf_derived_form: null argument");
+    *form = c->dp.pair;
     return BMF_OK;
 }
 
 int bmf_derived_row(bmf_ctx *c, uint64_t gram, uint8_t *out_row_bytes) {
     if (!c || !out_row_bytes) return fail(BMF_ERR_ARG, "bmf_derived_row: null argument");
-    if (!c->loaded || !c->d_pair) return fail(BMF_ERR_STATE, "no pair table: the context reads the index rows");
-    if (gram >= c->pair_rows) return fail(BMF_ERR_ARG, "row %llu is outside the pair table (%llu rows)", (unsigned long long)gram,
-                                          (unsigned long long)c->pair_rows);
+    if (!c->loaded || (!c->d_pair && !c->d_koff)) return fail(BMF_ERR_STATE, "no derived table: the context reads the index rows");
+    const uint64_t n = c->d_koff ? c->klist_kmers : c->pair_rows;
+    if (gram >= n) return fail(BMF_ERR_ARG, "row %llu is outside the derived table (%llu rows)", (unsigned long long)gram,
+                               (unsigned long long)n);
     HIP_TRY(hipSetDevice(c->p.device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out_row_bytes, c->d_pair + (size_t)gram * c->dp.pitch, (c->p.num_buckets + 7u) >> 3, hipMemcpyDeviceToHost));
+    const uint32_t row_bytes = (c->p.num_buckets + 7u) >> 3;
+    if (!c->d_koff) {
+        HIP_TRY(hipMemcpy(out_row_bytes, c->d_pair + (size_t)gram * c->dp.pitch, row_bytes, hipMemcpyDeviceToHost));
+        return BMF_OK;
+    }
+    // the k-mer's list, expanded to bits; kPadId fills its last unit
+    uint64_t ext[2];
+    HIP_TRY(hipMemcpy(ext, c->d_koff + gram, sizeof ext, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> ids((size_t)(ext[1] - ext[0]) * 8);
+    if (!ids.empty()) HIP_TRY(hipMemcpy(ids.data(), c->d_kids + ext[0] * 8, ids.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    memset(out_row_bytes, 0, row_bytes);
+    for (uint16_t id : ids)
+        if (id < c->p.num_buckets) out_row_bytes[id >> 3] |= (uint8_t)(1u << (id & 7u));
     return BMF_OK;
 }
 

@@ -47,8 +47,9 @@ struct DevParams {
     uint32_t max_live;   // two-pass variant: live chunks (= lanes) an item may bring to the recount kernel (16 or 32)
     uint32_t item_base;  // two-pass variant: first (window, orientation) item of this launch (the batch goes out in slices)
     uint32_t row_order;  // entry i of a sample's G row ids is the row of q-gram (row_order >> 4i) & 15: a permutation of 0..G-1
-    uint32_t E;          // list entries per sample: G row ids, or ceil(G/2) pair-row ids when `pair` is set
-    uint32_t pair;       // the lists hold rows of the pair table (bmf_pair_rows_kernel): ids of (q+1)-grams; its all-ones row is 4^(q+1)
+    uint32_t E;          // list entries per sample: G row ids, ceil(G/2) pair-row ids (pair == 1) or one k-mer (pair == 2)
+    uint32_t pair;       // 1: the lists hold rows of the pair table (bmf_pair_rows_kernel): ids of (q+1)-grams; its all-ones row is 4^(q+1)
+                         // 2: they hold the sampled k-mers' hashes, one per sample, unpadded (bmf_kmer_lists.hip.h)
 };
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
@@ -410,7 +411,10 @@ __global__ __launch_bounds__(1024, 8) void bmf_sample_kernel(   // 8 waves per S
                 }
                 cnt += (i1 >= 0) + (i2 >= 0);   // the rows the reference ANDs, whatever table the vote reads
             }
-            if (P.pair) {
+            if (P.pair == 2u) {         // per-k-mer lists (bmf_kmer_lists.hip.h): the entry is the k-mer itself
+                list_fwd[s] = h;
+                list_rc[s] = hr;
+            } else if (P.pair) {
                 // pair table: entry t is the (q+1)-gram that holds q-grams g and g + 1, g = min(2t, G - 2) -- for an odd
                 // G the last pair overlaps the one before it, and AND is idempotent
                 for (uint32_t t = 0; t < P.E; t++) {
@@ -422,7 +426,7 @@ __global__ __launch_bounds__(1024, 8) void bmf_sample_kernel(   // 8 waves per S
         }
         // pad both lists with the all-ones row (see bmf_vote_kernel)
         const uint32_t pad_row = P.pair ? 4u * P.qbits + 4u : P.ones_row;
-        for (uint32_t t = P.S * P.E + lane; t < P.list_len; t += kWave) {
+        for (uint32_t t = P.S * P.E + lane; t < P.list_len && P.pair != 2u; t += kWave) {
             list_fwd[t] = pad_row;
             list_rc[t] = pad_row;
         }

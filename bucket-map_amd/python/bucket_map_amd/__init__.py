@@ -79,6 +79,7 @@ SYMBOLS = {
     "bmf_info": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u32p]),
     "bmf_derived_info": (C.c_int, [C.c_void_p, _u32p, _u64p, _u64p]),
     "bmf_derived_row": (C.c_int, [C.c_void_p, C.c_uint64, _u8p]),
+    "bmf_derived_form": (C.c_int, [C.c_void_p, _u32p]),
     "bmf_pass1_rows": (C.c_int, [C.c_void_p, _u32p]),
     "bmf_pass1_fold": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bmf_batch_pass2_counts": (C.c_int, [C.c_void_p, C.c_void_p, _u32p, _u32p]),
@@ -411,12 +412,15 @@ class Filter:
         _check(lib().bmf_pass1_fold(self._h, C.byref(fold), C.byref(frows)))
         span, d_rows, d_bytes = C.c_uint32(), C.c_uint64(), C.c_uint64()
         _check(lib().bmf_derived_info(self._h, C.byref(span), C.byref(d_rows), C.byref(d_bytes)))
-        return {"row_pitch_bytes": v[0].value, "chunks_per_lane": v[1].value, "planes": v[2].value,
+        form = C.c_uint32()
+        _check(lib().bmf_derived_form(self._h, C.byref(form)))
+        return {"derived_form": ("rows", "pairs", "kmer_lists")[form.value], "row_pitch_bytes": v[0].value, "chunks_per_lane": v[1].value, "planes": v[2].value,
                 "rows_in_flight": v[3].value, "pass1_rows": r.value, "pass1_fold": fold.value, "pass1_fold_rows": frows.value,
                 "derived_span": span.value, "derived_bytes": d_bytes.value}
 
     def derived_row(self, gram: int) -> np.ndarray:
-        """Row `gram` of the pair table (bmf_derived_row): ceil(NB/8) bytes in the .qgram layout."""
+        """Row `gram` of the pair table, or the AND of k-mer `gram` expanded from its list (bmf_derived_row): ceil(NB/8)
+        bytes in the .qgram layout."""
         out = np.zeros((self.params.num_buckets + 7) >> 3, dtype=np.uint8)
         _check(lib().bmf_derived_row(self._h, gram, _ptr(out, _u8p)))
         return out

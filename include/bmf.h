@@ -199,6 +199,12 @@ int  bmf_derived_info(bmf_ctx *ctx, uint32_t *span, uint64_t *n_rows, uint64_t *
  * row standing for a q-gram that is not indexed -- to out_row_bytes, ceil(NB/8) bytes in the .qgram layout.
  * BMF_ERR_STATE when the context has no table. */
 int  bmf_derived_row(bmf_ctx *ctx, uint64_t gram, uint8_t *out_row_bytes);
+/* Which table the plain vote reads: 0 the index rows, 1 the pair table, 2 per-k-mer bucket-id lists -- for every k-mer
+ * x < 4^k the ascending 16-bit ids of the buckets in the AND of the rows of its k-q+1 q-grams, built instead of the pair
+ * table where the index is sparse enough (BMF_KMER_LISTS=0 never, =1 whatever the rule says; NB <= 65 535).  With the
+ * lists bmf_derived_info reports span = k-q+1, n_rows = 4^k and bytes = offsets + lists, and bmf_derived_row takes a
+ * k-mer and returns its AND, expanded from the list. */
+int  bmf_derived_form(bmf_ctx *ctx, uint32_t *form);
 /* BMF_FLAG_EARLY_EXIT only: index rows per sample the first pass of the two-pass pruning kernel streams
  * for the loaded index; 0 = the single-pass pruning kernel (or no pruning) serves it. */
 int  bmf_pass1_rows(bmf_ctx *ctx, uint32_t *out);
