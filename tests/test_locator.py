@@ -20,10 +20,20 @@ def revcomp(seq_codes):
     return 3 - seq_codes[::-1]
 
 
-def make_case(rng, *, n_buckets, bucket_len, read_len, n_reads, k=12, p=10, motif=None, sub=0.01, decoys=True, qual_b=25):
+# letters SeqAn3's dna4 folds to each rank (host/bm_common.h::dna4_rank): what `spelling` respells a genome with
+SPELLINGS = [np.frombuffer(s, np.uint8) for s in (b"AaNnRrWwMmDdHhVvXx-", b"CcYySsBb", b"GgKk", b"TtUu")]
+
+
+def make_case(rng, *, n_buckets, bucket_len, read_len, n_reads, k=12, p=10, motif=None, sub=0.01, decoys=True, qual_b=25,
+              lead=0, spelling=None):
     """Genome of n_buckets buckets (optionally built from a short repeated motif), reads with their sampled
     locator k-mers (bucket_locator.h:292-347 restated in numpy) and candidate (window, bucket, strand)
-    pairs: the true one plus decoys."""
+    pairs: the true one plus decoys.
+
+    lead: that many random bases in front of bucket 0 (bucket i starts at lead + i * bucket_len: any alignment).
+    spelling: a numpy Generator; every genome base is then spelled with a random letter of its rank (SPELLINGS) --
+    the reads are cut from the codes, so samples, candidates and truth are those of the plain genome.
+    Neither draws from `rng`: with the defaults the case is byte for byte what it was without them."""
     size = bucket_len + read_len
     if motif is None:
         genome = rng.integers(0, 4, n_buckets * bucket_len + read_len).astype(np.uint8)
@@ -32,7 +42,9 @@ def make_case(rng, *, n_buckets, bucket_len, read_len, n_reads, k=12, p=10, moti
         genome = np.tile(unit, (n_buckets * bucket_len + read_len) // motif + 1)[: n_buckets * bucket_len + read_len].copy()
         flips = rng.random(len(genome)) < 0.02                     # a few point differences between copies
         genome[flips] = rng.integers(0, 4, flips.sum())
-    bstart = (np.arange(n_buckets) * bucket_len).astype(np.uint64)
+    if lead:
+        genome = np.concatenate([np.random.default_rng([lead, len(genome)]).integers(0, 4, lead).astype(np.uint8), genome])
+    bstart = (lead + np.arange(n_buckets) * bucket_len).astype(np.uint64)
     blen = np.full(n_buckets, size, np.uint32)
     blen[-1] = len(genome) - int(bstart[-1])
     sh, sp, sl, pb, pw, pr, truth = [], [], [], [], [], [], []
@@ -63,7 +75,12 @@ def make_case(rng, *, n_buckets, bucket_len, read_len, n_reads, k=12, p=10, moti
         truth.append((b, start, rc))
     order = np.argsort(np.array(pb), kind="stable")                # candidates grouped by bucket
     pb, pw, pr = np.array(pb, np.uint32)[order], np.array(pw, np.uint32)[order], np.array(pr, np.uint8)[order]
-    return dict(genome=LETTERS[genome], bstart=bstart, blen=blen, sh=np.array(sh, np.uint32), sp=np.array(sp, np.uint16),
+    text = LETTERS[genome]
+    if spelling is not None:
+        for rank, letters in enumerate(SPELLINGS):
+            at = np.nonzero(genome == rank)[0]
+            text[at] = letters[spelling.integers(0, len(letters), len(at))]
+    return dict(genome=text, bstart=bstart, blen=blen, sh=np.array(sh, np.uint32), sp=np.array(sp, np.uint16),
                 sl=np.array(sl, np.uint32), pb=pb, pw=pw, pr=pr, truth=truth, k=k, p=p)
 
 
