@@ -23,9 +23,13 @@
 //                          looking at the counters.  misses = S - hits: an item whose highest count is at most S - F
 //                          is empty and is done; the others scan the counters once, in bucket order, for the buckets
 //                          at the maximum (ids staged in LDS: more than max_candidates of them is "cleared").
+//                          The adds are not waited for one by one: the eight of a unit are issued back to back, with no
+//                          branch per id (a padding id adds 0 where it harms nothing), and folded into the maximum after
+//                          the next unit's are issued (kmer_count_units).
 //                          A workgroup is one wave and one item, and starts by zeroing its counters: ceil(NB / 128 or
 //                          64) 16-byte LDS stores per lane round, far fewer instructions than a second walk over the
-//                          lists would be.
+//                          lists would be.  (One resident round of waves, each walking its items with the next items'
+//                          loads issued ahead, was built and measured slower than this: profiles/r07/README.md.)
 //                          Nothing depends on lists being short: the first 64 units of up to 16 lists are in flight
 //                          at once, what lies beyond them is walked four wave loads at a time.
 #pragma once
@@ -152,24 +156,59 @@ __global__ __launch_bounds__(kWave) void bmf_kmer_fill_kernel(const uint8_t *__r
 inline uint32_t kmer_vote_counter_bytes(uint32_t nb, uint32_t bits) { return ((nb * bits + 127u) / 128u) * 16u; }
 inline uint32_t kmer_vote_lds_bytes(uint32_t nb, uint32_t bits) { return kmer_vote_counter_bytes(nb, bits) + 64u * 4u + 16u; }
 
+// The eight ids of one unit, their adds issued back to back: old[j] is what the dword of id j held before.  An id that
+// is no bucket (kPadId, anything >= NB) adds 0, at its own dword where that lies inside the counters and else at the
+// lane's dword of the staging area (dword `spare`): it counts nowhere and no two lanes pile onto one address.  A lane
+// whose first id is no bucket holds no unit and takes no part.
 template <int BITS>
-__device__ __forceinline__ uint32_t kmer_hit(uint32_t *cnt, uint32_t id) {
-    constexpr uint32_t kPer = 32u / BITS, kMask = (1u << BITS) - 1u;
-    const uint32_t sh = (id % kPer) * BITS;
-    const uint32_t old = atomicAdd(&cnt[id / kPer], 1u << sh);
-    return ((old >> sh) & kMask) + 1u;
-}
-
-// the eight ids of one unit; returns the highest count any of them reached
-template <int BITS>
-__device__ __forceinline__ uint32_t kmer_hit_unit(uint32_t *cnt, const uint4 &u, uint32_t nb, uint32_t mx) {
+__device__ __forceinline__ void kmer_unit_issue(uint32_t *cnt, uint32_t spare, const uint4 &u, uint32_t nb, uint32_t (&old)[8]) {
+    constexpr uint32_t kPer = 32u / BITS;
     const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
-    for (int x = 0; x < 4; x++) {
-        const uint32_t lo = w[x] & 0xFFFFu, hi = w[x] >> 16;
-        if (lo < nb) mx = max(mx, kmer_hit<BITS>(cnt, lo));      // kPadId (and anything that is no bucket) counts nowhere
-        if (hi < nb) mx = max(mx, kmer_hit<BITS>(cnt, hi));
+    for (int j = 0; j < 8; j++) old[j] = 0;
+    if ((w[0] & 0xFFFFu) < nb) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t id = j & 1 ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu;
+            old[j] = atomicAdd(&cnt[min(id / kPer, spare)], id < nb ? 1u << ((id % kPer) * BITS) : 0u);
+        }
     }
+}
+
+// ... and the highest count any of them reached, once the adds have returned
+template <int BITS>
+__device__ __forceinline__ uint32_t kmer_unit_fold(const uint4 &u, uint32_t nb, const uint32_t (&old)[8], uint32_t mx) {
+    constexpr uint32_t kPer = 32u / BITS, kMask = (1u << BITS) - 1u;
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t id = j & 1 ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu;
+        mx = max(mx, id < nb ? ((old[j] >> ((id % kPer) * BITS)) & kMask) + 1u : 0u);
+    }
+    return mx;
+}
+
+// N units counted with no wait per add: the adds of unit i are issued before the returns of unit i - 1 are folded into mx
+// (LDS returns come back in order, so up to 16 are in flight; a lane without a unit skips its adds, which is why the
+// compiler's counted waits let a fold wait for at most the first add of the unit after its own).  after(i) runs when u[i]
+// has been folded.
+template <int BITS, int N, class After>
+__device__ __forceinline__ uint32_t kmer_count_units(uint32_t *cnt, uint32_t spare, const uint4 (&u)[N], uint32_t nb, uint32_t mx,
+                                                     After after) {
+    uint32_t old[2][8];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        kmer_unit_issue<BITS>(cnt, spare, u[i], nb, old[i & 1]);
+        if (i > 0) {
+            mx = kmer_unit_fold<BITS>(u[i - 1], nb, old[(i - 1) & 1], mx);
+            asm volatile("" : "+v"(mx) : : "memory");      // folded here, not after the last unit (the compiler sinks the
+                                                           // folds there, 128 returns live): the returns die now
+            after(i - 1);
+        }
+
+    }
+    mx = kmer_unit_fold<BITS>(u[N - 1], nb, old[(N - 1) & 1], mx);
+    after(N - 1);
     return mx;
 }
 
@@ -190,6 +229,7 @@ __global__ __launch_bounds__(kWave) void bmf_vote_kernel_lists(DevParams P, cons
     }
     const uint32_t n_dw = (P.nb + kPer - 1u) / kPer, n_q = (n_dw + 3u) >> 2;   // counter dwords, 16-byte groups of them
     uint32_t *stage = lds_cnt + n_q * 4u;      // [0..63] ids at the maximum, [64] how many
+    const uint32_t spare = n_q * 4u + lane;    // (adding 0 to a staged id changes nothing)
     for (uint32_t i = lane; i < n_q; i += kWave) reinterpret_cast<uint4 *>(lds_cnt)[i] = make_uint4(0, 0, 0, 0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -214,8 +254,7 @@ __global__ __launch_bounds__(kWave) void bmf_vote_kernel_lists(DevParams P, cons
             u[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
             if (lane < n) u[i] = units[f + lane];
         }
-#pragma unroll
-        for (int i = 0; i < 16; i++) mx = kmer_hit_unit<BITS>(lds_cnt, u[i], P.nb, mx);
+        mx = kmer_count_units<BITS>(lds_cnt, spare, u, P.nb, mx, [](int) {});
     }
     // what lies beyond 64 units (heavy k-mers; a k-mer with no indexed q-gram holds all NB ids): four wave loads at a time
     if (__ballot(n_units > (uint32_t)kWave) != 0) {
@@ -230,8 +269,7 @@ __global__ __launch_bounds__(kWave) void bmf_vote_kernel_lists(DevParams P, cons
                     u[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
                     if (t < n) u[i] = units[f + t];
                 }
-#pragma unroll
-                for (int i = 0; i < 4; i++) mx = kmer_hit_unit<BITS>(lds_cnt, u[i], P.nb, mx);
+                mx = kmer_count_units<BITS>(lds_cnt, spare, u, P.nb, mx, [](int) {});
             }
         }
     }
