@@ -14,6 +14,7 @@
 #include "bmv_clip.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_pair.hip.h"
+#include "bmv_rescue.hip.h"
 #include "bmv_screen.hip.h"
 
 #include <stdio.h>
@@ -209,6 +210,20 @@ struct bmv_ctx {
     std::vector<uint64_t> h_pr_s1, h_pr_s2;
     float ms_pair = 0.f;
     uint64_t pr_combinations = 0;
+    // bmv_rescue: the jobs' arrays (buffers of its own: the aligners' views are the fallback's), the planned views, the host
+    // results of bmv_rescued and what bmv_last_rescue_stats reports
+    DevBuf<uint64_t> rs_anchor_start, rs_contig_start, rs_contig_end, rs_query_start, rs_text_start;
+    DevBuf<uint32_t> rs_anchor_len, rs_anchor_query_len, rs_anchor_end, rs_query_len, rs_max_edits, rs_text_len, rs_list, rs_d, rs_end,
+        rs_out_edits, rs_out_end;
+    DevBuf<uint8_t> rs_anchor_rc, rs_text_rc, rs_out_proper;
+    DevBuf<unsigned long long> rs_count;
+    std::vector<uint64_t> h_rs_text_start;
+    std::vector<uint32_t> h_rs_text_len, h_rs_edits, h_rs_end;
+    std::vector<uint8_t> h_rs_text_rc, h_rs_proper;
+    float ms_rescue = 0.f;
+    uint64_t rs_cells = 0;
+    uint32_t rs_parts = 1;
+    uint32_t resident_lanes = 0;                // what the device keeps in flight at once (bmv_create)
 };
 
 namespace {
@@ -1734,6 +1749,234 @@ int bmv_align_paired(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, co
     }
     if (const int rc = best_realign(c, "bmv_align_paired", v, realign, r)) return rc;
     store_best(c, n, n_groups, cells, picked, r, total_cigar);
+    return BMV_OK;
+}
+
+// Mate rescue (include/bmv.h, bmv_rescue.hip.h): the jobs go to the device, the plan kernel writes their views, the distance
+// kernel runs per word count with the call's `parts`, the finish kernel applies the rule; the views and results to the host,
+// where bmv_rescued reads them.  Queries beyond the lane kernel's words are aligned in full on their planned views.
+int bmv_rescue(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *anchor_text_start, const uint32_t *anchor_text_len,
+               const uint8_t *anchor_text_rc, const uint32_t *anchor_query_len, const uint32_t *anchor_end, const uint64_t *contig_start,
+               const uint64_t *contig_end, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *max_edits, uint32_t n,
+               uint32_t min_frag, uint32_t max_frag) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_rescue: null argument");
+    if (!c->loaded) return fail(BMV_ERR_STATE, "bmv_rescue before bmv_load_genome");
+    if (n && (!anchor_text_start || !anchor_text_len || !anchor_text_rc || !anchor_query_len || !anchor_end || !contig_start || !contig_end ||
+              !query_start || !query_len || !max_edits || (n_read_bytes && !reads)))
+        return fail(BMV_ERR_ARG, "bmv_rescue: null argument");
+    if (min_frag > max_frag) return fail(BMV_ERR_ARG, "bmv_rescue: min_frag %u is larger than max_frag %u (job 0 and every other)", min_frag, max_frag);
+    for (uint32_t j = 0; j < n; j++) {
+        if (contig_start[j] > contig_end[j] || contig_end[j] > c->n_genome)
+            return fail(BMV_ERR_ARG, "job %u: contig [%llu, %llu) is not a range of the genome's %llu bases", j, (unsigned long long)contig_start[j],
+                        (unsigned long long)contig_end[j], (unsigned long long)c->n_genome);
+        if (anchor_end[j] > anchor_text_len[j])
+            return fail(BMV_ERR_ARG, "job %u: anchor_end %u lies beyond the anchor's view of %u bases", j, anchor_end[j], anchor_text_len[j]);
+        if (anchor_text_start[j] >> 62)
+            return fail(BMV_ERR_ARG, "job %u: anchor_text_start %llu does not fit the signed coordinates", j, (unsigned long long)anchor_text_start[j]);
+        if (anchor_text_start[j] > c->n_genome || anchor_text_len[j] > c->n_genome - anchor_text_start[j])
+            return fail(BMV_ERR_ARG, "job %u: the anchor's view lies outside the genome", j);
+        if (query_start[j] > n_read_bytes || query_len[j] > n_read_bytes - query_start[j])
+            return fail(BMV_ERR_ARG, "job %u: query lies outside the read buffer", j);
+        if ((uint64_t)max_frag + std::min(max_edits[j], query_len[j]) > UINT32_MAX)      // (the view holds at most max_frag + k columns)
+            return fail(BMV_ERR_ARG, "job %u: a view of max_frag %u plus %u edits does not fit 32 bits", j, max_frag, std::min(max_edits[j], query_len[j]));
+    }
+    c->h_rs_text_start.assign(n, 0);
+    c->h_rs_text_len.assign(n, 0);
+    c->h_rs_text_rc.assign(n, 0);
+    c->h_rs_edits.assign(n, BMV_BEYOND);
+    c->h_rs_end.assign(n, 0);
+    c->h_rs_proper.assign(n, 0);
+    c->ms_rescue = 0.f;
+    c->rs_cells = 0;
+    c->rs_parts = 1;
+    if (n == 0) return BMV_OK;
+
+    HIP_TRY(hipSetDevice(c->p.device));
+    if (c->resident_lanes == 0) {
+        int cus = 0, threads = 0;
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->p.device));
+        HIP_TRY(hipDeviceGetAttribute(&threads, hipDeviceAttributeMaxThreadsPerMultiProcessor, c->p.device));
+        c->resident_lanes = (uint32_t)std::max(cus, 1) * (uint32_t)std::max(threads, 64);
+    }
+    HIP_TRY(c->reads.need_exact((size_t)n_read_bytes + 64u));
+    HIP_TRY(need_exact_all(n, c->rs_anchor_start, c->rs_contig_start, c->rs_contig_end, c->rs_query_start, c->rs_text_start));
+    HIP_TRY(need_exact_all(n, c->rs_anchor_len, c->rs_anchor_query_len, c->rs_anchor_end, c->rs_query_len, c->rs_max_edits, c->rs_text_len,
+                           c->rs_list, c->rs_d, c->rs_end, c->rs_out_edits, c->rs_out_end));
+    HIP_TRY(need_exact_all(n, c->rs_anchor_rc, c->rs_text_rc, c->rs_out_proper));
+    HIP_TRY(c->rs_count.need_exact(1));
+    const size_t n8 = (size_t)n * 8, n4 = (size_t)n * 4;
+    if (n_read_bytes) HIP_TRY(hipMemcpyAsync(c->reads.p, reads, (size_t)n_read_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_anchor_start.p, anchor_text_start, n8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_anchor_len.p, anchor_text_len, n4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_anchor_rc.p, anchor_text_rc, n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_anchor_query_len.p, anchor_query_len, n4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_anchor_end.p, anchor_end, n4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_contig_start.p, contig_start, n8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_contig_end.p, contig_end, n8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_query_start.p, query_start, n8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_query_len.p, query_len, n4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_max_edits.p, max_edits, n4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->rs_count.p, 0, sizeof(unsigned long long), c->stream));
+    bmv::RescueJob j{};
+    j.anchor_text_start = c->rs_anchor_start.p;
+    j.anchor_text_len = c->rs_anchor_len.p;
+    j.anchor_text_rc = c->rs_anchor_rc.p;
+    j.anchor_query_len = c->rs_anchor_query_len.p;
+    j.anchor_end = c->rs_anchor_end.p;
+    j.contig_start = c->rs_contig_start.p;
+    j.contig_end = c->rs_contig_end.p;
+    j.max_edits = c->rs_max_edits.p;
+    j.n = n;
+    j.min_frag = (int64_t)min_frag;
+    j.max_frag = (int64_t)max_frag;
+    j.genome = c->genome.p;
+    j.reads = c->reads.p;
+    j.lut = c->lut.p;
+    j.text_start = c->rs_text_start.p;
+    j.text_len = c->rs_text_len.p;
+    j.text_rc = c->rs_text_rc.p;
+    j.query_start = c->rs_query_start.p;
+    j.query_len = c->rs_query_len.p;
+    j.d = c->rs_d.p;
+    j.end = c->rs_end.p;
+    j.cells = c->rs_count.p;
+    j.out_edits = c->rs_out_edits.p;
+    j.out_end = c->rs_out_end.p;
+    j.out_proper = c->rs_out_proper.p;
+
+    // 1. the views
+    const dim3 per_job((n + 255u) / 256u);
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_rescue_plan_kernel, per_job, dim3(256), 0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_rs_text_start.data(), c->rs_text_start.p, n8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_rs_text_len.data(), c->rs_text_len.p, n4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_rs_text_rc.data(), c->rs_text_rc.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms_plan = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_plan, c->ev0, c->ev1));
+
+    // 2. the jobs by word count; what the lane kernel does not take goes through the aligner (an empty view or query: beyond)
+    std::vector<uint32_t> by_words[bmv::kRescueLaneWords + 1], longs;
+    uint64_t columns = 0, warm = 0;
+    size_t n_listed = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        const uint32_t m = query_len[a], w = (m + 63u) / 64u;
+        if (m == 0u || c->h_rs_text_len[a] == 0u) continue;
+        if (w > bmv::kRescueLaneWords) {
+            longs.push_back(a);
+            continue;
+        }
+        by_words[w].push_back(a);
+        n_listed++;
+        columns += c->h_rs_text_len[a];
+        warm += (uint64_t)m + std::min(max_edits[a], m);
+    }
+    std::vector<uint32_t> h_d(n, BMV_BEYOND), h_end(n, 0u);
+    float ms_long = 0.f;
+    if (!longs.empty()) {
+        // bmv_align_long's results are the caller's last alignment call's: kept aside and put back
+        const uint32_t keep_n = c->n_last;
+        const uint64_t keep_cells = c->n_cells;
+        const float keep_ms = c->ms_kernels;
+        std::vector<int32_t> keep_score = std::move(c->h_score);
+        std::vector<uint32_t> keep_begin = std::move(c->h_begin), keep_cigar = std::move(c->h_cigar);
+        std::vector<uint64_t> keep_offset = std::move(c->h_offset);
+        const Views v{reads, n_read_bytes, c->h_rs_text_start.data(), c->h_rs_text_len.data(), c->h_rs_text_rc.data(), query_start, query_len, n};
+        SubResults sub;
+        const int rc = align_sub_batch(c, v, longs, sub);
+        c->n_last = keep_n;
+        c->n_cells = keep_cells;
+        c->ms_kernels = keep_ms;
+        c->h_score = std::move(keep_score);
+        c->h_begin = std::move(keep_begin);
+        c->h_cigar = std::move(keep_cigar);
+        c->h_offset = std::move(keep_offset);
+        if (rc) return rc;
+        for (size_t s = 0; s < longs.size(); s++) {
+            uint32_t r = 0;
+            for (uint64_t x = sub.offset[s]; x < sub.offset[s + 1]; x++)
+                if ((sub.cigar[x] & 15u) != BMV_OP_I) r += sub.cigar[x] >> 4;
+            h_d[longs[s]] = (uint32_t)(-(int64_t)sub.score[s]);
+            h_end[longs[s]] = sub.begin[s] + r;
+            c->rs_cells += (uint64_t)query_len[longs[s]] * c->h_rs_text_len[longs[s]];
+        }
+        ms_long = sub.ms;
+        HIP_TRY(hipSetDevice(c->p.device));
+    }
+
+    // 3. parts: as many as fill the card's resident lanes, and no part shorter than its m + k warm-up
+    uint32_t parts = 1;
+    if (const char *env = getenv("BMV_RESCUE_PARTS")) {
+        const long v = atol(env);
+        while (parts < 64u && (long)parts * 2 <= v) parts *= 2u;
+    } else if (n_listed) {
+        while (parts < 64u && (uint64_t)n_listed * parts * 2u <= c->resident_lanes && columns >= warm * parts * 2u) parts *= 2u;
+    }
+    c->rs_parts = parts;
+    uint32_t parts_log2 = 0;
+    while ((1u << parts_log2) < parts) parts_log2++;
+
+    // 4. distance and finish
+    std::vector<uint32_t> list;
+    list.reserve(n_listed);
+    for (uint32_t w = 1; w <= bmv::kRescueLaneWords; w++) list.insert(list.end(), by_words[w].begin(), by_words[w].end());
+    if (n_listed) HIP_TRY(hipMemcpyAsync(c->rs_list.p, list.data(), n_listed * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_d.p, h_d.data(), n4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rs_end.p, h_end.data(), n4, hipMemcpyHostToDevice, c->stream));
+    using rescue_fn = void (*)(bmv::RescueJob);
+    static const rescue_fn per_lane[bmv::kRescueLaneWords + 1] = {nullptr,
+                                                                  bmv::bmv_rescue_lane_kernel<1>, bmv::bmv_rescue_lane_kernel<2>,
+                                                                  bmv::bmv_rescue_lane_kernel<3>, bmv::bmv_rescue_lane_kernel<4>,
+                                                                  bmv::bmv_rescue_lane_kernel<5>, bmv::bmv_rescue_lane_kernel<6>,
+                                                                  bmv::bmv_rescue_lane_kernel<7>, bmv::bmv_rescue_lane_kernel<8>};
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    size_t at = 0;
+    for (uint32_t w = 1; w <= bmv::kRescueLaneWords; w++) {
+        const size_t count = by_words[w].size();
+        if (count == 0) continue;
+        j.list = c->rs_list.p + at;
+        j.count = (uint32_t)count;
+        j.parts_log2 = parts_log2;
+        const uint64_t waves = ((uint64_t)count * parts + bmv::kWave - 1u) / bmv::kWave;
+        hipLaunchKernelGGL(per_lane[w], dim3((uint32_t)waves), dim3(bmv::kWave), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        at += count;
+    }
+    hipLaunchKernelGGL(bmv::bmv_rescue_finish_kernel, per_job, dim3(256), 0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    unsigned long long steps = 0;
+    HIP_TRY(hipMemcpyAsync(c->h_rs_edits.data(), c->rs_out_edits.p, n4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_rs_end.data(), c->rs_out_end.p, n4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_rs_proper.data(), c->rs_out_proper.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&steps, c->rs_count.p, sizeof steps, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms_rest = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_rest, c->ev0, c->ev1));
+    c->ms_rescue = ms_plan + ms_long + ms_rest;
+    c->rs_cells += 64u * (uint64_t)steps;
+    return BMV_OK;
+}
+
+int bmv_rescued(bmv_ctx *c, uint64_t *out_text_start, uint32_t *out_text_len, uint8_t *out_text_rc, uint32_t *out_edits, uint32_t *out_end,
+                uint8_t *out_proper) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_rescued: null context");
+    copy_out(out_text_start, c->h_rs_text_start);
+    copy_out(out_text_len, c->h_rs_text_len);
+    copy_out(out_text_rc, c->h_rs_text_rc);
+    copy_out(out_edits, c->h_rs_edits);
+    copy_out(out_end, c->h_rs_end);
+    copy_out(out_proper, c->h_rs_proper);
+    return BMV_OK;
+}
+
+int bmv_last_rescue_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_cells, uint32_t *parts) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_rescue_stats: null context");
+    if (ms_kernels) *ms_kernels = c->ms_rescue;
+    if (n_cells) *n_cells = c->rs_cells;
+    if (parts) *parts = c->rs_parts;
     return BMV_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "bm_genome.h"
 #include "mapper.h"
 #include "pair_mapq.h"
+#include "pair_rescue.h"
 #include "sam_tags.h"
 
 #include <algorithm>
@@ -275,6 +276,61 @@ public:
         cigar_offset[n] = at;
         cigar.resize(at);
     }
+    // Mate rescue (bmv_rescue's contract, include/bmv.h): job j places the mate reads[query_start[j], +query_len[j]) beside its
+    // anchor -- a known alignment of its partner, given as select_pair takes one -- on the contig [contig_start[j],
+    // contig_end[j]), within max_edits[j] edits.  out: the view of pair_rescue.h's rescue_window per job, edits / end the
+    // query's distance to it and its end column when within min(max_edits, query_len) (kBeyond / 0 elsewhere, and for an
+    // empty view or query), proper as select_pair's between the anchor and the rescued mate.  This default plans on the host
+    // and aligns every view in full; the GPU verifier plans and decides score-only on the device.
+    struct rescued {
+        std::vector<uint64_t> text_start;
+        std::vector<uint32_t> text_len, edits, end;
+        std::vector<uint8_t> text_rc, proper;
+    };
+    virtual void rescue(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *anchor_text_start, const uint32_t *anchor_text_len,
+                        const uint8_t *anchor_text_rc, const uint32_t *anchor_query_len, const uint32_t *anchor_end,
+                        const uint64_t *contig_start, const uint64_t *contig_end, const uint64_t *query_start, const uint32_t *query_len,
+                        const uint32_t *max_edits, uint32_t n, uint32_t min_frag, uint32_t max_frag, rescued &out) {
+        out.text_start.assign(n, 0);
+        out.text_len.assign(n, 0);
+        out.text_rc.assign(n, 0);
+        out.edits.assign(n, kBeyond);
+        out.end.assign(n, 0);
+        out.proper.assign(n, 0);
+        std::vector<uint32_t> which, tl, ql;
+        std::vector<uint64_t> ts, qs;
+        std::vector<uint8_t> trc;
+        for (uint32_t j = 0; j < n; j++) {
+            const rescue_view v = rescue_window(anchor_text_start[j], anchor_text_len[j], anchor_text_rc[j] != 0, anchor_query_len[j],
+                                                anchor_end[j], contig_start[j], contig_end[j], query_len[j], max_edits[j], min_frag, max_frag);
+            out.text_start[j] = v.text_start;
+            out.text_len[j] = v.text_len;
+            out.text_rc[j] = v.text_rc;
+            if (v.text_len == 0 || query_len[j] == 0) continue;
+            which.push_back(j);
+            ts.push_back(v.text_start); tl.push_back(v.text_len); trc.push_back(v.text_rc);
+            qs.push_back(query_start[j]); ql.push_back(query_len[j]);
+        }
+        std::vector<int32_t> score;
+        std::vector<uint32_t> begin, cigar;
+        std::vector<uint64_t> cigar_offset;
+        if (!which.empty())
+            align(reads, n_read_bytes, ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), static_cast<uint32_t>(which.size()), score, begin,
+                  cigar_offset, cigar);
+        for (size_t s = 0; s < which.size(); s++) {
+            const uint32_t j = which[s];
+            const uint64_t d = static_cast<uint64_t>(-static_cast<int64_t>(score[s]));
+            if (d > std::min(max_edits[j], query_len[j])) continue;
+            uint32_t r = 0;
+            for (uint64_t x = cigar_offset[s]; x < cigar_offset[s + 1]; x++)
+                if ((cigar[x] & 15u) != 1u) r += cigar[x] >> 4;
+            out.edits[j] = static_cast<uint32_t>(d);
+            out.end[j] = begin[s] + r;
+            out.proper[j] = rescue_proper(anchor_text_start[j], anchor_text_len[j], anchor_text_rc[j] != 0, anchor_query_len[j], anchor_end[j],
+                                          rescue_view{out.text_start[j], out.text_len[j], out.text_rc[j]}, query_len[j], out.end[j], min_frag,
+                                          max_frag) ? 1 : 0;
+        }
+    }
 };
 
 // SAM text as seqan3::sam_file_output lays it out: records are appended to one buffer with
@@ -391,6 +447,7 @@ private:
     float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
     bool _paired = false;                        // --paired: records 2p and 2p + 1 of the FASTQ file are mates, placed together
     uint32_t _min_frag = 1, _max_frag = 1000;    // --frag-range: what a proper pair spans, leftmost to rightmost base
+    float _rescue_rate = -1.f;                   // >= 0: --rescue, a mate without a proper placement is sought beside its partner
     std::vector<uint8_t> flat_genome_;           // --annotate with a verifier that cannot annotate: the records back to back
     const Genome *genome_ = nullptr;
     std::vector<Bucket> buckets_;
@@ -604,6 +661,11 @@ public:
         _min_frag = min_frag;
         _max_frag = max_frag;
     }
+    // --rescue (implies --paired: the caller sets it): after a block's paired() call every pair without a proper combination
+    // gets the jobs of pair_rescue.h's select_rescue -- a mate's own winner within (uint32_t)(rate x its length) edits anchors
+    // the search for the other mate (alignment_verifier::rescue) --, and a mate that comes back within bound and proper gets the
+    // record of that placement, with its anchor's MAPQ, X0:i:1 and XR:i:1
+    void set_rescue(float rate) { _rescue_rate = rate; }
     void set_clip(uint32_t match, uint32_t penalty) {
         _clip = _annotate = true;
         _clip_match = match;
@@ -913,6 +975,8 @@ private:
             std::vector<uint32_t> contig, pick;                 // --paired: per alignment its @SQ entry; per read its pick
             std::vector<uint8_t> proper;                        // ... and per pair (reads 2p, 2p + 1 of the block)
             std::vector<uint64_t> s1, s2;
+            std::vector<uint32_t> rescued_at;                   // --rescue: per read the alignment (appended behind the groups') that
+                                                                // places it beside its mate, kBeyond when it was not rescued
             std::vector<uint8_t> text_rc;
             std::vector<int32_t> score;
             std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
@@ -930,6 +994,7 @@ private:
         const bool bounded = _max_edit_rate >= 0.f;             // --max-edit-rate: rejected alignments leave no record
         const bool best = _best_margin >= 0.f;                  // --best: neither do the alignments that did not win
         const bool paired = _paired;                            // --paired: --best with the pick of the pair in the winner's place
+        const bool rescue = paired && _rescue_rate >= 0.f;      // --rescue: pairs without a proper combination get a second look
         std::vector<uint32_t> bucket_ref;                       // per bucket the index of its @SQ entry (runs of equal names)
         if (paired) {
             if (locate_res.size() % 2u)
@@ -946,8 +1011,87 @@ private:
             const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
             return !((bounded || best) && b.score[a] == alignment_verifier::kRejected) && !(map_qual < quality_threshold);
         };
+        // --rescue, after paired(): the jobs of every pair that is not proper, the verifier's answer, and for each mate it
+        // places a full alignment appended behind the groups' -- on its view narrowed to the m + d columns before the end the
+        // rescue found, which yields the alignment the whole view would
+        auto rescue_block = [&](Block &b) {
+            const uint32_t kNone = alignment_verifier::kBeyond;
+            struct job { uint32_t anchor_read, query_read, pair, which; };
+            std::vector<job> jobs;
+            std::vector<uint64_t> a_ts, c0, c1, qs;
+            std::vector<uint32_t> a_tl, a_ql, a_end, ql, me;
+            std::vector<uint8_t> a_rc;
+            auto anchor_edits = [&](size_t r) { return b.winner[r] == kNone ? kNone : b.edits[b.winner[r]]; };
+            for (size_t p = 0; p < b.reads.size() / 2; p++) {
+                const uint32_t edits[2] = {anchor_edits(2 * p), anchor_edits(2 * p + 1)};
+                const uint32_t len[2] = {static_cast<uint32_t>(b.reads[2 * p].seq.size()), static_cast<uint32_t>(b.reads[2 * p + 1].seq.size())};
+                const rescue_choice c = select_rescue(b.proper[p] != 0, edits, len, _rescue_rate, nullptr, nullptr);
+                for (uint32_t i = 0; i < 2u; i++) {
+                    if (!c.job[i]) continue;
+                    const uint32_t ra = static_cast<uint32_t>(2 * p + i), rq = static_cast<uint32_t>(2 * p + 1 - i), a = b.winner[ra];
+                    const unsigned int bucket = std::get<0>(locate_res[b.first_read + ra][a - b.group_offset[ra]]);
+                    const uint64_t rec_start = bstart_[bucket] - buckets_[bucket].start;
+                    jobs.push_back({ra, rq, static_cast<uint32_t>(p), i});
+                    a_ts.push_back(b.text_start[a]); a_tl.push_back(b.text_len[a]); a_rc.push_back(b.text_rc[a]);
+                    a_ql.push_back(b.query_len[a]); a_end.push_back(b.end[a]);
+                    c0.push_back(rec_start); c1.push_back(rec_start + genome_->seqs[buckets_[bucket].record].size());
+                    qs.push_back(b.reads[rq].start); ql.push_back(len[1 - i]); me.push_back(c.max_edits[i]);
+                }
+            }
+            if (jobs.empty()) return;
+            alignment_verifier::rescued out;
+            _v->rescue(b.bases.data(), b.bases.size(), a_ts.data(), a_tl.data(), a_rc.data(), a_ql.data(), a_end.data(), c0.data(), c1.data(),
+                       qs.data(), ql.data(), me.data(), static_cast<uint32_t>(jobs.size()), _min_frag, _max_frag, out);
+            // per pair the job it keeps; its mate's placement, narrowed
+            std::vector<uint64_t> ts, nqs;
+            std::vector<uint32_t> tl, nql, readers;
+            std::vector<uint8_t> trc;
+            for (size_t j = 0; j < jobs.size();) {
+                size_t e = j;
+                uint32_t r_edits[2] = {kNone, kNone}, at[2] = {0, 0};
+                uint8_t r_proper[2] = {0, 0};
+                for (; e < jobs.size() && jobs[e].pair == jobs[j].pair; e++) {
+                    r_edits[jobs[e].which] = out.edits[e];
+                    r_proper[jobs[e].which] = out.proper[e];
+                    at[jobs[e].which] = static_cast<uint32_t>(e);
+                }
+                const size_t p = jobs[j].pair;
+                const uint32_t edits[2] = {anchor_edits(2 * p), anchor_edits(2 * p + 1)};
+                const uint32_t len[2] = {static_cast<uint32_t>(b.reads[2 * p].seq.size()), static_cast<uint32_t>(b.reads[2 * p + 1].seq.size())};
+                const rescue_choice c = select_rescue(false, edits, len, _rescue_rate, r_edits, r_proper);
+                j = e;
+                if (c.keep < 0) continue;
+                const uint32_t k = at[c.keep], rq = jobs[k].query_read;
+                const uint32_t span = std::min<uint64_t>(static_cast<uint64_t>(ql[k]) + out.edits[k], out.end[k]);
+                ts.push_back(out.text_rc[k] ? out.text_start[k] + out.text_len[k] - out.end[k] : out.text_start[k] + out.end[k] - span);
+                tl.push_back(span); trc.push_back(out.text_rc[k]);
+                nqs.push_back(qs[k]); nql.push_back(ql[k]); readers.push_back(rq);
+            }
+            if (readers.empty()) return;
+            std::vector<int32_t> score;
+            std::vector<uint32_t> begin, cigar;
+            std::vector<uint64_t> cigar_offset;
+            _v->align(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), nqs.data(), nql.data(), static_cast<uint32_t>(readers.size()),
+                      score, begin, cigar_offset, cigar);
+            for (size_t x = 0; x < readers.size(); x++) {
+                const uint32_t rq = readers[x];
+                // the mate's former winner, if it had one, gets no record
+                if (b.pick[rq] != kNone) b.score[b.pick[rq]] = alignment_verifier::kRejected;
+                b.rescued_at[rq] = static_cast<uint32_t>(b.text_start.size());
+                b.text_start.push_back(ts[x]); b.text_len.push_back(tl[x]); b.text_rc.push_back(trc[x]);
+                b.query_start.push_back(nqs[x]); b.query_len.push_back(nql[x]);
+                const bool beyond = bounded && -static_cast<int64_t>(score[x]) >
+                                                   static_cast<int64_t>(std::min(_max_edit_rate * static_cast<float>(nql[x]), 4e9f));
+                b.score.push_back(beyond ? alignment_verifier::kRejected : score[x]);
+                b.begin.push_back(begin[x]);
+                b.cigar.insert(b.cigar.end(), cigar.begin() + static_cast<ptrdiff_t>(cigar_offset[x]),
+                               cigar.begin() + static_cast<ptrdiff_t>(cigar_offset[x + 1]));
+                b.cigar_offset.push_back(b.cigar.size());
+            }
+        };
         auto align = [&](Block &b) {                            // on the worker thread
             try {
+                b.rescued_at.assign(b.reads.size(), alignment_verifier::kBeyond);
                 if (!b.text_start.empty() && paired) {
                     _v->paired(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                                b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.group_offset.data(),
@@ -956,6 +1100,7 @@ private:
                     for (size_t a = 0; bounded && a < b.score.size(); a++)
                         if (b.score[a] != alignment_verifier::kRejected && -static_cast<int64_t>(b.score[a]) > static_cast<int64_t>(b.max_edits[a]))
                             b.score[a] = alignment_verifier::kRejected;
+                    if (rescue) rescue_block(b);
                 } else if (!b.text_start.empty() && best) {
                     _v->best(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                              b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.group_offset.data(),
@@ -1014,8 +1159,29 @@ private:
             uint64_t pos = 0;                                   // 1-based, as written
             uint32_t ref_len = 0;
         };
+        // --rescue: where a rescued mate's view begins, as (bucket, offset in it): the bucket of the anchor's record that holds it
+        auto rescued_place = [&](const Block &b, size_t r) {
+            const size_t ra = r ^ 1u;
+            unsigned int bucket = std::get<0>(locate_res[b.first_read + ra][b.winner[ra] - b.group_offset[ra]]);
+            const uint32_t record = buckets_[bucket].record;
+            const uint64_t local = b.text_start[b.rescued_at[r]] - (bstart_[bucket] - buckets_[bucket].start);
+            while (bucket + 1u < buckets_.size() && buckets_[bucket + 1u].record == record && buckets_[bucket + 1u].start <= local) bucket++;
+            while (bucket > 0u && buckets_[bucket - 1u].record == record && buckets_[bucket].start > local) bucket--;
+            return std::make_pair(bucket, local - buckets_[bucket].start);
+        };
         auto mate_of = [&](const Block &b, size_t r) {
             mate_record m;
+            if (rescue && b.rescued_at[r] != alignment_verifier::kBeyond) {
+                const uint32_t a = b.rescued_at[r];
+                if (!is_written(b, a) || (_clip && b.ann.score[b.ann_slot[a]] == 0)) return m;
+                const auto [bucket, offset] = rescued_place(b, r);
+                m.has = true;
+                m.rc = b.text_rc[a] != 0;
+                m.bucket = bucket;
+                m.pos = static_cast<uint64_t>(b.ann.pos[b.ann_slot[a]]) + h.bucket_offsets[bucket] + offset + 1u;
+                m.ref_len = b.ann.ref_len[b.ann_slot[a]];
+                return m;
+            }
             const uint32_t a0 = b.group_offset[r];
             if (b.group_offset[r + 1] == a0 || b.pick[r] == alignment_verifier::kBeyond) return m;
             const uint32_t a = b.pick[r];
@@ -1033,23 +1199,62 @@ private:
             if (b.failed) std::rethrow_exception(b.failed);
             size_t a = 0;
             std::string cg, tags, rc_seq, rc_qual, best_tag;
+            // an annotated record of read r: alignment a, which begins ref_base bases into the @SQ entry rname
+            auto annotated = [&](size_t r, size_t a, std::string_view rname, size_t ref_base, bool is_original, unsigned int flags,
+                                 size_t map_qual, std::string_view last_tag, std::string_view rnext, uint64_t pnext, int64_t tlen) {
+                const uint32_t s = b.ann_slot[a];
+                const size_t ref_offset = static_cast<size_t>(b.ann.pos[s]) + ref_base;
+                const uint32_t *entry = b.ann.xcigar.data() + b.ann.xcigar_offset[s];
+                const size_t n_entries = b.ann.xcigar_offset[s + 1] - b.ann.xcigar_offset[s];
+                cg.clear();
+                sam_tags::append_cigar(cg, entry, n_entries);
+                if (cg.empty()) cg = "*";
+                tags = "NM:i:";
+                sam_tags::number(tags, b.ann.nm[s]);
+                tags += "\tMD:Z:";
+                sam_tags::append_md(tags, entry, n_entries, b.ann.ref_bases.data() + b.ann.ref_offset[s]);
+                if (_clip) {
+                    tags += "\tAS:i:";
+                    sam_tags::number(tags, static_cast<uint64_t>(b.ann.score[s]));
+                }
+                if (best) tags += "\t" + best_tag;
+                if (!last_tag.empty()) {
+                    tags += '\t';
+                    tags += last_tag;
+                }
+                if (!is_original && rc_seq.empty()) {
+                    sam_tags::append_revcomp(rc_seq, b.reads[r].seq);
+                    rc_qual.assign(b.reads[r].qual.rbegin(), b.reads[r].qual.rend());
+                }
+                sam.record(b.reads[r].id, (is_original ? 0 : 16) | flags, rname, ref_offset + 1, static_cast<uint8_t>(map_qual), cg,
+                           is_original ? b.reads[r].seq : rc_seq, is_original ? b.reads[r].qual : rc_qual, tags, rnext, pnext, tlen);
+                mapped_locations++;
+            };
+            auto own_quality = [&](size_t r) {                  // best_mapq of read r's own winner
+                const uint32_t a0 = b.group_offset[r];
+                return best_mapq(b.winner[r] - a0, b.edits.data() + a0, b.end.data() + a0, b.text_start.data() + a0, b.text_len.data() + a0,
+                                 b.text_rc.data() + a0, b.group_offset[r + 1] - a0, b.margin[r]);
+            };
             for (size_t r = 0; r < b.reads.size(); r++) {
                 rc_seq.clear();                                 // (--annotate: made for the read's first flag-16 record)
                 best_quality bq{0u, 0u};                        // --best: the MAPQ and X0 of the read's one record
                 const bool candidates = best && b.group_offset[r + 1] > b.group_offset[r];
                 const bool proper = paired && candidates && b.proper[r / 2] != 0;
+                // --rescue: this read was placed beside its mate / its mate was placed beside this read
+                const bool rescued = rescue && b.rescued_at[r] != alignment_verifier::kBeyond;
+                const bool anchors = rescue && b.rescued_at[r ^ 1u] != alignment_verifier::kBeyond;
                 if (proper) {
                     const uint32_t a0 = b.group_offset[r];
                     const size_t p = r / 2;
                     bq = pair_mate_mapq(pair_quality(b.s1[p], b.s2[p], static_cast<uint64_t>(b.margin[2 * p]) + b.margin[2 * p + 1]),
                                         b.pick[r] - a0, b.winner[r] - a0, b.edits.data() + a0, b.end.data() + a0, b.text_start.data() + a0,
                                         b.text_len.data() + a0, b.text_rc.data() + a0, b.group_offset[r + 1] - a0, b.margin[r]);
+                } else if (rescued) {
+                    bq = {own_quality(r ^ 1u).mapq, 1u};        // its place is only as unique as its anchor's
                 } else if (candidates) {
-                    const uint32_t a0 = b.group_offset[r];
-                    bq = best_mapq(b.winner[r] - a0, b.edits.data() + a0, b.end.data() + a0, b.text_start.data() + a0,
-                                   b.text_len.data() + a0, b.text_rc.data() + a0, b.group_offset[r + 1] - a0, b.margin[r]);
+                    bq = own_quality(r);
                 }
-                if (candidates) {
+                if (candidates || rescued) {
                     best_tag = "X0:i:";
                     sam_tags::number(best_tag, bq.x0);
                 }
@@ -1058,13 +1263,13 @@ private:
                 std::string_view rnext = "*";
                 uint64_t pnext = 0;
                 int64_t tlen = 0;
-                if (paired && candidates) {
+                if (paired && (candidates || rescued)) {
                     const mate_record me = mate_of(b, r), mate = mate_of(b, r ^ 1u);
                     pair_flags = 0x1u | (r % 2 ? 0x80u : 0x40u);
                     if (!mate.has) {
                         pair_flags |= 0x8u;
                     } else {
-                        if (proper) pair_flags |= 0x2u;
+                        if (proper || ((rescued || anchors) && me.has)) pair_flags |= 0x2u;
                         if (mate.rc) pair_flags |= 0x20u;
                         const bool same = bucket_ref[me.bucket] == bucket_ref[mate.bucket];
                         rnext = same ? std::string_view("=") : std::string_view(h.bucket_name[mate.bucket]);
@@ -1090,31 +1295,8 @@ private:
                     if (is_written(b, a) && _clip && b.ann.score[b.ann_slot[a]] == 0) {
                         // --clip: the kept range is empty (a kept column scores at least `match`): no record
                     } else if (is_written(b, a) && _annotate) {
-                        const uint32_t s = b.ann_slot[a];
-                        const int clipped = offset < 0 ? 0 : offset;
-                        const size_t ref_offset = static_cast<size_t>(b.ann.pos[s]) + h.bucket_offsets[bucket_id] + clipped;
-                        const uint32_t *entry = b.ann.xcigar.data() + b.ann.xcigar_offset[s];
-                        const size_t n_entries = b.ann.xcigar_offset[s + 1] - b.ann.xcigar_offset[s];
-                        cg.clear();
-                        sam_tags::append_cigar(cg, entry, n_entries);
-                        if (cg.empty()) cg = "*";
-                        tags = "NM:i:";
-                        sam_tags::number(tags, b.ann.nm[s]);
-                        tags += "\tMD:Z:";
-                        sam_tags::append_md(tags, entry, n_entries, b.ann.ref_bases.data() + b.ann.ref_offset[s]);
-                        if (_clip) {
-                            tags += "\tAS:i:";
-                            sam_tags::number(tags, static_cast<uint64_t>(b.ann.score[s]));
-                        }
-                        if (best) tags += "\t" + best_tag;
-                        if (!is_original && rc_seq.empty()) {
-                            sam_tags::append_revcomp(rc_seq, b.reads[r].seq);
-                            rc_qual.assign(b.reads[r].qual.rbegin(), b.reads[r].qual.rend());
-                        }
-                        sam.record(b.reads[r].id, (is_original ? 0 : 16) | pair_flags, h.bucket_name[bucket_id], ref_offset + 1,
-                                   static_cast<uint8_t>(map_qual), cg, is_original ? b.reads[r].seq : rc_seq,
-                                   is_original ? b.reads[r].qual : rc_qual, tags, rnext, pnext, tlen);
-                        mapped_locations++;
+                        annotated(r, a, h.bucket_name[bucket_id], h.bucket_offsets[bucket_id] + static_cast<size_t>(offset < 0 ? 0 : offset), is_original,
+                                  pair_flags, map_qual, {}, rnext, pnext, tlen);
                     } else if (is_written(b, a)) {
                         const int clipped = offset < 0 ? 0 : offset;
                         const size_t ref_offset = static_cast<size_t>(b.begin[a]) + h.bucket_offsets[bucket_id] + clipped;   // :576
@@ -1130,6 +1312,14 @@ private:
                         mapped_locations++;
                     }
                     a++;
+                }
+                if (rescued) {
+                    const uint32_t ra = b.rescued_at[r];
+                    if (is_written(b, ra) && !(_clip && b.ann.score[b.ann_slot[ra]] == 0)) {
+                        const auto [bucket, offset] = rescued_place(b, r);
+                        annotated(r, ra, h.bucket_name[bucket], h.bucket_offsets[bucket] + static_cast<size_t>(offset), b.text_rc[ra] == 0, pair_flags,
+                                  bq.mapq, "XR:i:1", rnext, pnext, tlen);
+                    }
                 }
             }
             b.reads.clear(); b.bases.clear();

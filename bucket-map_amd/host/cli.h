@@ -44,6 +44,10 @@ struct cmd_arguments {
                                   // the two are placed together and written with the pair's flags, RNEXT, PNEXT and TLEN
                                   // (implies --best and --annotate)
     unsigned int frag_min = 1, frag_max = 1000;      // --frag-range MIN,MAX (implies --paired): what a proper pair may span
+    bool rescue = false;          // --rescue (bucketmap_align, implies --paired): a mate without a proper placement is sought beside
+                                  // its partner's alignment (mate rescue) and written with XR:i:1
+    float rescue_rate = 0.1f;     // --rescue-rate R (implies --rescue): an anchor may have (uint32_t)(R * its length) edits, and so
+                                  // may the rescued mate
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -184,8 +188,18 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.frag_max = static_cast<unsigned>(hi);
             a.paired = true;
         }
+        else if (opt == "--rescue") a.rescue = true;
+        else if (opt == "--rescue-rate") {
+            const std::string s = value();
+            char *end = nullptr;
+            const float r = std::strtof(s.c_str(), &end);
+            if (s.empty() || *end != '\0' || !(r >= 0.f) || r > 1.f)
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a rate between 0 and 1.");
+            a.rescue_rate = r;
+            a.rescue = true;
+        }
 #else
-        else if (opt == "--paired" || opt == "--frag-range")
+        else if (opt == "--paired" || opt == "--frag-range" || opt == "--rescue" || opt == "--rescue-rate")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it cannot place mates together.");
 #endif
         else if (opt == "--clip-scores") {
@@ -212,6 +226,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         else throw parser_error("Unknown option " + opt + ". In case this is meant to be a non-option/argument/parameter, please specify the start of non-options with '--'.");
     }
     if (!have_indicator) throw parser_error("Option -i/--index-indicator is required but not set.");
+    if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;
     return a;
 }

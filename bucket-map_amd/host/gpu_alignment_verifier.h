@@ -214,6 +214,53 @@ public:
                   penalty);
     }
 
+    // bmv_rescue per device: the jobs -- independent of each other -- in contiguous ranges of equal cost, each device handed
+    // the span of the read buffer its queries cover
+    void rescue(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *anchor_text_start, const uint32_t *anchor_text_len,
+                const uint8_t *anchor_text_rc, const uint32_t *anchor_query_len, const uint32_t *anchor_end, const uint64_t *contig_start,
+                const uint64_t *contig_end, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *max_edits, uint32_t n,
+                uint32_t min_frag, uint32_t max_frag, rescued &out) override {
+        const size_t D = ctx_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        out.text_start.assign(n, 0);
+        out.text_len.assign(n, 0);
+        out.text_rc.assign(n, 0);
+        out.edits.assign(n, kBeyond);
+        out.end.assign(n, 0);
+        out.proper.assign(n, 0);
+        const std::vector<uint32_t> cut = cut_by_cost(n, D, [&](uint32_t j) { return static_cast<uint64_t>(query_len[j]) + 1u; });
+        std::vector<float> ms(D, 0.f);
+        std::vector<uint64_t> cells(D, 0);
+        std::vector<uint32_t> parts(D, 0);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t j0 = cut[d], m = cut[d + 1] - cut[d];
+            if (m == 0) return;
+            uint64_t lo = 0, hi = n_read_bytes;
+            std::vector<uint64_t> rebased;
+            if (D > 1) {
+                lo = ~0ull, hi = 0;
+                for (uint32_t j = j0; j < j0 + m; j++) {
+                    lo = std::min(lo, query_start[j]);
+                    hi = std::max(hi, query_start[j] + query_len[j]);
+                }
+                rebased.assign(query_start + j0, query_start + j0 + m);
+                for (uint64_t &q : rebased) q -= lo;
+            }
+            check(bmv_rescue(ctx_[d], reads + lo, hi - lo, anchor_text_start + j0, anchor_text_len + j0, anchor_text_rc + j0,
+                             anchor_query_len + j0, anchor_end + j0, contig_start + j0, contig_end + j0,
+                             D > 1 ? rebased.data() : query_start, query_len + j0, max_edits + j0, m, min_frag, max_frag),
+                  "the GPU mate rescue failed: ");
+            check(bmv_rescued(ctx_[d], out.text_start.data() + j0, out.text_len.data() + j0, out.text_rc.data() + j0, out.edits.data() + j0,
+                              out.end.data() + j0, out.proper.data() + j0),
+                  "reading the rescued mates failed: ");
+            bmv_last_rescue_stats(ctx_[d], &ms[d], &cells[d], &parts[d]);
+        });
+        uint32_t rescued_n = 0;
+        for (uint32_t j = 0; j < n; j++) rescued_n += out.proper[j] ? 1u : 0u;
+        std::cerr << "[BENCHMARK]\tGPU mate rescue: " << n << " jobs, " << sum(cells) << " cells, " << *std::max_element(parts.begin(), parts.end())
+                  << " parts a job; " << rescued_n << " within bound and proper; " << timing(ms, t0);
+    }
+
 private:
     // the views of a batch, as every call of the ABI takes them
     struct batch {

@@ -2,7 +2,8 @@
 // Compiled a second time with -DBM_ALIGN it is `bucketmap_align` (bucket_map/CMakeLists.txt:138): every
 // located candidate is verified by a pairwise alignment and written with MAPQ = 60 + score and a CIGAR
 // (--annotate: as forward-strand records with an =/X CIGAR, NM and MD; --clip: those with low-identity ends soft-clipped;
-// --paired: an interleaved FASTQ file, mates placed together and written as pairs).
+// --paired: an interleaved FASTQ file, mates placed together and written as pairs; --rescue: a mate without a proper
+// placement sought beside its partner).
 //
 //   bucketmap -x -i <name> --genome ref.fa                       index only (writes into the cwd)
 //   bucketmap -i <name> -q reads.fq -o out.sam --genome ref.fa    map (indexes first if needed)
@@ -134,6 +135,7 @@ int main(int argc, char **argv) {
         if (args.clip) loc.set_clip(args.clip_match, args.clip_penalty);
         if (args.best) loc.set_best(args.best_margin);
         if (args.paired) loc.set_paired(args.frag_min, args.frag_max);
+        if (args.rescue) loc.set_rescue(args.rescue_rate);
 #endif
         run_indexer();
         loc.initialize(genome, cwd, args.index_indicator);                                    // main.cpp:221

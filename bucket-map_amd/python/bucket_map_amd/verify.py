@@ -46,6 +46,10 @@ SYMBOLS = {
     "bmv_last_pair_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
     "bmv_align_paired": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u32p, C.c_uint32,
                                    _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p]),
+    "bmv_rescue": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u32p, _u32p, _u64p, _u64p, _u64p, _u32p, _u32p,
+                             C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bmv_rescued": (C.c_int, [C.c_void_p, _u64p, _u32p, _u8p, _u32p, _u32p, _u8p]),
+    "bmv_last_rescue_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p, _u32p]),
     "bmv_results": (C.c_int, [C.c_void_p, _i32p, _u32p, _u64p, _u32p]),
     "bmv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
     "bmv_annotate": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32,
@@ -254,6 +258,56 @@ def pair_mapq(proper, s1, s2, mates) -> list:
     return out
 
 
+def rescue_window(anchor_text_start, anchor_text_len, anchor_text_rc, anchor_query_len, anchor_end, contig_start, contig_end,
+                  query_len, max_edits, min_frag, max_frag) -> tuple:
+    """The window of bmv_rescue for one job in plain Python integers (include/bmv.h; host/pair_rescue.h is the C++ restatement):
+    where a mate of query_len bases may lie beside the anchor -- a known alignment of its partner, given as bmv_pair takes one
+    -- within min(max_edits, query_len) edits, cut to the contig [contig_start, contig_end).  Returns (text_start, text_len,
+    text_rc) of the view the mate is aligned against."""
+    ts, tl, m, end = int(anchor_text_start), int(anchor_text_len), int(query_len), int(anchor_end)
+    k, c0, c1, lo, hi = min(int(max_edits), m), int(contig_start), int(contig_end), int(min_frag), int(max_frag)
+    if int(anchor_text_rc):
+        la = ts + tl - end
+        ra = la + int(anchor_query_len)
+        z_lo, z_hi = ra + m - hi, min(la + m, ra, ra + m - lo)
+        ws, we, rc = max(c0, z_lo - m - k), min(c1, z_hi), 0
+    else:
+        ra = ts + end
+        la = ra - int(anchor_query_len)
+        x_lo, x_hi = max(la, ra - m, la + lo - m), la + hi - m
+        ws, we, rc = max(c0, x_lo), min(c1, x_hi + m + k), 1
+    return ws, max(0, we - ws), rc
+
+
+def rescue_bound(rate, length) -> int:
+    """(uint32_t)(rate x length) in single precision, as bucketmap_align --rescue-rate computes an edit bound."""
+    return int(np.float32(rate) * np.float32(length))
+
+
+def select_rescue(proper, anchor_edits, read_len, rate, rescued_edits=None, rescued_proper=None) -> dict:
+    """Which rescue jobs a pair gets and which result it keeps (host/pair_rescue.h, bucketmap_align --rescue).  proper: what
+    bmv_pair said of the pair; anchor_edits[i]: the edits of mate i's own winner (BEYOND: it has none); read_len[i]: mate i's
+    length.  A pair that is not proper gets job i -- anchored on mate i, its query the OTHER mate, max_edits = rescue_bound(rate,
+    the other's length) -- when mate i's winner is known with edits <= rescue_bound(rate, read_len[i]).  With the jobs' results
+    (rescued_edits[i], rescued_proper[i] of job i; ignored where there is no job): a job counts when it came back within bound
+    and proper; of two that count the smaller anchor_edits[i] + rescued_edits[i] wins, a tie goes to job 0.  Returns
+    {"jobs": [bool, bool], "max_edits": [int, int], "keep": None, 0 or 1}."""
+    jobs = [False, False]
+    bound = [rescue_bound(rate, read_len[1]), rescue_bound(rate, read_len[0])]
+    if not proper:
+        for i in range(2):
+            jobs[i] = int(anchor_edits[i]) != BEYOND and int(anchor_edits[i]) <= rescue_bound(rate, read_len[i])
+    keep = None
+    if rescued_edits is not None:
+        for i in range(2):
+            if not jobs[i] or int(rescued_edits[i]) == BEYOND or not int(rescued_proper[i]):
+                continue
+            total = int(anchor_edits[i]) + int(rescued_edits[i])
+            if keep is None or total < best:
+                keep, best = i, total
+    return {"jobs": jobs, "max_edits": bound, "keep": keep}
+
+
 class Verifier:
     """align_pairwise of the BM_ALIGN branch (bucket_locator.h:520-528,569-576) for batches, on one GPU."""
 
@@ -396,6 +450,37 @@ class Verifier:
         out.update({"score": score, "begin": begin, "cigar_offset": co, "cigar": cg[: total.value], "winner": winner[:n_groups],
                     "edits": edits[:n], "end": end[:n]})
         return out
+
+    def rescue(self, reads, anchor_text_start, anchor_text_len, anchor_text_rc, anchor_query_len, anchor_end, contig_start, contig_end,
+               query_start, query_len, max_edits, min_frag, max_frag) -> dict:
+        """bmv_rescue: job j places the mate reads[query_start[j], +query_len[j]) beside its anchor -- a known alignment of its
+        partner as bmv_pair takes one -- on the contig [contig_start[j], contig_end[j]), within max_edits[j] edits.  Returns
+        text_start, text_len, text_rc (the view rescue_window gives), edits and end (BEYOND / 0 beyond the bound) and proper."""
+        r = np.ascontiguousarray(reads, np.uint8)
+        ats, atl = np.ascontiguousarray(anchor_text_start, np.uint64), np.ascontiguousarray(anchor_text_len, np.uint32)
+        arc, aql = np.ascontiguousarray(anchor_text_rc, np.uint8), np.ascontiguousarray(anchor_query_len, np.uint32)
+        aen = np.ascontiguousarray(anchor_end, np.uint32)
+        c0, c1 = np.ascontiguousarray(contig_start, np.uint64), np.ascontiguousarray(contig_end, np.uint64)
+        qs, ql = np.ascontiguousarray(query_start, np.uint64), np.ascontiguousarray(query_len, np.uint32)
+        me = np.ascontiguousarray(max_edits, np.uint32)
+        n = len(ats)
+        if not (len(atl) == len(arc) == len(aql) == len(aen) == len(c0) == len(c1) == len(qs) == len(ql) == len(me) == n):
+            raise ValueError("one entry per job in every array")
+        _check(lib().bmv_rescue(self._h, _p(r, _u8p), len(r), _p(ats, _u64p), _p(atl, _u32p), _p(arc, _u8p), _p(aql, _u32p),
+                                _p(aen, _u32p), _p(c0, _u64p), _p(c1, _u64p), _p(qs, _u64p), _p(ql, _u32p), _p(me, _u32p), n,
+                                int(min_frag), int(max_frag)))
+        ts, tl, trc = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint8)
+        edits, end, proper = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint8)
+        _check(lib().bmv_rescued(self._h, _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(edits, _u32p), _p(end, _u32p),
+                                 _p(proper, _u8p)))
+        return {"text_start": ts[:n], "text_len": tl[:n], "text_rc": trc[:n], "edits": edits[:n], "end": end[:n],
+                "proper": proper[:n]}
+
+    def rescue_stats(self) -> dict:
+        """Of the last rescue: the kernels' ms, the cells they stand for and the parts a job was cut into."""
+        ms, cells, parts = C.c_float(), C.c_uint64(), C.c_uint32()
+        _check(lib().bmv_last_rescue_stats(self._h, C.byref(ms), C.byref(cells), C.byref(parts)))
+        return {"ms_kernels": ms.value, "cells": cells.value, "parts": parts.value}
 
     def pair_stats(self) -> dict:
         """Of the last pair or align_paired: the pair kernel's ms and the combinations it examined."""

@@ -184,6 +184,52 @@ int  bmv_align_paired(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes,
                       uint32_t n, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
                       const uint32_t *contig, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar);
 
+/* Mate rescue: a mate without a usable candidate (a repeat whose bucket list was cleared, k-mers that failed the quality filter,
+ * a wrong bucket) is sought beside a known alignment of its partner.  A call of its own, like bmv_pair, bmv_annotate and
+ * bmv_clip.  A batch holds n JOBS; job j places one mate, the query reads[query_start[j], +query_len[j]), beside an ANCHOR: a
+ * known alignment of its partner given as bmv_pair takes one -- the view anchor_text_start / anchor_text_len / anchor_text_rc,
+ * anchor_query_len and anchor_end -- on the contig [contig_start[j], contig_end[j]) of the concatenated genome.
+ * The window is derived on the device in signed 64-bit genome coordinates.  L, R and proper are exactly bmv_pair's; La, Ra are
+ * the anchor's by bmv_pair's two formulas.  With m = query_len[j], k = min(max_edits[j], m) and [c0, c1) the contig:
+ *   anchor forward      the mate is sought on the reverse strand (out_text_rc = 1); its admissible LEFT end is x in [x_lo, x_hi],
+ *                       x_lo = max(La, Ra - m, La + min_frag - m), x_hi = La + max_frag - m;
+ *                       the view is [ws, we), ws = max(c0, x_lo), we = min(c1, x_hi + m + k)
+ *   anchor reverse      the mate is sought forward (out_text_rc = 0); its admissible RIGHT end is z in [z_lo, z_hi],
+ *                       z_lo = Ra + m - max_frag, z_hi = min(La + m, Ra, Ra + m - min_frag);
+ *                       ws = max(c0, z_lo - m - k), we = min(c1, z_hi)
+ *   out_text_start = ws, out_text_len = max(0, we - ws)
+ * The far border of the view, as the aligner walks it, is the last admissible end, and there is room for m + k columns before
+ * the first admissible one: every alignment within k edits that ends admissibly lies inside the view, unless the contig cuts
+ * it, and there the cut is right.
+ * The result is exact and states no heuristic.  With (score, begin, CIGAR) what bmv_align_long returns for the query against
+ * the view, d = -score and end = begin + R (tie rule (1)): out_edits[j] = d and out_end[j] = end when d <= k, else BMV_BEYOND
+ * and 0; an empty view, m = 0 and a view shorter than m - k are all BMV_BEYOND.  out_proper[j] is bmv_pair's proper(anchor,
+ * rescued) evaluated on the rescued view and out_end, 0 when beyond.  A best placement that ends before the first admissible
+ * end is reported with its distance and proper = 0; the caller does not use it.
+ * Checks before anything runs (BMV_ERR_ARG, the message names the job, the context stays usable): min_frag <= max_frag;
+ * contig_start <= contig_end <= the genome's length; anchor_end <= anchor_text_len; the anchor's view inside the genome and
+ * anchor_text_start below 2^62; the query inside `reads`; max_frag + k below 2^32 (what a view may hold).  n = 0 is fine.  The
+ * call leaves untouched what bmv_results, bmv_best, bmv_pairs, bmv_annotations, bmv_clipped and their stats calls return.
+ * How (bmv_rescue.hip.h): a plan kernel writes the views; the distance kernel keeps every word of a query of up to 512 bases in
+ * one lane and runs the plain recurrence over the whole view (row 0 is free and the placement unknown: there is no band to
+ * keep), watching row m for a score <= k; a job is cut along the text into `parts` (a power of two, 1 .. 64) in neighbouring
+ * lanes, part p walking from max(0, b_p - m - k) with b_p = floor(p n / parts) and counting end columns in (b_p, b_{p+1}] --
+ * exact, because an alignment within k edits that ends at e begins at or after e - m - k -- and the parts' minima meet by
+ * shuffles, the later column winning a tie; a finish kernel applies the rule.  The host picks `parts` per call from the job
+ * count and the device's resident lanes, no part shorter than its warm-up (BMV_RESCUE_PARTS=<n> forces it: tests,
+ * experiments).  A query of more than 512 bases is aligned in full on its planned view: time, never a refusal. */
+int  bmv_rescue(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *anchor_text_start,
+                const uint32_t *anchor_text_len, const uint8_t *anchor_text_rc, const uint32_t *anchor_query_len,
+                const uint32_t *anchor_end, const uint64_t *contig_start, const uint64_t *contig_end, const uint64_t *query_start,
+                const uint32_t *query_len, const uint32_t *max_edits, uint32_t n, uint32_t min_frag, uint32_t max_frag);
+/* Of the last bmv_rescue: n entries each; any pointer may be NULL. */
+int  bmv_rescued(bmv_ctx *ctx, uint64_t *out_text_start, uint32_t *out_text_len, uint8_t *out_text_rc, uint32_t *out_edits,
+                 uint32_t *out_end, uint8_t *out_proper);
+/* Of the last bmv_rescue: the kernels' time in ms (plan, distance, finish, and the aligner's for queries beyond 512 bases), 64 x
+ * the (64-row word, text column) steps of the distance kernel -- warm-up columns included -- plus query_len x text_len of what
+ * the aligner took, and the parts a job was cut into.  Any pointer may be NULL. */
+int  bmv_last_rescue_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells, uint32_t *parts);
+
 /* Results of the last bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best or bmv_align_paired:
  *   out_score[a]        alignment.score() = -(edit distance)                       (bucket_locator.h:570)
  *   out_begin[a]        alignment.sequence1_begin_position(), 0-based in the text  (:576)

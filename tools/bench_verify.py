@@ -8,6 +8,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py --clip [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --best [--groups 20000 --len 10000 --text-len 11001] [--groups 200000 --len 300 --text-len 307]
     python tools/bench_verify.py --paired [--pairs 500000 --len 300]
+    python tools/bench_verify.py --rescue [--rescue-jobs 500000,4000 --rescue-len 150]
 
 Prints one JSON line: alignments/s and cell updates/s of the device kernels (HIP events inside bmv_align),
 the wall time of the call (host buffers in, results out), and the CPU restatement (oracle, full DP matrix,
@@ -262,8 +263,78 @@ def paired_main(args):
         "checks": {"first_pairs_identical_to_select_pairs": bool(ok)}}), flush=True)
 
 
+def rescue_main(args):
+    """Verifier.rescue on jobs of --rescue-len-base mates under the range 1,1000 and max_edits = 0.1 x len: the anchor at a random
+    place of a random genome, on either strand, the mate sampled from the other end of a fragment of 2 x len .. 900 bases with
+    substitutions at --sub.  Per job count of --rescue-jobs: the kernels' ms with the job cut into one part
+    (BMV_RESCUE_PARTS=1) and into the host's own choice of parts, and beside them Verifier.align_bounded on the same views under
+    the same bounds.  The results of the two rescue runs are held against each other and against align_bounded's scores.  One
+    JSON line per job count."""
+    from bucket_map_amd import verify
+
+    rng = np.random.default_rng(20251106)
+    m = args.rescue_len
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    genome = bases[rng.integers(0, 4, 64 << 20, dtype=np.uint8)]
+    v = verify.Verifier()
+    v.load_genome(genome)
+    for J in [int(x) for x in args.rescue_jobs.split(",")]:
+        frag = rng.integers(2 * m, 901, J)
+        left = rng.integers(2_000, len(genome) - 4_000, J)
+        anchor_rc = (np.arange(J) % 2).astype(np.uint8)         # the anchor is the reverse read: the mate lies at the left end
+        mate_at = np.where(anchor_rc != 0, left, left + frag - m)
+        anchor_at = np.where(anchor_rc != 0, left + frag - m, left)
+        reads = genome[mate_at[:, None] + np.arange(m)[None, :]]
+        reads[anchor_rc == 0] = comp[reads[anchor_rc == 0]][:, ::-1]
+        hit = rng.random(reads.shape) < args.sub
+        reads[hit] = bases[rng.integers(0, 4, int(hit.sum()))]
+        ats = (anchor_at - 3).astype(np.uint64)                 # the anchor's view: 3 bases of slack either side
+        atl = np.full(J, m + 7, np.uint32)
+        aend = np.where(anchor_rc != 0, m + 4, m + 3).astype(np.uint32)
+        jobs = (reads.reshape(-1), ats, atl, anchor_rc, np.full(J, m, np.uint32), aend, np.zeros(J, np.uint64),
+                np.full(J, len(genome), np.uint64), np.arange(J, dtype=np.uint64) * m, np.full(J, m, np.uint32),
+                np.full(J, m // 10, np.uint32))
+        runs = {}
+        for name, forced in (("one_part", "1"), ("host_choice", None)):
+            if forced is None:
+                os.environ.pop("BMV_RESCUE_PARTS", None)
+            else:
+                os.environ["BMV_RESCUE_PARTS"] = forced
+            ms, wall = [], []
+            for _ in range(args.repeat):
+                t0 = time.perf_counter()
+                got = v.rescue(*jobs, 1, 1000)
+                wall.append(time.perf_counter() - t0)
+                ms.append(v.rescue_stats()["ms_kernels"])
+            runs[name] = {"ms_kernels": ms, "wall_s": wall, "parts": v.rescue_stats()["parts"], "cells": v.rescue_stats()["cells"], "got": got}
+        os.environ.pop("BMV_RESCUE_PARTS", None)
+        one, own = runs["one_part"].pop("got"), runs["host_choice"].pop("got")
+        same = all(np.array_equal(one[k], own[k]) for k in one)
+        views = (jobs[0], own["text_start"], own["text_len"], own["text_rc"], jobs[8], jobs[9])
+        b_ms, b_wall = [], []
+        for _ in range(args.repeat):
+            t0 = time.perf_counter()
+            score, _, _, _ = v.align_bounded(*views, jobs[10])
+            b_wall.append(time.perf_counter() - t0)
+            b_ms.append(v.stats()["ms_kernels"])
+        d = np.where(score == verify.REJECTED, verify.BEYOND, -score.astype(np.int64)).astype(np.uint32)
+        print(json.dumps({
+            "metric": f"bmv_rescue kernels ms, {J} jobs", "value": min(runs["host_choice"]["ms_kernels"]), "unit": "ms",
+            "config": {"jobs": J, "query_len": m, "max_edits": m // 10, "frag_range": [1, 1000], "mean_view_len": float(own["text_len"].mean())},
+            "rescue_one_part": runs["one_part"], "rescue_host_choice": runs["host_choice"],
+            "align_bounded_same_views": {"ms_kernels": b_ms, "wall_s": b_wall},
+            "rescued_share": float((own["edits"] != verify.BEYOND).mean()), "proper_share": float(own["proper"].mean()),
+            "checks": {"parts_do_not_change_the_results": bool(same), "edits_equal_align_bounded": bool(np.array_equal(d, own["edits"]))}}),
+            flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rescue", action="store_true", help="Verifier.rescue beside Verifier.align_bounded on the same views (see rescue_main)")
+    ap.add_argument("--rescue-jobs", default="500000,4000", help="--rescue: the job counts, one run each")
+    ap.add_argument("--rescue-len", type=int, default=150, help="--rescue: the mates' length")
     ap.add_argument("--paired", action="store_true", help="Verifier.align_paired beside Verifier.align_best (see paired_main)")
     ap.add_argument("--pairs", type=int, default=500_000)
     ap.add_argument("--best", action="store_true", help="Verifier.align_best on groups of five candidates (see best_main)")
@@ -303,6 +374,8 @@ def main():
         return best_main(args)
     if args.paired:
         return paired_main(args)
+    if args.rescue:
+        return rescue_main(args)
 
     rng = np.random.default_rng(20240003)
     m = args.len
