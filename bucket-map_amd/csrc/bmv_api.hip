@@ -14,6 +14,7 @@
 #include "bmv_clip.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_pair.hip.h"
+#include "bmv_realign.hip.h"
 #include "bmv_rescue.hip.h"
 #include "bmv_screen.hip.h"
 
@@ -224,6 +225,19 @@ struct bmv_ctx {
     uint64_t rs_cells = 0;
     uint32_t rs_parts = 1;
     uint32_t resident_lanes = 0;                // what the device keeps in flight at once (bmv_create)
+    // bmv_realign: the plan per alignment, the direction codes and reversed entries of a piece, the outputs (the inputs go
+    // through bmv_annotate's buffers), the host results of bmv_realigned and what bmv_last_realign_stats reports
+    DevBuf<uint8_t> ra_pass, ra_codes;
+    DevBuf<uint64_t> ra_row_at, ra_ops_at, ra_offset;
+    DevBuf<uint32_t> ra_ops_rev, ra_begin, ra_end_lane, ra_nops, ra_cigar;
+    DevBuf<int32_t> ra_score;
+    std::vector<int32_t> h_ra_score;
+    std::vector<uint32_t> h_ra_begin, h_ra_cigar;
+    std::vector<uint8_t> h_ra_realigned;
+    std::vector<uint64_t> h_ra_offset;
+    float ms_realign = 0.f;
+    uint64_t ra_cells = 0;
+    uint32_t ra_passed = 0;
 };
 
 namespace {
@@ -2115,6 +2129,205 @@ int bmv_last_clip_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_last_clip_stats: null context");
     if (ms_kernels) *ms_kernels = c->h_cl.ms;
     if (n_columns) *n_columns = c->h_cl.n_columns;
+    return BMV_OK;
+}
+
+// The realignment pass (include/bmv.h, bmv_realign.hip.h): bmv_annotate's checks and upload; the plan -- which alignments
+// are passed through, the score bound, every realigned alignment's place in the scratch -- is made on the host from the
+// entries it has just validated; the batch is taken in pieces whose direction codes and reversed entries fit the scratch:
+// forward kernel, traceback, a 64-bit exclusive sum of the entry counts, the gather, the piece's entries to the host.
+int bmv_realign(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t mismatch, uint32_t gap_open,
+                uint32_t gap_extend, uint32_t band, uint64_t *total_cigar) {
+    if (!c || !total_cigar) return fail(BMV_ERR_ARG, "bmv_realign: null argument");
+    for (const uint32_t s : {match, mismatch, gap_open, gap_extend})
+        if (s < 1u || s > 1024u)
+            return fail(BMV_ERR_ARG, "bmv_realign: match, mismatch, gap_open and gap_extend must be in 1..1024 (got %u, %u, %u and %u)", match,
+                        mismatch, gap_open, gap_extend);
+    if (band < 1u || band > 31u) return fail(BMV_ERR_ARG, "bmv_realign: band must be in 1..31 (got %u)", band);
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_realign", v, true, begin && cigar_offset)) return rc;
+    uint64_t columns = 0;
+    if (const int rc = check_annotate_batch(c, "bmv_realign", v, begin, cigar_offset, cigar, &columns)) return rc;
+    // the plan: pass-through, the 32-bit bound, the scratch of every realigned alignment
+    const uint64_t widest = std::max(match, std::max(mismatch, gap_extend)), in_m = std::max(match, mismatch), cap = 63u - 2u * band;
+    const uint64_t budget = c->scratch_bytes;
+    std::vector<uint8_t> pass(n, 0);
+    std::vector<uint64_t> need(n, 0);                           // bytes of scratch
+    uint64_t cells = 0;
+    uint32_t n_passed = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        const uint64_t c0 = cigar_offset[a], c1 = cigar_offset[a + 1];
+        if (c0 == c1) {
+            pass[a] = 1;
+            n_passed++;
+            continue;
+        }
+        const uint64_t m = query_len[a];
+        uint64_t path = 0;                                      // what the given path can cost at most
+        for (uint64_t x = c0; x < c1; x++) {
+            const uint64_t len = cigar[x] >> 4;
+            if ((cigar[x] & 15u) == BMV_OP_M) {
+                path += len * in_m;
+            } else {
+                path += gap_open + len * gap_extend;
+                if ((cigar[x] & 15u) == BMV_OP_D && len > cap) pass[a] = 1;
+            }
+        }
+        const uint64_t both = m + text_len[a];
+        if (both * widest + gap_open >= (1ull << 30) || path + gap_open + both * gap_extend >= (1ull << 30))
+            return fail(BMV_ERR_UNSUPPORTED, "alignment %u: a query of %u bases against %u text bases (%llu CIGAR entries) under these scores does not fit 32-bit arithmetic",
+                        a, query_len[a], text_len[a], (unsigned long long)(c1 - c0));
+        if (pass[a]) {
+            n_passed++;
+            continue;
+        }
+        need[a] = m * 64u + (2u * m + 2u) * 4u;
+        cells += 64u * m;
+        if (need[a] > budget)
+            return fail(BMV_ERR_UNSUPPORTED, "alignment %u: a query of %u bases needs %llu bytes of direction codes; the scratch holds %llu (BMV_SCRATCH_MB)",
+                        a, query_len[a], (unsigned long long)need[a], (unsigned long long)budget);
+    }
+    c->h_ra_score.assign(n, 0);
+    c->h_ra_begin.assign(n, 0);
+    c->h_ra_realigned.assign(n, 0);
+    c->h_ra_offset.assign((size_t)n + 1, 0);
+    c->h_ra_cigar.clear();
+    c->ms_realign = 0.f;
+    c->ra_cells = cells;
+    c->ra_passed = n_passed;
+    *total_cigar = 0;
+    if (n == 0) return BMV_OK;
+
+    // pieces that fit the scratch; a realigned alignment's rows and reversed entries counted from its piece's first
+    std::vector<uint32_t> piece_at{0};
+    std::vector<uint64_t> row_at(n, 0), ops_at(n, 0);
+    uint64_t max_rows = 0, max_ops = 0;
+    {
+        uint64_t bytes = 0, rows = 0, ops = 0;
+        for (uint32_t a = 0; a < n; a++) {
+            if (bytes + need[a] > budget) {
+                piece_at.push_back(a);
+                bytes = rows = ops = 0;
+            }
+            row_at[a] = rows;
+            ops_at[a] = ops;
+            if (!pass[a]) {
+                rows += query_len[a];
+                ops += 2u * (uint64_t)query_len[a] + 2u;
+            }
+            bytes += need[a];
+            max_rows = std::max(max_rows, rows);
+            max_ops = std::max(max_ops, ops);
+        }
+        piece_at.push_back(n);
+    }
+    bmv::AnnotateJob in{};
+    std::vector<uint64_t> rebased;
+    if (const int rc = upload_annotate_batch(c, v, begin, cigar_offset, cigar, rebased, in)) return rc;
+    HIP_TRY(need_exact_all(n, c->ra_pass, c->ra_row_at, c->ra_ops_at, c->ra_score, c->ra_begin, c->ra_end_lane, c->ra_nops));
+    HIP_TRY(c->ra_offset.need_exact((size_t)n + 1u));
+    HIP_TRY(c->ra_codes.need_exact(with_headroom((size_t)max_rows * 64u, c->ra_codes.cap)));
+    HIP_TRY(c->ra_ops_rev.need_exact(with_headroom((size_t)max_ops, c->ra_ops_rev.cap)));
+    HIP_TRY(hipMemcpyAsync(c->ra_pass.p, pass.data(), n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ra_row_at.p, row_at.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ra_ops_at.p, ops_at.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    bmv::RealignJob j{};
+    j.genome = in.genome;
+    j.reads = in.reads;
+    j.text_start = in.text_start;
+    j.text_len = in.text_len;
+    j.text_rc = in.text_rc;
+    j.query_start = in.query_start;
+    j.query_len = in.query_len;
+    j.begin = in.begin;
+    j.cigar_offset = in.cigar_offset;
+    j.cigar = in.cigar;
+    j.pass = c->ra_pass.p;
+    j.row_at = c->ra_row_at.p;
+    j.ops_at = c->ra_ops_at.p;
+    j.match = (int32_t)match;
+    j.mismatch = (int32_t)mismatch;
+    j.open = (int32_t)gap_open;
+    j.ext = (int32_t)gap_extend;
+    j.band = band;
+    j.codes = c->ra_codes.p;
+    j.ops_rev = c->ra_ops_rev.p;
+    j.score = c->ra_score.p;
+    j.out_begin = c->ra_begin.p;
+    j.end_lane = c->ra_end_lane.p;
+    j.nops = c->ra_nops.p;
+    j.out_offset = c->ra_offset.p;
+    uint64_t *scan_tmp = reinterpret_cast<uint64_t *>(c->scan_tmp.p);
+    float ms_forward = 0.f, ms_trace = 0.f, ms_gather = 0.f;
+    std::vector<uint64_t> off;
+    for (size_t p = 0; p + 1 < piece_at.size(); p++) {
+        const uint32_t a0 = piece_at[p], cnt = piece_at[p + 1] - a0;
+        if (cnt == 0) continue;
+        j.first = a0;
+        j.count = cnt;
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        hipLaunchKernelGGL(bmv::bmv_realign_forward_kernel, dim3(cnt), dim3(64), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_forward += ms;
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        hipLaunchKernelGGL(bmv::bmv_realign_trace_kernel, dim3(cnt), dim3(64), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->ra_nops.p + a0, c->ra_offset.p, cnt, scan_tmp, c->stream));
+        off.resize((size_t)cnt + 1);
+        HIP_TRY(hipMemcpyAsync(off.data(), c->ra_offset.p, ((size_t)cnt + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_trace += ms;
+        const uint64_t n_entries = off[cnt], had = c->h_ra_cigar.size();
+        HIP_TRY(c->ra_cigar.need_exact(with_headroom((size_t)n_entries, c->ra_cigar.cap)));
+        j.out_cigar = c->ra_cigar.p;
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        hipLaunchKernelGGL(bmv::bmv_realign_gather_kernel, dim3((cnt + 31u) / 32u), dim3(256), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        c->h_ra_cigar.resize((size_t)(had + n_entries));
+        if (n_entries)
+            HIP_TRY(hipMemcpyAsync(c->h_ra_cigar.data() + had, c->ra_cigar.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_gather += ms;
+        for (uint32_t s = 0; s <= cnt; s++) c->h_ra_offset[(size_t)a0 + s] = had + off[s];
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_ra_score.data(), c->ra_score.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_ra_begin.data(), c->ra_begin.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t a = 0; a < n; a++) c->h_ra_realigned[a] = pass[a] ? 0 : 1;
+    c->ms_realign = ms_forward + ms_trace + ms_gather;
+    if (getenv("BMV_LOG_CLASSES"))
+        fprintf(stderr, "[bmv] realign: %u alignments (%u passed through) in %zu pieces, forward %.3f ms, traceback %.3f ms, scan and gather %.3f ms\n",
+                n, n_passed, piece_at.size() - 1, ms_forward, ms_trace, ms_gather);
+    *total_cigar = c->h_ra_cigar.size();
+    return BMV_OK;
+}
+
+int bmv_realigned(bmv_ctx *c, int32_t *out_score, uint32_t *out_begin, uint8_t *out_realigned, uint64_t *out_cigar_offset,
+                  uint32_t *out_cigar) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_realigned: null context");
+    copy_out(out_score, c->h_ra_score);
+    copy_out(out_begin, c->h_ra_begin);
+    copy_out(out_realigned, c->h_ra_realigned);
+    copy_out(out_cigar_offset, c->h_ra_offset);
+    copy_out(out_cigar, c->h_ra_cigar);
+    return BMV_OK;
+}
+
+int bmv_last_realign_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_cells, uint32_t *n_passed_through) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_realign_stats: null context");
+    if (ms_kernels) *ms_kernels = c->ms_realign;
+    if (n_cells) *n_cells = c->ra_cells;
+    if (n_passed_through) *n_passed_through = c->ra_passed;
     return BMV_OK;
 }
 

@@ -13,6 +13,7 @@
 // drops an exact hit at bucket offset 0, results are appended per read in bucket order.
 #pragma once
 
+#include "affine_realign.h"
 #include "best_mapq.h"
 #include "bm_genome.h"
 #include "mapper.h"
@@ -154,6 +155,20 @@ public:
         (void)reads; (void)n_read_bytes; (void)text_start; (void)text_len; (void)text_rc; (void)query_start; (void)query_len;
         (void)begin; (void)cigar_offset; (void)cigar; (void)n; (void)match; (void)penalty; (void)out;
         throw std::runtime_error("--clip: this build's alignment verifier has no clipping pass");
+    }
+    // The affine-gap realignment of alignments given with their begin and M/I/D CIGAR (bmv_realign's contract, include/bmv.h):
+    // per alignment the score, begin and entries of the best path inside the band that follows the given one, or -- passed
+    // through -- the given path with its affine score.  This default computes the contract on the host (affine_realign.h) and
+    // needs `genome`, the records back to back as the verifier's own copy lies; the GPU verifier realigns on the device
+    // (can_realign() true) and ignores it.
+    virtual bool can_realign() const { return false; }
+    virtual void realign(const uint8_t *genome, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                         const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                         const uint32_t *begin, const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n,
+                         const affine_scores &scores, realignment &out) {
+        (void)n_read_bytes;
+        affine::realign_on_host(genome, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, n, scores,
+                                out);
     }
     // The best alignment of every group (bmv_align_best's contract, include/bmv.h): group g owns the alignments
     // group_offset[g] .. group_offset[g + 1] - 1; with d = -score and end = begin + the M and D lengths, winner[g] is the lowest
@@ -444,6 +459,8 @@ private:
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
     uint32_t _clip_match = 1, _clip_penalty = 2;
+    bool _affine = false;                        // --affine: the written alignments realigned under affine gap costs, with AS
+    affine_scores _affine_scores{};
     float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
     bool _paired = false;                        // --paired: records 2p and 2p + 1 of the FASTQ file are mates, placed together
     uint32_t _min_frag = 1, _max_frag = 1000;    // --frag-range: what a proper pair spans, leftmost to rightmost base
@@ -666,6 +683,12 @@ public:
     // the search for the other mate (alignment_verifier::rescue) --, and a mate that comes back within bound and proper gets the
     // record of that placement, with its anchor's MAPQ, X0:i:1 and XR:i:1
     void set_rescue(float rate) { _rescue_rate = rate; }
+    // --affine: the --annotate layout, the written alignments through the verifier's realignment pass first (POS, CIGAR, NM and
+    // MD are the realigned path's; AS:i its affine score, unless --clip writes its own)
+    void set_affine(const affine_scores &scores) {
+        _affine = _annotate = true;
+        _affine_scores = scores;
+    }
     void set_clip(uint32_t match, uint32_t penalty) {
         _clip = _annotate = true;
         _clip_match = match;
@@ -981,6 +1004,7 @@ private:
             std::vector<int32_t> score;
             std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
             clipping ann;                        // (--clip fills score and the clips too)
+            std::vector<int32_t> affine_score;   // --affine: per slot of `ann` the realigned path's score
             unsigned int first_read = 0;
             std::exception_ptr failed;
         } blocks[2];
@@ -1005,7 +1029,7 @@ private:
         }
         // --annotate with a verifier that has no annotation pass (the oracle-backed test tools): sam_tags::annotate_on_host
         const bool annotate_here = _annotate && !_clip && !_v->can_annotate();
-        if (annotate_here && flat_genome_.empty())
+        if ((annotate_here || (_affine && !_v->can_realign())) && flat_genome_.empty())
             for (const auto &seq : genome_->seqs) flat_genome_.insert(flat_genome_.end(), seq.begin(), seq.end());
         auto is_written = [&](const Block &b, size_t a) {       // :570-573, and the edit bound
             const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
@@ -1133,6 +1157,15 @@ private:
                                   b.cigar.begin() + static_cast<ptrdiff_t>(b.cigar_offset[a + 1]));
                         co.push_back(cg.size());
                     }
+                    if (_affine) {                              // the realigned begin and entries take the edit path's place
+                        realignment ra;
+                        _v->realign(flat_genome_.data(), b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(),
+                                    bg.data(), co.data(), cg.data(), static_cast<uint32_t>(ts.size()), _affine_scores, ra);
+                        bg.swap(ra.begin);
+                        co.swap(ra.cigar_offset);
+                        cg.swap(ra.cigar);
+                        b.affine_score.swap(ra.score);
+                    }
                     if (_clip)
                         _v->clip(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
                                  co.data(), cg.data(), static_cast<uint32_t>(ts.size()), _clip_match, _clip_penalty, b.ann);
@@ -1216,6 +1249,9 @@ private:
                 if (_clip) {
                     tags += "\tAS:i:";
                     sam_tags::number(tags, static_cast<uint64_t>(b.ann.score[s]));
+                } else if (_affine) {
+                    tags += b.affine_score[s] < 0 ? "\tAS:i:-" : "\tAS:i:";
+                    sam_tags::number(tags, static_cast<uint64_t>(std::abs(static_cast<int64_t>(b.affine_score[s]))));
                 }
                 if (best) tags += "\t" + best_tag;
                 if (!last_tag.empty()) {

@@ -48,6 +48,12 @@ struct cmd_arguments {
                                   // its partner's alignment (mate rescue) and written with XR:i:1
     float rescue_rate = 0.1f;     // --rescue-rate R (implies --rescue): an anchor may have (uint32_t)(R * its length) edits, and so
                                   // may the rescued mate
+    bool affine = false;          // --affine (bucketmap_align): the written alignments are realigned under affine gap costs beside
+                                  // their edit path (bmv_realign); POS, CIGAR, NM and MD are the realigned path's, AS:i its score
+                                  // (implies --annotate)
+    unsigned int affine_match = 1, affine_mismatch = 4, affine_gap_open = 6, affine_gap_extend = 1;   // --affine-scores A,B,O,E
+                                  // (implies --affine), 1..1024 each; the default is the common short-read scale, a choice
+    unsigned int affine_band = 16;   // --affine-band W (implies --affine), 1..31: D entries of up to 63 - 2 W bases are realigned
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -198,7 +204,35 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.rescue_rate = r;
             a.rescue = true;
         }
+        else if (opt == "--affine") a.affine = true;
+        else if (opt == "--affine-scores") {
+            const std::string s = value();
+            unsigned long v[4] = {0, 0, 0, 0};
+            size_t pos = 0;
+            for (int f = 0; f < 4; f++) {
+                const size_t comma = f < 3 ? s.find(',', pos) : s.size();
+                if (comma == std::string::npos || (f == 3 && s.find(',', pos) != std::string::npos))
+                    throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be A,B,O,E such as 1,4,6,1.");
+                v[f] = as_uint(s.substr(pos, comma - pos));
+                if (v[f] < 1 || v[f] > 1024) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be four numbers in 1..1024.");
+                pos = comma + 1;
+            }
+            a.affine_match = static_cast<unsigned>(v[0]);
+            a.affine_mismatch = static_cast<unsigned>(v[1]);
+            a.affine_gap_open = static_cast<unsigned>(v[2]);
+            a.affine_gap_extend = static_cast<unsigned>(v[3]);
+            a.affine = true;
+        }
+        else if (opt == "--affine-band") {
+            const std::string s = value();
+            const unsigned long w = as_uint(s);
+            if (w < 1 || w > 31) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in 1..31.");
+            a.affine_band = static_cast<unsigned>(w);
+            a.affine = true;
+        }
 #else
+        else if (opt == "--affine" || opt == "--affine-scores" || opt == "--affine-band")
+            throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has nothing to realign.");
         else if (opt == "--paired" || opt == "--frag-range" || opt == "--rescue" || opt == "--rescue-rate")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it cannot place mates together.");
 #endif
@@ -228,6 +262,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (!have_indicator) throw parser_error("Option -i/--index-indicator is required but not set.");
     if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;
+    if (a.affine) a.annotate = true;
     return a;
 }
 

@@ -214,6 +214,46 @@ public:
                   penalty);
     }
 
+    // bmv_realign per device: the same cut, the results stitched as run() stitches the aligners'
+    bool can_realign() const override { return true; }
+    void realign(const uint8_t *, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                 const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                 const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, const affine_scores &sc, realignment &out) override {
+        const size_t D = ctx_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        const batch all{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+        out.score.assign(n, 0);
+        out.begin.assign(n, 0);
+        out.realigned.assign(n, 0);
+        out.cigar_offset.assign(static_cast<size_t>(n) + 1, 0);
+        const std::vector<uint32_t> cut = cut_by_cost(n, D, [&](uint32_t a) { return static_cast<uint64_t>(query_len[a]) + 1u; });
+        std::vector<uint64_t> total(D, 0), cells(D, 0);
+        std::vector<float> ms(D, 0.f);
+        std::vector<uint32_t> passed(D, 0);
+        for_each_device(D, [&](size_t d) {
+            if (cut[d + 1] == cut[d]) return;
+            const share s = slice(all, cut[d], cut[d + 1] - cut[d]);
+            check(bmv_realign(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, begin + s.a0,
+                              cigar_offset + s.a0, cigar, s.n, sc.match, sc.mismatch, sc.gap_open, sc.gap_extend, sc.band, &total[d]),
+                  "the GPU realignment pass failed: ");
+            bmv_last_realign_stats(ctx_[d], &ms[d], &cells[d], &passed[d]);
+        });
+        const std::vector<uint64_t> at = starts(total);
+        out.cigar.assign(at[D], 0);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
+            if (m == 0) return;
+            std::vector<uint64_t> off(static_cast<size_t>(m) + 1);
+            check(bmv_realigned(ctx_[d], out.score.data() + a0, out.begin.data() + a0, out.realigned.data() + a0, off.data(),
+                                out.cigar.data() + at[d]),
+                  "reading the realigned alignments failed: ");
+            stitch(out.cigar_offset, a0, m, off, at[d]);
+        });
+        out.cigar_offset[n] = at[D];
+        std::cerr << "[BENCHMARK]\tGPU affine realignment: " << n << " alignments, " << sum(cells) << " band cells, " << sum(passed)
+                  << " passed through; " << timing(ms, t0);
+    }
+
     // bmv_rescue per device: the jobs -- independent of each other -- in contiguous ranges of equal cost, each device handed
     // the span of the read buffer its queries cover
     void rescue(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *anchor_text_start, const uint32_t *anchor_text_len,

@@ -60,6 +60,10 @@ SYMBOLS = {
                            C.c_uint32, C.c_uint32, _u64p, _u64p]),
     "bmv_clipped": (C.c_int, [C.c_void_p, _i64p, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p, _u64p, _u8p]),
     "bmv_last_clip_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
+    "bmv_realign": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32,
+                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+    "bmv_realigned": (C.c_int, [C.c_void_p, _i32p, _u32p, _u8p, _u64p, _u32p]),
+    "bmv_last_realign_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p, _u32p]),
 }
 _ready = False
 
@@ -582,6 +586,31 @@ class Verifier:
         ms, cols = C.c_float(), C.c_uint64()
         _check(lib().bmv_last_clip_stats(self._h, C.byref(ms), C.byref(cols)))
         return {"ms_kernels": ms.value, "columns": cols.value}
+
+    def realign(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, match=1,
+                mismatch=4, gap_open=6, gap_extend=1, band=16) -> dict:
+        """bmv_realign on the alignments annotate takes: each is aligned again under affine gap costs inside the band of
+        `band` columns either side of its given path (include/bmv.h: the contract); one with a D entry longer than
+        63 - 2 band, or with an empty CIGAR, is passed through with the given path's affine score.  Returns a dict: score
+        i32[n], begin u32[n], realigned u8[n], cigar_offset u64[n+1], cigar u32[..] -- the shape of align's results, ready
+        for annotate or clip.  Leaves the results of every other call untouched."""
+        _keep, n, args = self._annotate_args(reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset,
+                                             cigar)
+        total = C.c_uint64()
+        _check(lib().bmv_realign(self._h, *args, int(match), int(mismatch), int(gap_open), int(gap_extend), int(band),
+                                 C.byref(total)))
+        score, out_begin, flag = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        off = np.zeros(n + 1, np.uint64)
+        cg = np.zeros(max(total.value, 1), np.uint32)
+        _check(lib().bmv_realigned(self._h, _p(score, _i32p), _p(out_begin, _u32p), _p(flag, _u8p), _p(off, _u64p), _p(cg, _u32p)))
+        return {"score": score, "begin": out_begin, "realigned": flag, "cigar_offset": off, "cigar": cg[: total.value]}
+
+    def realign_stats(self) -> dict:
+        """Of the last realign: kernel ms (forward, traceback, scan and gather), 64 x the query rows of the realigned
+        alignments, and the alignments passed through."""
+        ms, cells, passed = C.c_float(), C.c_uint64(), C.c_uint32()
+        _check(lib().bmv_last_realign_stats(self._h, C.byref(ms), C.byref(cells), C.byref(passed)))
+        return {"ms_kernels": ms.value, "cells": cells.value, "n_passed_through": passed.value}
 
     def stats(self) -> dict:
         ms, cells = C.c_float(), C.c_uint64()

@@ -316,6 +316,62 @@ int  bmv_clipped(bmv_ctx *ctx, int64_t *out_score, uint32_t *out_clip_left, uint
  * (sum of all CIGAR entry lengths). */
 int  bmv_last_clip_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_columns);
 
+/* The realignment pass: an affine-gap alignment beside a known edit path.  Everything the aligners return comes from unit
+ * costs, under which a 6-base deletion and six scattered 1-base gaps cost the same, so the traceback's tie rules decide where
+ * indels fall; consumers of SAM assume gap-affine alignments and an AS:i on a match / mismatch / gap-open / gap-extend scale.
+ * A full Gotoh matrix is out of the question, but the affine optimum lies near the edit path we hold: this post-pass runs the
+ * recurrence in a band of at most 64 columns that follows that path.  A call of its own, of the bmv_annotate / bmv_clip family:
+ * the same inputs (the views, begin, M/I/D entries 5' to 3' of the query, begin counted in the text as the aligner saw it) and
+ * the same checks on the host before anything is launched (BMV_ERR_ARG, the message names the alignment, nothing ran, the
+ * context stays usable); in addition 1 <= match, mismatch, gap_open, gap_extend <= 1024 and 1 <= band <= 31, else BMV_ERR_ARG;
+ * and, so that the kernel can work in 32 bits, per alignment with a non-empty CIGAR
+ *   (query_len + text_len) * max(match, mismatch, gap_extend) + gap_open < 2^30, and
+ *   the given path's own worst case -- max(match, mismatch) per M column, gap_open + L gap_extend per I or D entry of length L --
+ *   + gap_open + (query_len + text_len) * gap_extend < 2^30 (it bounds every cell of the band from below),
+ * else BMV_ERR_UNSUPPORTED, the message names the alignment.  The call leaves untouched what every other result or stats call
+ * returns.  The output (bmv_realigned) has the shape of bmv_results, so it can be handed straight to bmv_annotate or bmv_clip.
+ * The contract is exact and stated on the outputs only.  m = query_len, n = text_len, w = band; T is the text as the aligner
+ * saw it (reverse-complemented for text_rc != 0); equality is on dna4 ranks on both sides, as in bmv_annotate; cells are (i, j),
+ * 0 <= i <= m, 0 <= j <= n.
+ *   the given path     starts at (0, begin); an M column moves (+1, +1), I moves (+1, 0), D moves (0, +1).  p(i) is the first
+ *                      column the path visits in row i, q(i) the last
+ *   the band           row i holds the columns [max(0, p(i) - w), min(n, q(i) + w)]; everything else is absent.  An absent
+ *                      operand never wins a maximum; a cell all of whose operands are absent is absent
+ *   pass-through       if any row has q(i) - p(i) > 63 - 2w -- a D entry longer than 63 - 2w -- the alignment is not realigned,
+ *                      and neither is one with an empty CIGAR: out_realigned = 0, begin and the entries are returned as given,
+ *                      out_score is the affine score of the given path: +match per equal M column, -mismatch per unequal one,
+ *                      -(gap_open + L gap_extend) per I or D entry of length L (an empty CIGAR: score 0, no entries).
+ *                      Otherwise every row's band is at most 64 columns and out_realigned = 1
+ *   recurrence         s(i, j) = +match if query[i - 1] equals T[j - 1], else -mismatch  (i >= 1)
+ *                      H(0, j) = 0 on row 0's band; Ins(0, .) and Del(0, .) are absent
+ *                      Ins(i, j) = max(H(i - 1, j) - gap_open - gap_extend, Ins(i - 1, j) - gap_extend)
+ *                      Del(i, j) = max(H(i, j - 1) - gap_open - gap_extend, Del(i, j - 1) - gap_extend)
+ *                      H(i, j)   = max(H(i - 1, j - 1) + s(i, j), Ins(i, j), Del(i, j))
+ *   out_score          the maximum of H(m, j) over row m's band; the alignment ends at the LAST column that attains it (tie
+ *                      rule (1) above).  The given path lies inside the band, so out_score >= the given path's affine score
+ *   traceback          in H the order is diagonal, then Ins, then Del (tie rule (2)); in Ins and in Del a tie goes to "open",
+ *                      the shorter gap.  The walk stops when it reaches row 0 in state H; that column is out_begin.  Entries
+ *                      are M / I / D, 5' to 3' of the query, adjacent entries never share an op; a result never begins or ends
+ *                      with D
+ * Under these rules gaps in a repeat are pushed towards the START of the text AS THE ALIGNER SAW IT -- for text_rc != 0 that is
+ * the right end on the forward strand.  Normalising them on the forward strand is not part of this pass.
+ * The scores are a choice of the caller (the tool's default 1, 4, 6, 1 is the common short-read scale, not a measurement).
+ * How (bmv_realign.hip.h): a wave per alignment, a lane per band column, the wave stepping row by row along the CIGAR; the Del
+ * chain of a row by a prefix maximum across the lanes; a byte of direction codes per cell to the scratch, the batch taken in
+ * pieces that fit it (BMV_SCRATCH_MB applies; an alignment whose codes alone do not fit fails the call with
+ * BMV_ERR_UNSUPPORTED before anything runs); the traceback walks the codes 64 rows at a time out of LDS. */
+int  bmv_realign(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                 const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                 const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint32_t match, uint32_t mismatch,
+                 uint32_t gap_open, uint32_t gap_extend, uint32_t band, uint64_t *total_cigar);
+/* Results of the last bmv_realign: n entries each, out_cigar_offset n + 1, out_cigar total_cigar; any pointer may be NULL. */
+int  bmv_realigned(bmv_ctx *ctx, int32_t *out_score, uint32_t *out_begin, uint8_t *out_realigned, uint64_t *out_cigar_offset,
+                   uint32_t *out_cigar);
+/* Of the last bmv_realign: the kernels' time in ms (forward, traceback, scan and gather, all pieces), 64 x the query rows of
+ * the realigned alignments (the lanes a wave steps through, whatever the band), and the alignments passed through.  Any
+ * pointer may be NULL. */
+int  bmv_last_realign_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells, uint32_t *n_passed_through);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py --long [--long-reads 1000] [--long-len 100000]
     python tools/bench_verify.py --annotate [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --clip [--reads 20000 --len 10000 --indel-rate 0.1]
+    python tools/bench_verify.py --realign [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --best [--groups 20000 --len 10000 --text-len 11001] [--groups 200000 --len 300 --text-len 307]
     python tools/bench_verify.py --paired [--pairs 500000 --len 300]
     python tools/bench_verify.py --rescue [--rescue-jobs 500000,4000 --rescue-len 150]
@@ -359,6 +360,10 @@ def main():
                     help="also run Verifier.clip (match 1, penalty 2) and Verifier.annotate on the batch's results: the clipping "
                          "pass's kernels ms of every repeat, the columns walked, and the ratios to annotate's and to align's "
                          "kernels ms on the same batch")
+    ap.add_argument("--realign", action="store_true",
+                    help="also run Verifier.realign (scores 1,4,6,1, band 16) on the batch's results: the pass's kernels ms of every "
+                         "repeat with forward and traceback apart (the library's BMV_LOG_CLASSES line), band cells / time, and the "
+                         "ratio to align's kernels ms on the same batch")
     ap.add_argument("--decoys", type=float, default=0.0, metavar="F",
                     help="this share of the alignments takes its text window from an unrelated place (a wrong locus)")
     ap.add_argument("--long", action="store_true", help="Verifier.align_long on reads beyond 65 536 bases (see above)")
@@ -474,6 +479,40 @@ def main():
                 "checks": {"queries_are_covered": bool(by_op([4, 7, 8, 1]) == int(ql[np.diff(off.astype(np.int64)) > 0].sum())),
                            "scores_add_up": bool(int(got["score"].sum()) == by_op([7]) - 2 * int(got["nm"].sum()))}}
 
+    realign = None
+    if args.realign:
+        import re
+        import tempfile
+        r_ms, r_wall, r_parts = [], [], []
+        os.environ["BMV_LOG_CLASSES"] = "1"
+        for _ in range(args.repeat):
+            sys.stderr.flush()
+            with tempfile.TemporaryFile() as log:              # the library's own line, written to file descriptor 2
+                keep = os.dup(2)
+                os.dup2(log.fileno(), 2)
+                try:
+                    t0 = time.perf_counter()
+                    got = v.realign(reads, start, tl, rc, qs, ql, begin, off, cg)
+                    r_wall.append(time.perf_counter() - t0)
+                finally:
+                    os.dup2(keep, 2)
+                    os.close(keep)
+                log.seek(0)
+                line = log.read().decode(errors="replace")
+            found = re.search(r"forward ([0-9.]+) ms, traceback ([0-9.]+) ms, scan and gather ([0-9.]+) ms", line)
+            r_parts.append([float(x) for x in found.groups()] if found else None)
+            rst = v.realign_stats()
+            r_ms.append(rst["ms_kernels"])
+        del os.environ["BMV_LOG_CLASSES"]
+        lens = np.diff(got["cigar_offset"].astype(np.int64))
+        realign = {"ms_kernels_realign": r_ms, "ms_forward_traceback_gather": r_parts, "ms_kernels_align": all_ms,
+                   "wall_s_realign": r_wall, "band_cells": rst["cells"], "band_cells_per_s": rst["cells"] / (min(r_ms) * 1e-3),
+                   "passed_through": rst["n_passed_through"], "spread": (max(r_ms) - min(r_ms)) / min(r_ms),
+                   "realign_over_align": min(r_ms) / min(all_ms), "cigar_entries": int(len(got["cigar"])),
+                   "changed_cigars": int((lens != np.diff(off.astype(np.int64))).sum()),
+                   "checks": {"all_realigned": bool(got["realigned"].all() or rst["n_passed_through"] > 0),
+                              "score_at_least_the_edit_bound": bool((got["score"].astype(np.int64) >= ql.astype(np.int64) + 12 * score.astype(np.int64)).all())}}
+
     ns = min(args.cpu_sample, args.reads)
     same, cpu = None, None
     if ns > 0:                                         # (--cpu-sample 0: no oracle in the process at all -- bench.py's leg)
@@ -493,6 +532,7 @@ def main():
         "bounded": bounded,
         "annotate": annotate,
         "clip": clip,
+        "realign": realign,
         "checks": {"sample_identical_to_oracle": same},
     }))
 
