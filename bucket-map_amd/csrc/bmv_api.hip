@@ -12,6 +12,7 @@
 #include "bmv_annotate.hip.h"
 #include "bmv_best.hip.h"
 #include "bmv_clip.hip.h"
+#include "bmv_leftalign.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_pair.hip.h"
 #include "bmv_realign.hip.h"
@@ -238,6 +239,17 @@ struct bmv_ctx {
     float ms_realign = 0.f;
     uint64_t ra_cells = 0;
     uint32_t ra_passed = 0;
+    // bmv_leftalign: the stack slots of a piece and every alignment's place in them, the outputs (the inputs go through
+    // bmv_annotate's buffers), the host results of bmv_leftaligned and what bmv_last_leftalign_stats reports
+    DevBuf<uint64_t> la_slot_at, la_offset, la_compared;
+    DevBuf<uint32_t> la_stack, la_begin, la_nops, la_dropped, la_merges, la_cigar;
+    DevBuf<uint8_t> la_changed;
+    std::vector<uint32_t> h_la_begin, h_la_dropped, h_la_cigar;
+    std::vector<uint8_t> h_la_changed;
+    std::vector<uint64_t> h_la_offset;
+    float ms_leftalign = 0.f;
+    uint64_t la_n_compared = 0, la_n_merges = 0, la_n_dropped = 0;
+    uint32_t la_n_changed = 0;
 };
 
 namespace {
@@ -2328,6 +2340,168 @@ int bmv_last_realign_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_cells, uin
     if (ms_kernels) *ms_kernels = c->ms_realign;
     if (n_cells) *n_cells = c->ra_cells;
     if (n_passed_through) *n_passed_through = c->ra_passed;
+    return BMV_OK;
+}
+
+// The normalisation pass (include/bmv.h, bmv_leftalign.hip.h): bmv_annotate's checks and upload; every alignment gets a stack
+// slot of E + (gap entries) words in the scratch, the batch is taken in pieces whose slots fit it: the walk, a 64-bit
+// exclusive sum of the entry counts, the gather, the piece's entries to the host.
+int bmv_leftalign(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                  const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                  const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint64_t *total_cigar) {
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_leftalign", v, total_cigar != nullptr, begin && cigar_offset)) return rc;
+    uint64_t columns = 0;
+    if (const int rc = check_annotate_batch(c, "bmv_leftalign", v, begin, cigar_offset, cigar, &columns)) return rc;
+    // merged entries must fit 28 bits; the slot of every alignment
+    const uint64_t budget = c->scratch_bytes;
+    std::vector<uint64_t> need(n, 0);                           // words of scratch
+    for (uint32_t a = 0; a < n; a++) {
+        uint64_t by_op[3] = {0, 0, 0}, gaps = 0;
+        for (uint64_t x = cigar_offset[a]; x < cigar_offset[a + 1]; x++) {
+            by_op[cigar[x] & 15u] += cigar[x] >> 4;
+            if ((cigar[x] & 15u) != BMV_OP_M) gaps++;
+        }
+        for (uint32_t op = 0; op < 3u; op++)
+            if (by_op[op] >= (1ull << 28))
+                return fail(BMV_ERR_UNSUPPORTED, "alignment %u: its %c entries sum to %llu columns; a merged entry holds fewer than 2^28", a,
+                            "MID"[op], (unsigned long long)by_op[op]);
+        need[a] = cigar_offset[a + 1] - cigar_offset[a] + gaps;
+        if (need[a] * 4u > budget)
+            return fail(BMV_ERR_UNSUPPORTED, "alignment %u: %llu CIGAR entries need a stack of %llu bytes; the scratch holds %llu (BMV_SCRATCH_MB)", a,
+                        (unsigned long long)(cigar_offset[a + 1] - cigar_offset[a]), (unsigned long long)(need[a] * 4u),
+                        (unsigned long long)budget);
+    }
+    c->h_la_begin.assign(n, 0);
+    c->h_la_dropped.assign(n, 0);
+    c->h_la_changed.assign(n, 0);
+    c->h_la_offset.assign((size_t)n + 1, 0);
+    c->h_la_cigar.clear();
+    c->ms_leftalign = 0.f;
+    c->la_n_compared = c->la_n_merges = c->la_n_dropped = 0;
+    c->la_n_changed = 0;
+    *total_cigar = 0;
+    if (n == 0) return BMV_OK;
+
+    std::vector<uint32_t> piece_at{0};
+    std::vector<uint64_t> slot_at(n, 0);
+    uint64_t max_words = 0;
+    {
+        uint64_t words = 0;
+        for (uint32_t a = 0; a < n; a++) {
+            if ((words + need[a]) * 4u > budget) {
+                piece_at.push_back(a);
+                words = 0;
+            }
+            slot_at[a] = words;
+            words += need[a];
+            max_words = std::max(max_words, words);
+        }
+        piece_at.push_back(n);
+    }
+    bmv::AnnotateJob in{};
+    std::vector<uint64_t> rebased;
+    if (const int rc = upload_annotate_batch(c, v, begin, cigar_offset, cigar, rebased, in)) return rc;
+    HIP_TRY(need_exact_all(n, c->la_slot_at, c->la_compared, c->la_begin, c->la_nops, c->la_dropped, c->la_merges, c->la_changed));
+    HIP_TRY(c->la_offset.need_exact((size_t)n + 1u));
+    HIP_TRY(c->la_stack.need_exact(with_headroom((size_t)std::max<uint64_t>(max_words, 1u), c->la_stack.cap)));
+    HIP_TRY(hipMemcpyAsync(c->la_slot_at.p, slot_at.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    bmv::LeftAlignJob j{};
+    j.genome = in.genome;
+    j.reads = in.reads;
+    j.text_start = in.text_start;
+    j.text_len = in.text_len;
+    j.text_rc = in.text_rc;
+    j.query_start = in.query_start;
+    j.query_len = in.query_len;
+    j.begin = in.begin;
+    j.cigar_offset = in.cigar_offset;
+    j.cigar = in.cigar;
+    j.slot_at = c->la_slot_at.p;
+    j.stack = c->la_stack.p;
+    j.out_begin = c->la_begin.p;
+    j.nops = c->la_nops.p;
+    j.dropped = c->la_dropped.p;
+    j.merges = c->la_merges.p;
+    j.compared = c->la_compared.p;
+    j.changed = c->la_changed.p;
+    j.out_offset = c->la_offset.p;
+    uint64_t *scan_tmp = reinterpret_cast<uint64_t *>(c->scan_tmp.p);
+    float ms_walk = 0.f, ms_gather = 0.f;
+    std::vector<uint64_t> off;
+    for (size_t p = 0; p + 1 < piece_at.size(); p++) {
+        const uint32_t a0 = piece_at[p], cnt = piece_at[p + 1] - a0;
+        if (cnt == 0) continue;
+        j.first = a0;
+        j.count = cnt;
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        hipLaunchKernelGGL(bmv::bmv_leftalign_kernel, dim3((cnt + bmv::kLeftAlignWaves - 1u) / bmv::kLeftAlignWaves),
+                           dim3(64u * bmv::kLeftAlignWaves), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->la_nops.p + a0, c->la_offset.p, cnt, scan_tmp, c->stream));
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        off.resize((size_t)cnt + 1);
+        HIP_TRY(hipMemcpyAsync(off.data(), c->la_offset.p, ((size_t)cnt + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_walk += ms;
+        const uint64_t n_entries = off[cnt], had = c->h_la_cigar.size();
+        HIP_TRY(c->la_cigar.need_exact(with_headroom((size_t)std::max<uint64_t>(n_entries, 1u), c->la_cigar.cap)));
+        j.out_cigar = c->la_cigar.p;
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+        hipLaunchKernelGGL(bmv::bmv_leftalign_gather_kernel, dim3((cnt + 31u) / 32u), dim3(256), 0, c->stream, j);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        c->h_la_cigar.resize((size_t)(had + n_entries));
+        if (n_entries)
+            HIP_TRY(hipMemcpyAsync(c->h_la_cigar.data() + had, c->la_cigar.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_gather += ms;
+        for (uint32_t s = 0; s <= cnt; s++) c->h_la_offset[(size_t)a0 + s] = had + off[s];
+    }
+    std::vector<uint64_t> compared(n);
+    std::vector<uint32_t> merges(n);
+    HIP_TRY(hipMemcpyAsync(c->h_la_begin.data(), c->la_begin.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_la_dropped.data(), c->la_dropped.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_la_changed.data(), c->la_changed.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(compared.data(), c->la_compared.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(merges.data(), c->la_merges.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t a = 0; a < n; a++) {
+        c->la_n_compared += compared[a];
+        c->la_n_merges += merges[a];
+        c->la_n_dropped += c->h_la_dropped[a];
+        c->la_n_changed += c->h_la_changed[a] ? 1u : 0u;
+    }
+    c->ms_leftalign = ms_walk + ms_gather;
+    if (getenv("BMV_LOG_CLASSES"))
+        fprintf(stderr, "[bmv] leftalign: %u alignments (%u changed) in %zu pieces, walk and scan %.3f ms, gather %.3f ms\n", n,
+                c->la_n_changed, piece_at.size() - 1, ms_walk, ms_gather);
+    *total_cigar = c->h_la_cigar.size();
+    return BMV_OK;
+}
+
+int bmv_leftaligned(bmv_ctx *c, uint32_t *out_begin, uint64_t *out_cigar_offset, uint32_t *out_cigar, uint8_t *out_changed,
+                    uint32_t *out_dropped) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_leftaligned: null context");
+    copy_out(out_begin, c->h_la_begin);
+    copy_out(out_cigar_offset, c->h_la_offset);
+    copy_out(out_cigar, c->h_la_cigar);
+    copy_out(out_changed, c->h_la_changed);
+    copy_out(out_dropped, c->h_la_dropped);
+    return BMV_OK;
+}
+
+int bmv_last_leftalign_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_compared, uint32_t *n_changed, uint64_t *n_merges,
+                             uint64_t *n_dropped) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_leftalign_stats: null context");
+    if (ms_kernels) *ms_kernels = c->ms_leftalign;
+    if (n_compared) *n_compared = c->la_n_compared;
+    if (n_changed) *n_changed = c->la_n_changed;
+    if (n_merges) *n_merges = c->la_n_merges;
+    if (n_dropped) *n_dropped = c->la_n_dropped;
     return BMV_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "affine_realign.h"
 #include "best_mapq.h"
 #include "bm_genome.h"
+#include "left_align.h"
 #include "mapper.h"
 #include "pair_mapq.h"
 #include "pair_rescue.h"
@@ -169,6 +170,16 @@ public:
         (void)n_read_bytes;
         affine::realign_on_host(genome, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, n, scores,
                                 out);
+    }
+    // Every I and D entry of alignments given with their begin and M/I/D CIGAR moved to its leftmost equivalent place on the
+    // forward strand (bmv_leftalign's contract, include/bmv.h).  This default restates the rule on the host (left_align.h) and
+    // needs `genome` as realign's does; the GPU verifier normalises on the device (can_left_align() true) and ignores it.
+    virtual bool can_left_align() const { return false; }
+    virtual void left_align(const uint8_t *genome, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                            const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                            const uint32_t *begin, const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, left_alignment &out) {
+        (void)n_read_bytes;
+        leftalign::left_align_on_host(genome, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, n, out);
     }
     // The best alignment of every group (bmv_align_best's contract, include/bmv.h): group g owns the alignments
     // group_offset[g] .. group_offset[g + 1] - 1; with d = -score and end = begin + the M and D lengths, winner[g] is the lowest
@@ -461,6 +472,7 @@ private:
     uint32_t _clip_match = 1, _clip_penalty = 2;
     bool _affine = false;                        // --affine: the written alignments realigned under affine gap costs, with AS
     affine_scores _affine_scores{};
+    bool _left_align = false;                    // --left-align: the written alignments' indels at their leftmost forward place
     float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
     bool _paired = false;                        // --paired: records 2p and 2p + 1 of the FASTQ file are mates, placed together
     uint32_t _min_frag = 1, _max_frag = 1000;    // --frag-range: what a proper pair spans, leftmost to rightmost base
@@ -689,6 +701,10 @@ public:
         _affine = _annotate = true;
         _affine_scores = scores;
     }
+    // --left-align: the --annotate layout, the written alignments through the verifier's normalisation pass (after the
+    // realignment, before annotate or clip): POS, CIGAR, NM and MD are the normalised path's; with --affine and without --clip
+    // AS:i is computed from the written entries (sam_tags::affine_score)
+    void set_left_align() { _left_align = _annotate = true; }
     void set_clip(uint32_t match, uint32_t penalty) {
         _clip = _annotate = true;
         _clip_match = match;
@@ -1029,7 +1045,7 @@ private:
         }
         // --annotate with a verifier that has no annotation pass (the oracle-backed test tools): sam_tags::annotate_on_host
         const bool annotate_here = _annotate && !_clip && !_v->can_annotate();
-        if ((annotate_here || (_affine && !_v->can_realign())) && flat_genome_.empty())
+        if ((annotate_here || (_affine && !_v->can_realign()) || (_left_align && !_v->can_left_align())) && flat_genome_.empty())
             for (const auto &seq : genome_->seqs) flat_genome_.insert(flat_genome_.end(), seq.begin(), seq.end());
         auto is_written = [&](const Block &b, size_t a) {       // :570-573, and the edit bound
             const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
@@ -1166,6 +1182,14 @@ private:
                         cg.swap(ra.cigar);
                         b.affine_score.swap(ra.score);
                     }
+                    if (_left_align) {                          // ... and the normalised ones theirs
+                        left_alignment la;
+                        _v->left_align(flat_genome_.data(), b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(),
+                                       ql.data(), bg.data(), co.data(), cg.data(), static_cast<uint32_t>(ts.size()), la);
+                        bg.swap(la.begin);
+                        co.swap(la.cigar_offset);
+                        cg.swap(la.cigar);
+                    }
                     if (_clip)
                         _v->clip(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
                                  co.data(), cg.data(), static_cast<uint32_t>(ts.size()), _clip_match, _clip_penalty, b.ann);
@@ -1249,9 +1273,12 @@ private:
                 if (_clip) {
                     tags += "\tAS:i:";
                     sam_tags::number(tags, static_cast<uint64_t>(b.ann.score[s]));
-                } else if (_affine) {
-                    tags += b.affine_score[s] < 0 ? "\tAS:i:-" : "\tAS:i:";
-                    sam_tags::number(tags, static_cast<uint64_t>(std::abs(static_cast<int64_t>(b.affine_score[s]))));
+                } else if (_affine) {                           // (--left-align: merges and drops change the score)
+                    const int64_t as = _left_align ? sam_tags::affine_score(entry, n_entries, _affine_scores.match, _affine_scores.mismatch,
+                                                                            _affine_scores.gap_open, _affine_scores.gap_extend)
+                                                   : static_cast<int64_t>(b.affine_score[s]);
+                    tags += as < 0 ? "\tAS:i:-" : "\tAS:i:";
+                    sam_tags::number(tags, static_cast<uint64_t>(std::abs(as)));
                 }
                 if (best) tags += "\t" + best_tag;
                 if (!last_tag.empty()) {

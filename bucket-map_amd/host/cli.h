@@ -54,6 +54,9 @@ struct cmd_arguments {
     unsigned int affine_match = 1, affine_mismatch = 4, affine_gap_open = 6, affine_gap_extend = 1;   // --affine-scores A,B,O,E
                                   // (implies --affine), 1..1024 each; the default is the common short-read scale, a choice
     unsigned int affine_band = 16;   // --affine-band W (implies --affine), 1..31: D entries of up to 63 - 2 W bases are realigned
+    bool left_align = false;      // --left-align (bucketmap_align): the written alignments' I and D entries are moved to their
+                                  // leftmost equivalent place on the forward strand (bmv_leftalign), after --affine's realignment
+                                  // and before annotate or clip (implies --annotate)
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -230,7 +233,10 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.affine_band = static_cast<unsigned>(w);
             a.affine = true;
         }
+        else if (opt == "--left-align") a.left_align = true;
 #else
+        else if (opt == "--left-align")
+            throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has no indels to normalise.");
         else if (opt == "--affine" || opt == "--affine-scores" || opt == "--affine-band")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has nothing to realign.");
         else if (opt == "--paired" || opt == "--frag-range" || opt == "--rescue" || opt == "--rescue-rate")
@@ -262,7 +268,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (!have_indicator) throw parser_error("Option -i/--index-indicator is required but not set.");
     if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;
-    if (a.affine) a.annotate = true;
+    if (a.affine || a.left_align) a.annotate = true;
     return a;
 }
 

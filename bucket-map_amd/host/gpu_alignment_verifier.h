@@ -254,6 +254,48 @@ public:
                   << " passed through; " << timing(ms, t0);
     }
 
+    // bmv_leftalign per device: the same cut, the results stitched the same way
+    bool can_left_align() const override { return true; }
+    void left_align(const uint8_t *, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                    const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                    const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, left_alignment &out) override {
+        const size_t D = ctx_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        const batch all{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+        out.begin.assign(n, 0);
+        out.dropped.assign(n, 0);
+        out.changed.assign(n, 0);
+        out.cigar_offset.assign(static_cast<size_t>(n) + 1, 0);
+        const std::vector<uint32_t> cut = cut_by_cost(n, D, [&](uint32_t a) { return cigar_offset[a + 1] - cigar_offset[a] + 1u; });
+        std::vector<uint64_t> total(D, 0), compared(D, 0), merges(D, 0), dropped(D, 0);
+        std::vector<float> ms(D, 0.f);
+        std::vector<uint32_t> changed(D, 0);
+        for_each_device(D, [&](size_t d) {
+            if (cut[d + 1] == cut[d]) return;
+            const share s = slice(all, cut[d], cut[d + 1] - cut[d]);
+            check(bmv_leftalign(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, begin + s.a0,
+                                cigar_offset + s.a0, cigar, s.n, &total[d]),
+                  "the GPU indel normalisation pass failed: ");
+            bmv_last_leftalign_stats(ctx_[d], &ms[d], &compared[d], &changed[d], &merges[d], &dropped[d]);
+        });
+        const std::vector<uint64_t> at = starts(total);
+        out.cigar.assign(at[D], 0);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t a0 = cut[d], m = cut[d + 1] - cut[d];
+            if (m == 0) return;
+            std::vector<uint64_t> off(static_cast<size_t>(m) + 1);
+            check(bmv_leftaligned(ctx_[d], out.begin.data() + a0, off.data(), out.cigar.data() + at[d], out.changed.data() + a0,
+                                  out.dropped.data() + a0),
+                  "reading the normalised alignments failed: ");
+            stitch(out.cigar_offset, a0, m, off, at[d]);
+        });
+        out.cigar_offset[n] = at[D];
+        out.compared = sum(compared);
+        out.merges = sum(merges);
+        std::cerr << "[BENCHMARK]\tGPU indel normalisation: " << n << " alignments, " << sum(changed) << " changed, " << out.compared
+                  << " columns compared, " << out.merges << " merges, " << sum(dropped) << " bases dropped; " << timing(ms, t0);
+    }
+
     // bmv_rescue per device: the jobs -- independent of each other -- in contiguous ranges of equal cost, each device handed
     // the span of the read buffer its queries cover
     void rescue(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *anchor_text_start, const uint32_t *anchor_text_len,

@@ -135,6 +135,7 @@ int main(int argc, char **argv) {
         if (args.clip) loc.set_clip(args.clip_match, args.clip_penalty);
         if (args.affine)
             loc.set_affine(bm::affine_scores{args.affine_match, args.affine_mismatch, args.affine_gap_open, args.affine_gap_extend, args.affine_band});
+        if (args.left_align) loc.set_left_align();
         if (args.best) loc.set_best(args.best_margin);
         if (args.paired) loc.set_paired(args.frag_min, args.frag_max);
         if (args.rescue) loc.set_rescue(args.rescue_rate);

@@ -71,6 +71,21 @@ inline void append_md(std::string &out, const uint32_t *entry, size_t n, const u
     number(out, run);
 }
 
+// The affine score of written =/X/I/D entries (S adds nothing): match per = column, -mismatch per X column, -(gap_open +
+// L gap_extend) per I or D entry of length L.  bmv_realign's score of the same path; `--affine --left-align` writes it as
+// AS:i, since a merge or a dropped D changes the score the realignment returned.
+inline int64_t affine_score(const uint32_t *entry, size_t n, uint32_t match, uint32_t mismatch, uint32_t gap_open, uint32_t gap_extend) {
+    int64_t score = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t op = entry[i] & 15u;
+        const int64_t len = entry[i] >> 4;
+        if (op == 7u) score += len * match;
+        else if (op == 8u) score -= len * mismatch;
+        else if (op == 1u || op == 2u) score -= gap_open + len * static_cast<int64_t>(gap_extend);
+    }
+    return score;
+}
+
 // bmv_annotate's contract (include/bmv.h) restated for the host, over a genome laid out as the verifier's: forward-strand pos,
 // ref_len, =/X/I/D entries, NM and the reference letters under X and D columns of alignments given with their begin and M/I/D
 // CIGAR.  The locator uses it with a verifier that has no annotation pass of its own (the oracle-backed test tools); the product

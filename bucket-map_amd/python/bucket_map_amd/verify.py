@@ -64,6 +64,9 @@ SYMBOLS = {
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
     "bmv_realigned": (C.c_int, [C.c_void_p, _i32p, _u32p, _u8p, _u64p, _u32p]),
     "bmv_last_realign_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p, _u32p]),
+    "bmv_leftalign": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32, _u64p]),
+    "bmv_leftaligned": (C.c_int, [C.c_void_p, _u32p, _u64p, _u32p, _u8p, _u32p]),
+    "bmv_last_leftalign_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p, _u32p, _u64p, _u64p]),
 }
 _ready = False
 
@@ -120,6 +123,91 @@ def md_string(xcigar, ref_bases) -> str:
     if at != len(ref):
         raise ValueError(f"the entries cover {at} reference bases under X and D, {len(ref)} were given")
     return "".join(out) + str(run)
+
+
+_DNA4_RANK = bytes(1 if chr(b).upper() in "CYSB" else 2 if chr(b).upper() in "GK" else 3 if chr(b).upper() in "TU" else 0
+                   for b in range(256))
+
+
+def left_align(window, query, text_rc, begin, cigar) -> dict:
+    """bmv_leftalign's rule (include/bmv.h) for ONE alignment, in plain Python, for users of the ABI: `window` the text
+    window as it lies in the genome, `query` the read as sequenced, `begin` and the packed M/I/D `cigar` as the aligner
+    gave them.  Returns begin and cigar (a list) in the aligner's orientation, changed, dropped, and the compared columns
+    and merges the stats count.  The rule of host/left_align.h."""
+    W = bytes(window).translate(_DNA4_RANK)
+    Q = bytes(query).translate(_DNA4_RANK)
+    entries = [int(e) for e in cigar]
+    if not entries:
+        return {"begin": int(begin), "cigar": [], "changed": 0, "dropped": 0, "compared": 0, "merges": 0}
+    for op in range(3):
+        if sum(e >> 4 for e in entries if e & 15 == op) >= 1 << 28:
+            raise ValueError(f"the {'MID'[op]} entries sum to 2^28 columns or more: a merged entry would not fit 28 bits")
+    rc = bool(text_rc)
+    if rc:
+        Q = Q[::-1]
+        entries = entries[::-1]
+    ref_len = sum(e >> 4 for e in entries if e & 15 != 1)
+    pos = len(W) - int(begin) - ref_len if rc else int(begin)
+    p, q, dropped, compared, merges, moved = pos, 0, 0, 0, 0, False
+    stack = []
+
+    def append_m(n):
+        if n == 0:
+            return
+        if stack and stack[-1] & 15 == 0:
+            stack[-1] += n << 4
+        else:
+            stack.append(n << 4)
+
+    for e in entries:
+        op, L = e & 15, e >> 4
+        if op == 0:
+            append_m(L)
+            p += L
+            q += L
+            continue
+        p_after, q_after = p + (L if op == 2 else 0), q + (L if op == 1 else 0)
+        pend, keep = 0, True
+        while True:
+            if not stack:
+                if op == 2:
+                    pos += L
+                    dropped += L
+                    keep = False
+                break
+            top_op, k = stack[-1] & 15, stack[-1] >> 4
+            if top_op == 0:
+                s = 0
+                while s < k:
+                    compared += 1
+                    t = s + 1
+                    if (W[p - t] != W[p - t + L]) if op == 2 else (Q[q - t] != Q[q - t + L]):
+                        break
+                    s += 1
+                p, q, pend = p - s, q - s, pend + s
+                if s < k:
+                    stack[-1] = (k - s) << 4
+                    break
+                stack.pop()
+            elif top_op == op:
+                stack.pop()
+                L += k
+                if op == 2:
+                    p -= k
+                else:
+                    q -= k
+                merges += 1
+            else:
+                break
+        if keep:
+            stack.append(L << 4 | op)
+        append_m(pend)
+        moved = moved or pend != 0
+        p, q = p_after, q_after
+    if stack and stack[-1] & 15 == 2:
+        dropped += stack.pop() >> 4
+    return {"begin": len(W) - pos - (ref_len - dropped) if rc else pos, "cigar": stack[::-1] if rc else stack,
+            "changed": int(moved or dropped != 0), "dropped": dropped, "compared": compared, "merges": merges}
 
 
 def select_best(d, end, group_offset, margin):
@@ -611,6 +699,30 @@ class Verifier:
         ms, cells, passed = C.c_float(), C.c_uint64(), C.c_uint32()
         _check(lib().bmv_last_realign_stats(self._h, C.byref(ms), C.byref(cells), C.byref(passed)))
         return {"ms_kernels": ms.value, "cells": cells.value, "n_passed_through": passed.value}
+
+    def leftalign(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar) -> dict:
+        """bmv_leftalign on the alignments annotate takes: every I and D entry moved to its leftmost equivalent place on the
+        forward strand, same-op gaps that meet merged, a D that reaches either end dropped (include/bmv.h: the contract).
+        Returns a dict: begin u32[n], cigar_offset u64[n+1], cigar u32[..] -- the shape of align's results, ready for
+        annotate or clip --, changed u8[n], dropped u32[n].  Leaves the results of every other call untouched."""
+        _keep, n, args = self._annotate_args(reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset,
+                                             cigar)
+        total = C.c_uint64()
+        _check(lib().bmv_leftalign(self._h, *args, C.byref(total)))
+        out_begin, changed, dropped = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        off = np.zeros(n + 1, np.uint64)
+        cg = np.zeros(max(total.value, 1), np.uint32)
+        _check(lib().bmv_leftaligned(self._h, _p(out_begin, _u32p), _p(off, _u64p), _p(cg, _u32p), _p(changed, _u8p), _p(dropped, _u32p)))
+        return {"begin": out_begin, "cigar_offset": off, "cigar": cg[: total.value], "changed": changed, "dropped": dropped}
+
+    def leftalign_stats(self) -> dict:
+        """Of the last leftalign: kernel ms (walk, scan and gather), the columns compared, the alignments changed, the
+        merges and the dropped bases."""
+        ms, compared, changed, merges, dropped = C.c_float(), C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(lib().bmv_last_leftalign_stats(self._h, C.byref(ms), C.byref(compared), C.byref(changed), C.byref(merges),
+                                              C.byref(dropped)))
+        return {"ms_kernels": ms.value, "compared": compared.value, "n_changed": changed.value, "merges": merges.value,
+                "dropped": dropped.value}
 
     def stats(self) -> dict:
         ms, cells = C.c_float(), C.c_uint64()

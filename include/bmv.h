@@ -354,7 +354,7 @@ int  bmv_last_clip_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_columns);
  *                      are M / I / D, 5' to 3' of the query, adjacent entries never share an op; a result never begins or ends
  *                      with D
  * Under these rules gaps in a repeat are pushed towards the START of the text AS THE ALIGNER SAW IT -- for text_rc != 0 that is
- * the right end on the forward strand.  Normalising them on the forward strand is not part of this pass.
+ * the right end on the forward strand.  bmv_leftalign (below) normalises them on the forward strand.
  * The scores are a choice of the caller (the tool's default 1, 4, 6, 1 is the common short-read scale, not a measurement).
  * How (bmv_realign.hip.h): a wave per alignment, a lane per band column, the wave stepping row by row along the CIGAR; the Del
  * chain of a row by a prefix maximum across the lanes; a byte of direction codes per cell to the scratch, the batch taken in
@@ -371,6 +371,62 @@ int  bmv_realigned(bmv_ctx *ctx, int32_t *out_score, uint32_t *out_begin, uint8_
  * the realigned alignments (the lanes a wave steps through, whatever the band), and the alignments passed through.  Any
  * pointer may be NULL. */
 int  bmv_last_realign_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells, uint32_t *n_passed_through);
+
+/* The normalisation pass: every I and D entry of a known M/I/D path moved to its leftmost equivalent place ON THE FORWARD
+ * STRAND.  The aligners' tie rules, and bmv_realign's, push an indel that lies in a repeat (a homopolymer, a microsatellite,
+ * a tandem copy) towards the start of the text as the aligner saw it -- for a reverse-strand read the right end of the run on
+ * the forward strand --, so forward and reverse reads write the same event at two coordinates; every consumer of SAM assumes
+ * the leftmost one.  A call of its own, of the bmv_annotate / bmv_clip / bmv_realign family: bmv_annotate's inputs and its
+ * checks on the host before anything is launched (BMV_ERR_ARG, the message names the alignment, nothing ran, the context stays
+ * usable); in addition BMV_ERR_UNSUPPORTED, the message naming the alignment and nothing having run, when one alignment's I
+ * lengths or its D lengths (or its M lengths: M entries merge too) sum to 2^28 or more -- a merged entry would not fit 28
+ * bits --, or when one alignment's stack alone (4 bytes per entry and 4 more per gap entry) does not fit the scratch
+ * (BMV_SCRATCH_MB).  The call leaves untouched what every other result or stats call returns.  The output (bmv_leftaligned)
+ * has the shape of bmv_results / bmv_realigned -- begin and M/I/D entries in the aligner's orientation --, so it can be handed
+ * straight to bmv_annotate or bmv_clip.  The contract is exact and stated on the outputs only.
+ *   the forward view   of alignment a: W is the window as it lies in the genome; pos is bmv_annotate's pos; Qf is the query
+ *                      read along the forward strand (for text_rc != 0 its reverse complement); the entries are taken in
+ *                      forward order (for text_rc != 0 reversed).  Equality is on dna4 ranks on both sides, as in bmv_annotate;
+ *                      two complemented bases are equal exactly when the originals are, so nothing has to be complemented
+ *   the walk           through the entries left to right, the output kept as a stack, with a reference cursor p (from pos) and
+ *                      a query cursor q (from 0).  An M entry is appended (it merges with an M on top of the stack) and moves
+ *                      both cursors.  A gap entry of op g and length L begins at (p, q) and carries a count pend = 0 of the M
+ *                      columns it has passed.  For the gap, repeat:
+ *                        (1) the stack is empty: a D is dropped (pos += L, dropped += L), an I is pushed.  Stop.
+ *                        (2) the top is M of length k: s is the largest value <= k such that for every t = 1..s
+ *                            W[p - t] == W[p - t + L] (a D) / Qf[q - t] == Qf[q - t + L] (an I).  p -= s, q -= s, pend += s, the M
+ *                            becomes k - s.  If s < k, push the gap and stop; otherwise pop the emptied M and repeat.
+ *                        (3) the top is a gap of the same op and length L': pop it, L += L', p -= L' (a D) / q -= L' (an I),
+ *                            one merge is counted.  Repeat: the merged gap goes on moving under its new length.
+ *                        (4) the top is a gap of the other op: push the gap and stop.
+ *                      After the gap stops, an M of pend is appended (it merges with a following M) and the cursors stand
+ *                      behind the gap as given.  At the end of the walk a D on top of the stack is dropped, its length added
+ *                      to dropped.
+ *   what follows       each step swaps an M column for one of the same =/X status, so NM and any affine score change only
+ *                      through merges and drops: nm_out = nm_in - dropped; M + I lengths = query_len; pos' + R' <= text_len;
+ *                      adjacent entries never share an op; the result never begins or ends with D; it has at most E + (gap
+ *                      entries) entries; the pass is idempotent
+ *   out_begin          in the aligner's orientation: pos' for text_rc == 0, else text_len - pos' - R' (R' the M and D lengths
+ *                      of the result)
+ *   out_cigar          entries 5' to 3' of the query, at out_cigar_offset (n + 1)
+ *   out_changed        1 when a gap moved or bases were dropped -- exactly when begin or the entries differ from those given
+ *   out_dropped        the D bases dropped at the two ends
+ *   an empty CIGAR     begin as given, no entries, zeros
+ * How (bmv_leftalign.hip.h): a wave per alignment walks the entries in uniform registers, 64 fetched at a time; for a gap lane
+ * t - 1 compares the two bytes of shift t, one ballot and a count of trailing ones give up to 64 columns of shift a step; the
+ * stack's body lies in a slot of the scratch, the batch taken in pieces whose slots fit it; a scan and a gather put the
+ * entries in the aligner's order at packed offsets. */
+int  bmv_leftalign(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                   const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                   const uint64_t *cigar_offset, const uint32_t *cigar, uint32_t n, uint64_t *total_cigar);
+/* Results of the last bmv_leftalign: n entries each, out_cigar_offset n + 1, out_cigar total_cigar; any pointer may be NULL. */
+int  bmv_leftaligned(bmv_ctx *ctx, uint32_t *out_begin, uint64_t *out_cigar_offset, uint32_t *out_cigar, uint8_t *out_changed,
+                     uint32_t *out_dropped);
+/* Of the last bmv_leftalign: the kernels' time in ms (walk, scan and gather, all pieces), the columns compared -- every t
+ * tested in (2), the one that failed included --, the alignments changed, the merges (3) and the dropped bases.  Any pointer
+ * may be NULL. */
+int  bmv_last_leftalign_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_compared, uint32_t *n_changed, uint64_t *n_merges,
+                              uint64_t *n_dropped);
 
 #ifdef __cplusplus
 }

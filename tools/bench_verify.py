@@ -7,6 +7,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py --annotate [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --clip [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --realign [--reads 20000 --len 10000 --indel-rate 0.1]
+    python tools/bench_verify.py --leftalign [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --best [--groups 20000 --len 10000 --text-len 11001] [--groups 200000 --len 300 --text-len 307]
     python tools/bench_verify.py --paired [--pairs 500000 --len 300]
     python tools/bench_verify.py --rescue [--rescue-jobs 500000,4000 --rescue-len 150]
@@ -346,6 +347,9 @@ def main():
     ap.add_argument("--len", type=int, default=300)
     ap.add_argument("--indel-rate", type=float, default=0.02)
     ap.add_argument("--sub", type=float, default=0.002)
+    ap.add_argument("--indels", type=float, default=0.0, metavar="F",
+                    help="plant F x --len indel events of 1..3 bases in every read (half deletions, half insertions; default: "
+                         "substitutions only): what --leftalign needs to have anything to move")
     ap.add_argument("--cpu-sample", type=int, default=2000)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--mixed", type=int, default=0,
@@ -364,6 +368,10 @@ def main():
                     help="also run Verifier.realign (scores 1,4,6,1, band 16) on the batch's results: the pass's kernels ms of every "
                          "repeat with forward and traceback apart (the library's BMV_LOG_CLASSES line), band cells / time, and the "
                          "ratio to align's kernels ms on the same batch")
+    ap.add_argument("--leftalign", action="store_true",
+                    help="also run Verifier.leftalign and Verifier.annotate on the batch's results: the normalisation pass's "
+                         "kernels ms of every repeat, the columns compared, the alignments changed, the merges and dropped bases, "
+                         "and the ratio to annotate's kernels ms on the same batch")
     ap.add_argument("--decoys", type=float, default=0.0, metavar="F",
                     help="this share of the alignments takes its text window from an unrelated place (a wrong locus)")
     ap.add_argument("--long", action="store_true", help="Verifier.align_long on reads beyond 65 536 bases (see above)")
@@ -391,7 +399,26 @@ def main():
     rc = rng.integers(0, 2, args.reads).astype(np.uint8) * (0 if args.mixed else 1)
     # reads: the window's bases from offset 1 (so begin = 1), substitutions only + strand flips, built vectorised
     idx = start[:, None] + 1 + np.arange(m, dtype=np.uint64)[None, :]
+    inserted = None
+    if args.indels > 0:                                # --indels: events of 1..3 bases, half deletions, half insertions
+        k = max(1, int(round(args.indels * m)))
+        at = rng.integers(0, m, (args.reads, k))
+        size = rng.integers(1, 4, (args.reads, k))
+        dele = rng.random((args.reads, k)) < 0.5
+        row = np.broadcast_to(np.arange(args.reads)[:, None], at.shape)
+        shift = np.zeros((args.reads, m + 4), np.int32)  # a deletion skips window bases from its place on, an insertion lags behind
+        np.add.at(shift, (row[dele], at[dele]), size[dele].astype(np.int32))
+        np.add.at(shift, (row[~dele], at[~dele] + size[~dele]), -size[~dele].astype(np.int32))
+        shift = np.cumsum(shift[:, :m], axis=1)
+        inserted = np.zeros((args.reads, m + 4), bool)
+        for d in range(3):
+            sel = ~dele & (size > d)
+            inserted[row[sel], at[sel] + d] = True
+        inserted = inserted[:, :m]
+        idx = start[:, None] + np.clip(1 + np.arange(m, dtype=np.int64)[None, :] + shift, 0, width - 1).astype(np.uint64)
     reads = genome[idx]
+    if inserted is not None:
+        reads[inserted] = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, int(inserted.sum()))]
     comp = np.zeros(256, np.uint8)
     comp[list(b"ACGT")] = list(b"TGCA")
     flip = rc.astype(bool)
@@ -513,6 +540,27 @@ def main():
                    "checks": {"all_realigned": bool(got["realigned"].all() or rst["n_passed_through"] > 0),
                               "score_at_least_the_edit_bound": bool((got["score"].astype(np.int64) >= ql.astype(np.int64) + 12 * score.astype(np.int64)).all())}}
 
+    leftalign = None
+    if args.leftalign:
+        l_ms, l_wall, a_ms = [], [], []
+        for _ in range(args.repeat):
+            nm = v.annotate(reads, start, tl, rc, qs, ql, begin, off, cg)[0]
+            a_ms.append(v.annotate_stats()["ms_kernels"])
+            t0 = time.perf_counter()
+            got = v.leftalign(reads, start, tl, rc, qs, ql, begin, off, cg)
+            l_wall.append(time.perf_counter() - t0)
+            l_ms.append(v.leftalign_stats()["ms_kernels"])
+        lst = v.leftalign_stats()
+        nm2 = v.annotate(reads, start, tl, rc, qs, ql, got["begin"], got["cigar_offset"], got["cigar"])[0]
+        again = v.leftalign(reads, start, tl, rc, qs, ql, got["begin"], got["cigar_offset"], got["cigar"])
+        leftalign = {"ms_kernels_leftalign": l_ms, "ms_kernels_annotate": a_ms, "ms_kernels_align": all_ms, "wall_s_leftalign": l_wall,
+                     "columns_compared": lst["compared"], "changed": lst["n_changed"], "merges": lst["merges"],
+                     "dropped_bases": lst["dropped"], "gap_entries": int(((cg & 15) != 0).sum()),
+                     "spread": (max(l_ms) - min(l_ms)) / min(l_ms), "leftalign_over_annotate": min(l_ms) / min(a_ms),
+                     "checks": {"nm_is_nm_in_minus_dropped": bool(np.array_equal(nm2.astype(np.int64), nm.astype(np.int64) - got["dropped"])),
+                                "idempotent": bool(not again["changed"].any() and np.array_equal(again["cigar"], got["cigar"])
+                                                   and np.array_equal(again["begin"], got["begin"]))}}
+
     ns = min(args.cpu_sample, args.reads)
     same, cpu = None, None
     if ns > 0:                                         # (--cpu-sample 0: no oracle in the process at all -- bench.py's leg)
@@ -533,6 +581,7 @@ def main():
         "annotate": annotate,
         "clip": clip,
         "realign": realign,
+        "leftalign": leftalign,
         "checks": {"sample_identical_to_oracle": same},
     }))
 
