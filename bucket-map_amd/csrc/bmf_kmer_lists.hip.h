@@ -18,14 +18,35 @@
 //                          popcounts per round of 64 chunks)
 //   bmf_vote_kernel_lists  one wave per (window, orientation); the list entries of the sample kernel are the k-mer
 //                          hashes themselves (DevParams::pair == 2).  Per-wave hit counters in LDS, BITS = 4 (S <= 15)
-//                          or 8 bits per bucket packed in dwords, incremented with returning LDS atomic adds: the
-//                          value that comes back is the count before, so the wave knows its highest hit count without
-//                          looking at the counters.  misses = S - hits: an item whose highest count is at most S - F
-//                          is empty and is done; the others scan the counters once, in bucket order, for the buckets
-//                          at the maximum (ids staged in LDS: more than max_candidates of them is "cleared").
-//                          The adds are not waited for one by one: the eight of a unit are issued back to back, with no
-//                          branch per id (a padding id adds 0 where it harms nothing), and folded into the maximum after
-//                          the next unit's are issued (kmer_count_units).
+//                          or 8 bits per bucket packed in dwords, incremented with LDS atomic adds.  A returning add
+//                          brings back the count before, so the wave knows its highest hit count without looking at
+//                          the counters.  misses = S - hits: an item whose highest count is at most S - F is empty and
+//                          is done; the others scan the counters once, in bucket order, for the buckets at the
+//                          maximum (ids staged in LDS: more than max_candidates of them is "cleared").
+//                          Two phases.  The counter of bucket b ends at h(b), the number of the item's S lists that
+//                          hold b, and the kernel needs only whether max h >= S - F + 1 and, if so, max h exactly.
+//                          So the first n_plain = S - F lists (0 when F >= S) are counted with plain adds, no return
+//                          and no fold (kmer_unit_plain), then comes a fence, then the other lists with returning adds
+//                          (kmer_count_units).  After the plain phase no counter exceeds S - F, so a counter that ends
+//                          at h >= S - F + 1 takes its last increment from a returning add, which brings back h - 1
+//                          and folds h; if no counter gets that far the folded maximum is at most S - F and the item
+//                          is empty, as it should be.  Unlike the all-returning form this depends on the order of the
+//                          adds, and it is exact under two invariants:
+//                            1. at most S - F lists of an item are counted with plain adds, each of them wholly (its
+//                               first 64 units and whatever tail lies beyond them);
+//                            2. every plain add precedes the fence and every returning add follows it: plain heads,
+//                               then the plain lists' tails, the fence, then returning heads and returning tails.
+//                          The LDS executes one wave's instructions in issue order, so issue order is enough in
+//                          hardware; the wavefront-scope release/acquire pair with wave_barrier keeps the compiler from
+//                          moving a relaxed atomic across it (it compiles to no instruction).
+//                          The returning adds are not waited for one by one: the eight of a unit are issued back to
+//                          back, with no branch per id (a padding id adds 0 where it harms nothing), and folded into
+//                          the maximum after the next unit's are issued.  A plain padding id adds a nonzero value at
+//                          a dword nobody reads (kmer_unit_plain).
+//                          Both unit bodies stand in each of the 16 unrolled slots behind wave-uniform tests (slot
+//                          i is plain iff i < np, returning iff i >= np), not one kernel per plain count: 5 574
+//                          instructions, about 33 KiB of the 64 KiB instruction cache, and n_plain stays a run-time
+//                          value from DevParams.
 //                          A workgroup is one wave and one item, and starts by zeroing its counters: ceil(NB / 128 or
 //                          64) 16-byte LDS stores per lane round, far fewer instructions than a second walk over the
 //                          lists would be.  (One resident round of waves, each walking its items with the next items'
@@ -175,6 +196,28 @@ __device__ __forceinline__ void kmer_unit_issue(uint32_t *cnt, uint32_t spare, c
     }
 }
 
+// The eight ids of one unit of a plain list (see bmf_vote_kernel_lists): adds whose result nobody uses (ds_add_u32), so
+// nothing to wait for and nothing to fold.  A padding id adds its 1 << ... as well, where nobody reads: at the lane's dword
+// of the staging area (written only after the counting, read only below `total`), or, where its own dword lies inside
+// the counters (NB > 65 528 in the 4-bit form), in the top field of the last counter dword, which is no bucket (the scan
+// masks the fields >= NB, and a carry out of the top field leaves the dword).  That garbage is never read, and it spares
+// the add path the `id < nb` compare and select.
+// Precondition (bmf_kmer_fill_kernel keeps it): the only id >= NB in a list is kPadId, whose field is the top one of its
+// dword in both forms (field 7 of dword 8 191, field 3 of dword 16 383), and NB <= 65 535.  Any other id >= NB would
+// count in a bucket's field; kmer_unit_issue, which adds 0 for every id >= NB, does not need the precondition.
+template <int BITS>
+__device__ __forceinline__ void kmer_unit_plain(uint32_t *cnt, uint32_t spare, const uint4 &u, uint32_t nb) {
+    constexpr uint32_t kPer = 32u / BITS;
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+    if ((w[0] & 0xFFFFu) < nb) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t id = j & 1 ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu;
+            atomicAdd(&cnt[min(id / kPer, spare)], 1u << ((id % kPer) * BITS));
+        }
+    }
+}
+
 // ... and the highest count any of them reached, once the adds have returned
 template <int BITS>
 __device__ __forceinline__ uint32_t kmer_unit_fold(const uint4 &u, uint32_t nb, const uint32_t (&old)[8], uint32_t mx) {
@@ -191,24 +234,68 @@ __device__ __forceinline__ uint32_t kmer_unit_fold(const uint4 &u, uint32_t nb, 
 // N units counted with no wait per add: the adds of unit i are issued before the returns of unit i - 1 are folded into mx
 // (LDS returns come back in order, so up to 16 are in flight; a lane without a unit skips its adds, which is why the
 // compiler's counted waits let a fold wait for at most the first add of the unit after its own).  after(i) runs when u[i]
-// has been folded.
+// has been folded.  Only u[from .. N - 1] are counted (from < N, wave-uniform: the units before them belong to plain lists).
 template <int BITS, int N, class After>
 __device__ __forceinline__ uint32_t kmer_count_units(uint32_t *cnt, uint32_t spare, const uint4 (&u)[N], uint32_t nb, uint32_t mx,
-                                                     After after) {
+                                                     After after, uint32_t from = 0) {
     uint32_t old[2][8];
 #pragma unroll
     for (int i = 0; i < N; i++) {
+        if ((uint32_t)i < from) continue;
         kmer_unit_issue<BITS>(cnt, spare, u[i], nb, old[i & 1]);
-        if (i > 0) {
+        if ((uint32_t)i > from) {
             mx = kmer_unit_fold<BITS>(u[i - 1], nb, old[(i - 1) & 1], mx);
             asm volatile("" : "+v"(mx) : : "memory");      // folded here, not after the last unit (the compiler sinks the
                                                            // folds there, 128 returns live): the returns die now
             after(i - 1);
         }
-
     }
     mx = kmer_unit_fold<BITS>(u[N - 1], nb, old[(N - 1) & 1], mx);
     after(N - 1);
+    return mx;
+}
+
+// Lane s holds where the list of sample s starts (in units, two halves) and how many units it has.  The sample asked
+// for is wave-uniform, so its extent is read into scalar registers (no LDS permute): a unit's address is then a scalar
+// base plus the lane.
+struct KmerListExtents {
+    uint32_t first_lo, first_hi, n_units;
+    __device__ __forceinline__ uint32_t units_of(uint32_t s) const {
+        return (uint32_t)__builtin_amdgcn_readlane((int)n_units, (int)s);
+    }
+    __device__ __forceinline__ uint64_t first_of(uint32_t s) const {
+        return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)first_hi, (int)s) << 32) |
+               (uint32_t)__builtin_amdgcn_readlane((int)first_lo, (int)s);
+    }
+};
+
+// What lies beyond the first 64 units of the lists s_begin .. s_end - 1, four wave loads at a time: plain adds, or
+// returning ones folded into mx.
+template <int BITS, bool PLAIN>
+__device__ __forceinline__ uint32_t kmer_count_tails(uint32_t *cnt, uint32_t spare, const uint4 *__restrict__ units,
+                                                     const KmerListExtents &ext, uint32_t s_begin, uint32_t s_end, uint32_t nb,
+                                                     uint32_t mx) {
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t s = s_begin; s < s_end; s++) {
+        const uint32_t n = ext.units_of(s);
+        if (n <= (uint32_t)kWave) continue;
+        const uint4 *list = units + ext.first_of(s);
+        for (uint32_t at = kWave; at < n; at += 4u * kWave) {
+            uint4 u[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t t = at + (uint32_t)i * kWave + lane;
+                u[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+                if (t < n) u[i] = list[t];
+            }
+            if (PLAIN) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) kmer_unit_plain<BITS>(cnt, spare, u[i], nb);
+            } else {
+                mx = kmer_count_units<BITS>(cnt, spare, u, nb, mx, [](int) {});
+            }
+        }
+    }
     return mx;
 }
 
@@ -229,7 +316,9 @@ __global__ __launch_bounds__(kWave) void bmf_vote_kernel_lists(DevParams P, cons
     }
     const uint32_t n_dw = (P.nb + kPer - 1u) / kPer, n_q = (n_dw + 3u) >> 2;   // counter dwords, 16-byte groups of them
     uint32_t *stage = lds_cnt + n_q * 4u;      // [0..63] ids at the maximum, [64] how many
-    const uint32_t spare = n_q * 4u + lane;    // (adding 0 to a staged id changes nothing)
+    const uint32_t spare = n_q * 4u + lane;    // the lane's dword of the staging area, where its padding ids add: 0 from a
+                                               // returning unit, garbage from a plain one.  Harmless: every add precedes
+                                               // the scan, which overwrites stage[0 .. total - 1] before those are read
     for (uint32_t i = lane; i < n_q; i += kWave) reinterpret_cast<uint4 *>(lds_cnt)[i] = make_uint4(0, 0, 0, 0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -243,36 +332,37 @@ __global__ __launch_bounds__(kWave) void bmf_vote_kernel_lists(DevParams P, cons
         first = offsets[h];
         n_units = (uint32_t)(offsets[(size_t)h + 1u] - first);
     }
+    const KmerListExtents ext{(uint32_t)first, (uint32_t)(first >> 32), n_units};
+    const bool tails = __ballot(n_units > (uint32_t)kWave) != 0;   // heavy k-mers; one with no indexed q-gram holds all NB ids
+    const uint32_t n_plain = P.S > P.F ? P.S - P.F : 0u;           // lists 0 .. n_plain - 1 are the plain ones
+    bool fenced = n_plain == 0;                                    // no plain list: the kernel is the all-returning one
     uint32_t mx = 0;
     for (uint32_t s0 = 0; s0 < P.S; s0 += 16u) {
-        // the first 64 units of up to 16 lists, all issued before the first is counted
+        // the first 64 units of up to 16 lists, all issued before the first is counted.  No `s0 + i < S` test: S <= 64
+        // (the library refuses more), so s0 + i <= 63 names a lane, and a lane >= S holds n_units 0: nothing is loaded
         uint4 u[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) {
-            const uint64_t f = __shfl(first, (int)(s0 + i) & 63, kWave);
-            const uint32_t n = s0 + i < P.S ? __shfl(n_units, (int)(s0 + i) & 63, kWave) : 0u;
+            const uint32_t n = ext.units_of((s0 + i) & 63u);
             u[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-            if (lane < n) u[i] = units[f + lane];
+            if (lane < n) u[i] = units[ext.first_of((s0 + i) & 63u) + lane];
         }
-        mx = kmer_count_units<BITS>(lds_cnt, spare, u, P.nb, mx, [](int) {});
-    }
-    // what lies beyond 64 units (heavy k-mers; a k-mer with no indexed q-gram holds all NB ids): four wave loads at a time
-    if (__ballot(n_units > (uint32_t)kWave) != 0) {
-        for (uint32_t s = 0; s < P.S; s++) {
-            const uint64_t f = __shfl(first, (int)s, kWave);
-            const uint32_t n = __shfl(n_units, (int)s, kWave);
-            for (uint32_t at = kWave; at < n; at += 4u * kWave) {
-                uint4 u[4];
+        const uint32_t np = n_plain > s0 ? min(n_plain - s0, 16u) : 0u;    // the plain ones among these 16 come first
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const uint32_t t = at + (uint32_t)i * kWave + lane;
-                    u[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-                    if (t < n) u[i] = units[f + t];
-                }
-                mx = kmer_count_units<BITS>(lds_cnt, spare, u, P.nb, mx, [](int) {});
-            }
+        for (int i = 0; i < 16; i++)
+            if ((uint32_t)i < np) kmer_unit_plain<BITS>(lds_cnt, spare, u[i], P.nb);
+        if (np == 16u) continue;
+        if (!fenced) {
+            // the last plain head is issued: the plain lists' tails, then the fence of invariant 2, once
+            fenced = true;
+            if (tails) kmer_count_tails<BITS, true>(lds_cnt, spare, units, ext, 0u, n_plain, P.nb, 0u);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
+        mx = kmer_count_units<BITS>(lds_cnt, spare, u, P.nb, mx, [](int) {}, np);
     }
+    if (tails) mx = kmer_count_tails<BITS, false>(lds_cnt, spare, units, ext, n_plain, P.S, P.nb, mx);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, kWave));
     // fewest misses = S - mx; nothing below F misses: every level of the reference's filter is empty
