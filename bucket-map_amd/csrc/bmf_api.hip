@@ -160,6 +160,7 @@ struct bmf_ctx {
     uint64_t klist_kmers = 0, klist_bytes = 0;   // 4^k; bytes of offsets + lists
     int klist_bits = 0;              // bits per hit counter of the vote kernel: 4 (S <= 15) or 8
     size_t klist_lds = 0;
+    int klist_waves = 0;             // waves that share one item of the vote kernel (kmer_item_waves): 1, 2 or 4
     double klist_mean_bytes = 0.0;   // list bytes a sample meets, as the estimate found them (BMF_LOG_TUNE prints it)
     uint32_t list_cap = 0;           // ids per (window, orientation) a batch's list buffer is sized for: the G-rows form
     // constants
@@ -657,6 +658,39 @@ static bool kmer_lists_pay(double mean_list_bytes, uint32_t G, uint32_t row_byte
     return mean_list_bytes * kKmerListsRatio <= (double)((G + 1u) / 2u) * (double)row_bytes;
 }
 
+// bmf_vote_kernel_lists<bits, waves>
+static const void *kmer_vote_kernel(int bits, int waves) {
+    using namespace bmf;
+    if (bits == 4)
+        return waves == 4   ? reinterpret_cast<const void *>(bmf_vote_kernel_lists<4, 4>)
+               : waves == 2 ? reinterpret_cast<const void *>(bmf_vote_kernel_lists<4, 2>)
+                            : reinterpret_cast<const void *>(bmf_vote_kernel_lists<4, 1>);
+    return waves == 4   ? reinterpret_cast<const void *>(bmf_vote_kernel_lists<8, 4>)
+           : waves == 2 ? reinterpret_cast<const void *>(bmf_vote_kernel_lists<8, 2>)
+                        : reinterpret_cast<const void *>(bmf_vote_kernel_lists<8, 1>);
+}
+
+// Waves per item of the lists vote, chosen once per load.  The counters of an item take the LDS of one workgroup, and
+// the LDS decides how many workgroups c a CU holds (160 KiB over the one-wave kernel's bytes).  Items finish at the rate
+// resident workgroups / time per item, and W waves shorten an item's time, but not to 1 / W: the dependent loads ahead of
+// the first add and the barriers do not split (profiles/r12/README.md: time per item with two / four waves 0.84 / 0.59 of
+// one wave's at NB = 26 413, 0.53 / 0.40 at NB = 65 304; of four-wave workgroups the registers let 7 reside per CU).
+//   c > 16   one wave per item, as before: up to 32 one-wave workgroups fill the CU's 32 wave slots, and sharing an
+//            item would halve the resident items (17 .. 31 not measured; the tests' small NB lies far above)
+//   9 .. 16  two waves: as many workgroups, twice the waves (measured at c = 11, the headline shape: the vote kernel
+//            8.63 -> 7.29 ms; four waves 8.05 ms there, 7 workgroups)
+//   c <= 8   four waves: the LDS holds fewer workgroups than the registers do (measured at c = 5, NB = 65 304: 26.6 ms
+//            with one wave, 17.7 ms with two, 13.3 ms with four)
+// BMF_LISTS_ITEM_WAVES=1|2|4 forces a value (read here, at load).
+static int kmer_item_waves(size_t lds_one_wave) {
+    if (const char *env = getenv("BMF_LISTS_ITEM_WAVES")) {
+        const int w = atoi(env);
+        if (w == 1 || w == 2 || w == 4) return w;
+    }
+    const size_t resident = (size_t)(160u * 1024u) / std::max<size_t>(lds_one_wave, 1);
+    return resident > 16 ? 1 : (resident > 8 ? 2 : 4);
+}
+
 // The per-k-mer lists (bmf_kmer_lists.hip.h) for the index just loaded, considered before the pair table and under the
 // same gate.  True: they serve, and the pair table is not built.  False, with nothing left allocated: not eligible
 // (sliced rows; NB > 65 535, kPadId must be no bucket), BMF_KMER_LISTS=0, the rule above says no (BMF_KMER_LISTS=1
@@ -670,9 +704,9 @@ static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
     const uint64_t n_k = 1ull << (2 * c->p.k), n_prefix = n_k / 4;
     const uint32_t row_bytes = (d.nb + 7u) >> 3;
     const int bits = d.S <= 15u ? 4 : 8;
-    const size_t lds = bmf::kmer_vote_lds_bytes(d.nb, (uint32_t)bits);
-    const void *kernel = bits == 4 ? reinterpret_cast<const void *>(bmf::bmf_vote_kernel_lists<4>)
-                                   : reinterpret_cast<const void *>(bmf::bmf_vote_kernel_lists<8>);
+    const int waves = kmer_item_waves(bmf::kmer_vote_lds_bytes(d.nb, (uint32_t)bits));
+    const size_t lds = bmf::kmer_vote_lds_bytes(d.nb, (uint32_t)bits, (uint32_t)waves);
+    const void *kernel = kmer_vote_kernel(bits, waves);
     uint32_t *d_units = nullptr;
     uint64_t *d_off = nullptr, *d_tmp = nullptr;
     uint16_t *d_ids = nullptr;
@@ -714,6 +748,9 @@ static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
     if (getenv("BMF_LOG_TUNE"))
         fprintf(stderr, "bmf: k-mer lists: %.1f B per k-mer over %zu sampled (length-weighted: %.1f B met per sample), pair vote reads %u B per sample: %s\n",
                 16.0 * units / (double)sample.size(), sample.size(), c->klist_mean_bytes, (d.G + 1u) / 2u * row_bytes, pay ? "lists" : (forced ? "lists (forced)" : "pair table"));
+    if (getenv("BMF_LOG_TUNE") && (pay || forced))
+        fprintf(stderr, "bmf: k-mer lists vote: %d wave(s) per item, %zu B of LDS per workgroup (%zu workgroups per CU by LDS)%s\n", waves, lds,
+                (size_t)(160u * 1024u) / lds, getenv("BMF_LISTS_ITEM_WAVES") ? " (BMF_LISTS_ITEM_WAVES)" : "");
     if (!pay && !forced) return give_up();
     (void)hipFree(d_units);
     d_units = nullptr;
@@ -743,6 +780,7 @@ static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
     c->klist_bytes = bytes;
     c->klist_bits = bits;
     c->klist_lds = lds;
+    c->klist_waves = waves;
     set_entries_per_sample(c, 1u, 2u);
     return true;
 }
@@ -1344,8 +1382,9 @@ static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
             c->guard_pending = true;
         }
     } else if (c->dp.pair == 2u) {
-        auto kv = c->klist_bits == 4 ? bmf::bmf_vote_kernel_lists<4> : bmf::bmf_vote_kernel_lists<8>;
-        hipLaunchKernelGGL(kv, dim3(2 * n_windows), dim3(bmf::kWave), c->klist_lds, c->stream, c->dp, c->d_koff,
+        using KmerVote = void (*)(bmf::DevParams, const uint64_t *, const uint4 *, const uint32_t *, const uint32_t *, uint32_t *, uint32_t *);
+        auto kv = reinterpret_cast<KmerVote>(const_cast<void *>(kmer_vote_kernel(c->klist_bits, c->klist_waves)));
+        hipLaunchKernelGGL(kv, dim3(2 * n_windows), dim3(bmf::kWave * c->klist_waves), c->klist_lds, c->stream, c->dp, c->d_koff,
                            reinterpret_cast<const uint4 *>(c->d_kids), b->lists.p, b->list_n.p, b->counts.p, b->buckets.p);
     } else if (c->n_slices == 1) {
         hipLaunchKernelGGL(c->vote, dim3(2 * n_windows), dim3(bmf::kWave), 0, c->stream, c->dp, c->dp.pair ? c->d_pair : c->d_rows,
@@ -1980,6 +2019,12 @@ int bmf_derived_info(bmf_ctx *c, uint32_t *span, uint64_t *n_rows, uint64_t *byt
     if (span) *span = lists ? c->dp.G : (c->dp.pair ? 2u : 1u);
     if (n_rows) *n_rows = lists ? c->klist_kmers : c->pair_rows;
     if (bytes) *bytes = lists ? c->klist_bytes : c->pair_rows * c->dp.pitch;
+    return BMF_OK;
+}
+
+int bmf_lists_item_waves(bmf_ctx *c, uint32_t *waves) {
+    if (!c || !waves) return fail(BMF_ERR_ARG, "bmf_lists_item_waves: null argument");
+    *waves = c->dp.pair == 2u ? (uint32_t)c->klist_waves : 0u;
     return BMF_OK;
 }
 

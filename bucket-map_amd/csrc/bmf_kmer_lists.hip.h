@@ -16,8 +16,10 @@
 //   (bm_scan.hip.h)        units -> offsets
 //   bmf_kmer_fill_kernel   the same ANDs again, the ids written in order (ballot-free: a wave prefix sum of the lanes'
 //                          popcounts per round of 64 chunks)
-//   bmf_vote_kernel_lists  one wave per (window, orientation); the list entries of the sample kernel are the k-mer
-//                          hashes themselves (DevParams::pair == 2).  Per-wave hit counters in LDS, BITS = 4 (S <= 15)
+//   bmf_vote_kernel_lists  one workgroup of W waves per (window, orientation), W = 1 or, where the counters leave room for
+//                          few workgroups per CU, 2 or 4 (below: "Several waves per item"; what follows first describes
+//                          one wave); the list entries of the sample kernel are the k-mer
+//                          hashes themselves (DevParams::pair == 2).  Per-item hit counters in LDS, BITS = 4 (S <= 15)
 //                          or 8 bits per bucket packed in dwords, incremented with LDS atomic adds.  A returning add
 //                          brings back the count before, so the wave knows its highest hit count without looking at
 //                          the counters.  misses = S - hits: an item whose highest count is at most S - F is empty and
@@ -53,6 +55,42 @@
 //                          loads issued ahead, was built and measured slower than this: profiles/r07/README.md.)
 //                          Nothing depends on lists being short: the first 64 units of up to 16 lists are in flight
 //                          at once, what lies beyond them is walked four wave loads at a time.
+//                          Several waves per item (template parameter W; build_kmer_lists chooses once per load,
+//                          BMF_LISTS_ITEM_WAVES forces).  One wave needs about 12 us per item whatever runs beside it,
+//                          and at the headline shape the counters (13.2 KB) let 11 workgroups reside per CU: 11 waves
+//                          out of 32.  An item's S lists are independent streams of atomic adds into one array, so
+//                          W waves of one workgroup share the item and its counters: as many workgroups, W times the
+//                          waves, and each wave's chain of instructions, LDS round trips and zeroing about 1/W as long.
+//                            - Wave w owns the lists s = w, w + W, w + 2 W ... (lane j of the wave holds the extent of
+//                              its list j); its heads go K = 16 / W lists at a time.  A wave with no list (S <= w)
+//                              loads and adds nothing and takes part in every barrier.
+//                            - The zeroing stores are spread over the 64 W lanes; a workgroup barrier follows, since a
+//                              wave's adds land in dwords another wave zeroed.
+//                            - The two invariants hold for the workgroup: (1) at most S - F lists of the item are
+//                              plain, each wholly -- the first S - F in sample order as before, so the plain lists of
+//                              wave w are those of its share with s < S - F, the first ones of its own numbering;
+//                              (2) every plain add of every wave precedes every returning add of every wave: each wave
+//                              issues its plain heads and its plain lists' tails, waits for them (lgkmcnt(0): an LDS
+//                              operation has then been executed) and meets ONE workgroup barrier (kmer_item_sync),
+//                              then come its returning heads and tails.  The adds are atomic per dword, so after the
+//                              barrier no counter exceeds S - F, and a counter that ends at h >= S - F + 1 takes its
+//                              last increment, in the LDS's own order, from a returning add of some wave, which
+//                              brings back h - 1; that wave folds h.
+//                            - Each wave reduces its maximum; the W maxima meet in W dwords of LDS behind a barrier
+//                              (which also puts every add before the scan), so the "empty" exit is taken by all waves
+//                              or by none, like the list_n == 0 exit.  No wave leaves before a barrier others reach.
+//                            - Each wave scans a contiguous range of the counter groups and stages its ids in its own
+//                              64 dwords; the W match counts meet in LDS, the item is cleared iff their sum exceeds
+//                              max_candidates, else wave w writes its ids behind those of the waves before it: the
+//                              same bytes in out_buckets[0 .. count) as with one wave.
+//                            - A padding id of a plain unit adds at the dword of its own lane of its own wave in the
+//                              staging area (64 W dwords, none of them read before it is overwritten); where the
+//                              padding id's dword lies inside the counters (NB > 65 528) it is the top field of the
+//                              last dword, no bucket, for every wave alike.
+//                          LDS per workgroup: the counters + 256 W bytes of staging + 32 bytes of exchange words
+//                          (W > 1).  W = 1 compiles to the one-wave kernel as it was (wavefront-scope fences, no
+//                          barrier).  Registers: W = 2 is held to 6 waves per SIMD (75 VGPRs), so that 11 workgroups =
+//                          22 waves fit; W = 4 to 7 (67 VGPRs: 7 workgroups = 28 waves; 8 per SIMD would spill).
 #pragma once
 
 #include "bmf_kernels.hip.h"
@@ -173,9 +211,32 @@ __global__ __launch_bounds__(kWave) void bmf_kmer_fill_kernel(const uint8_t *__r
     }
 }
 
-// LDS bytes per wave of bmf_vote_kernel_lists: the counters, rounded up to whole 16-byte stores, then the staged ids
+// LDS bytes per workgroup of bmf_vote_kernel_lists: the counters, rounded up to whole 16-byte stores, then the staging
+// area: a dword per lane of each of the item's `waves` waves (its padding ids add there, its ids at the maximum are
+// staged there), and behind them, where several waves share the item, the words through which their maxima and their
+// match counts meet (2 per wave)
 inline uint32_t kmer_vote_counter_bytes(uint32_t nb, uint32_t bits) { return ((nb * bits + 127u) / 128u) * 16u; }
-inline uint32_t kmer_vote_lds_bytes(uint32_t nb, uint32_t bits) { return kmer_vote_counter_bytes(nb, bits) + 64u * 4u + 16u; }
+inline uint32_t kmer_vote_lds_bytes(uint32_t nb, uint32_t bits, uint32_t waves = 1u) {
+    return kmer_vote_counter_bytes(nb, bits) + waves * 64u * 4u + (waves == 1u ? 16u : 32u);
+}
+
+// What separates the phases of an item.  One wave: the LDS executes a wave's instructions in issue order, the
+// wavefront-scope pair only keeps the compiler from moving a relaxed atomic across (no instruction).  W > 1 waves: a
+// workgroup barrier behind a workgroup-scope release (the wave's LDS operations, plain adds included, have been
+// executed: s_waitcnt lgkmcnt(0)), so every LDS operation any wave issued before it precedes every one issued after it.
+// Every wave of the workgroup reaches every one of these, the same number of times.
+template <int W>
+__device__ __forceinline__ void kmer_item_sync() {
+    if constexpr (W == 1) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
 
 // The eight ids of one unit, their adds issued back to back: old[j] is what the dword of id j held before.  An id that
 // is no bucket (kPadId, anything >= NB) adds 0, at its own dword where that lies inside the counters and else at the
@@ -274,8 +335,7 @@ struct KmerListExtents {
 template <int BITS, bool PLAIN>
 __device__ __forceinline__ uint32_t kmer_count_tails(uint32_t *cnt, uint32_t spare, const uint4 *__restrict__ units,
                                                      const KmerListExtents &ext, uint32_t s_begin, uint32_t s_end, uint32_t nb,
-                                                     uint32_t mx) {
-    const uint32_t lane = threadIdx.x;
+                                                     uint32_t mx, uint32_t lane) {
     for (uint32_t s = s_begin; s < s_end; s++) {
         const uint32_t n = ext.units_of(s);
         if (n <= (uint32_t)kWave) continue;
@@ -299,87 +359,129 @@ __device__ __forceinline__ uint32_t kmer_count_tails(uint32_t *cnt, uint32_t spa
     return mx;
 }
 
-template <int BITS>
-__global__ __launch_bounds__(kWave) void bmf_vote_kernel_lists(DevParams P, const uint64_t *__restrict__ offsets,
-                                                              const uint4 *__restrict__ units,
-                                                              const uint32_t *__restrict__ kmer_lists,
-                                                              const uint32_t *__restrict__ list_n,
-                                                              uint32_t *__restrict__ out_counts,
-                                                              uint32_t *__restrict__ out_buckets) {
+// W waves per item (1, 2 or 4; the host chooses once per load).  Heads in flight per wave and batch: 16 lists for one
+// wave, 8 or 4 where the item's lists are shared out, so that the registers of a wave shrink as the waves per CU grow.
+template <int W>
+constexpr int kmer_vote_batch() { return W == 1 ? 16 : (W == 2 ? 8 : 4); }
+// ... and the waves per SIMD the registers must leave room for: 11 workgroups of 2 waves are 22 waves on 4 SIMDs; 4
+// waves per item get 7 (7 workgroups: at 8 per SIMD the kernel spills); one wave: 1, no demand
+template <int W>
+constexpr int kmer_vote_waves_per_simd() { return W == 1 ? 1 : (W == 2 ? 6 : 7); }
+
+template <int BITS, int W = 1>
+__global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_vote_waves_per_simd<W>()))) void bmf_vote_kernel_lists(DevParams P, const uint64_t *__restrict__ offsets,
+                                                                  const uint4 *__restrict__ units,
+                                                                  const uint32_t *__restrict__ kmer_lists,
+                                                                  const uint32_t *__restrict__ list_n,
+                                                                  uint32_t *__restrict__ out_counts,
+                                                                  uint32_t *__restrict__ out_buckets) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_cnt[];
+    static_assert(W == 1 || W == 2 || W == 4, "waves per item");
     constexpr uint32_t kPer = 32u / BITS, kField = (1u << BITS) - 1u;
     constexpr uint32_t kTop = BITS == 4 ? 0x88888888u : 0x80808080u, kLow = ~kTop;
-    const uint32_t lane = threadIdx.x, item = blockIdx.x;
-    if (list_n[item >> 1] == 0) {              // window rejected by the sample kernel
-        if (lane == 0) out_counts[item] = 0;
+    constexpr int K = kmer_vote_batch<W>();
+    const uint32_t tid = threadIdx.x, item = blockIdx.x;
+    // the wave's number within the item (scalar) and the lane within the wave
+    const uint32_t wave = W == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / (uint32_t)kWave));
+    const uint32_t lane = W == 1 ? tid : tid % (uint32_t)kWave;
+    if (list_n[item >> 1] == 0) {              // window rejected by the sample kernel (the whole workgroup leaves)
+        if (tid == 0) out_counts[item] = 0;
         return;
     }
     const uint32_t n_dw = (P.nb + kPer - 1u) / kPer, n_q = (n_dw + 3u) >> 2;   // counter dwords, 16-byte groups of them
-    uint32_t *stage = lds_cnt + n_q * 4u;      // [0..63] ids at the maximum, [64] how many
-    const uint32_t spare = n_q * 4u + lane;    // the lane's dword of the staging area, where its padding ids add: 0 from a
+    uint32_t *stage = lds_cnt + n_q * 4u + wave * (uint32_t)kWave;   // the wave's [0..63] ids at the maximum
+    uint32_t *xch = lds_cnt + n_q * 4u + (uint32_t)(W * kWave);      // W > 1: [w] wave w's maximum, [W + w] its matches
+    const uint32_t spare = n_q * 4u + tid;     // the lane's dword of the staging area, where its padding ids add: 0 from a
                                                // returning unit, garbage from a plain one.  Harmless: every add precedes
                                                // the scan, which overwrites stage[0 .. total - 1] before those are read
-    for (uint32_t i = lane; i < n_q; i += kWave) reinterpret_cast<uint4 *>(lds_cnt)[i] = make_uint4(0, 0, 0, 0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    // lane s holds the extent of sample s's list
+    // The wave's share of the item's lists: the lists s = wave + j W, j = 0 .. n_mine - 1, of which the first np_mine
+    // are plain (s < n_plain: the item's first S - F lists in sample order, as with one wave).  Lane j holds the extent
+    // of the wave's list j.  A wave with no list (S <= wave) loads and adds nothing.
+    const uint32_t n_plain = P.S > P.F ? P.S - P.F : 0u;           // lists 0 .. n_plain - 1 of the item are the plain ones
+    const uint32_t n_mine = W == 1 ? P.S : (P.S > wave ? (P.S - wave + (uint32_t)W - 1u) / (uint32_t)W : 0u);
+    const uint32_t np_mine = W == 1 ? n_plain : (n_plain > wave ? (n_plain - wave + (uint32_t)W - 1u) / (uint32_t)W : 0u);
     uint64_t first = 0;
     uint32_t n_units = 0;
-    if (lane < P.S) {
-        const uint32_t h = kmer_lists[(size_t)item * P.list_len + lane];
-        first = offsets[h];
-        n_units = (uint32_t)(offsets[(size_t)h + 1u] - first);
-    }
+    auto load_extents = [&]() {
+        if (lane < n_mine) {
+            const uint32_t h = kmer_lists[(size_t)item * P.list_len + wave + lane * (uint32_t)W];
+            first = offsets[h];
+            n_units = (uint32_t)(offsets[(size_t)h + 1u] - first);
+        }
+    };
+    if constexpr (W > 1) load_extents();       // two dependent loads, under way while the counters are zeroed
+    for (uint32_t i = tid; i < n_q; i += (uint32_t)(W * kWave)) reinterpret_cast<uint4 *>(lds_cnt)[i] = make_uint4(0, 0, 0, 0);
+    kmer_item_sync<W>();                       // W > 1: the wave's adds land in dwords another wave zeroed
+    if constexpr (W == 1) load_extents();
+
     const KmerListExtents ext{(uint32_t)first, (uint32_t)(first >> 32), n_units};
     const bool tails = __ballot(n_units > (uint32_t)kWave) != 0;   // heavy k-mers; one with no indexed q-gram holds all NB ids
-    const uint32_t n_plain = P.S > P.F ? P.S - P.F : 0u;           // lists 0 .. n_plain - 1 are the plain ones
     bool fenced = n_plain == 0;                                    // no plain list: the kernel is the all-returning one
     uint32_t mx = 0;
-    for (uint32_t s0 = 0; s0 < P.S; s0 += 16u) {
-        // the first 64 units of up to 16 lists, all issued before the first is counted.  No `s0 + i < S` test: S <= 64
-        // (the library refuses more), so s0 + i <= 63 names a lane, and a lane >= S holds n_units 0: nothing is loaded
-        uint4 u[16];
+    for (uint32_t s0 = 0; s0 < n_mine; s0 += (uint32_t)K) {
+        // the first 64 units of up to K lists, all issued before the first is counted.  No `s0 + i < n_mine` test:
+        // S <= 64 (the library refuses more), so s0 + i <= 63 names a lane, and a lane >= n_mine holds n_units 0:
+        // nothing is loaded
+        uint4 u[K];
 #pragma unroll
-        for (int i = 0; i < 16; i++) {
+        for (int i = 0; i < K; i++) {
             const uint32_t n = ext.units_of((s0 + i) & 63u);
             u[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
             if (lane < n) u[i] = units[ext.first_of((s0 + i) & 63u) + lane];
         }
-        const uint32_t np = n_plain > s0 ? min(n_plain - s0, 16u) : 0u;    // the plain ones among these 16 come first
+        const uint32_t np = np_mine > s0 ? min(np_mine - s0, (uint32_t)K) : 0u;   // the plain ones among these K come first
 #pragma unroll
-        for (int i = 0; i < 16; i++)
+        for (int i = 0; i < K; i++)
             if ((uint32_t)i < np) kmer_unit_plain<BITS>(lds_cnt, spare, u[i], P.nb);
-        if (np == 16u) continue;
+        if (np == (uint32_t)K) continue;
         if (!fenced) {
-            // the last plain head is issued: the plain lists' tails, then the fence of invariant 2, once
+            // the wave's last plain head is issued: its plain lists' tails, then the fence of invariant 2, once
             fenced = true;
-            if (tails) kmer_count_tails<BITS, true>(lds_cnt, spare, units, ext, 0u, n_plain, P.nb, 0u);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (tails) kmer_count_tails<BITS, true>(lds_cnt, spare, units, ext, 0u, np_mine, P.nb, 0u, lane);
+            kmer_item_sync<W>();
         }
         mx = kmer_count_units<BITS>(lds_cnt, spare, u, P.nb, mx, [](int) {}, np);
     }
-    if (tails) mx = kmer_count_tails<BITS, false>(lds_cnt, spare, units, ext, n_plain, P.S, P.nb, mx);
+    if constexpr (W > 1) {
+        // a wave whose lists are all plain, or that has none, has not met the fence in the loop: the others wait there
+        if (!fenced) {
+            if (tails) kmer_count_tails<BITS, true>(lds_cnt, spare, units, ext, 0u, np_mine, P.nb, 0u, lane);
+            kmer_item_sync<W>();
+        }
+    }
+    if (tails) mx = kmer_count_tails<BITS, false>(lds_cnt, spare, units, ext, np_mine, n_mine, P.nb, mx, lane);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, kWave));
+    if constexpr (W > 1) {
+        // the item's maximum is the highest of the waves': through xch, so that all of them leave here or none does
+        if (lane == 0) xch[wave] = mx;
+        kmer_item_sync<W>();                    // and every add of every wave precedes the scan
+#pragma unroll
+        for (int w = 0; w < W; w++) mx = max(mx, xch[w]);
+        mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
+    }
     // fewest misses = S - mx; nothing below F misses: every level of the reference's filter is empty
     if (mx + P.F <= P.S) {
-        if (lane == 0) out_counts[item] = 0;
+        if (tid == 0) out_counts[item] = 0;
         return;                                 // (the counters die with the workgroup)
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // the buckets whose counter is mx, in ascending order: lane l of round r holds counter dwords 4 (64 r + l) .. + 3
+    if constexpr (W == 1) kmer_item_sync<W>();
+    // the buckets whose counter is mx, in ascending order: lane l of round r holds counter dwords 4 (64 r + l) .. + 3.
+    // Wave w scans the rounds w R .. (w + 1) R - 1, R = ceil(rounds / W): contiguous, so the waves' ids, one wave after
+    // the other, are in ascending order
+    uint32_t q_begin = 0, q_end = n_q;
+    if constexpr (W > 1) {
+        const uint32_t per_wave = (((n_q + (uint32_t)kWave - 1u) / (uint32_t)kWave + (uint32_t)W - 1u) / (uint32_t)W) * (uint32_t)kWave;
+        q_begin = min(wave * per_wave, n_q);
+        q_end = min(q_begin + per_wave, n_q);
+    }
     const uint32_t want = mx * (0xFFFFFFFFu / kField);        // mx in every field
     uint32_t total = 0;
-    for (uint32_t q0 = 0; q0 < n_q; q0 += kWave) {
+    for (uint32_t q0 = q_begin; q0 < q_end; q0 += kWave) {
         const uint32_t qi = q0 + lane;
         uint4 v = make_uint4(~want, ~want, ~want, ~want);
-        if (qi < n_q) v = reinterpret_cast<const uint4 *>(lds_cnt)[qi];
+        if (qi < q_end) v = reinterpret_cast<const uint4 *>(lds_cnt)[qi];
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         uint32_t eq[4], pc = 0;
 #pragma unroll
@@ -409,17 +511,29 @@ __global__ __launch_bounds__(kWave) void bmf_vote_kernel_lists(DevParams P, cons
                 bits &= bits - 1u;
             }
         }
-        if (total > P.max_cand) break;          // cleared whatever follows (wave-uniform)
+        if (total > P.max_cand) break;          // cleared whatever follows (wave-uniform; W > 1: whatever the others found)
     }
-    if (total > P.max_cand) {                   // q_gram_mapper.h:471-476
-        if (lane == 0) out_counts[item] = 0;
+    uint32_t base = 0, all = total;             // ids of the waves before this one, of all waves
+    if constexpr (W > 1) {
+        if (lane == 0) xch[W + wave] = total;
+        kmer_item_sync<W>();
+        all = 0;
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)xch[W + w]);
+            if ((uint32_t)w < wave) base += t;
+            all += t;
+        }
+    }
+    if (all > P.max_cand) {                     // q_gram_mapper.h:471-476
+        if (tid == 0) out_counts[item] = 0;
         return;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < total) out_buckets[(size_t)item * P.max_cand + lane] = stage[lane];
-    if (lane == 0) out_counts[item] = total;
+    if constexpr (W == 1) kmer_item_sync<W>();
+    // all <= max_candidates <= 64: every id of every wave is staged
+    if (lane < total) out_buckets[(size_t)item * P.max_cand + base + lane] = stage[lane];
+    if (tid == 0) out_counts[item] = all;
 }
 
 }  // namespace bmf
+

@@ -80,6 +80,7 @@ SYMBOLS = {
     "bmf_derived_info": (C.c_int, [C.c_void_p, _u32p, _u64p, _u64p]),
     "bmf_derived_row": (C.c_int, [C.c_void_p, C.c_uint64, _u8p]),
     "bmf_derived_form": (C.c_int, [C.c_void_p, _u32p]),
+    "bmf_lists_item_waves": (C.c_int, [C.c_void_p, _u32p]),
     "bmf_pass1_rows": (C.c_int, [C.c_void_p, _u32p]),
     "bmf_pass1_fold": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bmf_batch_pass2_counts": (C.c_int, [C.c_void_p, C.c_void_p, _u32p, _u32p]),
@@ -414,7 +415,10 @@ class Filter:
         _check(lib().bmf_derived_info(self._h, C.byref(span), C.byref(d_rows), C.byref(d_bytes)))
         form = C.c_uint32()
         _check(lib().bmf_derived_form(self._h, C.byref(form)))
-        return {"derived_form": ("rows", "pairs", "kmer_lists")[form.value], "row_pitch_bytes": v[0].value, "chunks_per_lane": v[1].value, "planes": v[2].value,
+        item_waves = C.c_uint32()
+        _check(lib().bmf_lists_item_waves(self._h, C.byref(item_waves)))
+        return {"lists_item_waves": item_waves.value,
+"derived_form": ("rows", "pairs", "kmer_lists")[form.value], "row_pitch_bytes": v[0].value, "chunks_per_lane": v[1].value, "planes": v[2].value,
                 "rows_in_flight": v[3].value, "pass1_rows": r.value, "pass1_fold": fold.value, "pass1_fold_rows": frows.value,
                 "derived_span": span.value, "derived_bytes": d_bytes.value}
 

@@ -205,6 +205,10 @@ int  bmf_derived_row(bmf_ctx *ctx, uint64_t gram, uint8_t *out_row_bytes);
  * lists bmf_derived_info reports span = k-q+1, n_rows = 4^k and bytes = offsets + lists, and bmf_derived_row takes a
  * k-mer and returns its AND, expanded from the list. */
 int  bmf_derived_form(bmf_ctx *ctx, uint32_t *form);
+/* With the per-k-mer lists: how many waves of one workgroup share the hit counters of one (window, orientation) in the
+ * vote kernel -- 1, 2 or 4, chosen once at load from the LDS the counters take (BMF_LISTS_ITEM_WAVES=1|2|4 forces a
+ * value); the outputs do not depend on it.  0 when the lists do not serve. */
+int  bmf_lists_item_waves(bmf_ctx *ctx, uint32_t *waves);
 /* BMF_FLAG_EARLY_EXIT only: index rows per sample the first pass of the two-pass pruning kernel streams
  * for the loaded index; 0 = the single-pass pruning kernel (or no pruning) serves it. */
 int  bmf_pass1_rows(bmf_ctx *ctx, uint32_t *out);
