@@ -361,7 +361,12 @@ int bml_locate(bml_ctx *c, const uint32_t *sample_hash, const uint16_t *sample_p
                uint32_t n_pairs, int32_t *out_offset, uint32_t *out_votes) {
     if (!c) return fail(BML_ERR_ARG, "bml_locate: null context");
     if (!c->loaded) return fail(BML_ERR_STATE, "no genome loaded");
-    if (n_pairs == 0) return BML_OK;
+    if (n_pairs == 0) {                                         // still the last call: its stats are zeros, not the call's before
+        c->ms[0] = c->ms[1] = c->ms[2] = 0.f;
+        c->last_occ = 0;
+        c->last_heavy = 0;
+        return BML_OK;
+    }
     if (!sample_hash || !sample_pos || !seg_len || !pair_bucket || !pair_window || !pair_rc || !out_offset || !out_votes)
         return fail(BML_ERR_ARG, "bml_locate: null argument");
     const uint32_t p = c->p.num_samples;

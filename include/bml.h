@@ -93,7 +93,8 @@ int  bml_locate(bml_ctx *ctx, const uint32_t *sample_hash, const uint16_t *sampl
 
 /* Times of the last bml_locate in ms: ms_scan = its scan kernels, ms_replay = its vote kernels (HIP events on the
  * context's stream), ms_host = what the call spent outside those kernels from the first scan on (stream syncs, the
- * count downloads, growth of the occurrence buffer, placing the groups' segments) -- and the k-mer occurrences it handled. */
+ * count downloads, growth of the occurrence buffer, placing the groups' segments) -- and the k-mer occurrences it handled.
+ * A call with n_pairs = 0 is a call like any other: zeros here and in bml_last_heavy_candidates. */
 int  bml_last_stats(bml_ctx *ctx, float *ms_scan, float *ms_host, float *ms_replay, uint64_t *n_occurrences);
 
 /* Candidates of the last bml_locate that had more occurrences than one thread replays (repeats): they went through

@@ -120,7 +120,7 @@ int  bmv_last_bounded_stats(bmv_ctx *ctx, uint32_t *n_rejected, uint64_t *screen
  * how much work the call is, never what it returns.  Argument checks and limits are bmv_align_long's; in addition group_offset
  * must be as above and hint[g] smaller than the group's size (ignored for an empty group): BMV_ERR_ARG, the message names the
  * group, nothing ran and the context stays usable.  The call leaves untouched what bmv_annotations, bmv_clipped and their stats
- * calls return.
+ * calls return, and everything else outside its row of the table above bmv_results (bmv_last_bounded_stats included).
  * How (bmv_best.hip.h): the hinted alignment of every group is aligned in full by bmv_align_long (a group of one is finished
  * there); every other one goes through score-only kernels -- bmv_align_bounded's screen made to decide: under
  * k = min(hinted edits + margin, query_len) they give the exact (d, end), or the proof that d > k, or give up when the band
@@ -230,7 +230,26 @@ int  bmv_rescued(bmv_ctx *ctx, uint64_t *out_text_start, uint32_t *out_text_len,
  * the aligner took, and the parts a job was cut into.  Any pointer may be NULL. */
 int  bmv_last_rescue_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells, uint32_t *parts);
 
-/* Results of the last bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best or bmv_align_paired:
+/* Who owns what.  Every result accessor and every bmv_last_*_stats returns what ITS OWN last successful call left, whatever
+ * other calls the context has served since, however large their batches were:
+ *   bmv_results, bmv_last_stats          bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best, bmv_align_paired
+ *   bmv_last_bounded_stats               bmv_align_bounded alone: bmv_align_best and bmv_align_paired use the screen's recurrence
+ *                                        in kernels and counters of their own and leave it untouched, as do bmv_align and
+ *                                        bmv_align_long
+ *   bmv_best, bmv_last_best_stats        bmv_align_best, bmv_align_paired; after a plain bmv_align, bmv_align_long or
+ *                                        bmv_align_bounded they still return what the last of those two left (nothing, and
+ *                                        zeros, on a context that never made one)
+ *   bmv_pairs, bmv_last_pair_stats       bmv_pair, bmv_align_paired
+ *   bmv_rescued, bmv_last_rescue_stats   bmv_rescue; its fallback for queries beyond 512 bases runs bmv_align_long's kernels and
+ *                                        puts bmv_results and bmv_last_stats back as it found them
+ *   bmv_annotations, bmv_clipped, bmv_realigned, bmv_leftaligned and their stats: the one call each is named after
+ * A call changes nothing outside its row.  n = 0 is a successful call: it leaves empty results and zero counts in its row.  A
+ * call refused by its checks before anything runs -- every BMV_ERR_ARG, and BMV_ERR_UNSUPPORTED from bmv_align_long,
+ * bmv_realign and bmv_leftalign -- changes nothing at all.  One refusal comes later: bmv_align_bounded, bmv_align_best and
+ * bmv_align_paired hand sub-batches to bmv_align_long, and when an alignment's trace does not fit the scratch there
+ * (BMV_ERR_UNSUPPORTED) the call's own row is unspecified until the next successful call of that row; every other row stays.
+ *
+ * Results of the last bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best or bmv_align_paired:
  *   out_score[a]        alignment.score() = -(edit distance)                       (bucket_locator.h:570)
  *   out_begin[a]        alignment.sequence1_begin_position(), 0-based in the text  (:576)
  *   out_cigar_offset    n + 1 entries; alignment a owns out_cigar[offset[a] .. offset[a+1])
@@ -239,7 +258,9 @@ int  bmv_results(bmv_ctx *ctx, int32_t *out_score, uint32_t *out_begin, uint64_t
                  uint32_t *out_cigar);
 
 /* Kernel time of the last bmv_align (or bmv_align_long) in ms (edit-distance columns + traceback, all chunks) and the number
- * of dynamic-programming cells it stands for (sum of query_len * text_len). */
+ * of dynamic-programming cells it stands for (sum of query_len * text_len).  After bmv_align_bounded, bmv_align_best and
+ * bmv_align_paired: the whole call's kernel time, and the cells of the WHOLE batch -- the sum over every alignment handed in,
+ * also the ones rejected, beyond the margin or never aligned in full. */
 int  bmv_last_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells);
 
 /* The annotation pass: what a SAM record needs beyond score, begin and an M/I/D CIGAR, for alignments whose CIGARs are known.
