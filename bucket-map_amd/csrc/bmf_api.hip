@@ -154,7 +154,8 @@ struct bmf_ctx {
     uint8_t *d_pair = nullptr;
     uint64_t pair_rows = 0;          // rows of d_pair, the all-ones row included
     // Per-k-mer bucket-id lists (bmf_kmer_lists.hip.h), built instead of the pair table where build_kmer_lists' rule
-    // holds: the lists then hold one k-mer hash per sample (dp.pair == 2, dp.E == 1) and bmf_vote_kernel_lists serves.
+    // holds: the lists then hold one 64-bit list extent per sample (dp.pair == 2, dp.E == 2), which the sample kernel takes
+    // from d_koff, and bmf_vote_kernel_lists serves.
     uint64_t *d_koff = nullptr;      // 4^k + 1 offsets in 16-byte units
     uint16_t *d_kids = nullptr;
     uint64_t klist_kmers = 0, klist_bytes = 0;   // 4^k; bytes of offsets + lists
@@ -426,15 +427,17 @@ int bmf_create(const bmf_params *params, bmf_ctx **out) {
     return BMF_OK;
 }
 
-// E list entries per sample: G rows of the index (form 0), ceil(G/2) rows of the pair table (1) or the k-mer itself (2).
-// list_len = S*E ids, rounded up to the ring depth, plus one ring of padding (all-ones rows); never more than the
-// G-rows form's.
+// E list entries per sample: G rows of the index (form 0), ceil(G/2) rows of the pair table (1) or the two dwords of the
+// k-mer's list extent (2).  list_len = S*E ids, rounded up to the ring depth, plus one ring of padding (all-ones rows);
+// never more than the G-rows form's.  Form 2 has no ring and no padding: list_len = 2 S, even, so that the 64-bit
+// extents of every item are 8-byte aligned whatever the depth (3 is one); derived tables are built only for G >= 2
+// (build_pair_table), so 2 S <= S G there too, with equality for k = q + 1.
 static void set_entries_per_sample(bmf_ctx *c, uint32_t E, uint32_t form) {
     bmf::DevParams &d = c->dp;
     const uint32_t depth = (uint32_t)c->depth;
     d.E = E;
     d.pair = form;
-    d.list_len = (d.S * E + depth - 1u) / depth * depth + depth;
+    d.list_len = form == 2u ? d.S * E : (d.S * E + depth - 1u) / depth * depth + depth;
 }
 
 static void free_pair_table(bmf_ctx *c) {
@@ -695,7 +698,8 @@ static int kmer_item_waves(size_t lds_one_wave) {
 // same gate.  True: they serve, and the pair table is not built.  False, with nothing left allocated: not eligible
 // (sliced rows; NB > 65 535, kPadId must be no bucket), BMF_KMER_LISTS=0, the rule above says no (BMF_KMER_LISTS=1
 // overrides the rule, never the memory limits), the exact size exceeds BMF_DERIVED_MAX_MB or half of the free device
-// memory, or an allocation or launch failed -- the pair table is then built as before.
+// memory or the 48 bits a list entry has for a first unit, or an allocation or launch failed -- the pair table is then
+// built as before.
 static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
     const bmf::DevParams &d = c->dp;
     const char *env = getenv("BMF_KMER_LISTS");
@@ -770,7 +774,8 @@ static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
     d_units = nullptr;
     d_tmp = nullptr;
     const uint64_t bytes = total * 16 + (n_k + 1) * sizeof(uint64_t);
-    if (!room(bytes) || hipMalloc(reinterpret_cast<void **>(&d_ids), (size_t)std::max<uint64_t>(total, 1) * 16) != hipSuccess) return give_up();
+    // (a list entry holds a first unit below 2^48, kmer_extent_pack; no list exceeds 8 192 units, NB <= 65 535 above)
+    if (total > bmf::kKmerExtentFirstMax || !room(bytes) || hipMalloc(reinterpret_cast<void **>(&d_ids), (size_t)std::max<uint64_t>(total, 1) * 16) != hipSuccess) return give_up();
     hipLaunchKernelGGL(bmf::bmf_kmer_fill_kernel, dim3((unsigned)std::min<uint64_t>(n_prefix, 1u << 20)), dim3(bmf::kWave), 0, c->stream,
                        c->d_rows, c->d_k2i, d.n_kmers, d.qbits, d.G, d.pitch, d.nb, d.n_chunks, (uint32_t)n_prefix, d_off, d_ids);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return give_up();
@@ -781,7 +786,7 @@ static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
     c->klist_bits = bits;
     c->klist_lds = lds;
     c->klist_waves = waves;
-    set_entries_per_sample(c, 1u, 2u);
+    set_entries_per_sample(c, 2u, 2u);       // one 64-bit extent per sample: two dwords
     return true;
 }
 
@@ -1382,10 +1387,11 @@ static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
             c->guard_pending = true;
         }
     } else if (c->dp.pair == 2u) {
-        using KmerVote = void (*)(bmf::DevParams, const uint64_t *, const uint4 *, const uint32_t *, const uint32_t *, uint32_t *, uint32_t *);
+        using KmerVote = void (*)(bmf::DevParams, const uint4 *, const uint64_t *, const uint32_t *, uint32_t *, uint32_t *);
         auto kv = reinterpret_cast<KmerVote>(const_cast<void *>(kmer_vote_kernel(c->klist_bits, c->klist_waves)));
-        hipLaunchKernelGGL(kv, dim3(2 * n_windows), dim3(bmf::kWave * c->klist_waves), c->klist_lds, c->stream, c->dp, c->d_koff,
-                           reinterpret_cast<const uint4 *>(c->d_kids), b->lists.p, b->list_n.p, b->counts.p, b->buckets.p);
+        hipLaunchKernelGGL(kv, dim3(2 * n_windows), dim3(bmf::kWave * c->klist_waves), c->klist_lds, c->stream, c->dp,
+                           reinterpret_cast<const uint4 *>(c->d_kids), reinterpret_cast<const uint64_t *>(b->lists.p), b->list_n.p,
+                           b->counts.p, b->buckets.p);
     } else if (c->n_slices == 1) {
         hipLaunchKernelGGL(c->vote, dim3(2 * n_windows), dim3(bmf::kWave), 0, c->stream, c->dp, c->dp.pair ? c->d_pair : c->d_rows,
                            b->lists.p, b->list_n.p, b->counts.p, b->buckets.p, (uint32_t *)nullptr);
@@ -1543,9 +1549,10 @@ static int launch_filter(bmf_ctx *c, bmf_batch *b, const uint8_t *d_bases, const
         g.n_windows = b->n_windows;
         const unsigned wgs = std::min<unsigned>((b->n_windows + g.waves_per_wg - 1) / g.waves_per_wg, 2048u);
         auto fn = c->sample_bitmap_lds ? bmf::bmf_sample_kernel<true> : bmf::bmf_sample_kernel<false>;
+        // (d_koff as it is NOW: a reload frees and rebuilds the offsets, and is null unless the k-mer lists serve)
         hipLaunchKernelGGL(fn, dim3(wgs), dim3(g.waves_per_wg * bmf::kWave), c->sample_lds, c->stream, c->dp, g, d_bases, d_quals,
-                           b->win_start.p, b->win_len.p, c->d_qgram_ok, c->d_k2i, c->d_pos_table, b->lists.p, b->list_n.p,
-                           b->rows_anded.p);
+                           b->win_start.p, b->win_len.p, c->d_qgram_ok, c->d_k2i, c->d_pos_table,
+                           static_cast<const uint64_t *>(c->d_koff), b->lists.p, b->list_n.p, b->rows_anded.p);
     }
     if (ev) HIP_TRY(hipEventRecord(ev[1], c->stream));
     if (c->tunable && !c->tuned && b->n_windows >= c->tune_windows) {

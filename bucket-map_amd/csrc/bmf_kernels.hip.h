@@ -37,7 +37,7 @@ struct DevParams {
     uint32_t max_cand;
     uint32_t read_len;
     uint32_t max_kmers;  // read_len - k + 1
-    uint32_t list_len;   // row ids per (window, orientation): S*E rounded up to the ring depth, + depth (padding)
+    uint32_t list_len;   // row ids per (window, orientation): S*E rounded up to the ring depth, + depth (padding); pair == 2: S*E
     uint32_t n_chunks;   // ceil(ceil(NB/8)/16) : 16-byte chunks per row that hold buckets
     uint32_t pitch;      // bytes between rows in HBM (multiple of 128)
     uint32_t ones_row;   // id of the all-ones row appended after the index (for un-indexed q-grams)
@@ -47,10 +47,15 @@ struct DevParams {
     uint32_t max_live;   // two-pass variant: live chunks (= lanes) an item may bring to the recount kernel (16 or 32)
     uint32_t item_base;  // two-pass variant: first (window, orientation) item of this launch (the batch goes out in slices)
     uint32_t row_order;  // entry i of a sample's G row ids is the row of q-gram (row_order >> 4i) & 15: a permutation of 0..G-1
-    uint32_t E;          // list entries per sample: G row ids, ceil(G/2) pair-row ids (pair == 1) or one k-mer (pair == 2)
+    uint32_t E;          // list entries (dwords) per sample: G row ids, ceil(G/2) pair-row ids (pair == 1) or the two
+                         // halves of one list extent (pair == 2)
     uint32_t pair;       // 1: the lists hold rows of the pair table (bmf_pair_rows_kernel): ids of (q+1)-grams; its all-ones row is 4^(q+1)
-                         // 2: they hold the sampled k-mers' hashes, one per sample, unpadded (bmf_kmer_lists.hip.h)
+                         // 2: they hold the extents of the sampled k-mers' id lists, one 64-bit kmer_extent_pack per sample,
+                         //    unpadded (bmf_kmer_lists.hip.h)
 };
+
+// where a k-mer's id list starts and how many 16-byte units it has, in one 64-bit list entry (bmf_kmer_lists.hip.h)
+__host__ __device__ constexpr uint64_t kmer_extent_pack(uint64_t first, uint32_t n_units);
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
@@ -266,8 +271,8 @@ __global__ __launch_bounds__(1024, 8) void bmf_sample_kernel(   // 8 waves per S
     DevParams P, SampleGeom Gm, const uint8_t *__restrict__ bases, const uint8_t *__restrict__ quals,
     const uint64_t *__restrict__ win_start, const uint32_t *__restrict__ win_len,
     const uint32_t *__restrict__ qgram_ok, const int32_t *__restrict__ k2i,
-    const uint16_t *__restrict__ pos_table, uint32_t *__restrict__ row_lists,
-    uint32_t *__restrict__ list_n, uint32_t *__restrict__ rows_anded) {
+    const uint16_t *__restrict__ pos_table, const uint64_t *__restrict__ koff, uint32_t *__restrict__ row_lists,
+    uint32_t *__restrict__ list_n, uint32_t *__restrict__ rows_anded) {   // koff: the k-mer lists' offsets (pair == 2), else null
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t *okmap_lds = reinterpret_cast<uint32_t *>(smem);
@@ -411,9 +416,14 @@ __global__ __launch_bounds__(1024, 8) void bmf_sample_kernel(   // 8 waves per S
                 }
                 cnt += (i1 >= 0) + (i2 >= 0);   // the rows the reference ANDs, whatever table the vote reads
             }
-            if (P.pair == 2u) {         // per-k-mer lists (bmf_kmer_lists.hip.h): the entry is the k-mer itself
-                list_fwd[s] = h;
-                list_rc[s] = hr;
+            if (P.pair == 2u) {
+                // per-k-mer lists (bmf_kmer_lists.hip.h): the entry is the extent of the k-mer's list, so that the vote
+                // goes from its entry straight to the units.  The two reads of the offsets table, at random in a table
+                // far larger than the caches, are made here, where 16 waves per workgroup have latency to spare, and not
+                // by the vote, whose workgroup holds its LDS idle meanwhile.  list_len is even: the entries are 8-byte aligned
+                const uint64_t f = koff[h], fr = koff[hr];
+                reinterpret_cast<uint64_t *>(list_fwd)[s] = kmer_extent_pack(f, (uint32_t)(koff[(size_t)h + 1u] - f));
+                reinterpret_cast<uint64_t *>(list_rc)[s] = kmer_extent_pack(fr, (uint32_t)(koff[(size_t)hr + 1u] - fr));
             } else if (P.pair) {
                 // pair table: entry t is the (q+1)-gram that holds q-grams g and g + 1, g = min(2t, G - 2) -- for an odd
                 // G the last pair overlaps the one before it, and AND is idempotent

@@ -18,8 +18,10 @@
 //                          popcounts per round of 64 chunks)
 //   bmf_vote_kernel_lists  one workgroup of W waves per (window, orientation), W = 1 or, where the counters leave room for
 //                          few workgroups per CU, 2 or 4 (below: "Several waves per item"; what follows first describes
-//                          one wave); the list entries of the sample kernel are the k-mer
-//                          hashes themselves (DevParams::pair == 2).  Per-item hit counters in LDS, BITS = 4 (S <= 15)
+//                          one wave); the list entries of the sample kernel are the extents
+//                          of the sampled k-mers' lists (DevParams::pair == 2; kmer_extent_pack below: the sample
+//                          kernel reads offsets[x] and offsets[x + 1], so an item goes from {list_n, its extents},
+//                          loaded together, straight to the units).  Per-item hit counters in LDS, BITS = 4 (S <= 15)
 //                          or 8 bits per bucket packed in dwords, incremented with LDS atomic adds.  A returning add
 //                          brings back the count before, so the wave knows its highest hit count without looking at
 //                          the counters.  misses = S - hits: an item whose highest count is at most S - F is empty and
@@ -98,6 +100,27 @@
 namespace bmf {
 
 constexpr uint32_t kPadId = 0xFFFFu;
+
+// A list entry (DevParams::pair == 2): the extent of the sampled k-mer's list, written by the sample kernel from
+// offsets[x] and offsets[x + 1] -- the first unit in the low 48 bits, the unit count in the high 16.  The longest list
+// holds all of 65 535 ids, ceil(65 535 / 8) = 8 192 units; 2^48 units are 4 PiB of ids, far beyond any device, and
+// build_kmer_lists refuses a table that would not fit (the pair table serves then), like one that does not fit memory.
+constexpr uint64_t kKmerExtentFirstMax = (1ull << 48) - 1ull;
+constexpr uint32_t kKmerExtentUnitsMax = 0xFFFFu;
+__host__ __device__ constexpr uint64_t kmer_extent_pack(uint64_t first, uint32_t n_units) {
+    return first | ((uint64_t)n_units << 48);
+}
+__host__ __device__ constexpr uint64_t kmer_extent_first(uint64_t e) { return e & kKmerExtentFirstMax; }
+__host__ __device__ constexpr uint32_t kmer_extent_units(uint64_t e) { return (uint32_t)(e >> 48); }
+static_assert(kKmerExtentUnitsMax >= (65535u + 7u) / 8u, "the longest list: all of 65 535 ids");
+static_assert(kmer_extent_first(kmer_extent_pack(kKmerExtentFirstMax, kKmerExtentUnitsMax)) == kKmerExtentFirstMax &&
+                  kmer_extent_units(kmer_extent_pack(kKmerExtentFirstMax, kKmerExtentUnitsMax)) == kKmerExtentUnitsMax,
+              "both fields at their maxima");
+static_assert(kmer_extent_first(kmer_extent_pack(kKmerExtentFirstMax, 0u)) == kKmerExtentFirstMax &&
+                  kmer_extent_units(kmer_extent_pack(kKmerExtentFirstMax, 0u)) == 0u &&
+                  kmer_extent_first(kmer_extent_pack(0u, kKmerExtentUnitsMax)) == 0u &&
+                  kmer_extent_units(kmer_extent_pack(0u, kKmerExtentUnitsMax)) == kKmerExtentUnitsMax,
+              "neither field reaches into the other");
 
 // the AND of the G - 1 rows the four k-mers of prefix p share, and the rows of their four q-grams 0: chunk c
 struct KmerPrefixRows {
@@ -369,9 +392,8 @@ template <int W>
 constexpr int kmer_vote_waves_per_simd() { return W == 1 ? 1 : (W == 2 ? 6 : 7); }
 
 template <int BITS, int W = 1>
-__global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_vote_waves_per_simd<W>()))) void bmf_vote_kernel_lists(DevParams P, const uint64_t *__restrict__ offsets,
-                                                                  const uint4 *__restrict__ units,
-                                                                  const uint32_t *__restrict__ kmer_lists,
+__global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_vote_waves_per_simd<W>()))) void bmf_vote_kernel_lists(DevParams P, const uint4 *__restrict__ units,
+                                                                  const uint64_t *__restrict__ kmer_extents,
                                                                   const uint32_t *__restrict__ list_n,
                                                                   uint32_t *__restrict__ out_counts,
                                                                   uint32_t *__restrict__ out_buckets) {
@@ -384,6 +406,17 @@ __global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_
     // the wave's number within the item (scalar) and the lane within the wave
     const uint32_t wave = W == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / (uint32_t)kWave));
     const uint32_t lane = W == 1 ? tid : tid % (uint32_t)kWave;
+    // The wave's share of the item's lists: the lists s = wave + j W, j = 0 .. n_mine - 1, of which the first np_mine
+    // are plain (s < n_plain: the item's first S - F lists in sample order, as with one wave).  Lane j holds the extent
+    // of the wave's list j.  A wave with no list (S <= wave) loads and adds nothing.
+    const uint32_t n_plain = P.S > P.F ? P.S - P.F : 0u;           // lists 0 .. n_plain - 1 of the item are the plain ones
+    const uint32_t n_mine = W == 1 ? P.S : (P.S > wave ? (P.S - wave + (uint32_t)W - 1u) / (uint32_t)W : 0u);
+    const uint32_t np_mine = W == 1 ? n_plain : (n_plain > wave ? (n_plain - wave + (uint32_t)W - 1u) / (uint32_t)W : 0u);
+    // list_n and the extents are both addressed by `item` alone, so both loads are issued before the branch on list_n:
+    // one level of global-load latency ahead of the units, not two.  The extents of a rejected window are stale (an
+    // earlier batch's) or were never written: loaded, since the buffer is there for every window, and not used
+    uint64_t extent = 0;
+    if (lane < n_mine) extent = kmer_extents[(size_t)item * (P.list_len >> 1) + wave + lane * (uint32_t)W];
     if (list_n[item >> 1] == 0) {              // window rejected by the sample kernel (the whole workgroup leaves)
         if (tid == 0) out_counts[item] = 0;
         return;
@@ -395,26 +428,12 @@ __global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_
                                                // returning unit, garbage from a plain one.  Harmless: every add precedes
                                                // the scan, which overwrites stage[0 .. total - 1] before those are read
 
-    // The wave's share of the item's lists: the lists s = wave + j W, j = 0 .. n_mine - 1, of which the first np_mine
-    // are plain (s < n_plain: the item's first S - F lists in sample order, as with one wave).  Lane j holds the extent
-    // of the wave's list j.  A wave with no list (S <= wave) loads and adds nothing.
-    const uint32_t n_plain = P.S > P.F ? P.S - P.F : 0u;           // lists 0 .. n_plain - 1 of the item are the plain ones
-    const uint32_t n_mine = W == 1 ? P.S : (P.S > wave ? (P.S - wave + (uint32_t)W - 1u) / (uint32_t)W : 0u);
-    const uint32_t np_mine = W == 1 ? n_plain : (n_plain > wave ? (n_plain - wave + (uint32_t)W - 1u) / (uint32_t)W : 0u);
-    uint64_t first = 0;
-    uint32_t n_units = 0;
-    auto load_extents = [&]() {
-        if (lane < n_mine) {
-            const uint32_t h = kmer_lists[(size_t)item * P.list_len + wave + lane * (uint32_t)W];
-            first = offsets[h];
-            n_units = (uint32_t)(offsets[(size_t)h + 1u] - first);
-        }
-    };
-    if constexpr (W > 1) load_extents();       // two dependent loads, under way while the counters are zeroed
+    // (the extents arrive while the counters are zeroed)
     for (uint32_t i = tid; i < n_q; i += (uint32_t)(W * kWave)) reinterpret_cast<uint4 *>(lds_cnt)[i] = make_uint4(0, 0, 0, 0);
     kmer_item_sync<W>();                       // W > 1: the wave's adds land in dwords another wave zeroed
-    if constexpr (W == 1) load_extents();
 
+    const uint64_t first = kmer_extent_first(extent);               // a lane >= n_mine holds extent 0: no units
+    const uint32_t n_units = kmer_extent_units(extent);
     const KmerListExtents ext{(uint32_t)first, (uint32_t)(first >> 32), n_units};
     const bool tails = __ballot(n_units > (uint32_t)kWave) != 0;   // heavy k-mers; one with no indexed q-gram holds all NB ids
     bool fenced = n_plain == 0;                                    // no plain list: the kernel is the all-returning one
