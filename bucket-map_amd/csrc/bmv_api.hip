@@ -18,6 +18,7 @@
 #include "bmv_realign.hip.h"
 #include "bmv_rescue.hip.h"
 #include "bmv_screen.hip.h"
+#include "bmv_split.hip.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -154,7 +155,7 @@ constexpr uint32_t kSideStreams = 4;
 struct bmv_ctx {
     bmv_params p{};
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;   // (ev2: bmv_split times two kernels without a sync between them)
     hipStream_t side[kSideStreams] = {};       // length classes of one batch run side by side on these
     hipEvent_t side_done[kSideStreams] = {};
     bool loaded = false;
@@ -250,6 +251,15 @@ struct bmv_ctx {
     float ms_leftalign = 0.f;
     uint64_t la_n_compared = 0, la_n_merges = 0, la_n_dropped = 0;
     uint32_t la_n_changed = 0;
+    // bmv_split and bmv_split_pick: the range kernel's outputs, which are the pick kernel's inputs (the views, begin and the
+    // entries go through bmv_annotate's buffers), the pick's outputs, the host results of bmv_segments and what
+    // bmv_last_split_stats reports
+    DevBuf<int64_t> sp_score, sp_g_lo, sp_g_hi, sp_s2;
+    DevBuf<uint32_t> sp_q_lo, sp_q_hi, sp_contig, sp_group_offset, sp_n_seg, sp_seg;
+    std::vector<int64_t> h_sp_score, h_sp_g_lo, h_sp_g_hi, h_sp_s2;
+    std::vector<uint32_t> h_sp_q_lo, h_sp_q_hi, h_sp_n_seg, h_sp_seg;
+    float ms_sp_range = 0.f, ms_sp_pick = 0.f;
+    uint64_t sp_columns = 0, sp_segments = 0;
 };
 
 namespace {
@@ -1238,6 +1248,88 @@ int run_pair(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint3
     return BMV_OK;
 }
 
+// ---- bmv_split and bmv_split_pick ----
+// what the pick takes beyond the five arrays per alignment
+struct SplitArgs {
+    const uint32_t *contig;
+    uint32_t n;
+    const uint32_t *group_offset;
+    uint32_t n_groups, min_score, max_overlap_permille, max_segments;
+};
+
+int check_split_args(const char *who, const SplitArgs &a) {
+    if (a.min_score < 1u) return fail(BMV_ERR_ARG, "%s: min_score must be at least 1 (got %u)", who, a.min_score);
+    if (a.max_overlap_permille > 1000u)
+        return fail(BMV_ERR_ARG, "%s: max_overlap_permille must be in 0..1000 (got %u)", who, a.max_overlap_permille);
+    if (a.max_segments < 1u || a.max_segments > BMV_SPLIT_MAX_SEGMENTS)
+        return fail(BMV_ERR_ARG, "%s: max_segments must be in 1..%u (got %u)", who, BMV_SPLIT_MAX_SEGMENTS, a.max_segments);
+    return BMV_OK;
+}
+
+// what a checked call of either leaves before anything runs: n alignments of zeros, every group without a segment
+void reset_split(bmv_ctx *c, const SplitArgs &a, uint64_t columns) {
+    const size_t slots = (size_t)a.n_groups * a.max_segments;
+    c->h_sp_score.assign(a.n, 0);
+    c->h_sp_g_lo.assign(a.n, 0);
+    c->h_sp_g_hi.assign(a.n, 0);
+    c->h_sp_q_lo.assign(a.n, 0);
+    c->h_sp_q_hi.assign(a.n, 0);
+    c->h_sp_n_seg.assign(a.n_groups, 0);
+    c->h_sp_seg.assign(slots, BMV_BEYOND);
+    c->h_sp_s2.assign(slots, BMV_SPLIT_NONE);
+    c->ms_sp_range = c->ms_sp_pick = 0.f;
+    c->sp_columns = columns;
+    c->sp_segments = 0;
+}
+
+// The pick kernel over checked arguments (n_groups > 0), with score, q_lo, q_hi, g_lo, g_hi in sp_* and text_rc in the views'
+// buffer on the device -- or about to be written there by `range`, which launches the range kernel on the context's stream
+// (bmv_split; bmv_split_pick passes one that launches nothing and says so).  The groups go up first, so that the two kernels
+// run back to back between three events.  The pick's results to the host, where bmv_segments reads them.
+template <typename Range>
+int run_split_pick(bmv_ctx *c, const SplitArgs &a, bool has_range, Range range) {
+    const size_t n = a.n, n_groups = a.n_groups, slots = n_groups * a.max_segments;
+    HIP_TRY(c->sp_group_offset.need_exact(n_groups + 1u));
+    HIP_TRY(c->sp_n_seg.need_exact(n_groups));
+    HIP_TRY(need_exact_all(slots, c->sp_seg, c->sp_s2));
+    HIP_TRY(hipMemcpyAsync(c->sp_group_offset.p, a.group_offset, (n_groups + 1u) * 4, hipMemcpyHostToDevice, c->stream));
+    if (n && a.contig) {
+        HIP_TRY(c->sp_contig.need_exact(n));
+        HIP_TRY(hipMemcpyAsync(c->sp_contig.p, a.contig, n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    bmv::SplitPickJob j{};
+    j.score = c->sp_score.p;
+    j.q_lo = c->sp_q_lo.p;
+    j.q_hi = c->sp_q_hi.p;
+    j.g_lo = c->sp_g_lo.p;
+    j.g_hi = c->sp_g_hi.p;
+    j.text_rc = c->text_rc.p;
+    j.contig = (n && a.contig) ? c->sp_contig.p : nullptr;
+    j.group_offset = c->sp_group_offset.p;
+    j.n_groups = a.n_groups;
+    j.min_score = (int64_t)a.min_score;
+    j.max_overlap_permille = a.max_overlap_permille;
+    j.max_segments = a.max_segments;
+    j.n_seg = c->sp_n_seg.p;
+    j.seg = c->sp_seg.p;
+    j.s2 = c->sp_s2.p;
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(range());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_split_pick_kernel, dim3((a.n_groups + bmv::kSplitWaves - 1u) / bmv::kSplitWaves), dim3(bmv::kSplitWaves * 64u),
+                       0, c->stream, j);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev2, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_sp_n_seg.data(), c->sp_n_seg.p, n_groups * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_sp_seg.data(), c->sp_seg.p, slots * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_sp_s2.data(), c->sp_s2.p, slots * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&c->ms_sp_pick, c->ev1, c->ev2));
+    if (has_range) HIP_TRY(hipEventElapsedTime(&c->ms_sp_range, c->ev0, c->ev1));
+    for (const uint32_t k : c->h_sp_n_seg) c->sp_segments += k;
+    return BMV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1277,7 +1369,7 @@ int bmv_create(const bmv_params *params, bmv_ctx **out) {
         side_ok = side_ok && hipStreamCreateWithFlags(&c->side[k], hipStreamNonBlocking) == hipSuccess &&
                   hipEventCreateWithFlags(&c->side_done[k], hipEventDisableTiming) == hipSuccess;
     if (!side_ok || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess || hipEventCreate(&c->ev2) != hipSuccess ||
         c->lut.need_exact(256) != hipSuccess || hipMemcpy(c->lut.p, lut, 256, hipMemcpyHostToDevice) != hipSuccess) {
         bmv_destroy(c);
         return fail(BMV_ERR_HIP, "bmv_create: %s", hipGetErrorString(hipGetLastError()));
@@ -1301,6 +1393,7 @@ void bmv_destroy(bmv_ctx *c) {
     }
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->ev2) (void)hipEventDestroy(c->ev2);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2141,6 +2234,120 @@ int bmv_last_clip_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_last_clip_stats: null context");
     if (ms_kernels) *ms_kernels = c->h_cl.ms;
     if (n_columns) *n_columns = c->h_cl.n_columns;
+    return BMV_OK;
+}
+
+// Split alignments (include/bmv.h, bmv_split.hip.h): bmv_clip's checks and bmv_annotate's upload, then the range kernel and
+// the pick kernel back to back on the stream -- the ranges never visit the host on their way to the pick.
+int bmv_split(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+              const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+              const uint64_t *cigar_offset, const uint32_t *cigar, const uint32_t *contig, uint32_t n, const uint32_t *group_offset,
+              uint32_t n_groups, uint32_t match, uint32_t penalty, uint32_t min_score, uint32_t max_overlap_permille,
+              uint32_t max_segments) {
+    if (!c || !group_offset) return fail(BMV_ERR_ARG, "bmv_split: null argument");
+    if (match < 1u || match > 1024u || penalty < 1u || penalty > 1024u)
+        return fail(BMV_ERR_ARG, "bmv_split: match and penalty must be in 1..1024 (got %u and %u)", match, penalty);
+    const SplitArgs s{contig, n, group_offset, n_groups, min_score, max_overlap_permille, max_segments};
+    if (const int rc = check_split_args("bmv_split", s)) return rc;
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_split", v, true, begin && cigar_offset)) return rc;
+    if (const int rc = check_groups("bmv_split", group_offset, n_groups, n, nullptr)) return rc;
+    uint64_t columns = 0;
+    if (const int rc = check_annotate_batch(c, "bmv_split", v, begin, cigar_offset, cigar, &columns)) return rc;
+    for (uint32_t a = 0; a < n; a++)
+        if (text_start[a] >> 62)
+            return fail(BMV_ERR_ARG, "alignment %u: text_start %llu does not fit the signed coordinates", a, (unsigned long long)text_start[a]);
+    reset_split(c, s, columns);
+    if (n_groups == 0) return BMV_OK;                           // (then n = 0 too: check_groups)
+
+    bmv::SplitRangeJob j{};
+    std::vector<uint64_t> rebased;
+    HIP_TRY(hipSetDevice(c->p.device));
+    if (n) {
+        if (const int rc = upload_annotate_batch(c, v, begin, cigar_offset, cigar, rebased, j.a)) return rc;
+        HIP_TRY(need_exact_all(n, c->sp_score, c->sp_g_lo, c->sp_g_hi, c->sp_q_lo, c->sp_q_hi));
+    }
+    j.match = match;
+    j.penalty = penalty;
+    j.score = c->sp_score.p;
+    j.q_lo = c->sp_q_lo.p;
+    j.q_hi = c->sp_q_hi.p;
+    j.g_lo = c->sp_g_lo.p;
+    j.g_hi = c->sp_g_hi.p;
+    if (const int rc = run_split_pick(c, s, n != 0u, [&] {
+            if (n == 0u) return hipSuccess;
+            hipLaunchKernelGGL(bmv::bmv_split_range_kernel<bmv::kSplitWaves>, dim3((n + bmv::kSplitWaves - 1u) / bmv::kSplitWaves),
+                               dim3(64u * bmv::kSplitWaves), 0, c->stream, j);
+            return hipGetLastError();
+        }))
+        return rc;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(c->h_sp_score.data(), c->sp_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_sp_q_lo.data(), c->sp_q_lo.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_sp_q_hi.data(), c->sp_q_hi.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_sp_g_lo.data(), c->sp_g_lo.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_sp_g_hi.data(), c->sp_g_hi.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (getenv("BMV_LOG_CLASSES"))
+        fprintf(stderr, "[bmv] split: %u alignments in %u groups, range pass %.3f ms, pick %.3f ms\n", n, n_groups, c->ms_sp_range, c->ms_sp_pick);
+    return BMV_OK;
+}
+
+// The pick alone (include/bmv.h): the five arrays go to the device as given, the pick kernel runs, bmv_segments reads.
+int bmv_split_pick(bmv_ctx *c, const int64_t *score, const uint32_t *q_lo, const uint32_t *q_hi, const int64_t *g_lo, const int64_t *g_hi,
+                   const uint8_t *text_rc, const uint32_t *contig, uint32_t n, const uint32_t *group_offset, uint32_t n_groups,
+                   uint32_t min_score, uint32_t max_overlap_permille, uint32_t max_segments) {
+    if (!c || !group_offset || (n && (!score || !q_lo || !q_hi || !g_lo || !g_hi || !text_rc)))
+        return fail(BMV_ERR_ARG, "bmv_split_pick: null argument");
+    const SplitArgs s{contig, n, group_offset, n_groups, min_score, max_overlap_permille, max_segments};
+    if (const int rc = check_split_args("bmv_split_pick", s)) return rc;
+    if (const int rc = check_groups("bmv_split_pick", group_offset, n_groups, n, nullptr)) return rc;
+    for (uint32_t a = 0; a < n; a++) {
+        if (q_lo[a] > q_hi[a]) return fail(BMV_ERR_ARG, "alignment %u: q_lo %u lies behind q_hi %u", a, q_lo[a], q_hi[a]);
+        if (g_lo[a] > g_hi[a])
+            return fail(BMV_ERR_ARG, "alignment %u: g_lo %lld lies behind g_hi %lld", a, (long long)g_lo[a], (long long)g_hi[a]);
+    }
+    reset_split(c, s, 0);
+    c->h_sp_score.assign(score, score + n);
+    c->h_sp_q_lo.assign(q_lo, q_lo + n);
+    c->h_sp_q_hi.assign(q_hi, q_hi + n);
+    c->h_sp_g_lo.assign(g_lo, g_lo + n);
+    c->h_sp_g_hi.assign(g_hi, g_hi + n);
+    if (n_groups == 0) return BMV_OK;
+    HIP_TRY(hipSetDevice(c->p.device));
+    if (n) {
+        HIP_TRY(need_exact_all(n, c->sp_score, c->sp_g_lo, c->sp_g_hi, c->sp_q_lo, c->sp_q_hi, c->text_rc));
+        HIP_TRY(hipMemcpyAsync(c->sp_score.p, score, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->sp_q_lo.p, q_lo, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->sp_q_hi.p, q_hi, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->sp_g_lo.p, g_lo, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->sp_g_hi.p, g_hi, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->text_rc.p, text_rc, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    return run_split_pick(c, s, false, [] { return hipSuccess; });
+}
+
+int bmv_segments(bmv_ctx *c, int64_t *out_score, uint32_t *out_q_lo, uint32_t *out_q_hi, int64_t *out_g_lo, int64_t *out_g_hi,
+                 uint32_t *out_n_seg, uint32_t *out_seg, int64_t *out_s2) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_segments: null context");
+    copy_out(out_score, c->h_sp_score);
+    copy_out(out_q_lo, c->h_sp_q_lo);
+    copy_out(out_q_hi, c->h_sp_q_hi);
+    copy_out(out_g_lo, c->h_sp_g_lo);
+    copy_out(out_g_hi, c->h_sp_g_hi);
+    copy_out(out_n_seg, c->h_sp_n_seg);
+    copy_out(out_seg, c->h_sp_seg);
+    copy_out(out_s2, c->h_sp_s2);
+    return BMV_OK;
+}
+
+int bmv_last_split_stats(bmv_ctx *c, float *ms_range, float *ms_pick, uint64_t *n_columns, uint64_t *n_segments) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_split_stats: null context");
+    if (ms_range) *ms_range = c->ms_sp_range;
+    if (ms_pick) *ms_pick = c->ms_sp_pick;
+    if (n_columns) *n_columns = c->sp_columns;
+    if (n_segments) *n_segments = c->sp_segments;
     return BMV_OK;
 }
 

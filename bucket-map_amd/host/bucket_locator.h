@@ -21,6 +21,7 @@
 #include "pair_mapq.h"
 #include "pair_rescue.h"
 #include "sam_tags.h"
+#include "split_pick.h"
 
 #include <algorithm>
 #include <array>
@@ -156,6 +157,18 @@ public:
         (void)reads; (void)n_read_bytes; (void)text_start; (void)text_len; (void)text_rc; (void)query_start; (void)query_len;
         (void)begin; (void)cigar_offset; (void)cigar; (void)n; (void)match; (void)penalty; (void)out;
         throw std::runtime_error("--clip: this build's alignment verifier has no clipping pass");
+    }
+    // Split alignments (bmv_split's contract, include/bmv.h): per alignment the stretch clip would keep as a query interval in read
+    // orientation and a reference interval in genome coordinates, per group -- a read's candidates -- the non-conflicting
+    // stretches in chosen order with their competitor scores.  contig: per alignment, or null for one contig.  The rule rests
+    // on the clipping pass, so it is the GPU verifier's; a verifier without one says so.
+    virtual void split(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                       const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                       const uint64_t *cigar_offset, const uint32_t *cigar, const uint32_t *contig, uint32_t n, const uint32_t *group_offset,
+                       uint32_t n_groups, const split_params &params, split_result &out) {
+        (void)reads; (void)n_read_bytes; (void)text_start; (void)text_len; (void)text_rc; (void)query_start; (void)query_len;
+        (void)begin; (void)cigar_offset; (void)cigar; (void)contig; (void)n; (void)group_offset; (void)n_groups; (void)params; (void)out;
+        throw std::runtime_error("--split: this build's alignment verifier has no clipping pass to split by");
     }
     // The affine-gap realignment of alignments given with their begin and M/I/D CIGAR (bmv_realign's contract, include/bmv.h):
     // per alignment the score, begin and entries of the best path inside the band that follows the given one, or -- passed
@@ -473,6 +486,8 @@ private:
     bool _affine = false;                        // --affine: the written alignments realigned under affine gap costs, with AS
     affine_scores _affine_scores{};
     bool _left_align = false;                    // --left-align: the written alignments' indels at their leftmost forward place
+    bool _split = false;                         // --split: per read the non-conflicting clipped stretches of its candidates, a
+    split_params _split_params{};                // primary and 0x800 supplementary records tied by SA:Z (the scores are --clip's)
     float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
     bool _paired = false;                        // --paired: records 2p and 2p + 1 of the FASTQ file are mates, placed together
     uint32_t _min_frag = 1, _max_frag = 1000;    // --frag-range: what a proper pair spans, leftmost to rightmost base
@@ -709,6 +724,15 @@ public:
         _clip = _annotate = true;
         _clip_match = match;
         _clip_penalty = penalty;
+    }
+    // --split: the --clip layout; of a read's candidates the verifier's split pass chooses the segments, only those go through
+    // realign / left_align / clip, and they are written in chosen order: the first as the primary record, the others with flag
+    // 0x800, MAPQ from split_mapq, and -- two or more -- each with an SA:Z tag naming the others (split_pick.h).  Needs set_clip.
+    void set_split(uint32_t min_score, uint32_t max_overlap_permille, uint32_t max_segments) {
+        _split = true;
+        _split_params.min_score = min_score;
+        _split_params.max_overlap_permille = max_overlap_permille;
+        _split_params.max_segments = max_segments;
     }
 
     int get_allowed_mismatch() const { return allowed_mismatch; }
@@ -1021,6 +1045,8 @@ private:
             std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
             clipping ann;                        // (--clip fills score and the clips too)
             std::vector<int32_t> affine_score;   // --affine: per slot of `ann` the realigned path's score
+            split_result split;                  // --split: the verifier's answer for the block, a group per read ...
+            std::vector<uint8_t> chosen;         // ... and per alignment whether it is one of its read's segments
             unsigned int first_read = 0;
             std::exception_ptr failed;
         } blocks[2];
@@ -1036,6 +1062,11 @@ private:
         const bool paired = _paired;                            // --paired: --best with the pick of the pair in the winner's place
         const bool rescue = paired && _rescue_rate >= 0.f;      // --rescue: pairs without a proper combination get a second look
         std::vector<uint32_t> bucket_ref;                       // per bucket the index of its @SQ entry (runs of equal names)
+        const bool split = _split;                              // --split: the chosen segments of a read, and only they
+        if (split && !_clip) throw std::runtime_error("--split writes --clip's records: set_clip comes first");
+        if (split)
+            for (size_t bk = 0; bk < h.bucket_name.size(); bk++)
+                bucket_ref.push_back(bk == 0 ? 0u : bucket_ref[bk - 1] + (h.bucket_name[bk] == h.bucket_name[bk - 1] ? 0u : 1u));
         if (paired) {
             if (locate_res.size() % 2u)
                 throw std::runtime_error(sequence_file + " holds " + std::to_string(locate_res.size()) +
@@ -1048,6 +1079,7 @@ private:
         if ((annotate_here || (_affine && !_v->can_realign()) || (_left_align && !_v->can_left_align())) && flat_genome_.empty())
             for (const auto &seq : genome_->seqs) flat_genome_.insert(flat_genome_.end(), seq.begin(), seq.end());
         auto is_written = [&](const Block &b, size_t a) {       // :570-573, and the edit bound
+            if (split) return b.chosen[a] != 0;                 // (--split: 60 + score means nothing for a part of a read)
             const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
             return !((bounded || best) && b.score[a] == alignment_verifier::kRejected) && !(map_qual < quality_threshold);
         };
@@ -1158,6 +1190,21 @@ private:
                     _v->align(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                               b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.score, b.begin,
                               b.cigar_offset, b.cigar);
+                if (split) {                                    // every candidate's range and the pick, a group per read
+                    const uint32_t n_groups = static_cast<uint32_t>(b.reads.size());
+                    split_params sp = _split_params;
+                    sp.match = _clip_match;
+                    sp.penalty = _clip_penalty;
+                    b.chosen.assign(b.text_start.size(), 0);
+                    b.split.n_seg.assign(n_groups, 0);
+                    if (!b.text_start.empty()) {
+                        _v->split(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(), b.query_start.data(),
+                                  b.query_len.data(), b.begin.data(), b.cigar_offset.data(), b.cigar.data(), b.contig.data(),
+                                  static_cast<uint32_t>(b.text_start.size()), b.group_offset.data(), n_groups, sp, b.split);
+                        for (const uint32_t a : b.split.seg)
+                            if (a != kSplitBeyond) b.chosen[a] = 1;
+                    }
+                }
                 if (_annotate && !b.text_start.empty()) {       // the alignments that will be written, as a batch of their own
                     const size_t n = b.text_start.size();
                     std::vector<uint64_t> ts, qs, co{0};
@@ -1353,6 +1400,10 @@ private:
                         for (uint64_t x = b.cigar_offset[a]; x < b.cigar_offset[a + 1]; x++) dump << (b.cigar[x] >> 4) << "MID"[b.cigar[x] & 15u];
                         dump << (b.cigar_offset[a] == b.cigar_offset[a + 1] ? "*\n" : "\n");
                     }
+                    if (split) {                                // (the read's records follow the loop, in chosen order)
+                        a++;
+                        continue;
+                    }
                     const unsigned int wrapped = 60u + static_cast<unsigned int>(b.score[a]);        // :570
                     const size_t map_qual = best ? bq.mapq : wrapped;
                     if (is_written(b, a) && _clip && b.ann.score[b.ann_slot[a]] == 0) {
@@ -1375,6 +1426,39 @@ private:
                         mapped_locations++;
                     }
                     a++;
+                }
+                if (split) {
+                    // --split: the chosen segments of which the final clip kept something, in chosen order; the first written
+                    // one is the primary
+                    const uint32_t a0 = b.group_offset[r], ms = _split_params.max_segments;
+                    struct segment { uint32_t a; unsigned int mapq, bucket; size_t ref_base; bool is_original; };
+                    std::vector<segment> segs;
+                    for (uint32_t k = 0; k < b.split.n_seg[r]; k++) {
+                        const uint32_t c = b.split.seg[r * ms + k];
+                        if (b.ann.score[b.ann_slot[c]] == 0) continue;
+                        const locate_t &loc = locate_res[b.first_read + r][c - a0];
+                        const int offset = std::get<1>(loc);
+                        segs.push_back({c, split_mapq(b.split.score[c], b.split.s2[r * ms + k]), std::get<0>(loc),
+                                        h.bucket_offsets[std::get<0>(loc)] + static_cast<size_t>(offset < 0 ? 0 : offset), std::get<4>(loc)});
+                    }
+                    std::vector<std::string> sa(segs.size());
+                    for (size_t i = 0; segs.size() > 1 && i < segs.size(); i++) {
+                        const uint32_t s = b.ann_slot[segs[i].a];
+                        append_sa_entry(sa[i], h.bucket_name[segs[i].bucket], b.ann.pos[s] + segs[i].ref_base, !segs[i].is_original,
+                                        b.ann.xcigar.data() + b.ann.xcigar_offset[s], b.ann.xcigar_offset[s + 1] - b.ann.xcigar_offset[s],
+                                        segs[i].mapq, b.ann.nm[s]);
+                    }
+                    std::string sa_tag;
+                    for (size_t i = 0; i < segs.size(); i++) {
+                        sa_tag.clear();
+                        if (segs.size() > 1) {
+                            sa_tag = "SA:Z:";
+                            for (size_t o = 0; o < segs.size(); o++)
+                                if (o != i) sa_tag += sa[o];
+                        }
+                        annotated(r, segs[i].a, h.bucket_name[segs[i].bucket], segs[i].ref_base, segs[i].is_original, i ? 0x800u : 0u,
+                                  segs[i].mapq, sa_tag, "*", 0, 0);
+                    }
                 }
                 if (rescued) {
                     const uint32_t ra = b.rescued_at[r];
@@ -1433,9 +1517,10 @@ private:
                     b.text_rc.push_back(is_original ? 0 : 1);                                               // :563-567
                     b.query_start.push_back(b.reads.back().start);
                     b.query_len.push_back(static_cast<uint32_t>(len));
-                    if (paired) b.contig.push_back(bucket_ref[bucket_id]);
+                    if (paired || split) b.contig.push_back(bucket_ref[bucket_id]);
                     if (bounded) b.max_edits.push_back(static_cast<uint32_t>(std::min(_max_edit_rate * static_cast<float>(len), 4e9f)));
                 }
+                if (split) b.group_offset.push_back(static_cast<uint32_t>(b.text_start.size()));
                 if (best) {
                     // the read's group: the hint is the candidate with the most locator votes, the first of them
                     uint32_t at = 0, most = 0, k = 0;

@@ -57,6 +57,12 @@ struct cmd_arguments {
     bool left_align = false;      // --left-align (bucketmap_align): the written alignments' I and D entries are moved to their
                                   // leftmost equivalent place on the forward strand (bmv_leftalign), after --affine's realignment
                                   // and before annotate or clip (implies --annotate)
+    bool split = false;           // --split (bucketmap_align): a read that spans a breakpoint is written as one primary record and
+                                  // 0x800 supplementary records, tied together by SA:Z tags (bmv_split; implies --clip)
+    unsigned long split_min_score = 40;   // --split-min-score N (implies --split), 1..2^31: the clipping score a segment needs
+    float split_overlap = 0.5f;   // --split-overlap R (implies --split), 0..1: what two segments may share of the shorter one's
+                                  // part of the read; bmv_split takes (uint32_t)(R * 1000) permille
+    unsigned int split_max = 8;   // --split-max N (implies --split), 1..16: segments per read
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -234,7 +240,31 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.affine = true;
         }
         else if (opt == "--left-align") a.left_align = true;
+        else if (opt == "--split") a.split = true;
+        else if (opt == "--split-min-score") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            if (v < 1 || v > 0x80000000ul) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in 1..2^31.");
+            a.split_min_score = v;
+            a.split = true;
+        }
+        else if (opt == "--split-overlap") {
+            const std::string s = value();
+            const float r = as_float(s);
+            if (!(r >= 0.f) || r > 1.f) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a rate between 0 and 1.");
+            a.split_overlap = r;
+            a.split = true;
+        }
+        else if (opt == "--split-max") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            if (v < 1 || v > 16) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in 1..16.");
+            a.split_max = static_cast<unsigned>(v);
+            a.split = true;
+        }
 #else
+        else if (opt == "--split" || opt == "--split-min-score" || opt == "--split-overlap" || opt == "--split-max")
+            throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has no alignments to split.");
         else if (opt == "--left-align")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has no indels to normalise.");
         else if (opt == "--affine" || opt == "--affine-scores" || opt == "--affine-band")
@@ -266,6 +296,12 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         else throw parser_error("Unknown option " + opt + ". In case this is meant to be a non-option/argument/parameter, please specify the start of non-options with '--'.");
     }
     if (!have_indicator) throw parser_error("Option -i/--index-indicator is required but not set.");
+    if (a.split && (a.best || a.paired || a.rescue || a.max_edit_rate >= 0.f))
+        throw parser_error(std::string("Option --split cannot be combined with ") +
+                           (a.rescue ? "--rescue" : a.paired ? "--paired" : a.best ? "--best" : "--max-edit-rate") +
+                           ": they judge a read by the edits of one end-to-end alignment, which mean nothing for a read that "
+                           "spans a breakpoint.");
+    if (a.split) a.clip = a.annotate = true;
     if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;
     if (a.affine || a.left_align) a.annotate = true;

@@ -214,6 +214,62 @@ public:
                   penalty);
     }
 
+    // bmv_split per device: the batch is cut at GROUP borders into ranges of about equal column count (a read's candidates stay
+    // on one device: the pick compares them with each other); the chosen indices are rebased to the batch
+    void split(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len, const uint8_t *text_rc,
+               const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin, const uint64_t *cigar_offset,
+               const uint32_t *cigar, const uint32_t *contig, uint32_t n, const uint32_t *group_offset, uint32_t n_groups,
+               const split_params &p, split_result &out) override {
+        const size_t D = ctx_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        const batch all{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+        const size_t ms = p.max_segments;
+        out.score.assign(n, 0);
+        out.q_lo.assign(n, 0);
+        out.q_hi.assign(n, 0);
+        out.g_lo.assign(n, 0);
+        out.g_hi.assign(n, 0);
+        out.n_seg.assign(n_groups, 0);
+        out.seg.assign(n_groups * ms, kSplitBeyond);
+        out.s2.assign(n_groups * ms, kSplitNone);
+        const std::vector<uint32_t> cut = cut_by_cost(n_groups, D, [&](uint32_t g) {
+            uint64_t columns = 1;
+            for (uint64_t x = cigar_offset[group_offset[g]]; x < cigar_offset[group_offset[g + 1]]; x++) columns += cigar[x] >> 4;
+            return columns;
+        });
+        std::vector<float> ms_range(D, 0.f), ms_pick(D, 0.f);
+        std::vector<uint64_t> columns(D, 0), segments(D, 0);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
+            if (ng == 0) return;
+            const uint32_t a0 = group_offset[g0];
+            const share s = slice(all, a0, group_offset[g0 + ng] - a0);
+            std::vector<uint32_t> off;                          // the range's groups, counted from its first alignment
+            if (D > 1) {
+                off.assign(group_offset + g0, group_offset + g0 + ng + 1);
+                for (uint32_t &o : off) o -= a0;
+            }
+            check(bmv_split(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, begin + s.a0,
+                            cigar_offset + s.a0, cigar, contig ? contig + s.a0 : nullptr, s.n, D > 1 ? off.data() : group_offset, ng, p.match,
+                            p.penalty, p.min_score, p.max_overlap_permille, p.max_segments),
+                  "the GPU split pass failed: ");
+            check(bmv_segments(ctx_[d], out.score.data() + a0, out.q_lo.data() + a0, out.q_hi.data() + a0, out.g_lo.data() + a0,
+                               out.g_hi.data() + a0, out.n_seg.data() + g0, out.seg.data() + g0 * ms, out.s2.data() + g0 * ms),
+                  "reading the split alignments failed: ");
+            for (size_t x = g0 * ms; x < (g0 + ng) * ms; x++)
+                if (out.seg[x] != kSplitBeyond) out.seg[x] += a0;
+            float r = 0.f, k = 0.f;
+            bmv_last_split_stats(ctx_[d], &r, &k, &columns[d], &segments[d]);
+            ms_range[d] = r;
+            ms_pick[d] = k;
+        });
+        std::vector<float> both(D, 0.f);
+        for (size_t d = 0; d < D; d++) both[d] = ms_range[d] + ms_pick[d];
+        std::cerr << "[BENCHMARK]\tGPU split alignments: " << n << " alignments in " << n_groups << " groups, " << sum(columns) << " columns, "
+                  << sum(segments) << " segments; range pass " << *std::max_element(ms_range.begin(), ms_range.end()) << " ms, pick "
+                  << *std::max_element(ms_pick.begin(), ms_pick.end()) << " ms; " << timing(both, t0);
+    }
+
     // bmv_realign per device: the same cut, the results stitched as run() stitches the aligners'
     bool can_realign() const override { return true; }
     void realign(const uint8_t *, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,

@@ -136,6 +136,9 @@ int main(int argc, char **argv) {
         if (args.affine)
             loc.set_affine(bm::affine_scores{args.affine_match, args.affine_mismatch, args.affine_gap_open, args.affine_gap_extend, args.affine_band});
         if (args.left_align) loc.set_left_align();
+        if (args.split)
+            loc.set_split(static_cast<uint32_t>(std::min<unsigned long>(args.split_min_score, 0x80000000ul)),
+                          static_cast<uint32_t>(args.split_overlap * 1000), args.split_max);
         if (args.best) loc.set_best(args.best_margin);
         if (args.paired) loc.set_paired(args.frag_min, args.frag_max);
         if (args.rescue) loc.set_rescue(args.rescue_rate);

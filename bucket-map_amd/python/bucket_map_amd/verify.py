@@ -11,6 +11,8 @@ BMV_OK = 0
 REJECTED = -(2 ** 31)     # BMV_REJECTED: the score of an alignment beyond its edit bound (align_bounded)
 BEYOND = 2 ** 32 - 1      # BMV_BEYOND: no winner (an empty group) / edits beyond best + margin (align_best)
 PAIR_NONE = 2 ** 64 - 1   # BMV_PAIR_NONE: no proper combination (s1) / none at another locus (s2)
+SPLIT_NONE = -(2 ** 63)   # BMV_SPLIT_NONE: a chosen segment without a competitor (s2)
+SPLIT_MAX_SEGMENTS = 16   # BMV_SPLIT_MAX_SEGMENTS
 
 
 class BmvError(RuntimeError):
@@ -67,6 +69,12 @@ SYMBOLS = {
     "bmv_leftalign": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32, _u64p]),
     "bmv_leftaligned": (C.c_int, [C.c_void_p, _u32p, _u64p, _u32p, _u8p, _u32p]),
     "bmv_last_leftalign_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p, _u32p, _u64p, _u64p]),
+    "bmv_split": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, _u32p, C.c_uint32,
+                            _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bmv_split_pick": (C.c_int, [C.c_void_p, _i64p, _u32p, _u32p, _i64p, _i64p, _u8p, _u32p, C.c_uint32, _u32p, C.c_uint32,
+                                 C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bmv_segments": (C.c_int, [C.c_void_p, _i64p, _u32p, _u32p, _i64p, _i64p, _u32p, _u32p, _i64p]),
+    "bmv_last_split_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), _u64p, _u64p]),
 }
 _ready = False
 
@@ -208,6 +216,128 @@ def left_align(window, query, text_rc, begin, cigar) -> dict:
         dropped += stack.pop() >> 4
     return {"begin": len(W) - pos - (ref_len - dropped) if rc else pos, "cigar": stack[::-1] if rc else stack,
             "changed": int(moved or dropped != 0), "dropped": dropped, "compared": compared, "merges": merges}
+
+
+def clip_range(window, query, text_rc, begin, cigar, match=1, penalty=2) -> dict:
+    """bmv_clip's range rule (include/bmv.h) for ONE alignment, in plain Python, for users of the ABI: `window` the text
+    window as it lies in the genome, `query` the read as sequenced, `begin` and the packed M/I/D `cigar` as the aligner gave
+    them.  The columns are taken in forward-strand order; an = column weighs +match, an X, I or D column -penalty; the kept
+    range [l, r) has the greatest sum, among equals the smallest r, then the largest l.  Returns score, clip_left, clip_right,
+    pos and ref_len as bmv_clip reports them, l and r, and what bmv_split derives per alignment: q_lo and q_hi (the kept query
+    interval in READ orientation), g_off_lo = pos and g_off_hi = pos + ref_len (add text_start for g_lo and g_hi)."""
+    w, q = bytes(bytearray(window)), bytes(bytearray(query))
+    m, rc = len(q), bool(text_rc)
+    ents = [(int(e) & 15, int(e) >> 4) for e in cigar]
+    if not ents:
+        return {"score": 0, "clip_left": 0, "clip_right": 0, "pos": 0, "ref_len": 0, "l": 0, "r": 0, "q_lo": 0, "q_hi": m,
+                "g_off_lo": 0, "g_off_hi": 0}
+    ref_all = sum(n for op, n in ents if op != 1)
+    ti, qi = (len(w) - int(begin) - ref_all) if rc else int(begin), 0
+    if rc:
+        ents.reverse()
+    p, col = 0, 0
+    low, low_at = 0, (0, ti, qi)                # the least prefix sum so far, at its latest border: (column, ti, qi)
+    best, best_l, best_r = 0, (0, ti, qi), (0, ti, qi)
+    for op, n in ents:
+        for _ in range(n):
+            if op == 0:
+                tr = _DNA4_RANK[w[ti]]
+                qr = (_DNA4_RANK[q[m - 1 - qi]] ^ 3) if rc else _DNA4_RANK[q[qi]]
+                p += match if tr == qr else -penalty
+                ti, qi = ti + 1, qi + 1
+            elif op == 1:
+                p -= penalty
+                qi += 1
+            else:
+                p -= penalty
+                ti += 1
+            col += 1
+            here = (col, ti, qi)
+            if p - low > best:                  # (strictly: the smallest r; `low` sits at its latest border: the largest l)
+                best, best_l, best_r = p - low, low_at, here
+            if p <= low:
+                low, low_at = p, here
+    if best == 0:
+        cl, cr, pos, ref_len, l, r = 0, m, 0, 0, 0, 0
+    else:
+        cl, cr, pos, ref_len, l, r = best_l[2], m - best_r[2], best_l[1], best_r[1] - best_l[1], best_l[0], best_r[0]
+    return {"score": best, "clip_left": cl, "clip_right": cr, "pos": pos, "ref_len": ref_len, "l": l, "r": r,
+            "q_lo": cr if rc else cl, "q_hi": m - (cl if rc else cr), "g_off_lo": pos, "g_off_hi": pos + ref_len}
+
+
+def split_conflict(a, b, q_lo, q_hi, g_lo, g_hi, text_rc, contig, max_overlap_permille) -> tuple:
+    """(dup, conflict, ovl_q) of two alignments under bmv_split's rules (include/bmv.h)."""
+    ovl_q = max(0, min(int(q_hi[a]), int(q_hi[b])) - max(int(q_lo[a]), int(q_lo[b])))
+    ovl_g = max(0, min(int(g_hi[a]), int(g_hi[b])) - max(int(g_lo[a]), int(g_lo[b])))
+    same = (contig is None or int(contig[a]) == int(contig[b])) and bool(text_rc[a]) == bool(text_rc[b])
+    dup = same and ovl_g > 0 and ovl_q > 0
+    shorter = min(int(q_hi[a]) - int(q_lo[a]), int(q_hi[b]) - int(q_lo[b]))
+    return dup, dup or ovl_q * 1000 > int(max_overlap_permille) * shorter, ovl_q
+
+
+def select_segments(score, q_lo, q_hi, g_lo, g_hi, text_rc, group_offset, min_score, max_overlap_permille, max_segments,
+                    contig=None) -> dict:
+    """bmv_split's pick (include/bmv.h) over numbers, in plain Python: per group the chosen list -- while it is shorter than
+    max_segments, the eligible alignment (score >= min_score) that conflicts with none of the chosen and has the greatest
+    score, the lowest batch index among equals -- and per chosen one the competitor score s2.  Returns n_seg u32[n_groups],
+    seg u32[n_groups, max_segments] (BEYOND in unused slots) and s2 i64[n_groups, max_segments] (SPLIT_NONE)."""
+    n_groups = len(group_offset) - 1
+    n_seg = np.zeros(n_groups, np.uint32)
+    seg = np.full((n_groups, int(max_segments)), BEYOND, np.uint32)
+    s2 = np.full((n_groups, int(max_segments)), SPLIT_NONE, np.int64)
+    arrays = (q_lo, q_hi, g_lo, g_hi, text_rc, contig, max_overlap_permille)
+    for g in range(n_groups):
+        members = range(int(group_offset[g]), int(group_offset[g + 1]))
+        chosen = []
+        while len(chosen) < int(max_segments):
+            top = None
+            for a in members:
+                if a in chosen or int(score[a]) < int(min_score) or any(split_conflict(a, c, *arrays)[1] for c in chosen):
+                    continue
+                if top is None or int(score[a]) > int(score[top]):
+                    top = a
+            if top is None:
+                break
+            chosen.append(top)
+        n_seg[g] = len(chosen)
+        for k, c in enumerate(chosen):
+            seg[g, k] = c
+            for a in members:
+                if a in chosen or int(score[a]) <= 0:
+                    continue
+                dup, _, ovl_q = split_conflict(a, c, *arrays)
+                if not dup and 2 * ovl_q >= int(q_hi[c]) - int(q_lo[c]):
+                    s2[g, k] = max(int(s2[g, k]), int(score[a]))
+    return {"n_seg": n_seg, "seg": seg, "s2": s2}
+
+
+def split_mapq(s1, s2) -> int:
+    """The MAPQ of a chosen segment from its score and its competitor's (host/split_pick.h; a definition by choice, like
+    best_mapq): 60 without a competitor, 0 when the competitor is no worse, else (s1 - s2) * 60 / s1."""
+    s1, s2 = int(s1), int(s2)
+    if s2 == SPLIT_NONE:
+        return 60
+    if s2 >= s1 or s1 <= 0:                      # (a chosen segment has s1 >= min_score >= 1)
+        return 0
+    return (s1 - s2) * 60 // s1
+
+
+def sa_entry(rname, pos0, reverse, xcigar, mapq, nm) -> str:
+    """One entry of SAM's SA:Z tag (host/split_pick.h): rname,pos,strand,CIGAR,mapQ,NM; -- pos 1-based, the written CIGAR with
+    its = and X runs merged into M."""
+    out, run = [], 0
+    for e in xcigar:
+        op, n = int(e) & 15, int(e) >> 4
+        if op in (0, 7, 8):
+            run += n
+            continue
+        if run:
+            out.append(f"{run}M")
+            run = 0
+        out.append(f"{n}{'MIDNSHP=X'[op]}")
+    if run:
+        out.append(f"{run}M")
+    return f"{rname},{int(pos0) + 1},{'-' if reverse else '+'},{''.join(out)},{int(mapq)},{int(nm)};"
 
 
 def select_best(d, end, group_offset, margin):
@@ -674,6 +804,64 @@ class Verifier:
         ms, cols = C.c_float(), C.c_uint64()
         _check(lib().bmv_last_clip_stats(self._h, C.byref(ms), C.byref(cols)))
         return {"ms_kernels": ms.value, "columns": cols.value}
+
+    def _segments(self, n, n_groups, max_segments) -> dict:
+        score, g_lo, g_hi = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+        q_lo, q_hi = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        slots = n_groups * max_segments
+        n_seg, seg, s2 = np.zeros(max(n_groups, 1), np.uint32), np.zeros(max(slots, 1), np.uint32), np.zeros(max(slots, 1), np.int64)
+        _check(lib().bmv_segments(self._h, _p(score, _i64p), _p(q_lo, _u32p), _p(q_hi, _u32p), _p(g_lo, _i64p), _p(g_hi, _i64p),
+                                  _p(n_seg, _u32p), _p(seg, _u32p), _p(s2, _i64p)))
+        return {"score": score[:n], "q_lo": q_lo[:n], "q_hi": q_hi[:n], "g_lo": g_lo[:n], "g_hi": g_hi[:n], "n_seg": n_seg[:n_groups],
+                "seg": seg[:slots].reshape(n_groups, max_segments), "s2": s2[:slots].reshape(n_groups, max_segments)}
+
+    @staticmethod
+    def _contig_arg(contig, n):
+        if contig is None:
+            return None, None
+        cn = np.ascontiguousarray(contig, np.uint32)
+        if len(cn) != n:
+            raise ValueError("contig must hold one entry per alignment")
+        return cn, _p(cn, _u32p)
+
+    def split(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, group_offset,
+              match=1, penalty=2, min_score=40, max_overlap_permille=500, max_segments=8, contig=None) -> dict:
+        """bmv_split on the alignments clip takes, grouped by read as align_best takes them: per alignment the stretch clip
+        would keep (score i64[n], q_lo / q_hi u32[n] in read orientation, g_lo / g_hi i64[n] in genome coordinates), per group
+        the non-conflicting stretches in chosen order, primary first (n_seg u32[n_groups], seg u32[n_groups, max_segments] with
+        BEYOND in unused slots) and their competitor scores (s2 i64[n_groups, max_segments], SPLIT_NONE); include/bmv.h has
+        the contract, clip_range and select_segments restate it.  Leaves the results of every other call untouched."""
+        _keep, n, args = self._annotate_args(reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset,
+                                             cigar)
+        off = np.ascontiguousarray(group_offset, np.uint32)
+        n_groups = len(off) - 1
+        if n_groups < 0:
+            raise ValueError("n_groups + 1 entries in group_offset")
+        _cn, cp = self._contig_arg(contig, n)
+        _check(lib().bmv_split(self._h, *args[:-1], cp, n, _p(off, _u32p), n_groups, int(match), int(penalty), int(min_score),
+                               int(max_overlap_permille), int(max_segments)))
+        return self._segments(n, n_groups, int(max_segments))
+
+    def split_pick(self, score, q_lo, q_hi, g_lo, g_hi, text_rc, group_offset, min_score=40, max_overlap_permille=500,
+                   max_segments=8, contig=None) -> dict:
+        """bmv_split_pick: split's pick alone over alignments given by numbers, as pair is.  Returns what split returns."""
+        sc, gl, gh = (np.ascontiguousarray(x, np.int64) for x in (score, g_lo, g_hi))
+        ql, qh = np.ascontiguousarray(q_lo, np.uint32), np.ascontiguousarray(q_hi, np.uint32)
+        trc, off = np.ascontiguousarray(text_rc, np.uint8), np.ascontiguousarray(group_offset, np.uint32)
+        n, n_groups = len(sc), len(off) - 1
+        if n_groups < 0 or not (len(gl) == len(gh) == len(ql) == len(qh) == len(trc) == n):
+            raise ValueError("one entry per alignment in every array, n_groups + 1 in group_offset")
+        _cn, cp = self._contig_arg(contig, n)
+        _check(lib().bmv_split_pick(self._h, _p(sc, _i64p), _p(ql, _u32p), _p(qh, _u32p), _p(gl, _i64p), _p(gh, _i64p), _p(trc, _u8p),
+                                    cp, n, _p(off, _u32p), n_groups, int(min_score), int(max_overlap_permille), int(max_segments)))
+        return self._segments(n, n_groups, int(max_segments))
+
+    def split_stats(self) -> dict:
+        """Of the last split or split_pick: the range kernel's and the pick kernel's ms, the alignment columns walked and
+        the segments chosen."""
+        ms_r, ms_p, cols, segs = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+        _check(lib().bmv_last_split_stats(self._h, C.byref(ms_r), C.byref(ms_p), C.byref(cols), C.byref(segs)))
+        return {"ms_range": ms_r.value, "ms_pick": ms_p.value, "columns": cols.value, "n_segments": segs.value}
 
     def realign(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, match=1,
                 mismatch=4, gap_open=6, gap_extend=1, band=16) -> dict:

@@ -242,6 +242,7 @@ int  bmv_last_rescue_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells, u
  *   bmv_pairs, bmv_last_pair_stats       bmv_pair, bmv_align_paired
  *   bmv_rescued, bmv_last_rescue_stats   bmv_rescue; its fallback for queries beyond 512 bases runs bmv_align_long's kernels and
  *                                        puts bmv_results and bmv_last_stats back as it found them
+ *   bmv_segments, bmv_last_split_stats   bmv_split, bmv_split_pick
  *   bmv_annotations, bmv_clipped, bmv_realigned, bmv_leftaligned and their stats: the one call each is named after
  * A call changes nothing outside its row.  n = 0 is a successful call: it leaves empty results and zero counts in its row.  A
  * call refused by its checks before anything runs -- every BMV_ERR_ARG, and BMV_ERR_UNSUPPORTED from bmv_align_long,
@@ -448,6 +449,63 @@ int  bmv_leftaligned(bmv_ctx *ctx, uint32_t *out_begin, uint64_t *out_cigar_offs
  * may be NULL. */
 int  bmv_last_leftalign_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_compared, uint32_t *n_changed, uint64_t *n_merges,
                               uint64_t *n_dropped);
+
+/* Split alignments: of a read's candidate alignments, the ones that together describe a read spanning a breakpoint (a
+ * translocation, a large deletion, a chimeric ligation) -- one primary and up to max_segments - 1 supplementary segments,
+ * each candidate cut down to the stretch bmv_clip would keep, no two chosen ones claiming the same part of the read.  A call of
+ * its own, of the bmv_annotate / bmv_clip / bmv_pair family: bmv_clip's inputs (the views, begin, M/I/D entries from any align
+ * call, match, penalty), groups as bmv_align_best takes them (a group is one read's candidates), contig[a] as in bmv_pair (NULL:
+ * one contig), min_score >= 1, max_overlap_permille in 0 .. 1000, 1 <= max_segments <= BMV_SPLIT_MAX_SEGMENTS.  The contract is
+ * exact and stated on the outputs only; group size, lane chunking and device count do not show in them.
+ * Per alignment a, with m = query_len[a]:
+ *   S(a), cl, cr, pos, ref_len   exactly bmv_clip's score, clip_left, clip_right, pos and ref_len for the same inputs (the same
+ *                       tie rules: smallest r, then largest l; an empty CIGAR gives zeros, an alignment without an = column
+ *                       zeros and cr = m)
+ *   q_lo, q_hi          the kept query interval in READ orientation: q_lo = text_rc ? cr : cl, q_hi = m - (text_rc ? cl : cr);
+ *                       qlen = q_hi - q_lo
+ *   g_lo, g_hi          the kept reference interval in forward genome coordinates, signed 64-bit: g_lo = text_start + pos,
+ *                       g_hi = g_lo + ref_len
+ *   eligible(a)         S(a) >= min_score
+ *   ovl_q(a, b)         max(0, min(q_hi) - max(q_lo)); ovl_g the same on the g intervals
+ *   dup(a, b)           same contig, same text_rc, ovl_g > 0 and ovl_q > 0: one alignment found through two windows or buckets
+ *   conflict(a, b)      dup(a, b), or ovl_q(a, b) * 1000 > max_overlap_permille * min(qlen(a), qlen(b)), in 64 bits
+ * Per group the chosen list C starts empty; while |C| < max_segments: among the eligible a not in C with no conflict(a, c) for
+ * any c in C, the one with the greatest S -- the lowest batch index among equals -- is appended; the list ends when there is
+ * none.  C[0] is the primary, the rest are supplementary, in that order.  For each chosen c the competitor score s2(c) is the
+ * greatest S(a) over the group's a that are not in C, have S(a) > 0, are no dup of c and cover at least half of it
+ * (2 * ovl_q(a, c) >= qlen(c)); BMV_SPLIT_NONE when there is none.
+ * What is a choice, not a measurement: the pairwise overlap rule, dup, the competitor rule, and ONE range per candidate -- an
+ * inversion in the middle of a read keeps one range that spans it and loses the inverted part.
+ * Checks before anything is launched: everything bmv_clip refuses, group_offset as in bmv_align_best, the parameter ranges
+ * above, text_start below 2^62: BMV_ERR_ARG, the message names the alignment or group, nothing ran and the context stays usable.
+ * The call leaves untouched what every other result or stats call returns; n = 0 and n_groups = 0 succeed with empty results.
+ * How (bmv_split.hip.h): the range kernel is bmv_clip's range walk -- a wave per alignment, 64 columns of an M entry a step --
+ * carrying the text and query cursors of the running minimum and of the best range along, so that ONE walk gives what bmv_clip
+ * takes its range and its count pass for; the pick kernel runs a wave per group, the candidates in the lanes 64 at a time, a
+ * round per segment: every candidate is tested again against the chosen intervals (kept one per lane and broadcast), the
+ * round's winner is a maximum across the wave, a last sweep gives s2.  Nothing goes back to the host in between. */
+#define BMV_SPLIT_MAX_SEGMENTS 16u
+#define BMV_SPLIT_NONE INT64_MIN
+int  bmv_split(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+               const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+               const uint64_t *cigar_offset, const uint32_t *cigar, const uint32_t *contig, uint32_t n, const uint32_t *group_offset,
+               uint32_t n_groups, uint32_t match, uint32_t penalty, uint32_t min_score, uint32_t max_overlap_permille,
+               uint32_t max_segments);
+/* The pick alone, over numbers, as bmv_pair is: score, q_lo, q_hi, g_lo, g_hi as bmv_segments returns them.  In addition to the
+ * group and parameter checks: q_lo <= q_hi and g_lo <= g_hi per alignment (BMV_ERR_ARG, the message names the alignment).  It
+ * fills the same result row: bmv_segments returns the five arrays as given. */
+int  bmv_split_pick(bmv_ctx *ctx, const int64_t *score, const uint32_t *q_lo, const uint32_t *q_hi, const int64_t *g_lo,
+                    const int64_t *g_hi, const uint8_t *text_rc, const uint32_t *contig, uint32_t n, const uint32_t *group_offset,
+                    uint32_t n_groups, uint32_t min_score, uint32_t max_overlap_permille, uint32_t max_segments);
+/* Of the last bmv_split or bmv_split_pick: out_score, out_q_lo, out_q_hi, out_g_lo, out_g_hi n entries each; out_n_seg n_groups
+ * entries, |C| per group; out_seg and out_s2 n_groups * max_segments entries: the batch indices of group g's chosen alignments
+ * in chosen order from g * max_segments on, and their competitor scores; unused slots hold BMV_BEYOND and BMV_SPLIT_NONE.  Any
+ * pointer may be NULL. */
+int  bmv_segments(bmv_ctx *ctx, int64_t *out_score, uint32_t *out_q_lo, uint32_t *out_q_hi, int64_t *out_g_lo, int64_t *out_g_hi,
+                  uint32_t *out_n_seg, uint32_t *out_seg, int64_t *out_s2);
+/* Of the last bmv_split or bmv_split_pick: the range kernel's and the pick kernel's time in ms (ms_range 0 after
+ * bmv_split_pick), the alignment columns the range kernel walked and the segments chosen in all.  Any pointer may be NULL. */
+int  bmv_last_split_stats(bmv_ctx *ctx, float *ms_range, float *ms_pick, uint64_t *n_columns, uint64_t *n_segments);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py --best [--groups 20000 --len 10000 --text-len 11001] [--groups 200000 --len 300 --text-len 307]
     python tools/bench_verify.py --paired [--pairs 500000 --len 300]
     python tools/bench_verify.py --rescue [--rescue-jobs 500000,4000 --rescue-len 150]
+    python tools/bench_verify.py --split [--reads 200000 --len 300] [--reads 20000 --len 10000]
 
 Prints one JSON line: alignments/s and cell updates/s of the device kernels (HIP events inside bmv_align),
 the wall time of the call (host buffers in, results out), and the CPU restatement (oracle, full DP matrix,
@@ -265,6 +266,89 @@ def paired_main(args):
         "checks": {"first_pairs_identical_to_select_pairs": bool(ok)}}), flush=True)
 
 
+def split_main(args):
+    """Verifier.split on --reads groups of five candidates: a read of --len bases is a chimera of two halves from unrelated
+    places (the second half on the reverse strand for every other read); its candidates, in random order, are the two windows
+    that hold the whole read laid around either half -- as the locator places a long read's window -- and three unrelated
+    windows.  Every candidate is aligned in full (Verifier.align) once; then --repeat calls of split (ms_range, ms_pick) and,
+    on the same batch in the same process, --repeat calls of the unchanged Verifier.clip (its kernel ms: the yardstick).  The
+    first groups are held against verify.clip_range and verify.select_segments, every score against clip's.  One JSON line."""
+    from bucket_map_amd import verify
+
+    rng = np.random.default_rng(20261014)
+    R, m = args.reads, args.len
+    n = m + 1 + int(np.float32(args.indel_rate) * np.float32(m))
+    h, lead = m // 2, (n - m) // 2
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    genome = bases[rng.integers(0, 4, 64 << 20, dtype=np.uint8)]
+    A = rng.integers(m + lead, len(genome) - 2 * n, R)
+    B = rng.integers(m + lead, len(genome) - 2 * n, R)
+    second_rc = np.arange(R) % 2 == 1
+    reads = np.empty((R, m), np.uint8)
+    for r0 in range(0, R, 4096):
+        sl = slice(r0, min(R, r0 + 4096))
+        reads[sl, :h] = genome[A[sl, None] + np.arange(h)]
+        two = genome[B[sl, None] + np.arange(m - h)]
+        reads[sl, h:] = np.where(second_rc[sl, None], comp[two][:, ::-1], two)
+    hit = rng.random(reads.shape) < args.sub
+    reads[hit] = bases[rng.integers(0, 4, int(hit.sum()))]
+    # the window around the first half begins `lead` before it; around the second half: h + lead before it on the forward
+    # strand, `lead` before it on the reverse strand (there the read's second half comes first)
+    own = np.stack([A - lead, np.where(second_rc, B - lead, B - h - lead)], 1)
+    cand = np.concatenate([own, rng.integers(0, len(genome) - n, (R, 3))], 1).astype(np.uint64)
+    strand = np.concatenate([np.zeros((R, 1), np.uint8), second_rc[:, None].astype(np.uint8), rng.integers(0, 2, (R, 3)).astype(np.uint8)], 1)
+    order = np.argsort(rng.random((R, 5)), axis=1)
+    ts = np.take_along_axis(cand, order, axis=1).reshape(-1)
+    rc = np.take_along_axis(strand, order, axis=1).reshape(-1)
+    N = 5 * R
+    tl, ql = np.full(N, n, np.uint32), np.full(N, m, np.uint32)
+    qs = np.repeat(np.arange(R, dtype=np.uint64) * m, 5)
+    groups = np.arange(R + 1, dtype=np.uint32) * 5
+    reads = reads.reshape(-1)
+    v = verify.Verifier()
+    v.load_genome(genome)
+    batch = (reads, ts, tl, rc, qs, ql)
+    t0 = time.perf_counter()
+    _, begin, off, cg = v.align(*batch)
+    align_s = time.perf_counter() - t0
+    split, clip = {"ms_range": [], "ms_pick": [], "wall_s": []}, {"ms_kernels": [], "wall_s": []}
+    for _ in range(args.repeat):
+        t0 = time.perf_counter()
+        got = v.split(*batch, begin, off, cg, groups)
+        split["wall_s"].append(time.perf_counter() - t0)
+        st = v.split_stats()
+        split["ms_range"].append(st["ms_range"])
+        split["ms_pick"].append(st["ms_pick"])
+    for _ in range(args.repeat):
+        t0 = time.perf_counter()
+        clipped = v.clip(*batch, begin, off, cg)
+        clip["wall_s"].append(time.perf_counter() - t0)
+        clip["ms_kernels"].append(v.clip_stats()["ms_kernels"])
+    k = max(10, min(500, 200_000 // m, R))
+    want = {key: [] for key in ("score", "q_lo", "q_hi", "g_lo", "g_hi")}
+    for a in range(5 * k):
+        c = verify.clip_range(genome[int(ts[a]): int(ts[a]) + n], reads[int(qs[a]): int(qs[a]) + m], int(rc[a]), int(begin[a]),
+                              cg[int(off[a]): int(off[a + 1])])
+        for key, x in (("score", c["score"]), ("q_lo", c["q_lo"]), ("q_hi", c["q_hi"]), ("g_lo", int(ts[a]) + c["g_off_lo"]),
+                       ("g_hi", int(ts[a]) + c["g_off_hi"])):
+            want[key].append(x)
+    pick = verify.select_segments(want["score"], want["q_lo"], want["q_hi"], want["g_lo"], want["g_hi"], rc[: 5 * k], groups[: k + 1], 40, 500, 8)
+    ok = all(got[key][: 5 * k].tolist() == want[key] for key in want) and all(np.array_equal(got[key][:k], pick[key]) for key in pick)
+    print(json.dumps({
+        "metric": "bmv_split range pass ms", "value": min(split["ms_range"]), "unit": "ms",
+        "config": {"reads": R, "candidates_per_read": 5, "query_len": m, "text_len": n, "sub": args.sub, "min_score": 40,
+                   "max_overlap_permille": 500, "max_segments": 8, "clip_scores": [1, 2]},
+        "ms_range": split["ms_range"], "ms_pick": split["ms_pick"], "columns": st["columns"],
+        "columns_per_s": st["columns"] / (min(split["ms_range"]) * 1e-3), "segments": st["n_segments"],
+        "reads_with_two_segments": float((got["n_seg"] == 2).mean()),
+        "ms_kernels_of_bmv_clip_same_batch": clip["ms_kernels"], "range_pass_over_clip": min(split["ms_range"]) / min(clip["ms_kernels"]),
+        "split": split, "clip": clip, "align_wall_s": align_s,
+        "checks": {"first_groups_identical_to_the_restatement": bool(ok),
+                   "every_score_is_clips": bool(np.array_equal(got["score"], clipped["score"]))}}), flush=True)
+
+
 def rescue_main(args):
     """Verifier.rescue on jobs of --rescue-len-base mates under the range 1,1000 and max_edits = 0.1 x len: the anchor at a random
     place of a random genome, on either strand, the mate sampled from the other end of a fragment of 2 x len .. 900 bases with
@@ -337,6 +421,7 @@ def main():
     ap.add_argument("--rescue", action="store_true", help="Verifier.rescue beside Verifier.align_bounded on the same views (see rescue_main)")
     ap.add_argument("--rescue-jobs", default="500000,4000", help="--rescue: the job counts, one run each")
     ap.add_argument("--rescue-len", type=int, default=150, help="--rescue: the mates' length")
+    ap.add_argument("--split", action="store_true", help="Verifier.split beside Verifier.clip on groups of five candidates (see split_main)")
     ap.add_argument("--paired", action="store_true", help="Verifier.align_paired beside Verifier.align_best (see paired_main)")
     ap.add_argument("--pairs", type=int, default=500_000)
     ap.add_argument("--best", action="store_true", help="Verifier.align_best on groups of five candidates (see best_main)")
@@ -389,6 +474,8 @@ def main():
         return paired_main(args)
     if args.rescue:
         return rescue_main(args)
+    if args.split:
+        return split_main(args)
 
     rng = np.random.default_rng(20240003)
     m = args.len
