@@ -12,6 +12,7 @@
 #include "bmv_annotate.hip.h"
 #include "bmv_best.hip.h"
 #include "bmv_clip.hip.h"
+#include "bmv_frag.hip.h"
 #include "bmv_leftalign.hip.h"
 #include "bmv_long.hip.h"
 #include "bmv_pair.hip.h"
@@ -25,6 +26,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
@@ -151,6 +153,10 @@ struct EmitHost {
 
 constexpr uint32_t kSideStreams = 4;
 
+namespace {
+struct PairedPending;       // defined beside bmv_paired_begin
+}
+
 // Every device buffer is a DevBuf: `delete` frees them all, bmv_destroy handles only what has an order.
 struct bmv_ctx {
     bmv_params p{};
@@ -213,6 +219,16 @@ struct bmv_ctx {
     std::vector<uint64_t> h_pr_s1, h_pr_s2;
     float ms_pair = 0.f;
     uint64_t pr_combinations = 0;
+    // bmv_frag_spans and bmv_paired_begin with cap > 0: the spans and the bins (the inputs are the pair kernel's), the host
+    // results of bmv_frag and what bmv_last_frag_stats reports
+    DevBuf<uint32_t> fr_span, fr_hist;
+    std::vector<uint32_t> h_fr_span;
+    std::vector<uint64_t> h_fr_hist;
+    float ms_frag = 0.f;
+    uint32_t fr_informative = 0;
+    // what a successful bmv_paired_begin leaves for bmv_paired_finish; gone after the finish, and after any other call of the
+    // bmv_results row
+    std::shared_ptr<PairedPending> pending;
     // bmv_rescue: the jobs' arrays (buffers of its own: the aligners' views are the fallback's), the planned views, the host
     // results of bmv_rescued and what bmv_last_rescue_stats reports
     DevBuf<uint64_t> rs_anchor_start, rs_contig_start, rs_contig_end, rs_query_start, rs_text_start;
@@ -421,6 +437,7 @@ void pack_cigars(bmv_ctx *c, uint32_t n, const std::vector<uint32_t> &pool, cons
 
 void store_results(bmv_ctx *c, uint32_t n, uint64_t cells, float ms, std::vector<int32_t> &score, std::vector<uint32_t> &begin,
                    const std::vector<uint32_t> &pool, const std::vector<uint64_t> &at, const std::vector<uint64_t> &len, uint64_t *total_cigar) {
+    c->pending.reset();         // the row has a new owner: a bmv_paired_begin before it is no longer pending
     c->n_last = n;
     c->n_cells = cells;
     c->ms_kernels = ms;
@@ -976,6 +993,8 @@ struct BestRounds {
           out_end(n, 0u) {}
 };
 
+void leave_pending(bmv_ctx *c);         // (beside bmv_paired_begin)
+
 // The rounds bmv_align_best and bmv_align_paired share, on a checked batch: the seeds -- one alignment per group, the hinted
 // one -- in full by bmv_align_long; every other alignment through the distance kernels under k = seed's edits + margin, and
 // what they leave undecided in full as well; the pick on the device, which restricts (d, end) to d <= best + margin.
@@ -986,6 +1005,7 @@ int best_rounds(bmv_ctx *c, const char *who, const Views &v, const uint32_t *gro
     const uint32_t from = long_from();
     BestFull &f = r.f;
     std::vector<uint32_t> &full = r.full, &h_d = r.d, &h_end = r.end, &h_winner = r.winner, &h_edits = r.edits, &h_out_end = r.out_end;
+    leave_pending(c);           // (a call that fails before its first full alignment has not dropped the pending begin yet)
     c->bs_n_seed = c->bs_n_distance = c->bs_n_beyond = c->bs_n_undecided = c->bs_n_realigned = 0;
     c->bs_cells = 0;
     c->ms_distance = c->ms_pick = 0.f;
@@ -1185,24 +1205,11 @@ int check_pair_args(const char *who, const PairArgs &a) {
     return BMV_OK;
 }
 
-// The pair kernel over checked arguments, with edits and end where they lie on the device (offsets_there: bs_group_offset holds
-// the offsets already); the results to the host, where bmv_pairs reads them.
-int run_pair(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint32_t *d_end, bool offsets_there) {
-    const uint32_t n = a.n, n_groups = a.n_groups, n_pairs = a.n_groups / 2u;
-    c->h_pr_pick.assign(n_groups, BMV_BEYOND);
-    c->h_pr_winner.assign(n_groups, BMV_BEYOND);
-    c->h_pr_proper.assign(n_pairs, 0);
-    c->h_pr_s1.assign(n_pairs, BMV_PAIR_NONE);
-    c->h_pr_s2.assign(n_pairs, BMV_PAIR_NONE);
-    c->ms_pair = 0.f;
-    c->pr_combinations = 0;
-    if (n_pairs == 0) return BMV_OK;
-    for (uint32_t p = 0; p < n_pairs; p++)
-        c->pr_combinations += (uint64_t)(a.group_offset[2u * p + 1u] - a.group_offset[2u * p]) * (a.group_offset[2u * p + 2u] - a.group_offset[2u * p + 1u]);
-    HIP_TRY(hipSetDevice(c->p.device));
+// What the pair kernel and the span kernel read, on its way to the device (the context's device is current, n_groups > 0): the
+// views without reads, the contigs and -- unless offsets_there -- the offsets; j's inputs point at them.
+int upload_pair_inputs(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint32_t *d_end, bool offsets_there, bmv::PairJob &j) {
+    const uint32_t n = a.n, n_groups = a.n_groups;
     HIP_TRY(need_exact_all(n, c->text_start, c->text_len, c->text_rc, c->query_len));
-    HIP_TRY(need_exact_all(n_groups, c->pr_pick, c->pr_winner));
-    HIP_TRY(need_exact_all(n_pairs, c->pr_proper, c->pr_s1, c->pr_s2));
     HIP_TRY(c->bs_group_offset.need_exact((size_t)n_groups + 1u));
     if (n) {
         HIP_TRY(hipMemcpyAsync(c->text_start.p, a.text_start, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
@@ -1216,7 +1223,6 @@ int run_pair(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint3
     }
     if (!offsets_there)
         HIP_TRY(hipMemcpyAsync(c->bs_group_offset.p, a.group_offset, ((size_t)n_groups + 1u) * 4, hipMemcpyHostToDevice, c->stream));
-    bmv::PairJob j{};
     j.text_start = c->text_start.p;
     j.text_len = c->text_len.p;
     j.text_rc = c->text_rc.p;
@@ -1225,9 +1231,31 @@ int run_pair(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint3
     j.end = d_end;
     j.contig = (n && a.contig) ? c->pr_contig.p : nullptr;
     j.group_offset = c->bs_group_offset.p;
-    j.n_pairs = n_pairs;
+    j.n_pairs = n_groups / 2u;
     j.min_frag = (int64_t)a.min_frag;
     j.max_frag = (int64_t)a.max_frag;
+    return BMV_OK;
+}
+
+// The pair kernel over checked arguments, with edits and end where they lie on the device (offsets_there: bs_group_offset holds
+// the offsets already); the results to the host, where bmv_pairs reads them.
+int run_pair(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint32_t *d_end, bool offsets_there) {
+    const uint32_t n_groups = a.n_groups, n_pairs = a.n_groups / 2u;
+    c->h_pr_pick.assign(n_groups, BMV_BEYOND);
+    c->h_pr_winner.assign(n_groups, BMV_BEYOND);
+    c->h_pr_proper.assign(n_pairs, 0);
+    c->h_pr_s1.assign(n_pairs, BMV_PAIR_NONE);
+    c->h_pr_s2.assign(n_pairs, BMV_PAIR_NONE);
+    c->ms_pair = 0.f;
+    c->pr_combinations = 0;
+    if (n_pairs == 0) return BMV_OK;
+    for (uint32_t p = 0; p < n_pairs; p++)
+        c->pr_combinations += (uint64_t)(a.group_offset[2u * p + 1u] - a.group_offset[2u * p]) * (a.group_offset[2u * p + 2u] - a.group_offset[2u * p + 1u]);
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(need_exact_all(n_groups, c->pr_pick, c->pr_winner));
+    HIP_TRY(need_exact_all(n_pairs, c->pr_proper, c->pr_s1, c->pr_s2));
+    bmv::PairJob j{};
+    if (const int rc = upload_pair_inputs(c, a, d_edits, d_end, offsets_there, j)) return rc;
     j.pick = c->pr_pick.p;
     j.winner = c->pr_winner.p;
     j.proper = c->pr_proper.p;
@@ -1245,6 +1273,162 @@ int run_pair(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint3
     HIP_TRY(hipMemcpyAsync(c->h_pr_s2.data(), c->pr_s2.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipEventElapsedTime(&c->ms_pair, c->ev0, c->ev1));
+    return BMV_OK;
+}
+
+// ---- bmv_frag_spans ----
+int check_frag_cap(const char *who, uint32_t cap) {
+    if (cap < 1u || cap > bmv::kFragMaxCap) return fail(BMV_ERR_ARG, "%s: cap %u, a fragment cap is 1 .. %u", who, cap, bmv::kFragMaxCap);
+    return BMV_OK;
+}
+
+// The span and histogram kernels over checked arguments (a.min_frag = 1, a.max_frag = cap), with edits and end where they lie
+// on the device; spans and bins to the host, where bmv_frag reads them.  The bins are zeroed here, every call.
+int run_frag(bmv_ctx *c, const PairArgs &a, const uint32_t *d_edits, const uint32_t *d_end, bool offsets_there) {
+    const uint32_t n_pairs = a.n_groups / 2u, n_bins = a.max_frag + 1u;
+    c->h_fr_span.assign(n_pairs, 0u);
+    c->h_fr_hist.assign(n_bins, 0u);
+    c->ms_frag = 0.f;
+    c->fr_informative = 0;
+    if (n_pairs == 0) return BMV_OK;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(c->fr_span.need_exact(n_pairs));
+    HIP_TRY(c->fr_hist.need_exact(n_bins));
+    bmv::FragJob j{};
+    if (const int rc = upload_pair_inputs(c, a, d_edits, d_end, offsets_there, j.P)) return rc;
+    j.span = c->fr_span.p;
+    HIP_TRY(hipMemsetAsync(c->fr_hist.p, 0, (size_t)n_bins * 4, c->stream));
+    // the histogram's grid: resident, and no more blocks than have n_bins spans each to count (a block's fixed cost is
+    // zeroing and flushing its n_bins private bins)
+    const bool in_lds = n_bins <= bmv::kFragLdsBins;
+    const size_t lds_bytes = in_lds ? (size_t)n_bins * 4 : 0;
+    int per_cu = 0, cus = 0;
+    if (in_lds)
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bmv::bmv_frag_hist_lds_kernel, (int)bmv::kFragHistThreads, lds_bytes));
+    else
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bmv::bmv_frag_hist_global_kernel, (int)bmv::kFragHistThreads, 0));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->p.device));
+    const uint32_t resident = (uint32_t)std::max(per_cu, 1) * (uint32_t)std::max(cus, 1);
+    const uint32_t per_block = std::max(in_lds ? n_bins : 0u, bmv::kFragHistThreads * 8u);
+    const uint32_t blocks = std::min(resident, (n_pairs + per_block - 1u) / per_block);
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmv::bmv_frag_span_kernel, dim3((n_pairs + bmv::kPairWaves - 1u) / bmv::kPairWaves), dim3(bmv::kPairWaves * bmv::kWave), 0,
+                       c->stream, j);
+    HIP_TRY(hipGetLastError());
+    if (in_lds)
+        hipLaunchKernelGGL(bmv::bmv_frag_hist_lds_kernel, dim3(blocks), dim3(bmv::kFragHistThreads), lds_bytes, c->stream, c->fr_span.p, n_pairs,
+                           n_bins, c->fr_hist.p);
+    else
+        hipLaunchKernelGGL(bmv::bmv_frag_hist_global_kernel, dim3(blocks), dim3(bmv::kFragHistThreads), 0, c->stream, c->fr_span.p, n_pairs,
+                           n_bins, c->fr_hist.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    std::vector<uint32_t> bins(n_bins);
+    HIP_TRY(hipMemcpyAsync(c->h_fr_span.data(), c->fr_span.p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(bins.data(), c->fr_hist.p, (size_t)n_bins * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&c->ms_frag, c->ev0, c->ev1));
+    std::copy(bins.begin(), bins.end(), c->h_fr_hist.begin());
+    c->fr_informative = n_pairs - bins[0];
+    if (getenv("BMV_LOG_CLASSES"))
+        fprintf(stderr, "[bmv] frag: %u pairs, %u bins %s, %u blocks of %u lanes (%d resident per CU on %d CUs), %.3f ms\n", n_pairs, n_bins,
+                in_lds ? "in LDS" : "by global atomics", blocks, bmv::kFragHistThreads, per_cu, cus, c->ms_frag);
+    return BMV_OK;
+}
+
+// ---- bmv_paired_begin and bmv_paired_finish ----
+// What begin leaves for finish: the caller's arrays (valid and unchanged until finish returns), the checked batch's cell count
+// and the rounds' host state.  edits_there / offsets_there: bs_edits and bs_out_end / bs_group_offset still hold the restricted
+// (edits, end) / the offsets -- bmv_pair and bmv_frag_spans put arrays of their own there and clear both (leave_pending).
+struct PairedPending {
+    Views v;
+    const uint32_t *group_offset, *contig;
+    uint32_t n_groups;
+    uint64_t cells;
+    BestRounds r;
+    bool edits_there = false, offsets_there = false;
+    PairedPending(const Views &v_, const uint32_t *group_offset_, const uint32_t *contig_, uint32_t n_groups_, uint64_t cells_)
+        : v(v_), group_offset(group_offset_), contig(contig_), n_groups(n_groups_), cells(cells_), r(v_.n, n_groups_) {}
+};
+
+// bs_edits, bs_out_end and bs_group_offset are about to hold another call's arrays
+void leave_pending(bmv_ctx *c) {
+    if (c->pending) c->pending->edits_there = c->pending->offsets_there = false;
+}
+
+// edits and end of the rounds to the device, where the rounds themselves did not leave them
+int upload_best_outputs(bmv_ctx *c, const BestRounds &r, uint32_t n) {
+    if (!n) return BMV_OK;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(need_exact_all(n, c->bs_edits, c->bs_out_end));
+    HIP_TRY(hipMemcpyAsync(c->bs_edits.p, r.edits.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->bs_out_end.p, r.out_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    return BMV_OK;
+}
+
+// The first half of bmv_align_paired under the name `who`: its checks except the range, the rounds, and for cap > 0 the spans.
+int paired_begin(bmv_ctx *c, const char *who, const Views &v, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin,
+                 const uint32_t *hint, const uint32_t *contig, uint32_t min_frag, uint32_t max_frag, uint32_t cap, bool outputs_ok) {
+    if (c) c->pending.reset();      // a new begin, accepted or refused, ends the one before it
+    if (const int rc = check_view_args(c, who, v, outputs_ok && group_offset, true)) return rc;
+    if (n_groups && !margin) return fail(BMV_ERR_ARG, "%s: null argument", who);
+    if (const int rc = check_groups(who, group_offset, n_groups, v.n, hint)) return rc;
+    const PairArgs a{v.text_start, v.text_len, v.text_rc, v.query_len, contig, v.n, group_offset, n_groups, min_frag, max_frag};
+    if (const int rc = check_pair_args(who, a)) return rc;
+    if (cap)
+        if (const int rc = check_frag_cap(who, cap)) return rc;
+    uint64_t cells = 0;
+    if (const int rc = check_view_ranges(c, v, false, &cells)) return rc;
+
+    // 1. and 2.
+    auto pend = std::make_shared<PairedPending>(v, group_offset, contig, n_groups, cells);
+    BestRounds &r = pend->r;
+    if (const int rc = best_rounds(c, who, v, group_offset, n_groups, margin, hint, r)) return rc;
+    // (every group its seed alone: the host holds the distances, nothing went to the device)
+    if (!r.on_device)
+        if (const int rc = upload_best_outputs(c, r, v.n)) return rc;
+    pend->edits_there = v.n != 0;
+    pend->offsets_there = r.on_device;
+    if (cap) {
+        PairArgs fa = a;
+        fa.min_frag = 1u;
+        fa.max_frag = cap;
+        if (const int rc = run_frag(c, fa, c->bs_edits.p, c->bs_out_end.p, r.on_device)) return rc;
+        r.f.ms += c->ms_frag;
+        pend->offsets_there = pend->offsets_there || n_groups >= 2u;
+    }
+    c->pending = std::move(pend);
+    return BMV_OK;
+}
+
+// The second half: 3. the pair kernel under the range, 4. the picks that have no full alignment yet, and the results.
+int paired_finish(bmv_ctx *c, const char *who, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar) {
+    if (!c || !total_cigar) return fail(BMV_ERR_ARG, "%s: null argument", who);
+    if (!c->pending) return fail(BMV_ERR_STATE, "%s: no bmv_paired_begin is pending (none made, finished already, or another call aligned since)", who);
+    if (min_frag > max_frag) return fail(BMV_ERR_ARG, "%s: min_frag %u is larger than max_frag %u", who, min_frag, max_frag);
+    const std::shared_ptr<PairedPending> pend = std::move(c->pending);      // (the full alignments below drop the context's)
+    c->pending.reset();
+    const Views &v = pend->v;
+    BestRounds &r = pend->r;
+    const uint32_t n = v.n, n_groups = pend->n_groups;
+    const uint32_t *group_offset = pend->group_offset;
+    const PairArgs a{v.text_start, v.text_len, v.text_rc, v.query_len, pend->contig, n, group_offset, n_groups, min_frag, max_frag};
+    if (!pend->edits_there)
+        if (const int rc = upload_best_outputs(c, r, n)) return rc;
+    if (const int rc = run_pair(c, a, c->bs_edits.p, c->bs_out_end.p, pend->offsets_there)) return rc;
+    r.f.ms += c->ms_pair;
+    std::vector<uint8_t> picked(n, 0);
+    std::vector<uint32_t> realign;
+    for (uint32_t g = 0; g < n_groups; g++) {
+        const uint32_t x = c->h_pr_pick[g];
+        if (x == BMV_BEYOND) continue;
+        if (x < group_offset[g] || x >= group_offset[g + 1] || r.edits[x] == bmv::kBestBeyond)
+            return fail(BMV_ERR_STATE, "%s: the pair kernel picked alignment %u for group %u", who, x, g);
+        picked[x] = 1;
+        if (!r.full[x]) realign.push_back(x);
+    }
+    if (const int rc = best_realign(c, who, v, realign, r)) return rc;
+    store_best(c, n, n_groups, pend->cells, picked, r, total_cigar);
     return BMV_OK;
 }
 
@@ -1421,6 +1605,7 @@ int bmv_align(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uin
     const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
     uint64_t cells = 0;
     if (const int rc = check_views(c, "bmv_align", v, total_cigar != nullptr, true, true, &cells)) return rc;
+    c->pending.reset();         // (as store_results: every other call of the row comes through one of the two)
     c->n_last = n;
     c->n_cells = cells;
     c->ms_kernels = 0.f;
@@ -1803,6 +1988,7 @@ int bmv_pair(bmv_ctx *c, const uint64_t *text_start, const uint32_t *text_len, c
     const PairArgs a{text_start, text_len, text_rc, query_len, contig, n, group_offset, n_groups, min_frag, max_frag};
     if (const int rc = check_pair_args("bmv_pair", a)) return rc;
     HIP_TRY(hipSetDevice(c->p.device));
+    leave_pending(c);
     HIP_TRY(need_exact_all(n, c->bs_edits, c->bs_out_end));
     if (n) {
         HIP_TRY(hipMemcpyAsync(c->bs_edits.p, edits, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -1834,40 +2020,59 @@ int bmv_align_paired(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, co
                      const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
                      const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
                      const uint32_t *contig, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar) {
+    // one copy of the steps: begin without the spans, then finish
     const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
-    if (const int rc = check_view_args(c, "bmv_align_paired", v, total_cigar && group_offset, true)) return rc;
-    if (n_groups && !margin) return fail(BMV_ERR_ARG, "bmv_align_paired: null argument");
-    if (const int rc = check_groups("bmv_align_paired", group_offset, n_groups, n, hint)) return rc;
-    const PairArgs a{text_start, text_len, text_rc, query_len, contig, n, group_offset, n_groups, min_frag, max_frag};
-    if (const int rc = check_pair_args("bmv_align_paired", a)) return rc;
-    uint64_t cells = 0;
-    if (const int rc = check_view_ranges(c, v, false, &cells)) return rc;
+    if (const int rc = paired_begin(c, "bmv_align_paired", v, group_offset, n_groups, margin, hint, contig, min_frag, max_frag, 0u, total_cigar != nullptr))
+        return rc;
+    return paired_finish(c, "bmv_align_paired", min_frag, max_frag, total_cigar);
+}
 
-    // 1. and 2.
-    BestRounds r(n, n_groups);
-    if (const int rc = best_rounds(c, "bmv_align_paired", v, group_offset, n_groups, margin, hint, r)) return rc;
-    // 3. the pair kernel (every group its seed alone: the host holds the distances, nothing went to the device)
-    if (!r.on_device && n) {
-        HIP_TRY(hipSetDevice(c->p.device));
-        HIP_TRY(need_exact_all(n, c->bs_edits, c->bs_out_end));
-        HIP_TRY(hipMemcpyAsync(c->bs_edits.p, r.edits.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->bs_out_end.p, r.out_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+// bmv_align_paired in two halves (include/bmv.h): between them the caller reads the spans of this and of other contexts and
+// settles on one range.
+int bmv_paired_begin(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                     const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
+                     const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                     const uint32_t *contig, uint32_t cap) {
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    return paired_begin(c, "bmv_paired_begin", v, group_offset, n_groups, margin, hint, contig, 1u, 1u, cap, true);
+}
+
+int bmv_paired_finish(bmv_ctx *c, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar) {
+    return paired_finish(c, "bmv_paired_finish", min_frag, max_frag, total_cigar);
+}
+
+// The spans and their histogram alone (include/bmv.h, bmv_frag.hip.h): edits and end go to the device, the two kernels run,
+// bmv_frag reads.
+int bmv_frag_spans(bmv_ctx *c, const uint64_t *text_start, const uint32_t *text_len, const uint8_t *text_rc, const uint32_t *query_len,
+                   const uint32_t *edits, const uint32_t *end, const uint32_t *contig, uint32_t n, const uint32_t *group_offset,
+                   uint32_t n_groups, uint32_t cap) {
+    if (!c || !group_offset || (n && (!text_start || !text_len || !text_rc || !query_len || !edits || !end)))
+        return fail(BMV_ERR_ARG, "bmv_frag_spans: null argument");
+    if (const int rc = check_groups("bmv_frag_spans", group_offset, n_groups, n, nullptr)) return rc;
+    const PairArgs a{text_start, text_len, text_rc, query_len, contig, n, group_offset, n_groups, 1u, cap};
+    if (const int rc = check_frag_cap("bmv_frag_spans", cap)) return rc;
+    if (const int rc = check_pair_args("bmv_frag_spans", a)) return rc;
+    HIP_TRY(hipSetDevice(c->p.device));
+    leave_pending(c);
+    HIP_TRY(need_exact_all(n, c->bs_edits, c->bs_out_end));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(c->bs_edits.p, edits, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->bs_out_end.p, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     }
-    if (const int rc = run_pair(c, a, c->bs_edits.p, c->bs_out_end.p, r.on_device)) return rc;
-    r.f.ms += c->ms_pair;
-    // 4. the picks that have no full alignment yet
-    std::vector<uint8_t> picked(n, 0);
-    std::vector<uint32_t> realign;
-    for (uint32_t g = 0; g < n_groups; g++) {
-        const uint32_t x = c->h_pr_pick[g];
-        if (x == BMV_BEYOND) continue;
-        if (x < group_offset[g] || x >= group_offset[g + 1] || r.edits[x] == bmv::kBestBeyond)
-            return fail(BMV_ERR_STATE, "bmv_align_paired: the pair kernel picked alignment %u for group %u", x, g);
-        picked[x] = 1;
-        if (!r.full[x]) realign.push_back(x);
-    }
-    if (const int rc = best_realign(c, "bmv_align_paired", v, realign, r)) return rc;
-    store_best(c, n, n_groups, cells, picked, r, total_cigar);
+    return run_frag(c, a, c->bs_edits.p, c->bs_out_end.p, false);
+}
+
+int bmv_frag(bmv_ctx *c, uint32_t *out_span, uint64_t *out_hist) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_frag: null context");
+    copy_out(out_span, c->h_fr_span);
+    copy_out(out_hist, c->h_fr_hist);
+    return BMV_OK;
+}
+
+int bmv_last_frag_stats(bmv_ctx *c, float *ms_kernels, uint32_t *n_informative) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_frag_stats: null context");
+    if (ms_kernels) *ms_kernels = c->ms_frag;
+    if (n_informative) *n_informative = c->fr_informative;
     return BMV_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "affine_realign.h"
 #include "best_mapq.h"
 #include "bm_genome.h"
+#include "frag_range.h"
 #include "left_align.h"
 #include "mapper.h"
 #include "pair_mapq.h"
@@ -266,6 +267,67 @@ public:
                         std::vector<uint32_t> &pick, std::vector<uint8_t> &proper, std::vector<uint64_t> &s1, std::vector<uint64_t> &s2) {
         (void)hint;
         if (n_groups & 1u) throw std::runtime_error("paired: an odd number of groups");
+        paired_distances(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset, n_groups, margin, score,
+                         begin, cigar_offset, cigar, winner, edits, end);
+        paired_pick(text_start, text_len, text_rc, query_len, n, group_offset, n_groups, contig, min_frag, max_frag, score, begin, cigar_offset,
+                    cigar, edits, end, pick, proper, s1, s2);
+    }
+    // What a learned range was made of: the applied range, whether it was learned (else it is the fallback), the informative
+    // pairs and the three quartiles (0 when not learned).
+    struct frag_learned {
+        uint32_t applied_min = 0, applied_max = 0;
+        bool learned = false;
+        uint64_t n_informative = 0;
+        uint32_t quartiles[3] = {0, 0, 0};
+    };
+    // paired() under a range learned from the batch itself (bmv_frag_spans' contract, include/bmv.h, and frag_range.h): the
+    // spans of the batch's pairs under `cap`, their histogram, bm::frag_range with min_pairs and the fallback range, then the
+    // pick under the applied range.  Everything paired() returns, plus what was learned.  This default aligns everything and
+    // does the rest on the host; the GPU verifier leaves a histogram per device, adds them and picks on every device under the
+    // one range.
+    virtual void paired_auto(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                             const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
+                             const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                             const uint32_t *contig, uint32_t cap, uint32_t min_pairs, uint32_t fallback_min, uint32_t fallback_max,
+                             std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
+                             std::vector<uint32_t> &cigar, std::vector<uint32_t> &winner, std::vector<uint32_t> &edits,
+                             std::vector<uint32_t> &end, std::vector<uint32_t> &pick, std::vector<uint8_t> &proper, std::vector<uint64_t> &s1,
+                             std::vector<uint64_t> &s2, frag_learned &learned) {
+        (void)hint;
+        if (n_groups & 1u) throw std::runtime_error("paired: an odd number of groups");
+        if (cap < 1u || cap > 65535u) throw std::runtime_error("paired: a fragment cap is 1 .. 65535");
+        paired_distances(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset, n_groups, margin, score,
+                         begin, cigar_offset, cigar, winner, edits, end);
+        std::vector<uint64_t> hist(static_cast<size_t>(cap) + 1u, 0);
+        for (uint32_t p = 0; p < n_groups / 2u; p++)
+            hist[frag_span(text_start, text_len, text_rc, query_len, edits.data(), end.data(), contig, group_offset[2 * p],
+                           group_offset[2 * p + 1], group_offset[2 * p + 2], cap)]++;
+        learned = learn(hist, min_pairs, fallback_min, fallback_max);
+        paired_pick(text_start, text_len, text_rc, query_len, n, group_offset, n_groups, contig, learned.applied_min, learned.applied_max, score,
+                    begin, cigar_offset, cigar, edits, end, pick, proper, s1, s2);
+    }
+
+protected:
+    static frag_learned learn(const std::vector<uint64_t> &hist, uint32_t min_pairs, uint32_t fallback_min, uint32_t fallback_max) {
+        const frag_range_result r = frag_range(hist.data(), hist.size(), min_pairs, fallback_min, fallback_max);
+        frag_learned out;
+        out.applied_min = r.min_frag;
+        out.applied_max = r.max_frag;
+        out.learned = r.learned;
+        out.n_informative = r.n_informative;
+        out.quartiles[0] = r.q1;
+        out.quartiles[1] = r.q2;
+        out.quartiles[2] = r.q3;
+        return out;
+    }
+
+private:
+    // the default paired()'s first step: everything aligned, (edits, end) restricted to best + margin per group
+    void paired_distances(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                          const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n,
+                          const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, std::vector<int32_t> &score,
+                          std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset, std::vector<uint32_t> &cigar,
+                          std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end) {
         align(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, score, begin, cigar_offset, cigar);
         winner.assign(n_groups, kBeyond);
         edits.assign(n, kBeyond);
@@ -285,6 +347,13 @@ public:
                 end[a] = begin[a] + r;
             }
         }
+    }
+    // ... and its second: the pick under a range, and only the picks keep their results
+    void paired_pick(const uint64_t *text_start, const uint32_t *text_len, const uint8_t *text_rc, const uint32_t *query_len, uint32_t n,
+                     const uint32_t *group_offset, uint32_t n_groups, const uint32_t *contig, uint32_t min_frag, uint32_t max_frag,
+                     std::vector<int32_t> &score, std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset,
+                     std::vector<uint32_t> &cigar, const std::vector<uint32_t> &edits, const std::vector<uint32_t> &end,
+                     std::vector<uint32_t> &pick, std::vector<uint8_t> &proper, std::vector<uint64_t> &s1, std::vector<uint64_t> &s2) {
         pick.assign(n_groups, kBeyond);
         proper.assign(n_groups / 2u, 0);
         s1.assign(n_groups / 2u, kPairNone);
@@ -315,6 +384,8 @@ public:
         cigar_offset[n] = at;
         cigar.resize(at);
     }
+
+public:
     // Mate rescue (bmv_rescue's contract, include/bmv.h): job j places the mate reads[query_start[j], +query_len[j]) beside its
     // anchor -- a known alignment of its partner, given as select_pair takes one -- on the contig [contig_start[j],
     // contig_end[j]), within max_edits[j] edits.  out: the view of pair_rescue.h's rescue_window per job, edits / end the
@@ -491,6 +562,8 @@ private:
     float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
     bool _paired = false;                        // --paired: records 2p and 2p + 1 of the FASTQ file are mates, placed together
     uint32_t _min_frag = 1, _max_frag = 1000;    // --frag-range: what a proper pair spans, leftmost to rightmost base
+    bool _frag_auto = false;                     // --frag-auto: every verifier block learns the range from its own pairs
+    uint32_t _frag_cap = 10000, _frag_min_pairs = 64;
     float _rescue_rate = -1.f;                   // >= 0: --rescue, a mate without a proper placement is sought beside its partner
     std::vector<uint8_t> flat_genome_;           // --annotate with a verifier that cannot annotate: the records back to back
     const Genome *genome_ = nullptr;
@@ -704,6 +777,15 @@ public:
         if (_best_margin < 0.f) _best_margin = 0.05f;
         _min_frag = min_frag;
         _max_frag = max_frag;
+    }
+    // --frag-auto (implies --paired: the caller sets it): every verifier block learns its range from its own pairs
+    // (alignment_verifier::paired_auto; spans up to cap, at least min_pairs informative pairs, else --frag-range's); the block's
+    // range is what its rescue uses too, a block's result depends on nothing outside it, and every block says on stderr what it
+    // applied
+    void set_frag_auto(uint32_t cap, uint32_t min_pairs) {
+        _frag_auto = true;
+        _frag_cap = cap;
+        _frag_min_pairs = min_pairs;
     }
     // --rescue (implies --paired: the caller sets it): after a block's paired() call every pair without a proper combination
     // gets the jobs of pair_rescue.h's select_rescue -- a mate's own winner within (uint32_t)(rate x its length) edits anchors
@@ -1036,6 +1118,7 @@ private:
             std::vector<uint32_t> text_len, query_len, begin, cigar, max_edits;
             std::vector<uint32_t> group_offset{0}, margin, hint, winner, edits, end;    // --best: a group per read
             std::vector<uint32_t> contig, pick;                 // --paired: per alignment its @SQ entry; per read its pick
+            uint32_t min_frag = 0, max_frag = 0;                // --paired: the range the block's pick was made under
             std::vector<uint8_t> proper;                        // ... and per pair (reads 2p, 2p + 1 of the block)
             std::vector<uint64_t> s1, s2;
             std::vector<uint32_t> rescued_at;                   // --rescue: per read the alignment (appended behind the groups') that
@@ -1113,7 +1196,7 @@ private:
             if (jobs.empty()) return;
             alignment_verifier::rescued out;
             _v->rescue(b.bases.data(), b.bases.size(), a_ts.data(), a_tl.data(), a_rc.data(), a_ql.data(), a_end.data(), c0.data(), c1.data(),
-                       qs.data(), ql.data(), me.data(), static_cast<uint32_t>(jobs.size()), _min_frag, _max_frag, out);
+                       qs.data(), ql.data(), me.data(), static_cast<uint32_t>(jobs.size()), b.min_frag, b.max_frag, out);
             // per pair the job it keeps; its mate's placement, narrowed
             std::vector<uint64_t> ts, nqs;
             std::vector<uint32_t> tl, nql, readers;
@@ -1164,11 +1247,34 @@ private:
         auto align = [&](Block &b) {                            // on the worker thread
             try {
                 b.rescued_at.assign(b.reads.size(), alignment_verifier::kBeyond);
-                if (!b.text_start.empty() && paired) {
+                b.min_frag = _min_frag;
+                b.max_frag = _max_frag;
+                if (paired && _frag_auto && !b.reads.empty()) {
+                    alignment_verifier::frag_learned fl;
+                    fl.applied_min = _min_frag;
+                    fl.applied_max = _max_frag;
+                    if (!b.text_start.empty())
+                        _v->paired_auto(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
+                                        b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()),
+                                        b.group_offset.data(), static_cast<uint32_t>(b.margin.size()), b.margin.data(), b.hint.data(),
+                                        b.contig.data(), _frag_cap, _frag_min_pairs, _min_frag, _max_frag, b.score, b.begin, b.cigar_offset,
+                                        b.cigar, b.winner, b.edits, b.end, b.pick, b.proper, b.s1, b.s2, fl);
+                    b.min_frag = fl.applied_min;
+                    b.max_frag = fl.applied_max;
+                    std::string line = "[INFO]\tfragment range: " + std::to_string(fl.applied_min) + "," + std::to_string(fl.applied_max);
+                    const std::string of = std::to_string(fl.n_informative) + " of " + std::to_string(b.reads.size() / 2);
+                    if (fl.learned)
+                        line += " learned from " + of + " pairs (quartiles " + std::to_string(fl.quartiles[0]) + " " +
+                                std::to_string(fl.quartiles[1]) + " " + std::to_string(fl.quartiles[2]) + ")\n";
+                    else
+                        line += " kept, " + of + " pairs informative\n";
+                    std::cerr << line;
+                } else if (!b.text_start.empty() && paired)
                     _v->paired(b.bases.data(), b.bases.size(), b.text_start.data(), b.text_len.data(), b.text_rc.data(),
                                b.query_start.data(), b.query_len.data(), static_cast<uint32_t>(b.text_start.size()), b.group_offset.data(),
                                static_cast<uint32_t>(b.margin.size()), b.margin.data(), b.hint.data(), b.contig.data(), _min_frag, _max_frag,
                                b.score, b.begin, b.cigar_offset, b.cigar, b.winner, b.edits, b.end, b.pick, b.proper, b.s1, b.s2);
+                if (!b.text_start.empty() && paired) {
                     for (size_t a = 0; bounded && a < b.score.size(); a++)
                         if (b.score[a] != alignment_verifier::kRejected && -static_cast<int64_t>(b.score[a]) > static_cast<int64_t>(b.max_edits[a]))
                             b.score[a] = alignment_verifier::kRejected;

@@ -44,6 +44,10 @@ struct cmd_arguments {
                                   // the two are placed together and written with the pair's flags, RNEXT, PNEXT and TLEN
                                   // (implies --best and --annotate)
     unsigned int frag_min = 1, frag_max = 1000;      // --frag-range MIN,MAX (implies --paired): what a proper pair may span
+    bool frag_auto = false;       // --frag-auto (implies --paired): the range is learned from every verifier block's own pairs;
+                                  // --frag-range is then the range of a block with too few informative pairs
+    unsigned int frag_cap = 10000;        // --frag-cap N (implies --frag-auto): the longest span that counts as a fragment, 1 .. 65535
+    unsigned int frag_min_pairs = 64;     // --frag-min-pairs N (implies --frag-auto): informative pairs a block needs to learn from
     bool rescue = false;          // --rescue (bucketmap_align, implies --paired): a mate without a proper placement is sought beside
                                   // its partner's alignment (mate rescue) and written with XR:i:1
     float rescue_rate = 0.1f;     // --rescue-rate R (implies --rescue): an anchor may have (uint32_t)(R * its length) edits, and so
@@ -203,6 +207,21 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.frag_max = static_cast<unsigned>(hi);
             a.paired = true;
         }
+        else if (opt == "--frag-auto") a.frag_auto = a.paired = true;
+        else if (opt == "--frag-cap") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            if (v < 1 || v > 65535) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in 1..65535.");
+            a.frag_cap = static_cast<unsigned>(v);
+            a.frag_auto = a.paired = true;
+        }
+        else if (opt == "--frag-min-pairs") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            if (v > 0xFFFFFFFFul) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number below 2^32.");
+            a.frag_min_pairs = static_cast<unsigned>(v);
+            a.frag_auto = a.paired = true;
+        }
         else if (opt == "--rescue") a.rescue = true;
         else if (opt == "--rescue-rate") {
             const std::string s = value();
@@ -269,7 +288,8 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has no indels to normalise.");
         else if (opt == "--affine" || opt == "--affine-scores" || opt == "--affine-band")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has nothing to realign.");
-        else if (opt == "--paired" || opt == "--frag-range" || opt == "--rescue" || opt == "--rescue-rate")
+        else if (opt == "--paired" || opt == "--frag-range" || opt == "--frag-auto" || opt == "--frag-cap" || opt == "--frag-min-pairs" ||
+                 opt == "--rescue" || opt == "--rescue-rate")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it cannot place mates together.");
 #endif
         else if (opt == "--clip-scores") {
@@ -298,7 +318,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (!have_indicator) throw parser_error("Option -i/--index-indicator is required but not set.");
     if (a.split && (a.best || a.paired || a.rescue || a.max_edit_rate >= 0.f))
         throw parser_error(std::string("Option --split cannot be combined with ") +
-                           (a.rescue ? "--rescue" : a.paired ? "--paired" : a.best ? "--best" : "--max-edit-rate") +
+                           (a.rescue ? "--rescue" : a.frag_auto ? "--frag-auto" : a.paired ? "--paired" : a.best ? "--best" : "--max-edit-rate") +
                            ": they judge a read by the edits of one end-to-end alignment, which mean nothing for a read that "
                            "spans a breakpoint.");
     if (a.split) a.clip = a.annotate = true;

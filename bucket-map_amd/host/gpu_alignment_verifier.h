@@ -87,7 +87,23 @@ public:
                 std::vector<uint32_t> &cigar, std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end,
                 std::vector<uint32_t> &pick, std::vector<uint8_t> &proper, std::vector<uint64_t> &s1, std::vector<uint64_t> &s2) override {
         if (n_groups & 1u) throw std::runtime_error("paired: an odd number of groups");
-        pair_io io{contig, min_frag, max_frag, &pick, &proper, &s1, &s2};
+        pair_io io{contig, min_frag, max_frag, &pick, &proper, &s1, &s2, 0, 0, nullptr};
+        grouped(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset, n_groups, margin, hint, &io, score,
+                begin, cigar_offset, cigar, winner, edits, end);
+    }
+
+    // bmv_paired_begin per device, the devices' span histograms added and one range derived from the sum, bmv_paired_finish
+    // per device under that range: the range is the whole batch's, however the batch was cut
+    void paired_auto(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                     const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, uint32_t n, const uint32_t *group_offset,
+                     uint32_t n_groups, const uint32_t *margin, const uint32_t *hint, const uint32_t *contig, uint32_t cap,
+                     uint32_t min_pairs, uint32_t fallback_min, uint32_t fallback_max, std::vector<int32_t> &score,
+                     std::vector<uint32_t> &begin, std::vector<uint64_t> &cigar_offset, std::vector<uint32_t> &cigar,
+                     std::vector<uint32_t> &winner, std::vector<uint32_t> &edits, std::vector<uint32_t> &end, std::vector<uint32_t> &pick,
+                     std::vector<uint8_t> &proper, std::vector<uint64_t> &s1, std::vector<uint64_t> &s2, frag_learned &learned) override {
+        if (n_groups & 1u) throw std::runtime_error("paired: an odd number of groups");
+        if (cap < 1u || cap > 65535u) throw std::runtime_error("paired: a fragment cap is 1 .. 65535");
+        pair_io io{contig, fallback_min, fallback_max, &pick, &proper, &s1, &s2, cap, min_pairs, &learned};
         grouped(reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n, group_offset, n_groups, margin, hint, &io, score,
                 begin, cigar_offset, cigar, winner, edits, end);
     }
@@ -102,6 +118,8 @@ private:
         std::vector<uint32_t> *pick;
         std::vector<uint8_t> *proper;
         std::vector<uint64_t> *s1, *s2;
+        uint32_t cap, min_pairs;        // paired_auto(): learned != nullptr, and min_frag / max_frag are the fallback
+        frag_learned *learned;
     };
 
     // best() (pairs == nullptr) and paired(): the unit the batch is cut at is a group, or a pair of groups
@@ -137,17 +155,53 @@ private:
         std::vector<uint64_t> total(D, 0), cells(D, 0), dist_cells(D, 0);
         std::vector<float> ms(D, 0.f);
         std::vector<std::array<uint32_t, 5>> counts(D, std::array<uint32_t, 5>{});
+        std::vector<std::vector<uint32_t>> offs(D);             // per range its groups, counted from its first alignment
+        std::vector<share> shares(D);
+        for (size_t d = 0; d < D; d++) {
+            const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
+            if (ng == 0) continue;
+            const uint32_t a0 = group_offset[g0];
+            shares[d] = slice(all, a0, group_offset[g0 + ng] - a0);
+            if (D > 1) {
+                offs[d].assign(group_offset + g0, group_offset + g0 + ng + 1);
+                for (uint32_t &o : offs[d]) o -= a0;
+            }
+        }
+        const bool learn_range = pairs && pairs->learned;
+        uint32_t min_frag = pairs ? pairs->min_frag : 0u, max_frag = pairs ? pairs->max_frag : 0u;
+        std::vector<float> ms_frag(D, 0.f);
+        if (learn_range) {
+            // the first half on every device, the histograms added, one range
+            const size_t bins = static_cast<size_t>(pairs->cap) + 1u;
+            std::vector<std::vector<uint64_t>> hist(D);
+            for_each_device(D, [&](size_t d) {
+                const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
+                if (ng == 0) return;
+                const share &s = shares[d];
+                check(bmv_paired_begin(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, s.n,
+                                       D > 1 ? offs[d].data() : group_offset, ng, margin + g0, hint ? hint + g0 : nullptr,
+                                       pairs->contig ? pairs->contig + s.a0 : nullptr, pairs->cap),
+                      "the GPU alignment verifier failed: ");
+                hist[d].assign(bins, 0);
+                check(bmv_frag(ctx_[d], nullptr, hist[d].data()), "reading the fragment spans failed: ");
+                bmv_last_frag_stats(ctx_[d], &ms_frag[d], nullptr);
+            });
+            std::vector<uint64_t> whole(bins, 0);
+            for (size_t d = 0; d < D; d++)
+                for (size_t b = 0; b < hist[d].size(); b++) whole[b] += hist[d][b];
+            *pairs->learned = learn(whole, pairs->min_pairs, pairs->min_frag, pairs->max_frag);
+            min_frag = pairs->learned->applied_min;
+            max_frag = pairs->learned->applied_max;
+        }
         for_each_device(D, [&](size_t d) {
             const uint32_t g0 = cut[d], ng = cut[d + 1] - cut[d];
             if (ng == 0) return;
-            const uint32_t a0 = group_offset[g0];
-            const share s = slice(all, a0, group_offset[g0 + ng] - a0);
-            std::vector<uint32_t> off;                          // the range's groups, counted from its first alignment
-            if (D > 1) {
-                off.assign(group_offset + g0, group_offset + g0 + ng + 1);
-                for (uint32_t &o : off) o -= a0;
-            }
-            if (pairs) {
+            const share &s = shares[d];
+            const std::vector<uint32_t> &off = offs[d];
+            if (learn_range) {
+                check(bmv_paired_finish(ctx_[d], min_frag, max_frag, &total[d]), "the GPU alignment verifier failed: ");
+                bmv_last_pair_stats(ctx_[d], &ms_pair[d], &combinations[d]);
+            } else if (pairs) {
                 check(bmv_align_paired(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len, s.n,
                                        D > 1 ? off.data() : group_offset, ng, margin + g0, hint ? hint + g0 : nullptr,
                                        pairs->contig ? pairs->contig + s.a0 : nullptr, pairs->min_frag, pairs->max_frag, &total[d]),
@@ -191,6 +245,8 @@ private:
             float slowest = 0;
             for (const float x : ms_pair) slowest = std::max(slowest, x);
             pair_part = "the pair kernel " + std::to_string(sum(combinations)) + " combinations in " + std::to_string(slowest) + " ms; ";
+            if (learn_range)
+                pair_part += "the span and histogram kernels " + std::to_string(*std::max_element(ms_frag.begin(), ms_frag.end())) + " ms; ";
         }
         std::cerr << "[BENCHMARK]\tGPU alignment verification, " << (pairs ? "best per pair: " : "best per read: ") << n << " alignments in "
                   << n_groups << " groups, " << sum(cells) << " cells; " << all_counts[0] << " seeds, " << all_counts[1]
@@ -418,6 +474,7 @@ private:
         std::vector<uint64_t> rebased;      // several devices: what query_start points to, counted from the share's first read byte
         share() = default;
         share(share &&) = default;          // (a move keeps the vector's storage; a copy would leave query_start behind)
+        share &operator=(share &&) = default;
     };
     // One device: the whole batch as it came, no copies (a0 = 0, n = the batch's).  Several: only the span lo .. hi of the read
     // buffer the share's queries cover, query_start rebased to it, every pointer advanced by a0.

@@ -141,6 +141,7 @@ int main(int argc, char **argv) {
                           static_cast<uint32_t>(args.split_overlap * 1000), args.split_max);
         if (args.best) loc.set_best(args.best_margin);
         if (args.paired) loc.set_paired(args.frag_min, args.frag_max);
+        if (args.frag_auto) loc.set_frag_auto(args.frag_cap, args.frag_min_pairs);
         if (args.rescue) loc.set_rescue(args.rescue_rate);
 #endif
         run_indexer();

@@ -48,6 +48,12 @@ SYMBOLS = {
     "bmv_last_pair_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
     "bmv_align_paired": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u32p, C.c_uint32,
                                    _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p]),
+    "bmv_frag_spans": (C.c_int, [C.c_void_p, _u64p, _u32p, _u8p, _u32p, _u32p, _u32p, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32]),
+    "bmv_frag": (C.c_int, [C.c_void_p, _u32p, _u64p]),
+    "bmv_last_frag_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u32p]),
+    "bmv_paired_begin": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, C.c_uint32, _u32p, C.c_uint32,
+                                   _u32p, _u32p, _u32p, C.c_uint32]),
+    "bmv_paired_finish": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u64p]),
     "bmv_rescue": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u32p, _u32p, _u64p, _u64p, _u64p, _u32p, _u32p,
                              C.c_uint32, C.c_uint32, C.c_uint32]),
     "bmv_rescued": (C.c_int, [C.c_void_p, _u64p, _u32p, _u8p, _u32p, _u32p, _u8p]),
@@ -452,6 +458,73 @@ def select_pairs(text_start, text_len, text_rc, query_len, edits, end, group_off
     return {"pick": pick, "proper": proper, "s1": s1, "s2": s2, "winner": winner}
 
 
+FRAG_MAX_CAP = 65535
+
+
+def frag_spans(text_start, text_len, text_rc, query_len, edits, end, group_offset, cap, contig=None):
+    """The contract of bmv_frag_spans in plain numpy (include/bmv.h): span u32[n_groups // 2].  A group is settled when it has
+    an own winner (the lowest known index with the smallest edits) and every known alignment of the group lies at the winner's
+    locus; span[p] is R(r) - L(f) of the two own winners when both groups are settled and the winners are proper under
+    min_frag = 1, max_frag = cap, else 0."""
+    off = np.asarray(group_offset, np.int64)
+    ed = np.asarray(edits).astype(np.int64)
+    n, n_groups = len(ed), len(off) - 1
+    if n_groups < 0 or n_groups % 2 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise ValueError("group_offset must run from 0 to the number of alignments without decreasing, over an even number of groups")
+    if not 1 <= int(cap) <= FRAG_MAX_CAP:
+        raise ValueError(f"cap must lie in 1 .. {FRAG_MAX_CAP}")
+    left, right, at = pair_coordinates(text_start, text_len, text_rc, query_len, end)
+    rc = np.asarray(text_rc) != 0
+    ctg = np.zeros(n, np.int64) if contig is None else np.asarray(contig).astype(np.int64)
+    known = ed != BEYOND
+
+    def settled_winner(a0, a1):
+        if not known[a0:a1].any():
+            return None
+        w = a0 + int(np.argmin(np.where(known[a0:a1], ed[a0:a1], 2 ** 40)))
+        k = known[a0:a1]
+        return w if ((rc[a0:a1][k] == rc[w]) & (at[a0:a1][k] == at[w])).all() else None
+
+    span = np.zeros(n_groups // 2, np.uint32)
+    for p in range(n_groups // 2):
+        i, j = settled_winner(int(off[2 * p]), int(off[2 * p + 1])), settled_winner(int(off[2 * p + 1]), int(off[2 * p + 2]))
+        if i is None or j is None or rc[i] == rc[j] or ctg[i] != ctg[j]:
+            continue
+        f, r = (j, i) if rc[i] else (i, j)
+        frag = int(right[r]) - int(left[f])
+        if left[f] <= left[r] and right[f] <= right[r] and 1 <= frag <= int(cap):
+            span[p] = frag
+    return span
+
+
+def frag_histogram(span, cap):
+    """hist u64[cap + 1]: hist[s] is the number of pairs with span == s; hist[0] counts the uninformative pairs."""
+    span = np.asarray(span).astype(np.int64)
+    if not 1 <= int(cap) <= FRAG_MAX_CAP:
+        raise ValueError(f"cap must lie in 1 .. {FRAG_MAX_CAP}")
+    if len(span) and (span.min() < 0 or span.max() > int(cap)):
+        raise ValueError("a span beyond cap")
+    return np.bincount(span, minlength=int(cap) + 1).astype(np.uint64)
+
+
+def frag_range(hist, min_pairs, fallback) -> dict:
+    """The range from a histogram (host/frag_range.h; a definition by choice, DESIGN 4.4).  n = the sum of hist[s] over s >= 1;
+    learned iff n >= max(1, min_pairs), else the fallback (min_frag, max_frag) comes back unchanged.  With v the informative
+    spans in ascending order, Qk = v[k * n // 4] for k = 1, 2, 3, IQR = Q3 - Q1, slack = max(3 * IQR, ceil(Q2 / 4)),
+    min_frag = max(1, Q1 - slack), max_frag = Q3 + slack.  Returns a dict: min_frag, max_frag, learned, n_informative,
+    quartiles (a tuple, (0, 0, 0) when not learned)."""
+    h = [int(x) for x in np.asarray(hist).tolist()]
+    n = sum(h[1:])
+    out = {"min_frag": int(fallback[0]), "max_frag": int(fallback[1]), "learned": False, "n_informative": n, "quartiles": (0, 0, 0)}
+    if n < max(1, int(min_pairs)):
+        return out
+    upto = np.cumsum(np.asarray(h[1:], np.int64))               # v[i] is the first s with upto[s - 1] > i
+    q = [1 +int(np.searchsorted(upto, k * n // 4, side="right")) for k in (1, 2, 3)]
+    slack = max(3 * (q[2] - q[0]), -(-q[1] // 4))
+    out.update({"min_frag": max(1, q[0] - slack), "max_frag": q[2] + slack, "learned": True, "quartiles": tuple(q)})
+    return out
+
+
 def pair_mapq(proper, s1, s2, mates) -> list:
     """MAPQ and X0 of the two mates of one pair (host/pair_mapq.h; a definition by choice).  mates: two dicts, one
     per mate, of the mate's own group -- pick and winner (indices INSIDE the group, as select_pairs / align_paired return them
@@ -661,6 +734,10 @@ class Verifier:
         _check(lib().bmv_align_paired(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
                                       _p(ql, _u32p), n, _p(off, _u32p), n_groups, _p(mg, _u32p), hp, cp, int(min_frag),
                                       int(max_frag), C.byref(total)))
+        return self._paired_results(n, n_groups, total.value)
+
+    def _paired_results(self, n, n_groups, total) -> dict:
+        total = C.c_uint64(total)
         score, begin = np.zeros(n, np.int32), np.zeros(n, np.uint32)
         co = np.zeros(n + 1, np.uint64)
         cg = np.zeros(max(total.value, 1), np.uint32)
@@ -672,6 +749,87 @@ class Verifier:
         out.update({"score": score, "begin": begin, "cigar_offset": co, "cigar": cg[: total.value], "winner": winner[:n_groups],
                     "edits": edits[:n], "end": end[:n]})
         return out
+
+    def _frag(self, n_pairs, cap) -> dict:
+        span, hist = np.zeros(max(n_pairs, 1), np.uint32), np.zeros(int(cap) + 1, np.uint64)
+        _check(lib().bmv_frag(self._h, _p(span, _u32p), _p(hist, _u64p)))
+        return {"span": span[:n_pairs], "hist": hist}
+
+    def frag(self, n_pairs, cap) -> dict:
+        """bmv_frag: span u32[n_pairs] and hist u64[cap + 1] of the last frag_spans or paired_begin with cap > 0 -- the caller
+        says how large that call was."""
+        return self._frag(int(n_pairs), int(cap))
+
+    def frag_spans(self, text_start, text_len, text_rc, query_len, edits, end, group_offset, cap, contig=None) -> dict:
+        """bmv_frag_spans: the fragment spans over alignments given by numbers alone, as pair takes them.  Returns span (what
+        the module's frag_spans returns) and hist (frag_histogram of it)."""
+        ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
+        trc, ql = np.ascontiguousarray(text_rc, np.uint8), np.ascontiguousarray(query_len, np.uint32)
+        ed, en = np.ascontiguousarray(edits, np.uint32), np.ascontiguousarray(end, np.uint32)
+        off = np.ascontiguousarray(group_offset, np.uint32)
+        n, n_groups = len(ts), len(off) - 1
+        if n_groups < 0 or not (len(tl) == len(trc) == len(ql) == len(ed) == len(en) == n):
+            raise ValueError("one entry per alignment in every array, n_groups + 1 in group_offset")
+        cp = None
+        if contig is not None:
+            cn = np.ascontiguousarray(contig, np.uint32)
+            if len(cn) != n:
+                raise ValueError("contig must hold one entry per alignment")
+            cp = _p(cn, _u32p)
+        _check(lib().bmv_frag_spans(self._h, _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(ql, _u32p), _p(ed, _u32p), _p(en, _u32p), cp,
+                                    n, _p(off, _u32p), n_groups, int(cap)))
+        return self._frag(n_groups // 2, cap)
+
+    def frag_stats(self) -> dict:
+        """Of the last frag_spans or paired_begin with cap > 0: the two kernels' ms and the informative pairs."""
+        ms, inf = C.c_float(), C.c_uint32()
+        _check(lib().bmv_last_frag_stats(self._h, C.byref(ms), C.byref(inf)))
+        return {"ms_kernels": ms.value, "n_informative": inf.value}
+
+    def paired_begin(self, reads, text_start, text_len, text_rc, query_start, query_len, group_offset, margin, cap, hint=None,
+                     contig=None):
+        """bmv_paired_begin: the first half of align_paired -- everything but the pick under a range.  cap > 0 also computes the
+        fragment spans of the batch; returns frag's dict then, None for cap = 0.  The arrays are kept alive (and must stay
+        unchanged) until paired_finish."""
+        r = np.ascontiguousarray(reads, np.uint8)
+        ts, tl = np.ascontiguousarray(text_start, np.uint64), np.ascontiguousarray(text_len, np.uint32)
+        trc = np.ascontiguousarray(text_rc, np.uint8)
+        qs, ql = np.ascontiguousarray(query_start, np.uint64), np.ascontiguousarray(query_len, np.uint32)
+        off, mg = np.ascontiguousarray(group_offset, np.uint32), np.ascontiguousarray(margin, np.uint32)
+        n, n_groups = len(ts), len(off) - 1
+        if n_groups < 0 or len(mg) != n_groups:
+            raise ValueError("group_offset holds n_groups + 1 entries, margin n_groups")
+        if not (len(tl) == len(trc) == len(qs) == len(ql) == n):
+            raise ValueError("one entry per alignment in every array")
+        hn = cn = hp = cp = None
+        if hint is not None:
+            hn = np.ascontiguousarray(hint, np.uint32)
+            if len(hn) != n_groups:
+                raise ValueError("hint must hold one index per group")
+            hp = _p(hn, _u32p)
+        if contig is not None:
+            cn = np.ascontiguousarray(contig, np.uint32)
+            if len(cn) != n:
+                raise ValueError("contig must hold one entry per alignment")
+            cp = _p(cn, _u32p)
+        _check(lib().bmv_paired_begin(self._h, _p(r, _u8p), len(r), _p(ts, _u64p), _p(tl, _u32p), _p(trc, _u8p), _p(qs, _u64p),
+                                      _p(ql, _u32p), n, _p(off, _u32p), n_groups, _p(mg, _u32p), hp, cp, int(cap)))
+        self._pending = (n, n_groups, (r, ts, tl, trc, qs, ql, off, mg, hn, cn))
+        return self._frag(n_groups // 2, cap) if int(cap) else None
+
+    def paired_finish(self, min_frag, max_frag) -> dict:
+        """bmv_paired_finish: the pick under [min_frag, max_frag] and the picks' full alignments; returns exactly what
+        align_paired with that range returns for the batch of the pending paired_begin."""
+        n, n_groups, _ = getattr(self, "_pending", None) or (0, 0, None)
+        total = C.c_uint64()
+        try:
+            _check(lib().bmv_paired_finish(self._h, int(min_frag), int(max_frag), C.byref(total)))
+        except BmvError as e:
+            if e.code != 1:                     # (BMV_ERR_ARG: the begin stays pending)
+                self._pending = None
+            raise
+        self._pending = None
+        return self._paired_results(n, n_groups, total.value)
 
     def rescue(self, reads, anchor_text_start, anchor_text_len, anchor_text_rc, anchor_query_len, anchor_end, contig_start, contig_end,
                query_start, query_len, max_edits, min_frag, max_frag) -> dict:

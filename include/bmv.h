@@ -184,6 +184,59 @@ int  bmv_align_paired(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes,
                       uint32_t n, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
                       const uint32_t *contig, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar);
 
+/* The fragment spans: what a batch of pairs says about the range a proper pair may span, so that the range can be learned from
+ * the data instead of being typed.  A call of its own over numbers alone, like bmv_pair, with bmv_pair's arguments; known, L, R,
+ * locus, own winner and proper are bmv_pair's, word for word.  Integers only:
+ *   settled(g)          group g has an own winner w and every known alignment of the group has locus == locus(w).  (Overlapping
+ *                       windows of neighbouring buckets find one alignment twice; that does not unsettle a group.  Over the
+ *                       alignments within best + margin -- what bmv_paired_begin looks at -- settled is exactly "best_mapq
+ *                       would say 60".)
+ *   span[p]             with w1, w2 the own winners of the groups 2p and 2p + 1: R(r) - L(f) when both groups are settled and
+ *                       proper(w1, w2) holds under min_frag = 1, max_frag = cap; else 0, the pair is uninformative
+ *   hist[s]             for 0 <= s <= cap the number of pairs with span == s; hist[0] counts the uninformative pairs and the
+ *                       sum over hist is n_groups / 2
+ * The range itself is the host's (bm::frag_range, host/frag_range.h; verify.frag_range), from one histogram or from the sum of
+ * several: n = the sum of hist[s] over s >= 1; learned iff n >= max(1, min_pairs), else the caller's fallback range unchanged;
+ * with v the informative spans in ascending order, Qk = v[floor(k n / 4)] for k = 1, 2, 3, IQR = Q3 - Q1,
+ * slack = max(3 IQR, ceil(Q2 / 4)), min_frag = max(1, Q1 - slack) in signed arithmetic, max_frag = Q3 + slack.  A definition by
+ * choice, like the MAPQ scales.
+ * Checks: bmv_pair's, and 1 <= cap <= 65 535: BMV_ERR_ARG, nothing ran and the context stays usable.  The call leaves untouched
+ * what every other result call returns.
+ * How (bmv_frag.hip.h): the span kernel is a wave per pair -- the two own winners, then the settled test as a walk over either
+ * group in lane chunks of 64 with a ballot each --; the histogram kernel strides a resident grid over span[], the bins private
+ * to a block in LDS while cap + 1 <= 16 384 and only the non-zero ones flushed by global atomic adds, beyond that global atomic
+ * adds, one per distinct span among a wave's 64.  The call zeroes the device bins itself, every time. */
+int  bmv_frag_spans(bmv_ctx *ctx, const uint64_t *text_start, const uint32_t *text_len, const uint8_t *text_rc,
+                    const uint32_t *query_len, const uint32_t *edits, const uint32_t *end, const uint32_t *contig, uint32_t n,
+                    const uint32_t *group_offset, uint32_t n_groups, uint32_t cap);
+/* Of the last bmv_frag_spans or bmv_paired_begin with cap > 0: out_span n_groups / 2 entries, out_hist cap + 1; either may be
+ * NULL. */
+int  bmv_frag(bmv_ctx *ctx, uint32_t *out_span, uint64_t *out_hist);
+/* Of the same: the two kernels' time in ms and the informative pairs, the sum of hist[s] over s >= 1. */
+int  bmv_last_frag_stats(bmv_ctx *ctx, float *ms_kernels, uint32_t *n_informative);
+
+/* bmv_align_paired in two halves, so that the range can be settled between them -- from the spans of this context and of every
+ * other context that holds a share of the same block of reads.  bmv_align_paired itself is begin(cap = 0) + finish.
+ * bmv_paired_begin: bmv_align_paired's arguments without the range, its checks except the range's, plus cap: 0, or as
+ * bmv_frag_spans checks it.  Runs bmv_align_best's seed and distance rounds and the restriction; for cap > 0 the two
+ * bmv_frag_spans kernels on the restricted (edits, end) where they lie on the device, which fills bmv_frag's row (cap = 0 leaves
+ * that row as it is).  The arrays passed in must stay valid and unchanged until bmv_paired_finish returns: the picks are aligned
+ * from them.  Until then the bmv_results row is unspecified.
+ * bmv_paired_finish: the pair kernel under [min_frag, max_frag], the full alignment of every pick that has none yet, the
+ * results.  After it bmv_results, bmv_best, bmv_pairs, bmv_last_best_stats, bmv_last_pair_stats and bmv_last_stats return
+ * exactly what bmv_align_paired with that range returns for the batch (bmv_last_stats' ms includes the frag kernels').
+ * min_frag > max_frag: BMV_ERR_ARG, and the begin stays pending -- a corrected call may follow.  BMV_ERR_STATE, nothing ran and
+ * the context stays usable, when no successful begin is pending: none was made, finish ran already (also one that failed later
+ * than its checks), or another call that aligns came in between -- bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best,
+ * bmv_align_paired, a new bmv_paired_begin that failed (the two end a pending begin even when their own checks refuse
+ * them: the one exception to "a refused call changes nothing"), and bmv_rescue when it falls back to the aligner.  bmv_frag_spans,
+ * bmv_frag, bmv_pair and every result accessor may come in between. */
+int  bmv_paired_begin(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                      const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                      uint32_t n, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
+                      const uint32_t *contig, uint32_t cap);
+int  bmv_paired_finish(bmv_ctx *ctx, uint32_t min_frag, uint32_t max_frag, uint64_t *total_cigar);
+
 /* Mate rescue: a mate without a usable candidate (a repeat whose bucket list was cleared, k-mers that failed the quality filter,
  * a wrong bucket) is sought beside a known alignment of its partner.  A call of its own, like bmv_pair, bmv_annotate and
  * bmv_clip.  A batch holds n JOBS; job j places one mate, the query reads[query_start[j], +query_len[j]), beside an ANCHOR: a
@@ -232,14 +285,16 @@ int  bmv_last_rescue_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells, u
 
 /* Who owns what.  Every result accessor and every bmv_last_*_stats returns what ITS OWN last successful call left, whatever
  * other calls the context has served since, however large their batches were:
- *   bmv_results, bmv_last_stats          bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best, bmv_align_paired
+ *   bmv_results, bmv_last_stats          bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best, bmv_align_paired, and
+ *                                        bmv_paired_begin + bmv_paired_finish, which count as bmv_align_paired in every row
  *   bmv_last_bounded_stats               bmv_align_bounded alone: bmv_align_best and bmv_align_paired use the screen's recurrence
  *                                        in kernels and counters of their own and leave it untouched, as do bmv_align and
  *                                        bmv_align_long
  *   bmv_best, bmv_last_best_stats        bmv_align_best, bmv_align_paired; after a plain bmv_align, bmv_align_long or
  *                                        bmv_align_bounded they still return what the last of those two left (nothing, and
  *                                        zeros, on a context that never made one)
- *   bmv_pairs, bmv_last_pair_stats       bmv_pair, bmv_align_paired
+ *   bmv_pairs, bmv_last_pair_stats       bmv_pair, bmv_align_paired, bmv_paired_finish
+ *   bmv_frag, bmv_last_frag_stats        bmv_frag_spans, bmv_paired_begin with cap > 0
  *   bmv_rescued, bmv_last_rescue_stats   bmv_rescue; its fallback for queries beyond 512 bases runs bmv_align_long's kernels and
  *                                        puts bmv_results and bmv_last_stats back as it found them
  *   bmv_segments, bmv_last_split_stats   bmv_split, bmv_split_pick

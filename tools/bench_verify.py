@@ -9,7 +9,7 @@ work on BASELINE configs[1]: one located candidate per read, text window = read 
     python tools/bench_verify.py --realign [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --leftalign [--reads 20000 --len 10000 --indel-rate 0.1]
     python tools/bench_verify.py --best [--groups 20000 --len 10000 --text-len 11001] [--groups 200000 --len 300 --text-len 307]
-    python tools/bench_verify.py --paired [--pairs 500000 --len 300]
+    python tools/bench_verify.py --paired [--pairs 500000 --len 300] [--frag-auto [--frag-cap 10000]]
     python tools/bench_verify.py --rescue [--rescue-jobs 500000,4000 --rescue-len 150]
     python tools/bench_verify.py --split [--reads 200000 --len 300] [--reads 20000 --len 10000]
 
@@ -252,6 +252,26 @@ def paired_main(args):
         pair["ms_kernels"].append(v.stats()["ms_kernels"])
         pair["ms_pair"].append(v.pair_stats()["ms_pair"])
     st, pst = v.best_stats(), v.pair_stats()
+    auto = None
+    if args.frag_auto:
+        # --frag-auto: the same batch through paired_begin (cap 10 000: the tool's default) + paired_finish under the range its
+        # own histogram gives; ms_frag is the span and histogram kernels, ms_kernels the whole of begin + finish
+        auto = {"ms_kernels": [], "ms_frag": [], "ms_pair": [], "wall_s": []}
+        for _ in range(args.repeat):
+            t0 = time.perf_counter()
+            frag = v.paired_begin(*batch, off, mg, args.frag_cap, hint)
+            learned = verify.frag_range(frag["hist"], 64, (1, 1000))
+            v.paired_finish(learned["min_frag"], learned["max_frag"])
+            auto["wall_s"].append(time.perf_counter() - t0)
+            auto["ms_kernels"].append(v.stats()["ms_kernels"])
+            auto["ms_frag"].append(v.frag_stats()["ms_kernels"])
+            auto["ms_pair"].append(v.pair_stats()["ms_pair"])
+        spans = verify.frag_spans(ts[: 6 * min(P, 2000)], tl[: 6 * min(P, 2000)], rc[: 6 * min(P, 2000)], ql[: 6 * min(P, 2000)],
+                                  got["edits"][: 6 * min(P, 2000)], got["end"][: 6 * min(P, 2000)], off[: 2 * min(P, 2000) + 1], args.frag_cap)
+        auto.update({"cap": args.frag_cap, "histogram_path": "LDS" if args.frag_cap + 1 <= 16384 else "global atomics",
+                     "range": [learned["min_frag"], learned["max_frag"]], "learned": learned["learned"],
+                     "n_informative": v.frag_stats()["n_informative"], "quartiles": list(learned["quartiles"]),
+                     "first_pairs_identical_to_frag_spans": bool(np.array_equal(frag["span"][: len(spans)], spans))})
     k = min(P, 2000)
     want = verify.select_pairs(ts[: 6 * k], tl[: 6 * k], rc[: 6 * k], ql[: 6 * k], got["edits"][: 6 * k], got["end"][: 6 * k],
                                off[: 2 * k + 1], 1, 1000)
@@ -263,6 +283,7 @@ def paired_main(args):
         "proper_share": float(got["proper"].mean()), "pairs_with_a_second_combination": float((got["s2"] != verify.PAIR_NONE).mean()),
         "pick_is_not_the_own_winner": float((got["pick"] != got["winner"]).mean()),
         "align_best": best, "align_paired": {**pair, "n_realigned": st["n_realigned"], "n_seed": st["n_seed"]},
+        **({"frag_auto": auto} if auto else {}),
         "checks": {"first_pairs_identical_to_select_pairs": bool(ok)}}), flush=True)
 
 
@@ -424,6 +445,8 @@ def main():
     ap.add_argument("--split", action="store_true", help="Verifier.split beside Verifier.clip on groups of five candidates (see split_main)")
     ap.add_argument("--paired", action="store_true", help="Verifier.align_paired beside Verifier.align_best (see paired_main)")
     ap.add_argument("--pairs", type=int, default=500_000)
+    ap.add_argument("--frag-auto", action="store_true", help="--paired: also paired_begin + paired_finish under the learned range")
+    ap.add_argument("--frag-cap", type=int, default=10_000, help="--frag-auto: the cap (beyond 16 383 the histogram uses global atomics)")
     ap.add_argument("--best", action="store_true", help="Verifier.align_best on groups of five candidates (see best_main)")
     ap.add_argument("--groups", type=int, default=20_000)
     ap.add_argument("--text-len", type=int, default=0, help="--best: the window's length (default: as the tool computes it)")
