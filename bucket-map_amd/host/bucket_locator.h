@@ -14,7 +14,9 @@
 #pragma once
 
 #include "affine_realign.h"
+#include "bam.h"
 #include "best_mapq.h"
+#include "bgzf.h"
 #include "bm_genome.h"
 #include "frag_range.h"
 #include "left_align.h"
@@ -446,11 +448,66 @@ public:
 // SAM text as seqan3::sam_file_output lays it out: records are appended to one buffer with
 // std::to_chars and go to the file a few megabytes at a time (a million `ostream <<` chains were the slowest stage
 // of the tool after the device work had shrunk to milliseconds).
+//
+// With a block_compressor the same records leave as BAM (-o x.bam): flush() encodes the buffer's complete lines
+// (host/bam.h), cuts the BAM stream every kBgzfBlockMax bytes -- by size alone, so the file does not depend on where the
+// flushes fell -- and hands the whole blocks to the compressor in one call (the device in the product, host/bgzf.h
+// elsewhere; the same bytes); the remainder is carried to the next flush, the header is a block of its own and close()
+// appends the BGZF end-of-file block.
 class sam_text {
     std::ofstream out_;
     std::string buf_, writing_;     // the buffer being filled / the one a writer thread is putting into the file
     std::thread writer_;
     bool write_failed_ = false;
+    block_compressor *bam_ = nullptr;   // non-null: BAM
+    bam_ref_index ref_index_;
+    std::string stream_;                // BAM: encoded records not yet in a block
+    std::vector<uint8_t> blocks_;
+    bool closed_ = false;
+
+    // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer
+    void encode_buffer(bool all) {
+        // a few threads, each a run of whole lines; their records are appended in order (one thread encodes 640 MB of
+        // text in half a second: as long as the device takes for everything else)
+        // (BM_BAM_ENCODE_BYTES: the text size from which a flush is shared out, for the tests; default 1 MiB)
+        static const size_t share_from = [] {
+            const char *e = std::getenv("BM_BAM_ENCODE_BYTES");
+            return e ? static_cast<size_t>(std::strtoull(e, nullptr, 10)) : size_t{1} << 20;
+        }();
+        const unsigned T = buf_.size() < share_from ? 1u : std::min(8u, std::max(2u, std::thread::hardware_concurrency()));
+        std::vector<size_t> cut(T + 1, buf_.size());
+        cut[0] = 0;
+        for (unsigned t = 1; t < T; t++) {
+            const size_t nl = buf_.find('\n', std::max(cut[t - 1], buf_.size() / T * t));
+            cut[t] = nl == std::string::npos ? buf_.size() : nl + 1;
+        }
+        std::vector<std::string> part(T);
+        std::vector<std::exception_ptr> failed(T);
+        auto encode = [&](unsigned t) {
+            try {
+                for (size_t at = cut[t]; at < cut[t + 1];) {
+                    size_t e = buf_.find('\n', at);
+                    if (e == std::string::npos) e = buf_.size();
+                    sam_line_to_bam(std::string_view(buf_).substr(at, e - at), ref_index_, t ? part[t] : stream_);
+                    at = e + 1;
+                }
+            } catch (...) {
+                failed[t] = std::current_exception();
+            }
+        };
+        std::vector<std::thread> pool;
+        for (unsigned t = 1; t < T; t++) pool.emplace_back(encode, t);
+        encode(0);
+        for (auto &th : pool) th.join();
+        for (unsigned t = 0; t < T; t++)
+            if (failed[t]) std::rethrow_exception(failed[t]);
+        for (unsigned t = 1; t < T; t++) stream_.append(part[t]);
+        const size_t take = all ? stream_.size() : stream_.size() / kBgzfBlockMax * kBgzfBlockMax;
+        blocks_.clear();
+        if (take) bam_->deflate(reinterpret_cast<const uint8_t *>(stream_.data()), take, blocks_);
+        stream_.erase(0, take);
+        buf_.assign(reinterpret_cast<const char *>(blocks_.data()), blocks_.size());
+    }
 
     void join_writer() {
         if (writer_.joinable()) writer_.join();
@@ -465,14 +522,14 @@ class sam_text {
     void number(uint64_t v) { number(buf_, v); }
 
 public:
-    explicit sam_text(std::filesystem::path const &file) : out_(file, std::ios::binary) {
+    explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr) : out_(file, std::ios::binary), bam_(bam) {
         if (!out_) throw std::runtime_error("cannot write " + file.string());
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
     ~sam_text() {
         try {
-            flush();
+            if (!closed_) flush();
             join_writer();
         } catch (...) {
         }
@@ -480,6 +537,7 @@ public:
     // the filled buffer goes to the file on a thread of its own while the next one is filled (records are formatted at
     // about the speed the file system takes them: one after the other they cost twice)
     void flush() {
+        if (bam_) encode_buffer(false);
         join_writer();
         writing_.swap(buf_);
         buf_.clear();
@@ -490,7 +548,16 @@ public:
     }
     // everything written (call before reading the file back or reporting success)
     void close() {
-        flush();
+        if (bam_ && !closed_) {
+            encode_buffer(true);
+            buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
+            join_writer();
+            out_.write(buf_.data(), static_cast<std::streamsize>(buf_.size()));
+            buf_.clear();
+        } else if (!closed_) {
+            flush();
+        }
+        closed_ = true;
         join_writer();
         out_.flush();
         if (!out_) throw std::runtime_error("writing the SAM file failed");
@@ -503,6 +570,15 @@ public:
             buf_ += "\tLN:";
             number(ref_lengths[i]);
             buf_ += '\n';
+        }
+        if (bam_) {                                   // the BAM header: blocks of its own, before any record
+            std::string head;
+            bam_header(buf_, ref_ids, ref_lengths, head, ref_index_);
+            blocks_.clear();
+            bam_->deflate(reinterpret_cast<const uint8_t *>(head.data()), head.size(), blocks_);
+            join_writer();
+            out_.write(reinterpret_cast<const char *>(blocks_.data()), static_cast<std::streamsize>(blocks_.size()));
+            buf_.clear();
         }
     }
     // QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL [tags: "NM:i:3\tMD:Z:..." -- appended after a tab when not empty];
@@ -550,6 +626,7 @@ private:
     mapper *_m;
     offset_scanner *_s;
     alignment_verifier *_v = nullptr;            // non-null: the BM_ALIGN behaviour
+    block_compressor *_bam = nullptr;            // non-null: the output file is BAM, its BGZF blocks made by this
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
@@ -760,6 +837,7 @@ public:
 
     // bucketmap_align: every located candidate is verified by a pairwise alignment before it is written
     void set_verifier(alignment_verifier *v) { _v = v; }
+    void set_compressor(block_compressor *c) { _bam = c; }   // the output file is BAM (-o x.bam)
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
     // --annotate: write_verified writes every record on the forward strand (POS, SEQ, QUAL, =/X/I/D CIGAR) with NM and MD
@@ -1016,7 +1094,7 @@ public:
         auto locate_res = locate_reads(sequence_file);
         const sam_header h = read_bucket_ids(index_file);
 
-        sam_text sam(sam_file);
+        sam_text sam(sam_file, _bam);
         sam.header(h.ref_ids, h.ref_lengths);
         unsigned int read_id = 0, mapped_locations = 0;
         auto t0 = std::chrono::steady_clock::now();

@@ -165,8 +165,8 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         } else if (opt == "-i" || opt == "--index-indicator") { a.index_indicator = value(); have_indicator = true; }
         else if (opt == "-o" || opt == "--output-file") {
             a.output_sam_path = value();
-            if (!has_ext(a.output_sam_path, {"sam"}))
-                throw parser_error("Validation failed for option -o/--output-file: Expected one of the following valid extensions: [sam]!");
+            if (!has_ext(a.output_sam_path, {"sam", "bam"}))   // the extension decides: SAM text, or BAM (BGZF blocks, bmz.h)
+                throw parser_error("Validation failed for option -o/--output-file: Expected one of the following valid extensions: [sam, bam]!");
             if (std::filesystem::exists(a.output_sam_path))
                 throw parser_error("Validation failed for option -o/--output-file: The file " + a.output_sam_path.string() + " already exists!");
         } else if (opt == "-k" || opt == "--index-seed") a.index_seed_length = static_cast<uint8_t>(as_uint(value()));

@@ -25,6 +25,9 @@ std::unique_ptr<bm::mapper> bm_make_mapper(const bm::cmd_arguments &args, unsign
 std::unique_ptr<bm::offset_scanner> bm_make_scanner(const bm::cmd_arguments &args, int allowed_mismatch, int allowed_indel);
 // bucketmap_align only: where align_pairwise runs (the MI355X verifier in the product).
 std::unique_ptr<bm::alignment_verifier> bm_make_verifier(const bm::cmd_arguments &args);
+// -o x.bam: who deflates the BGZF blocks.  Weak: a build that does not define it (the oracle-backed test tools) gets the
+// host rule of bgzf.h, whose bytes are the same.
+std::unique_ptr<bm::block_compressor> bm_make_compressor(const bm::cmd_arguments &args) __attribute__((weak));
 // --gpu-index: fills ix with the rows built on the device; false = not available in this build.
 bool bm_gpu_index(const bm::cmd_arguments &args, const bm::Genome &genome, unsigned int num_buckets, bm::QgramIndex &ix);
 // Whatever the build's devices need before their first use (HIP start-up and code objects: a third of a second), begun
@@ -127,6 +130,11 @@ int main(int argc, char **argv) {
         bm::bucket_locator loc(map.get(), scanner.get(), args.bucket_len, args.max_read_length, args.query_seed_length,
                                args.allowed_seed_miss_rate, args.locator_allowed_indel_rate,
                                static_cast<unsigned int>(args.locator_sample_size), args.average_base_quality);
+        std::unique_ptr<bm::block_compressor> compressor;
+        if (args.output_sam_path.extension() == ".bam") {
+            compressor = bm_make_compressor ? bm_make_compressor(args) : std::make_unique<bm::block_compressor>();
+            loc.set_compressor(compressor.get());
+        }
 #ifdef BM_ALIGN
         std::unique_ptr<bm::alignment_verifier> verifier = bm_make_verifier(args);
         loc.set_verifier(verifier.get());

@@ -1,6 +1,8 @@
 // make_mapper_gpu.cpp -- the product's factories: the MI355X filter behind bm::mapper and the MI355X
 // locator scan behind bm::offset_scanner.
 // (main.cpp:202-209: q_gram_mapper<BM_BUCKET_NUM> map(BM_BUCKET_LEN, read_len, k, q, S, fault, d, b))
+#include "../../include/bmz.h"
+#include "bgzf.h"
 #include "bm_indexer.h"
 #include "cli.h"
 #include "gpu_alignment_verifier.h"
@@ -103,6 +105,34 @@ std::unique_ptr<bm::offset_scanner> bm_make_scanner(const bm::cmd_arguments &arg
 
 std::unique_ptr<bm::alignment_verifier> bm_make_verifier(const bm::cmd_arguments &args) {
     return std::make_unique<bm::gpu_alignment_verifier>(args.gpus);
+}
+
+// -o x.bam: the BGZF blocks of the BAM stream are deflated on the first device of --gpus (bmz_deflate; the rule and so
+// the bytes are those of host/bgzf.h).  No host fall-back: a failing device call ends the run.
+namespace {
+class gpu_block_compressor : public bm::block_compressor {
+    bmz_ctx *ctx_ = nullptr;
+
+public:
+    explicit gpu_block_compressor(int device) {
+        if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
+    }
+    ~gpu_block_compressor() override { bmz_destroy(ctx_); }
+    gpu_block_compressor(const gpu_block_compressor &) = delete;
+    gpu_block_compressor &operator=(const gpu_block_compressor &) = delete;
+    void deflate(const uint8_t *in, size_t n, std::vector<uint8_t> &out) override {
+        const size_t before = out.size();
+        out.resize(before + bmz_bound(n, BMZ_BLOCK_MAX));
+        uint64_t got = 0;
+        if (bmz_deflate(ctx_, in, n, BMZ_BLOCK_MAX, out.data() + before, out.size() - before, &got) != BMZ_OK)
+            throw std::runtime_error(std::string("bmz_deflate: ") + bmz_last_error());
+        out.resize(before + got);
+    }
+};
+}  // namespace
+
+std::unique_ptr<bm::block_compressor> bm_make_compressor(const bm::cmd_arguments &args) {
+    return std::make_unique<gpu_block_compressor>(args.gpus.empty() ? 0 : args.gpus.front());
 }
 
 void bm_report_resources(const bm::cmd_arguments &args) {
