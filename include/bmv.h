@@ -201,7 +201,8 @@ int  bmv_align_paired(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes,
  * slack = max(3 IQR, ceil(Q2 / 4)), min_frag = max(1, Q1 - slack) in signed arithmetic, max_frag = Q3 + slack.  A definition by
  * choice, like the MAPQ scales.
  * Checks: bmv_pair's, and 1 <= cap <= 65 535: BMV_ERR_ARG, nothing ran and the context stays usable.  The call leaves untouched
- * what every other result call returns.
+ * what every other result or stats call returns -- those of bmv_annotate, bmv_clip, bmv_realign, bmv_leftalign, bmv_split,
+ * bmv_split_pick and bmv_rescue too -- and a pending bmv_paired_begin stays pending.
  * How (bmv_frag.hip.h): the span kernel is a wave per pair -- the two own winners, then the settled test as a walk over either
  * group in lane chunks of 64 with a ballot each --; the histogram kernel strides a resident grid over span[], the bins private
  * to a block in LDS while cap + 1 <= 16 384 and only the non-zero ones flushed by global atomic adds, beyond that global atomic
@@ -230,7 +231,10 @@ int  bmv_last_frag_stats(bmv_ctx *ctx, float *ms_kernels, uint32_t *n_informativ
  * than its checks), or another call that aligns came in between -- bmv_align, bmv_align_long, bmv_align_bounded, bmv_align_best,
  * bmv_align_paired, a new bmv_paired_begin that failed (the two end a pending begin even when their own checks refuse
  * them: the one exception to "a refused call changes nothing"), and bmv_rescue when it falls back to the aligner.  bmv_frag_spans,
- * bmv_frag, bmv_pair and every result accessor may come in between. */
+ * bmv_frag, bmv_pair and every result accessor may come in between.  So may bmv_annotate, bmv_clip, bmv_realign, bmv_leftalign,
+ * bmv_split, bmv_split_pick and a bmv_rescue none of whose queries has more than 512 bases: they neither end the begin nor
+ * write where it left its arrays.  Whatever came in between, and however large its batch was, the finish returns what
+ * bmv_align_paired returns for the begin's batch. */
 int  bmv_paired_begin(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
                       const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
                       uint32_t n, const uint32_t *group_offset, uint32_t n_groups, const uint32_t *margin, const uint32_t *hint,
@@ -533,7 +537,9 @@ int  bmv_last_leftalign_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_compa
  * inversion in the middle of a read keeps one range that spans it and loses the inverted part.
  * Checks before anything is launched: everything bmv_clip refuses, group_offset as in bmv_align_best, the parameter ranges
  * above, text_start below 2^62: BMV_ERR_ARG, the message names the alignment or group, nothing ran and the context stays usable.
- * The call leaves untouched what every other result or stats call returns; n = 0 and n_groups = 0 succeed with empty results.
+ * The call leaves untouched what every other result or stats call returns -- those of bmv_frag_spans, bmv_pair, bmv_rescue,
+ * bmv_annotate, bmv_clip, bmv_realign and bmv_leftalign too -- and a pending bmv_paired_begin stays pending; n = 0 and
+ * n_groups = 0 succeed with empty results.
  * How (bmv_split.hip.h): the range kernel is bmv_clip's range walk -- a wave per alignment, 64 columns of an M entry a step --
  * carrying the text and query cursors of the running minimum and of the best range along, so that ONE walk gives what bmv_clip
  * takes its range and its count pass for; the pick kernel runs a wave per group, the candidates in the lanes 64 at a time, a

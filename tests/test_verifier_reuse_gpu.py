@@ -8,8 +8,14 @@ big left its values; queries of 0, 33, 64 and 200 bases: other words-per-lane cl
 of big is in range for buffers that only grow, so a missed initialisation shows as a wrong answer, never as a wild access.
 
 Every comparison is exact: against the CPU oracle of the call (oracle.oracle_c for the alignments, the plain restatements of
-bucket_map_amd.verify, tests/test_annotate.py, tests/test_clip.py, tests/test_realign.py and tests/test_leftalign.py for the
-rest) and against the same call on a fresh context.  Timings (the ms_* fields) are compared nowhere.
+bucket_map_amd.verify -- select_best, select_pairs, frag_spans, frag_histogram, clip_range and select_segments, which
+tests/test_pair.py, tests/test_frag.py and tests/test_split.py hold against brute force --, tests/test_annotate.py,
+tests/test_clip.py, tests/test_realign.py and tests/test_leftalign.py for the rest) and against the same call on a fresh
+context.  Timings (the ms_* fields) are compared nowhere.
+
+One state outlives a call on the device: bmv_paired_begin leaves its batch's (edits, end) and group offsets there for
+bmv_paired_finish.  The tests "between the two halves" put a larger batch with other offsets through every call that may come
+in between, and every call that ends a pending begin through its refusal.
 
 The one place where the oracle covers less than the batch: test_realign.restate_realign is a Python loop over the band (17 ms
 per 150-base alignment), so of a BIG realign batch the oracle restates the first 70 alignments, every 16th and the ones either
@@ -56,10 +62,30 @@ OWNS = {
     "clip": ("clipped", "clip_stats"),
     "realign": ("realigned", "realign_stats"),
     "leftalign": ("leftaligned", "leftalign_stats"),
+    # bmv_paired_begin with cap > 0, then bmv_paired_finish: bmv_align_paired's rows and bmv_frag's.  (With cap = 0 the two
+    # halves ARE align_paired: World.halves_call files them under that key, and the frag row must stay as it was found.)
+    "paired_halves": ("results", "stats", "best", "best_stats", "pairs", "pair_stats", "frag", "frag_stats"),
+    "frag_spans": ("frag", "frag_stats"),
+    "split": ("segments", "split_stats"),
+    "split_pick": ("segments", "split_stats"),
 }
-ACCESSORS = ("results", "best", "pairs", "rescued", "annotations", "clipped", "realigned", "leftaligned")
-STATS = ("stats", "bounded_stats", "best_stats", "pair_stats", "rescue_stats", "annotate_stats", "clip_stats", "realign_stats",
-         "leftalign_stats")
+ACCESSORS = ("results", "best", "pairs", "frag", "rescued", "segments", "annotations", "clipped", "realigned", "leftaligned")
+STATS = ("stats", "bounded_stats", "best_stats", "pair_stats", "frag_stats", "rescue_stats", "split_stats", "annotate_stats", "clip_stats",
+         "realign_stats", "leftalign_stats")
+# what every accessor fills, in the order of its C signature
+SHAPES = {"results": ("int32", "uint32", "uint64", "uint32"), "best": ("uint32",) * 3, "pairs": ("uint32", "uint8", "uint64", "uint64", "uint32"),
+          "frag": ("uint32", "uint64"), "rescued": ("uint64", "uint32", "uint8", "uint32", "uint32", "uint8"),
+          "segments": ("int64", "uint32", "uint32", "int64", "int64", "uint32", "uint32", "int64"),
+          "annotations": ("uint32", "uint32", "uint32", "uint64", "uint32", "uint64", "uint8"),
+          "clipped": ("int64",) + ("uint32",) * 5 + ("uint64", "uint32", "uint64", "uint8"),
+          "realigned": ("int32", "uint32", "uint8", "uint64", "uint32"), "leftaligned": ("uint32", "uint64", "uint32", "uint8", "uint32")}
+# the eleven entry points the table had when seeds 1 .. 4 of the last test were drawn: they keep their draws
+ELEVEN = ("align", "align_long", "align_bounded", "align_best", "align_paired", "pair", "rescue", "annotate", "clip", "realign", "leftalign")
+# big split batches: match and penalty, under which an alignment keeps its longest stretch without an edit; min_score,
+# max_overlap_permille -- only stretches that share nine tenths of the shorter one conflict, so a large group fills many slots --,
+# max_segments
+SPLIT_BIG = ((1, 30), (15, 900, 16))
+SPLIT_SIZES = (1, 63, 64, 65, 130)    # their group sizes, over and over: either side of a wave's 64 lanes
 PTR = {"int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "int64": C.c_int64, "uint8": C.c_uint8}
 
 
@@ -144,6 +170,21 @@ def _five(genome, v, calls, scratch_mb=None, fresh=True):
 
 def _offsets(lens):
     return np.concatenate([[0], np.cumsum(np.asarray(lens, np.int64))]).astype(np.uint64)
+
+
+def _sized_groups(n, sizes):
+    """group offsets over n alignments: groups of sizes[0], sizes[1], ... over and over, the last one cut"""
+    off, k = [0], 0
+    while off[-1] < n:
+        off.append(min(n, off[-1] + sizes[k % len(sizes)]))
+        k += 1
+    return np.array(off, np.uint32)
+
+
+def _cut_groups(off, n):
+    """the groups of the first n alignments, the last one cut"""
+    off = [int(x) for x in off if x <= n]
+    return np.array(off if off[-1] == n else off + [n], np.uint32)
 
 
 def _pack(entries):
@@ -468,6 +509,130 @@ class World:
         assert len(ts) == n and (len(off) - 1) % 2 == 0
         return (np.array(ts, np.uint64), np.array(tl, np.uint32), np.array(trc, np.uint8), np.array(ql, np.uint32), np.array(ed, np.uint32),
                 np.array(en, np.uint32)), np.array(off, np.uint32)
+
+    # ---- frag_spans, paired_begin + paired_finish
+    def frag_want(self, arrays, off, cap, contig):
+        """verify.frag_spans and frag_histogram: bmv_frag's two arrays and the informative pairs"""
+        from bucket_map_amd import verify
+        ts, tl, trc, ql, ed, en = arrays
+        span = verify.frag_spans(ts, tl, trc, ql, ed, en, off, cap, contig)
+        hist = verify.frag_histogram(span, cap)
+        assert int(hist.sum()) == (len(off) - 1) // 2 and len(hist) == cap + 1
+        return [span, hist], {"n_informative": int((span != 0).sum())}
+
+    def frag_call(self, arrays, off, cap, contig, what):
+        ts, tl, trc, ql, ed, en = arrays
+        want, counts = self.frag_want(arrays, off, cap, contig)
+        return Call("frag_spans", what, lambda v: v.frag_spans(ts, tl, trc, ql, ed, en, off, cap, contig), {"frag": want}, {"frag_stats": counts})
+
+    def frag_small(self, n):
+        """n alignments by numbers alone, L = left and R = left + 30 on either strand: a pair with an empty first group; a pair
+        of one candidate each that spans 40 .. 99 bases (informative under cap = 100); an unsettled pair -- two known loci in its
+        first group --; a settled pair that spans 430 bases (beyond cap = 100); over and over."""
+        ts, tl, trc, ql, ed, en, off = [], [], [], [], [], [], [0]
+
+        def add(rc, left, edits, m=30):
+            ts.append(left - (10 if rc else 5)); tl.append(m + 15); trc.append(rc); ql.append(m); ed.append(edits); en.append(m + 5)
+        k = 0
+        while len(ts) < n:
+            kind = (0, 1, 2, 3)[k % 4]
+            if len(ts) + (1, 2, 3, 2)[kind] > n:
+                kind = 0
+            if kind == 0:
+                off.append(len(ts))
+                add(1, 1040 + k, k % 3)
+            elif kind == 1:
+                add(0, 1000, k % 3)
+                off.append(len(ts))
+                add(1, 1000 + (40 + (7 * k) % 60) - 30, 0)
+            elif kind == 2:
+                add(0, 1000, 1); add(0, 1007, 2)
+                off.append(len(ts))
+                add(1, 1040, 0)
+            else:
+                add(0, 1000, 0)
+                off.append(len(ts))
+                add(1, 1400, 0)
+            off.append(len(ts))
+            k += 1
+        assert len(ts) == n and (len(off) - 1) % 2 == 0
+        return (np.array(ts, np.uint64), np.array(tl, np.uint32), np.array(trc, np.uint8), np.array(ql, np.uint32), np.array(ed, np.uint32),
+                np.array(en, np.uint32)), np.array(off, np.uint32)
+
+    def halves_call(self, gb, hint, cap, lo, hi, what):
+        """bmv_paired_begin under cap, then bmv_paired_finish under [lo, hi]: bmv_align_paired's oracle in its rows, and for
+        cap > 0 the spans of what bmv_best returns in bmv_frag's.  cap = 0 IS align_paired, and is filed as that: the frag row
+        is then nobody's, and _make holds it to what it was."""
+        paired, _ = self.paired_call(gb, hint, lo, hi, what)
+        batch, off, margin, contig = gb["batch"], gb["off"], gb["margin"], gb["contig"]
+        want, counts = dict(paired.want), dict(paired.counts)
+        if cap:
+            _, edits, out_end, _ = self.best_want(gb)
+            want["frag"], counts["frag_stats"] = self.frag_want((batch[1], batch[2], batch[3], batch[5], edits, out_end), off, cap, contig)
+
+        def run(v):
+            frag = v.paired_begin(*batch, off, margin, cap, gb[hint], contig)
+            assert (frag is None) == (cap == 0)
+            v.paired_finish(lo, hi)
+        return Call("paired_halves" if cap else "align_paired", what, run, want, counts)
+
+    # ---- split, split_pick
+    def split_ranges(self, key, paths, scores):
+        """verify.clip_range per alignment: the five per-alignment arrays of bmv_segments"""
+        def make():
+            from bucket_map_amd import verify
+            batch, begins, cigars = paths
+            out = {k: [] for k in ("score", "q_lo", "q_hi", "g_lo", "g_hi")}
+            for a in range(len(begins)):
+                window, rc, query = self.views(batch, a)
+                r = verify.clip_range(window, query, rc, begins[a], _pack(cigars[a]), *scores)
+                out["score"].append(r["score"]); out["q_lo"].append(r["q_lo"]); out["q_hi"].append(r["q_hi"])
+                out["g_lo"].append(int(batch[1][a]) + r["g_off_lo"]); out["g_hi"].append(int(batch[1][a]) + r["g_off_hi"])
+            return [np.array(out[k], t) for k, t in (("score", np.int64), ("q_lo", np.uint32), ("q_hi", np.uint32), ("g_lo", np.int64), ("g_hi", np.int64))]
+        return self.once(("split ranges", key, scores), make)
+
+    def split_call(self, entry, key, paths, five, off, contig, scores, params, what):
+        """bmv_split on paths or bmv_split_pick on `five`, their ranges: the ranges as given and verify.select_segments over them"""
+        from bucket_map_amd import verify
+        batch, begins, cigars = paths
+        pick = self.once(("split pick", key, scores, params, contig is None),
+                         lambda: verify.select_segments(*five, batch[3], off, *params, contig))
+        want = [*five, pick["n_seg"], pick["seg"].reshape(-1), pick["s2"].reshape(-1)]
+        counts = {"columns": int(sum(k for c in cigars for _, k in c)) if entry == "split" else 0, "n_segments": int(pick["n_seg"].sum())}
+        if entry == "split":
+            c_off, cg = _packed(cigars)
+            run = lambda v: v.split(*batch, begins, c_off, cg, off, *scores, *params, contig)                     # noqa: E731
+        else:
+            run = lambda v: v.split_pick(*five, batch[3], off, *params, contig)                                   # noqa: E731
+        return Call(entry, what, run, {"segments": want}, {"split_stats": counts}), pick
+
+    def split_first(self, entry, n, params=None):
+        """`entry` on the first n of the 2 100 big paths in groups of SPLIT_SIZES, with contigs"""
+        batch, begins, cigars = paths = self.big_paths()
+        scores, params = SPLIT_BIG[0], params or SPLIT_BIG[1]
+        five = [x[:n] for x in self.split_ranges("big", paths, scores)]
+        off = _cut_groups(_sized_groups(BIG, SPLIT_SIZES), n)
+        contig = (batch[1][:n] >= 30_000).astype(np.uint32)
+        return self.split_call(entry, ("first", n), (_sub(batch, np.arange(n)), begins[:n], cigars[:n]), five, off, contig, scores, params,
+                               f"{entry} of {n}")
+
+    def split_small(self, entry, n, max_segments):
+        """`entry` on the small paths in groups of 0, 2 and 2, without contigs: an empty group, a group of an empty CIGAR and an
+        alignment without any = column (nobody reaches min_score), a group that has a segment, over and over; then the real ones"""
+        paths = self.small_paths(n)
+        scores, params = CLIP, (40, 500, max_segments)
+        five = self.split_ranges(("small", n), paths, scores)
+        return self.split_call(entry, ("small", n), paths, five, _sized_groups(n, (0, 2, 2)), None, scores, params,
+                               f"{entry} of {n}, max_segments {max_segments}")
+
+    def split_calls(self, entry, n):
+        """the five steps: 16 segments a group and contigs in big; 1, then 3, and no contigs in small"""
+        none = (_Batch().args(), [], [])
+        five = [np.zeros(0, t) for t in (np.int64, np.uint32, np.uint32, np.int64, np.int64)]
+        empty, _ = self.split_call(entry, "empty", none, five, np.zeros(1, np.uint32), None, CLIP, (40, 500, 8), f"{entry} of 0")
+        big, pick = self.split_first(entry, BIG)
+        steps = [big, self.split_small(entry, n, 1)[0], empty, self.split_small(entry, n, 3)[0], big]
+        return steps, pick
 
     # ---- rescue
     def rescue_want(self, args, lo, hi):
@@ -874,6 +1039,205 @@ def test_the_passes_back_to_back(world, ctx, order, n):
         _make(ctx, call, state, f"step {k}, {call.what}")
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SMALL)
+@pytest.mark.parametrize("entry", ["split", "split_pick"])
+def test_split(world, ctx, entry, n):
+    """bmv_split and bmv_split_pick.  Stale: sp_score / sp_q_lo / sp_q_hi / sp_g_lo / sp_g_hi (an empty CIGAR and an alignment
+    without an = column write their zeros over big's ranges), sp_group_offset, sp_contig -- small passes contig = NULL after a
+    call that passed contigs --, sp_n_seg, sp_seg and sp_s2: big fills 16 slots a group, small has 1 and then 3 slots a group, so
+    group g's slots begin where another group's lay, and a group that leaves early -- no members, or nobody at min_score -- must
+    still write n_seg = 0 and BMV_BEYOND / BMV_SPLIT_NONE over every one of its slots; text_rc, which bmv_split_pick puts into
+    the views' buffer.  Big: 2 100 alignments under scores that keep a part of each, in groups of 1, 63, 64, 65 and 130."""
+    from bucket_map_amd import verify
+    calls, pick = world.split_calls(entry, n)
+    sizes = np.diff(_sized_groups(BIG, SPLIT_SIZES).astype(np.int64))
+    assert set(SPLIT_SIZES) <= set(sizes.tolist()) and pick["n_seg"].max() >= 4 and (pick["n_seg"][sizes >= 63] >= 2).sum() > 15
+    assert (pick["s2"][:, 0] != verify.SPLIT_NONE).sum() > 10 and 0 < (world.big_paths()[0][1] >= 30_000).sum() < BIG
+    for ms in (1, 3):                                          # what the small batches claim to hold, on the restatement's output
+        _, small = world.split_small(entry, n, ms)
+        cigars, off = world.small_paths(n)[2], _sized_groups(n, (0, 2, 2))
+        early = [g for g in range(len(off) - 1) if g % 3 < 2 and off[g + 1] <= (2 * n) // 3 + (n == 3)]
+        assert len(early) >= 2 and any(off[g] == off[g + 1] for g in early) and any(cigars[a] == [] for g in early for a in range(off[g], off[g + 1]))
+        assert not small["n_seg"][early].any() and (small["seg"][early] == BEYOND).all() and (small["s2"][early] == verify.SPLIT_NONE).all()
+        assert small["seg"].shape[1] == ms and (n == 3 or small["n_seg"].any())
+    state = {}
+    for k, call in enumerate(calls):
+        _make(ctx, call, state, f"step {k}, {call.what}")
+    for call in calls[:4]:
+        _fresh_agrees(world.genome, call)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SMALL)
+def test_frag_spans(world, ctx, n):
+    """bmv_frag_spans.  Stale: bs_edits, bs_out_end and bs_group_offset (shared with bmv_align_best and bmv_pair), pr_contig --
+    small passes contig = NULL after a call that passed contigs --, fr_span (a pair with an empty group, an unsettled one and
+    one beyond cap write their 0) and fr_hist: big counts under cap = 65 535 by global atomics, small under cap = 100 in LDS,
+    then big again, and the bins are the call's own every time -- hist sums to n_groups / 2 (World.frag_want asserts it of the
+    restatement, which the call must equal).  Big: what bmv_align_best's oracle leaves for its 2 100 alignments."""
+    big = world.big_groups()
+    _, edits, out_end, _ = world.best_want(big)
+    b = big["batch"]
+    arrays, off = world.frag_small(n)
+    calls = {"big": world.frag_call((b[1], b[2], b[3], b[5], edits, out_end), big["off"], 65_535, big["contig"], f"frag_spans of {BIG}"),
+             "small": world.frag_call(arrays, off, 100, None, f"frag_spans of {n}"),
+             "empty": world.frag_call(tuple(x[:0] for x in arrays), np.zeros(1, np.uint32), 100, None, "frag_spans of 0")}
+    span = calls["big"].want["frag"][0]
+    assert (span != 0).sum() > 50 and (span == 0).sum() > 50 and len(set(span.tolist())) > 40
+    span, sizes = calls["small"].want["frag"][0], np.diff(off.astype(np.int64))
+    assert (sizes == 0).any() and (span != 0).any() and span.max() <= 100 and (span == 0).sum() >= (1 if n == 3 else 3 * (len(span) // 4))
+    _five(world.genome, ctx, calls)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ctx", [None, 1], indirect=True, ids=["scratch by default", "1 MB of scratch"])
+@pytest.mark.parametrize("n", SMALL)
+def test_paired_begin_and_finish(world, ctx, n, request):
+    """bmv_paired_begin with cap > 0, then bmv_paired_finish: every step is bmv_align_paired's oracle in that call's six rows
+    -- and bmv_align_paired itself with the same range on a fresh context is held to the same arrays --, and the spans of what
+    bmv_best returns in bmv_frag's two.  Stale: everything test_align_paired and test_frag_spans name, between the two halves
+    too.  Big under cap = 65 535, small and empty under cap = 1 000; a sixth step makes the small batch's halves with cap = 0,
+    which is bmv_align_paired and must leave bmv_frag and its stats as the big batch before it left them."""
+    scratch_mb = request.node.callspec.params["ctx"]
+    big, small, none = world.big_groups(), world.small_groups(n), world.no_groups()
+    calls = {"big": world.halves_call(big, "wrong", 65_535, 200, 700, f"the halves of {BIG}"),
+             "small": world.halves_call(small, "right", 1_000, 200, 700, f"the halves of {n}"),
+             "empty": world.halves_call(none, "right", 1_000, 200, 700, "the halves of 0")}
+    assert (calls["big"].want["frag"][0] != 0).sum() > 50 and not calls["small"].want["frag"][0].any()
+    state = {}
+    for k, step in enumerate(STEPS):
+        call = world.halves_call(big, "right", 65_535, 200, 700, f"the halves of {BIG}, right hints") if k == 4 else calls[step]
+        _make(ctx, call, state, f"step {k}, {call.what}")
+    held = [x.copy() for x in state["frag"]]
+    call = world.halves_call(small, "right", 0, 200, 700, f"the halves of {n}, cap 0")
+    assert call.entry == "align_paired" and "frag" not in call.want
+    _make(ctx, call, state, f"step 5, {call.what}")
+    _assert_arrays(_read(ctx, "frag", held), held, "bmv_frag after the halves with cap 0")
+    for step in ("big", "small", "empty"):
+        _fresh_agrees(world.genome, calls[step], scratch_mb)
+    for gb, hint, what in ((big, "wrong", BIG), (small, "right", n), (none, "right", 0)):
+        _fresh_agrees(world.genome, world.paired_call(gb, hint, 200, 700, f"align_paired of {what}")[0], scratch_mb)
+
+
+# ------------------------------------------------------------------------------------------------ between the two halves
+
+BETWEEN = ("frag_spans", "pair", "frag", "annotate", "clip", "realign", "leftalign", "split", "split_pick", "rescue", "accessors")
+ENDING = ("align", "align_long", "align_bounded", "align_best", "align_paired", "a refused paired_begin", "rescue beyond 512 bases")
+RANGE = (200, 700)
+
+
+def _halves_batches(world):
+    """A: the first 70 groups of the big groups, with contigs.  B, by numbers alone: every alignment of the big groups but the
+    first and the last group's -- 2 000 and more, and group g of B is group g + 1 of big, so hardly an offset of B is A's.  That the
+    test cannot pass by accident is asserted here, on the CPU: were bmv_paired_finish to pick over what B's call left in
+    bs_edits / bs_out_end under A's offsets, or over A's (edits, end) under what B's call left in bs_group_offset, it would
+    pick otherwise for some pair of A."""
+    def make():
+        from bucket_map_amd import verify
+        big = world.big_groups()
+        a_gb = _first_groups(world, int(big["off"][70]))
+        assert len(a_gb["off"]) == 71
+        _, a_ed, a_en, _ = world.best_want(a_gb)
+        _, ed, en, _ = world.best_want(big)
+        off, bt = big["off"].astype(np.int64), big["batch"]
+        lo, hi = int(off[1]), int(off[-2])
+        b_off = (off[1:-1] - off[1]).astype(np.uint32)
+        b = {"arrays": tuple(x[lo:hi] for x in (bt[1], bt[2], bt[3], bt[5], ed, en)), "off": b_off, "contig": big["contig"][lo:hi]}
+        assert (len(b_off) - 1) % 2 == 0 and hi - lo > 4 * len(a_ed) and (b_off[1:71] != a_gb["off"][1:]).sum() >= 60
+        at = a_gb["batch"]
+        views, n_a = (at[1], at[2], at[3], at[5]), len(a_ed)
+        true = verify.select_pairs(*views, a_ed, a_en, a_gb["off"], *RANGE, a_gb["contig"])["pick"]
+        stale_edits = verify.select_pairs(*views, b["arrays"][4][:n_a], b["arrays"][5][:n_a], a_gb["off"], *RANGE, a_gb["contig"])["pick"]
+        size = int(b_off[70])                                    # what 70 groups under B's offsets reach of A's arrays (beyond them: nothing known)
+        fit = lambda x, fill: np.concatenate([x, np.full(max(size - n_a, 0), fill, x.dtype)])[:size]      # noqa: E731
+        stale_offsets = verify.select_pairs(*(fit(x, 0) for x in views), fit(a_ed, BEYOND), fit(a_en, 0), b_off[:71], *RANGE,
+                                            fit(a_gb["contig"], 0))["pick"]
+        assert (stale_edits != true).any() and (stale_offsets != true).any(), "A and B would not tell a stale buffer from a fresh one"
+        return a_gb, b
+    return world.once("the halves' batches", make)
+
+
+def _read_everything(v):
+    """every accessor and every stats call, whatever they hold"""
+    for name in ACCESSORS:
+        _read(v, name, [np.zeros(0, t) for t in SHAPES[name]])
+    for name in STATS:
+        _counts(v, name)
+
+
+def _begin(world, v, state):
+    """bmv_paired_begin on A with cap = 1 000, which fills bmv_frag's row; returns A's groups, B and what finish must leave"""
+    a_gb, b = _halves_batches(world)
+    want = world.halves_call(a_gb, "right", 1_000, *RANGE, "the halves of A")
+    frag = v.paired_begin(*a_gb["batch"], a_gb["off"], a_gb["margin"], 1_000, a_gb["right"], a_gb["contig"])
+    _assert_arrays([frag["span"], frag["hist"]], want.want["frag"], "bmv_paired_begin's spans")
+    state["frag"], state["frag_stats"] = want.want["frag"], _counts(v, "frag_stats")
+    assert state["frag_stats"] == want.counts["frag_stats"]
+    paired = world.paired_call(a_gb, "right", *RANGE, "align_paired of A")[0]
+    return a_gb, b, paired
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("between", BETWEEN)
+def test_calls_that_may_come_between_the_halves(world, ctx, between):
+    """bmv_paired_begin keeps (edits, end) and the group offsets of its batch A on the device for bmv_paired_finish -- the one
+    state of the library that outlives a call there.  One call on a larger batch B with other group offsets comes in between;
+    the finish then leaves, row for row, what bmv_align_paired leaves for A under the same range on a fresh context (the
+    oracle's arrays for both).  bmv_pair and bmv_frag_spans put B's arrays where A's lay; the passes, the split calls and a
+    rescue of queries of at most 512 bases use the views' buffers and their own; the accessors use none.  The in-between call
+    is held to its own oracle too, and after the finish its row is still what it left."""
+    state = {}
+    a_gb, b, paired = _begin(world, ctx, state)
+    if between == "frag_spans":
+        call = world.frag_call(b["arrays"], b["off"], 65_535, b["contig"], "frag_spans of B")
+    elif between == "pair":
+        call = world.pair_call(b["arrays"], b["off"], 1, 5_000, b["contig"], "pair of B")[0]
+    elif between in ("frag", "accessors"):
+        call = None
+    else:
+        call = _any_call(world, between, BIG)
+    if call is not None:
+        if between == "rescue":
+            assert call.want["rescued"][1].max() > 0 and max(world.rescue_big()[9]) <= 512
+        _make(ctx, call, state, f"between the halves: {call.what}")
+    elif between == "frag":
+        got = ctx.frag(35, 1_000)
+        _assert_arrays([got["span"], got["hist"]], state["frag"], "bmv_frag between the halves")
+        ctx.frag_stats()
+    else:
+        _read_everything(ctx)
+    finish = Call("align_paired", f"bmv_paired_finish of A after {between}", lambda v: v.paired_finish(*RANGE), paired.want, paired.counts)
+    _make(ctx, finish, state, finish.what)
+    world.once("A on a fresh context", lambda: _fresh_agrees(world.genome, paired))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ending", ENDING)
+def test_calls_that_end_a_pending_begin(world, ctx, ending):
+    """Every call that aligns ends a pending bmv_paired_begin -- bmv_rescue too, when a query beyond 512 bases sends it to the
+    aligner, and a new begin that its checks refuse: bmv_paired_finish then says BMV_ERR_STATE and changes nothing, and the
+    context serves bmv_align_paired of the same batch as a fresh one would."""
+    from bucket_map_amd import verify
+    state = {}
+    a_gb, b, paired = _begin(world, ctx, state)
+    if ending == "a refused paired_begin":
+        with pytest.raises(verify.BmvError) as e:
+            ctx.paired_begin(*a_gb["batch"], a_gb["off"], a_gb["margin"], 65_536, a_gb["right"], a_gb["contig"])
+        assert e.value.code == 1 and "cap" in str(e.value)
+    else:
+        if ending == "rescue beyond 512 bases":
+            small = world.rescue_small(3)
+            assert (small[9] > 512).any()
+            call = world.rescue_call(small, 1, 5000, "rescue of 3 kinds that leave early")
+        else:
+            call = _any_call(world, ending, 3 if ending == "align_paired" else 70)
+        _make(ctx, call, state, f"after the begin: {call.what}")
+    refused = Call("align_paired", f"bmv_paired_finish after {ending}", lambda v: v.paired_finish(*RANGE), refused=3)
+    _make(ctx, refused, state, refused.what)
+    _make(ctx, paired, state, f"{paired.what} after {ending}")
+
+
 # ------------------------------------------------------------------------------------------------ "leaves untouched"
 
 def _prefix_groups(off, n):
@@ -886,6 +1250,16 @@ def _prefix_groups(off, n):
     return np.array(off, np.uint32)
 
 
+def _first_groups(world, n):
+    """the first n alignments of the big groups, in big's groups and with its margins, hints and contigs"""
+    big, idx = world.big_groups(), np.arange(n)
+    off = _prefix_groups(big["off"], n)
+    g = len(off) - 1
+    hint = np.minimum(np.resize(big["right"], g), np.maximum(np.diff(off.astype(np.int64)), 1) - 1).astype(np.uint32)
+    return {"batch": _sub(big["batch"], idx), "off": off, "margin": np.resize(big["margin"], g).astype(np.uint32), "full": _take(big["full"], idx),
+            "contig": big["contig"][:n], "right": hint}
+
+
 def _any_call(world, entry, n):
     """`entry` on the first n items of its big batch, with the oracle's results for them"""
     idx = np.arange(n)
@@ -896,20 +1270,23 @@ def _any_call(world, entry, n):
         world.bounded_calls(3)
         batch, full = world.memo["bounded big"]
         return world.bounded_call(_sub(batch, idx), _take(full, idx), (8 + idx % 9).astype(np.uint32), f"align_bounded of {n}")[0]
-    if entry in ("align_best", "align_paired", "pair"):
-        big = world.big_groups()
-        off = _prefix_groups(big["off"], n)
-        g = len(off) - 1
-        hint = np.minimum(np.resize(big["right"], g), np.maximum(np.diff(off.astype(np.int64)), 1) - 1).astype(np.uint32)
-        gb = {"batch": _sub(big["batch"], idx), "off": off, "margin": np.resize(big["margin"], g).astype(np.uint32), "full": _take(big["full"], idx),
-              "contig": big["contig"][:n], "right": hint}
+    if entry in ("align_best", "align_paired", "pair", "frag_spans", "paired_halves", "the halves with cap 0"):
+        gb = _first_groups(world, n)
         if entry == "align_best":
             return world.best_call(gb, "right", f"align_best of {n}")
         if entry == "align_paired":
             return world.paired_call(gb, "right", 200, 700, f"align_paired of {n}")[0]
+        if entry == "paired_halves":                           # (the largest cap only where the batch is large: 65 536 bins to check)
+            return world.halves_call(gb, "right", 65_535 if n == BIG else 1_000, 200, 700, f"the halves of {n}")
+        if entry == "the halves with cap 0":
+            return world.halves_call(gb, "right", 0, 200, 700, f"the halves of {n}, cap 0")
         _, edits, out_end, _ = world.best_want(gb)
-        b = gb["batch"]
+        b, off = gb["batch"], gb["off"]
+        if entry == "frag_spans":
+            return world.frag_call((b[1], b[2], b[3], b[5], edits, out_end), off, 65_535 if n == BIG else 100, gb["contig"], f"frag_spans of {n}")
         return world.pair_call((b[1], b[2], b[3], b[5], edits, out_end), off, 200, 700, gb["contig"], f"pair of {n}")[0]
+    if entry in ("split", "split_pick"):                       # (fewer slots a group where the batch is cut)
+        return world.split_first(entry, n, None if n == BIG else (SPLIT_BIG[1][0], SPLIT_BIG[1][1], (1, 3, 8)[n % 3]))[0]
     if entry == "rescue":
         args = world.rescue_big()
         return world.rescue_call((args[0], *(x[:n] for x in args[1:])), 1, 600, f"rescue of {n}")
@@ -919,12 +1296,34 @@ def _any_call(world, entry, n):
     return world.path_call(entry, ("first", n), (_sub(batch, idx), begins[:n], cigars[:n]), f"{entry} of {n}")
 
 
-def _refusal(world, rng):
+def _new_refusal(world, rng):
+    """... of the entries beyond ELEVEN: max_segments beyond 16, q_lo behind q_hi, a cap beyond 65 535 -- of bmv_frag_spans, and
+    of bmv_paired_begin, which is then no begin at all: no finish follows"""
+    batch, begins, cigars = world.big_paths()
+    three, off3 = _sub(batch, np.arange(3)), np.array([0, 1, 3], np.uint32)
+    which = int(rng.integers(0, 4))
+    if which == 0:
+        c_off, cg = _packed(cigars[:3])
+        return Call("split", "split with 17 segments a group", lambda v: v.split(*three, begins[:3], c_off, cg, off3, max_segments=17), refused=1)
+    if which == 1:
+        return Call("split_pick", "split_pick with q_lo behind q_hi",
+                    lambda v: v.split_pick([50, 60, 70], [0, 9, 0], [10, 8, 10], [0, 0, 0], [10, 10, 10], [0, 1, 0], off3), refused=1)
+    big = world.big_groups()
+    b = _sub(big["batch"], np.arange(3))
+    if which == 2:
+        return Call("frag_spans", "frag_spans with a cap beyond 65 535",
+                    lambda v: v.frag_spans(b[1], b[2], b[3], b[5], np.zeros(3, np.uint32), b[5], off3, 65_536), refused=1)
+    return Call("paired_halves", "paired_begin with a cap beyond 65 535", lambda v: v.paired_begin(*b, off3, np.ones(2, np.uint32), 65_536), refused=1)
+
+
+def _refusal(world, rng, kinds=5):
     """a call that is refused before anything runs: it owns nothing"""
     g = world.genome
     batch, _ = world.big_reads()
     three = _sub(batch, np.arange(3))
-    kind = int(rng.integers(0, 5))
+    kind = int(rng.integers(0, kinds))
+    if kind == 5:
+        return _new_refusal(world, rng)
     if kind == 0:                                              # a text outside the genome, through any call that takes views
         outside = (three[0], np.array([0, len(g) - 100, 0], np.uint64), *three[2:])
         entry = ("align", "align_long", "align_bounded", "align_best", "annotate", "clip")[int(rng.integers(0, 6))]
@@ -972,19 +1371,26 @@ def _refusal(world, rng):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed,sizes", [(1, (0, 1, 3, 70, BIG)), (2, (0, 1, 3, 70, BIG)), (3, (0, 1, 3, 70, BIG)), (4, (BIG,))],
-                         ids=["seed 1", "seed 2", "seed 3", "seed 4, every n 2100"])
-def test_every_call_leaves_the_others_results_untouched(world, seed, sizes):
-    """40 calls drawn over all eleven entry points, one in five a refusal (a text outside the genome, an odd n_groups,
+@pytest.mark.parametrize("seed,sizes,table", [(1, (0, 1, 3, 70, BIG), ELEVEN), (2, (0, 1, 3, 70, BIG), ELEVEN), (3, (0, 1, 3, 70, BIG), ELEVEN),
+                                               (4, (BIG,), ELEVEN), (5, (0, 1, 3, 70, BIG), None), (6, (0, 1, 3, 70, BIG), None), (7, (BIG,), None)],
+                         ids=["seed 1", "seed 2", "seed 3", "seed 4, every n 2100", "seed 5, every entry", "seed 6, every entry",
+                              "seed 7, every entry, every n 2100"])
+def test_every_call_leaves_the_others_results_untouched(world, seed, sizes, table):
+    """40 calls drawn over eleven entry points (seeds 1 .. 4: the table as it stood when they were drawn), or 55 over every key
+    of OWNS and the two halves with cap = 0, which are bmv_align_paired (seeds 5 .. 7); one in five a refusal (a text outside the
+    genome, an odd n_groups,
     min_frag > max_frag, a trace beyond the scratch -- which bmv_align_long refuses before anything runs, and bmv_align_bounded and
-    bmv_align_best after they handed a sub-batch on: their own row is then unspecified, every other one stays --), on a context
+    bmv_align_best after they handed a sub-batch on: their own row is then unspecified, every other one stays --; from seed 5 on
+    also what bmv_split, bmv_split_pick, bmv_frag_spans and bmv_paired_begin refuse), on a context
     of 4 096-base limits and 1 MB of scratch.  After every call
-    each of bmv_results, bmv_best, bmv_pairs, bmv_rescued, bmv_annotations, bmv_clipped, bmv_realigned and bmv_leftaligned, and
+    each of bmv_results, bmv_best, bmv_pairs, bmv_frag, bmv_rescued, bmv_segments, bmv_annotations, bmv_clipped, bmv_realigned and
+    bmv_leftaligned, and
     the count fields of every bmv_last_*_stats, is what its own last successful call left: the oracle's for the owner (OWNS),
     unchanged for everybody else.  With every n 2 100 no buffer is ever reallocated."""
     from bucket_map_amd import verify
     rng = np.random.default_rng(seed)
-    entries = sorted(OWNS)
+    entries = sorted(table or (*OWNS, "the halves with cap 0"))
+    calls, kinds = (40, 5) if table else (55, 6)
     old = os.environ.get("BMV_SCRATCH_MB")
     os.environ["BMV_SCRATCH_MB"] = "1"
     try:
@@ -997,9 +1403,9 @@ def test_every_call_leaves_the_others_results_untouched(world, seed, sizes):
     v.load_genome(world.genome)
     state, seen, first, refused = {}, set(), [entries[x] for x in rng.permutation(len(entries))], 0     # every entry point once, then any
     try:
-        for k in range(40):
+        for k in range(calls):
             if k % 5 == 4:
-                call = _refusal(world, rng)
+                call = _refusal(world, rng, kinds)
                 refused += 1
             else:
                 entry = first.pop() if first else entries[int(rng.integers(0, len(entries)))]
@@ -1008,4 +1414,5 @@ def test_every_call_leaves_the_others_results_untouched(world, seed, sizes):
             seen |= set(state)
     finally:
         v.close()
-    assert refused == 8 and seen == set(ACCESSORS) | set(STATS)
+    assert refused == calls // 5 and seen == {row for entry in (table or OWNS) for row in OWNS[entry]}
+    assert table or seen == set(ACCESSORS) | set(STATS)
