@@ -1,7 +1,5 @@
 // bmz_api.hip -- host side of the BGZF block compressor (include/bmz.h): buffers, the launch, the packed download.
-#include "../../include/bmz.h"
-
-#include "bm_hip_util.h"
+#include "bmz_ctx.hip.h"
 #include "bmz_kernels.hip.h"
 
 #define HIP_TRY(expr) BM_HIP_TRY(expr, BMZ_ERR_HIP)
@@ -10,18 +8,50 @@ using bmhip::DevBuf;
 
 static_assert(BMZ_BLOCK_MAX == bmz::kBlockMax && BMZ_HASH_BITS == bmz::kHashBits, "bmz.h and the kernels disagree");
 
-struct bmz_ctx {
-    int device = 0;
-    uint32_t n_cu = 1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    DevBuf<uint8_t> in, stage, out, forms;
-    DevBuf<uint32_t> tokens, sizes;
-    DevBuf<uint64_t> offsets, scan_tmp;
-    std::vector<uint64_t> h_offsets{0};
-    float ms_kernels = 0.f;
-    uint32_t n_form[3] = {0, 0, 0};
-};
+// the launch sequence of a call: the deflate kernel over the blocks, the scan of their sizes, the gather of the slots, and
+// the packed download (bmz_ctx.hip.h)
+int bmz_deflate_device(bmz_ctx *c, const uint8_t *d_in, uint64_t n_bytes, uint32_t block_bytes, uint8_t *out, uint64_t out_cap,
+                       uint64_t *out_bytes) {
+    const uint32_t n_blocks = (uint32_t)((n_bytes + block_bytes - 1) / block_bytes);
+    *out_bytes = 0;
+    c->h_offsets.assign(1, 0);
+    c->ms_kernels = 0.f;
+    c->n_form[0] = c->n_form[1] = c->n_form[2] = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t stride = bmz::slot_stride(block_bytes), grid = std::min(n_blocks, c->n_cu);
+    HIP_TRY(c->stage.need((size_t)n_blocks * stride));
+    HIP_TRY(c->out.need((size_t)bmz_bound(n_bytes, block_bytes)));
+    HIP_TRY(c->tokens.need((size_t)grid * bmz::kBlockMax));
+    HIP_TRY(c->sizes.need(n_blocks));
+    HIP_TRY(c->forms.need(n_blocks));
+    HIP_TRY(c->offsets.need((size_t)n_blocks + 1));
+    HIP_TRY(c->scan_tmp.need(bmscan::tmp_elems(n_blocks)));
+
+    HIP_TRY(hipMemsetAsync(c->stage.p, 0, (size_t)n_blocks * stride, c->stream));
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(bmz::deflate_kernel, dim3(grid), dim3(bmz::kThreads), 0, c->stream, d_in, n_bytes, block_bytes, n_blocks,
+                       c->stage.p, c->tokens.p, c->sizes.p, c->forms.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->sizes.p, c->offsets.p, n_blocks, c->scan_tmp.p, c->stream));
+    hipLaunchKernelGGL(bmz::gather_kernel, dim3(n_blocks), dim3(bmz::kThreads), 0, c->stream, c->stage.p, stride, c->sizes.p,
+                       c->offsets.p, c->out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    c->h_offsets.resize((size_t)n_blocks + 1);
+    std::vector<uint8_t> forms(n_blocks);
+    HIP_TRY(hipMemcpyAsync(c->h_offsets.data(), c->offsets.p, ((size_t)n_blocks + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(forms.data(), c->forms.p, n_blocks, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint64_t total = c->h_offsets[n_blocks];
+    if (total > out_cap) return fail(BMZ_ERR_HIP, "bmz_deflate: the blocks take %llu bytes, beyond the bound", (unsigned long long)total);
+    HIP_TRY(hipMemcpyAsync(out, c->out.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&c->ms_kernels, c->ev0, c->ev1));
+    for (uint8_t f : forms)
+        if (f < 3) c->n_form[f]++;
+    *out_bytes = total;
+    return BMZ_OK;
+}
 
 extern "C" {
 
@@ -88,41 +118,9 @@ int bmz_deflate(bmz_ctx *c, const uint8_t *in, uint64_t n_bytes, uint32_t block_
     if (n_blocks == 0) return BMZ_OK;
 
     HIP_TRY(hipSetDevice(c->device));
-    const uint32_t stride = bmz::slot_stride(block_bytes), grid = std::min(n_blocks, c->n_cu);
     HIP_TRY(c->in.need((size_t)n_bytes + 8));
-    HIP_TRY(c->stage.need((size_t)n_blocks * stride));
-    HIP_TRY(c->out.need((size_t)bmz_bound(n_bytes, block_bytes)));
-    HIP_TRY(c->tokens.need((size_t)grid * bmz::kBlockMax));
-    HIP_TRY(c->sizes.need(n_blocks));
-    HIP_TRY(c->forms.need(n_blocks));
-    HIP_TRY(c->offsets.need((size_t)n_blocks + 1));
-    HIP_TRY(c->scan_tmp.need(bmscan::tmp_elems(n_blocks)));
-
     HIP_TRY(hipMemcpyAsync(c->in.p, in, (size_t)n_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->stage.p, 0, (size_t)n_blocks * stride, c->stream));
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(bmz::deflate_kernel, dim3(grid), dim3(bmz::kThreads), 0, c->stream, c->in.p, n_bytes, block_bytes, n_blocks,
-                       c->stage.p, c->tokens.p, c->sizes.p, c->forms.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(bmscan::exclusive_sum<uint64_t>(c->sizes.p, c->offsets.p, n_blocks, c->scan_tmp.p, c->stream));
-    hipLaunchKernelGGL(bmz::gather_kernel, dim3(n_blocks), dim3(bmz::kThreads), 0, c->stream, c->stage.p, stride, c->sizes.p,
-                       c->offsets.p, c->out.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    c->h_offsets.resize((size_t)n_blocks + 1);
-    std::vector<uint8_t> forms(n_blocks);
-    HIP_TRY(hipMemcpyAsync(c->h_offsets.data(), c->offsets.p, ((size_t)n_blocks + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(forms.data(), c->forms.p, n_blocks, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint64_t total = c->h_offsets[n_blocks];
-    if (total > out_cap) return fail(BMZ_ERR_HIP, "bmz_deflate: the blocks take %llu bytes, beyond the bound", (unsigned long long)total);
-    HIP_TRY(hipMemcpyAsync(out, c->out.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&c->ms_kernels, c->ev0, c->ev1));
-    for (uint8_t f : forms)
-        if (f < 3) c->n_form[f]++;
-    *out_bytes = total;
-    return BMZ_OK;
+    return bmz_deflate_device(c, c->in.p, n_bytes, block_bytes, out, out_cap, out_bytes);
 }
 
 int bmz_blocks(bmz_ctx *c, uint64_t *out_offset) {

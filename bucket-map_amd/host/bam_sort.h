@@ -1,0 +1,295 @@
+// bam_sort.h -- coordinate-sorted BAM with a .bai index (-o x.bam --sort): the run buffer, the merge of several runs and the
+// index.  The order is that of include/bms.h (bam_sort_key in bgzf.h: refID, then pos + 1, stable); who sorts a run is the
+// block_compressor (the device in the product, std::stable_sort elsewhere: the same permutation).
+//
+// Records are kept, with their offsets, in a run of at most run_bytes of BAM stream (--sort-mem; BM_SORT_RUN_BYTES for the
+// tests).  One run: one sort_deflate call at finish().  Several: every full run is sorted (sort_records) and written raw to
+// <out>.sort.<k>.tmp; finish() merges the runs by key, ties to the lower run number -- the stable sort of the whole input --
+// and deflates the merged stream in pieces of whole blocks.  Blocks are cut by size alone, so both ways give the same bytes.
+//
+// THE INDEX (SAM spec 5.2), fixed so that the file is a function of the sorted records:
+//   - a record at sorted-stream offset so has the virtual offset file_offset(block so / 65280) << 16 | so % 65280; block file
+//     offsets are read from the BSIZE fields of the emitted blocks, after the header's blocks; the end of the stream on a
+//     block border points at the EOF block;
+//   - a record covers [max(pos, 0), pos + reference length of its CIGAR) -- one base if that is empty; for a CG:B,I long CIGAR
+//     the placeholder's N carries the length -- and its bin is the record's own bin field;
+//   - bins ascending; one chunk per maximal run of consecutive records with the same (refID, bin), from the first record's
+//     offset to the offset after the last; no further merging;
+//   - linear index in 16 384-base windows: ioffset[w] = the offset of the first record that overlaps w, an untouched window
+//     takes the next touched one's value, n_intv = the last touched window + 1;
+//   - pseudo-bin 37450 for every reference with a record: (first, end) offsets, then (records without 0x4, records with 0x4);
+//   - n_no_coor = the records with refID = -1; a reference without records has n_bin = 0 and n_intv = 0.
+//   A record that ends beyond 2^29 cannot be binned by this format: it is refused (CSI is out of scope).
+#pragma once
+
+#include "bgzf.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <filesystem>
+#include <fstream>
+#include <functional>
+#include <map>
+#include <memory>
+#include <ostream>
+#include <queue>
+#include <stdexcept>
+#include <string>
+#include <utility>
+
+namespace bm {
+
+// --sort-mem N (MiB) as bytes, unless BM_SORT_RUN_BYTES says otherwise (the tests force several runs on small inputs)
+inline size_t bam_sort_run_bytes(size_t mem_mib) {
+    if (const char *e = std::getenv("BM_SORT_RUN_BYTES")) {
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v) return static_cast<size_t>(v);
+    }
+    return mem_mib << 20;
+}
+
+class bai_builder {
+    static constexpr uint64_t kNone = ~uint64_t{0};
+    static constexpr uint32_t kPseudoBin = 37450;
+    struct ref_entry {
+        std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;   // stream offsets until write()
+        std::vector<uint64_t> linear;
+        uint64_t first = 0, end = 0, n_mapped = 0, n_unmapped = 0;
+        bool any = false;
+    };
+    std::vector<ref_entry> refs_;
+    uint64_t n_no_coor_ = 0;
+    int64_t run_ref_ = -1;                // the open chunk
+    uint32_t run_bin_ = 0;
+    uint64_t run_beg_ = 0, run_end_ = 0;
+
+    static uint32_t u32(const uint8_t *p) {
+        uint32_t v;
+        std::memcpy(&v, p, 4);
+        return v;
+    }
+    static uint32_t u16(const uint8_t *p) { return static_cast<uint32_t>(p[0]) | static_cast<uint32_t>(p[1]) << 8; }
+    void close_run() {
+        if (run_ref_ >= 0) refs_[static_cast<size_t>(run_ref_)].bins[run_bin_].emplace_back(run_beg_, run_end_);
+        run_ref_ = -1;
+    }
+
+public:
+    explicit bai_builder(size_t n_ref) : refs_(n_ref) {}
+
+    // the records in sorted order: rec[0, len) starts at offset so of the sorted stream
+    void add(const uint8_t *rec, uint64_t so, uint64_t len) {
+        const int32_t ref = static_cast<int32_t>(u32(rec + 4)), pos = static_cast<int32_t>(u32(rec + 8));
+        if (ref < 0) {
+            close_run();
+            n_no_coor_++;
+            return;
+        }
+        if (static_cast<size_t>(ref) >= refs_.size()) throw std::runtime_error("--sort: a record names reference " + std::to_string(ref) + ", the header has " + std::to_string(refs_.size()));
+        const uint32_t l_name = rec[12], bin = u16(rec + 14), n_cigar = u16(rec + 16), flag = u16(rec + 18);
+        if (36ull + l_name + 4ull * n_cigar > len) throw std::runtime_error("--sort: a record's CIGAR lies beyond its end");
+        uint64_t ref_len = 0;
+        for (uint32_t k = 0; k < n_cigar; k++) {
+            const uint32_t c = u32(rec + 36 + l_name + 4 * k), op = c & 15u;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += c >> 4;
+        }
+        const uint64_t beg = pos < 0 ? 0 : static_cast<uint64_t>(pos);
+        const int64_t past = static_cast<int64_t>(pos) + static_cast<int64_t>(ref_len ? ref_len : 1);
+        const uint64_t end = past <= static_cast<int64_t>(beg) ? beg + 1 : static_cast<uint64_t>(past);
+        if (end > (uint64_t{1} << 29))
+            throw std::runtime_error("--sort: a record ends at base " + std::to_string(end) + ", beyond the 2^29 a .bai index can hold");
+        ref_entry &e = refs_[static_cast<size_t>(ref)];
+        if (run_ref_ == ref && run_bin_ == bin) {
+            run_end_ = so + len;
+        } else {
+            close_run();
+            run_ref_ = ref, run_bin_ = bin, run_beg_ = so, run_end_ = so + len;
+        }
+        const size_t w0 = static_cast<size_t>(beg >> 14), w1 = static_cast<size_t>((end - 1) >> 14);
+        if (e.linear.size() <= w1) e.linear.resize(w1 + 1, kNone);
+        for (size_t w = w0; w <= w1; w++)
+            if (e.linear[w] == kNone) e.linear[w] = so;
+        if (!e.any) e.first = so;
+        e.any = true;
+        e.end = so + len;
+        (flag & 4u ? e.n_unmapped : e.n_mapped)++;
+    }
+
+    // voffset: sorted-stream offset -> virtual file offset
+    void write(std::ostream &out, const std::function<uint64_t(uint64_t)> &voffset) {
+        close_run();
+        auto p32 = [&](uint32_t v) { out.write(reinterpret_cast<const char *>(&v), 4); };   // little-endian hosts only, as bgzf.h
+        auto p64 = [&](uint64_t v) { out.write(reinterpret_cast<const char *>(&v), 8); };
+        out.write("BAI\1", 4);
+        p32(static_cast<uint32_t>(refs_.size()));
+        for (ref_entry &e : refs_) {
+            p32(static_cast<uint32_t>(e.bins.size() + (e.any ? 1 : 0)));
+            for (const auto &[bin, chunks] : e.bins) {
+                p32(bin);
+                p32(static_cast<uint32_t>(chunks.size()));
+                for (const auto &[a, b] : chunks) p64(voffset(a)), p64(voffset(b));
+            }
+            if (e.any) {
+                p32(kPseudoBin);
+                p32(2);
+                p64(voffset(e.first)), p64(voffset(e.end));
+                p64(e.n_mapped), p64(e.n_unmapped);
+            }
+            p32(static_cast<uint32_t>(e.linear.size()));
+            uint64_t next = kNone;
+            for (size_t w = e.linear.size(); w-- > 0;) {
+                if (e.linear[w] == kNone) e.linear[w] = next;
+                next = e.linear[w];
+            }
+            for (uint64_t so : e.linear) p64(voffset(so));
+        }
+        p64(n_no_coor_);
+    }
+};
+
+class bam_sorter {
+    block_compressor *z_;
+    std::string out_path_;
+    size_t run_bytes_;
+    std::vector<uint8_t> run_;
+    std::vector<uint64_t> off_{0};
+    std::vector<std::string> tmp_;
+    uint64_t n_records_ = 0;
+    uint32_t passes_ = 0;
+
+    static uint32_t u32(const uint8_t *p) {
+        uint32_t v;
+        std::memcpy(&v, p, 4);
+        return v;
+    }
+    void remove_tmp() noexcept {
+        for (const std::string &t : tmp_) std::remove(t.c_str());
+        tmp_.clear();
+    }
+    // the run, sorted, as a raw file of its own
+    void spill() {
+        std::vector<uint8_t> sorted;
+        std::vector<uint32_t> perm;
+        std::vector<uint64_t> so;
+        z_->sort_records(run_.data(), run_.size(), off_.data(), off_.size() - 1, sorted, perm, so);
+        passes_ = std::max(passes_, z_->last_sort_passes());
+        tmp_.push_back(out_path_ + ".sort." + std::to_string(tmp_.size()) + ".tmp");   // listed first: removed whatever happens next
+        std::ofstream f(tmp_.back(), std::ios::binary);
+        f.write(reinterpret_cast<const char *>(sorted.data()), static_cast<std::streamsize>(sorted.size()));
+        f.close();
+        if (!f) throw std::runtime_error("--sort: cannot write " + tmp_.back());
+        run_.clear();
+        off_.assign(1, 0);
+    }
+
+    struct run_reader {
+        std::ifstream f;
+        std::vector<uint8_t> rec;
+        bool next() {
+            uint8_t head[4];
+            if (!f.read(reinterpret_cast<char *>(head), 4)) return false;
+            const uint32_t size = u32(head);
+            rec.resize(4 + static_cast<size_t>(size));
+            std::memcpy(rec.data(), head, 4);
+            if (!f.read(reinterpret_cast<char *>(rec.data()) + 4, size)) throw std::runtime_error("--sort: a run file ends inside a record");
+            return true;
+        }
+    };
+
+public:
+    bam_sorter(block_compressor *z, const std::filesystem::path &out_path, size_t run_bytes)
+        : z_(z), out_path_(out_path.string()), run_bytes_(std::max<size_t>(run_bytes, 1)) {}
+    ~bam_sorter() { remove_tmp(); }
+    bam_sorter(const bam_sorter &) = delete;
+    bam_sorter &operator=(const bam_sorter &) = delete;
+
+    uint64_t n_records() const { return n_records_; }
+    size_t n_runs() const { return n_runs_; }
+    uint32_t n_passes() const { return passes_; }
+
+    // whole records, back to back
+    void add(const uint8_t *recs, size_t n) {
+        for (size_t at = 0; at < n;) {
+            if (n - at < 4) throw std::runtime_error("--sort: a truncated record");
+            const size_t len = 4 + static_cast<size_t>(u32(recs + at));
+            if (len < 36 || len > n - at) throw std::runtime_error("--sort: a record of " + std::to_string(len) + " bytes");
+            if (off_.size() > 1 && (run_.size() + len > run_bytes_ || off_.size() > 0x7FFFFFFFu)) spill();
+            run_.insert(run_.end(), recs + at, recs + at + len);
+            off_.push_back(run_.size());
+            n_records_++;
+            at += len;
+        }
+    }
+
+    // the sorted records as BGZF blocks and the EOF block to `out` (which holds header_bytes of header blocks already), the
+    // index to <out path>.bai
+    void finish(std::ostream &out, uint64_t header_bytes, size_t n_ref) {
+        bai_builder bai(n_ref);
+        std::vector<uint64_t> block_at{header_bytes};
+        std::vector<uint8_t> blocks;
+        auto emit = [&]() {                              // the blocks made so far: to the file, their offsets noted
+            for (size_t at = 0; at < blocks.size();) {
+                const size_t size = (static_cast<size_t>(blocks[at + 16]) | static_cast<size_t>(blocks[at + 17]) << 8) + 1;
+                block_at.push_back(block_at.back() + size);
+                at += size;
+            }
+            out.write(reinterpret_cast<const char *>(blocks.data()), static_cast<std::streamsize>(blocks.size()));
+            blocks.clear();
+        };
+        if (tmp_.empty()) {
+            n_runs_ = off_.size() > 1 ? 1 : 0;
+            std::vector<uint32_t> perm;
+            std::vector<uint64_t> so;
+            z_->sort_deflate(run_.data(), run_.size(), off_.data(), off_.size() - 1, blocks, perm, so);
+            passes_ = z_->last_sort_passes();
+            for (size_t k = 0; k + 1 < off_.size(); k++) bai.add(run_.data() + off_[perm[k]], so[k], so[k + 1] - so[k]);
+            emit();
+        } else {
+            if (off_.size() > 1) spill();
+            n_runs_ = tmp_.size();
+            std::vector<uint8_t>().swap(run_);
+            std::vector<std::unique_ptr<run_reader>> reader;
+            using item = std::pair<uint64_t, size_t>;    // (key, run): the lower run wins a tie, and a run is in order already
+            std::priority_queue<item, std::vector<item>, std::greater<item>> heap;
+            for (size_t r = 0; r < tmp_.size(); r++) {
+                reader.push_back(std::make_unique<run_reader>());
+                reader[r]->f.open(tmp_[r], std::ios::binary);
+                if (!reader[r]->f) throw std::runtime_error("--sort: cannot read " + tmp_[r]);
+                if (reader[r]->next()) heap.emplace(bam_sort_key(reader[r]->rec.data()), r);
+            }
+            constexpr size_t kPiece = size_t{64} * kBgzfBlockMax;
+            std::vector<uint8_t> merged;
+            uint64_t so = 0;
+            while (!heap.empty()) {
+                const size_t r = heap.top().second;
+                heap.pop();
+                const std::vector<uint8_t> &rec = reader[r]->rec;
+                bai.add(rec.data(), so, rec.size());
+                so += rec.size();
+                merged.insert(merged.end(), rec.begin(), rec.end());
+                if (merged.size() >= kPiece) {
+                    const size_t take = merged.size() / kBgzfBlockMax * kBgzfBlockMax;
+                    z_->deflate(merged.data(), take, blocks);
+                    emit();
+                    merged.erase(merged.begin(), merged.begin() + static_cast<std::ptrdiff_t>(take));
+                }
+                if (reader[r]->next()) heap.emplace(bam_sort_key(reader[r]->rec.data()), r);
+            }
+            if (!merged.empty()) z_->deflate(merged.data(), merged.size(), blocks);
+            emit();
+            reader.clear();
+        }
+        out.write(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
+        if (!out) throw std::runtime_error("--sort: writing " + out_path_ + " failed");
+        std::ofstream index(out_path_ + ".bai", std::ios::binary);
+        bai.write(index, [&](uint64_t so) { return block_at[static_cast<size_t>(so / kBgzfBlockMax)] << 16 | so % kBgzfBlockMax; });
+        index.close();
+        if (!index) throw std::runtime_error("--sort: cannot write " + out_path_ + ".bai");
+        remove_tmp();
+    }
+
+private:
+    size_t n_runs_ = 0;
+};
+
+}  // namespace bm

@@ -260,6 +260,15 @@ inline size_t bgzf_deflate_block(const uint8_t *in, uint32_t n, uint8_t *out, in
     return total;
 }
 
+// The coordinate-sort key of a BAM record (rec points at its block_size): (uint32)refID << 32 | (uint32)(pos + 1), so
+// refID = -1 sorts last and pos = -1 before pos = 0.  include/bms.h states the same rule for the device.
+inline uint64_t bam_sort_key(const uint8_t *rec) {
+    uint32_t ref, pos;
+    std::memcpy(&ref, rec + 4, 4);
+    std::memcpy(&pos, rec + 8, 4);
+    return static_cast<uint64_t>(ref) << 32 | static_cast<uint32_t>(pos + 1u);
+}
+
 // Who deflates the BAM stream: blocks are cut by size alone (kBgzfBlockMax bytes, the last one shorter), each becomes one
 // BGZF block, appended to `out` in order.  The default is the host rule above; the product plugs in the device
 // (gpu_block_compressor in make_mapper_gpu.cpp), whose bytes are the same.
@@ -273,6 +282,37 @@ struct block_compressor {
             out.resize(before + bgzf_deflate_block(in + at, len, out.data() + before));
         }
     }
+
+    // --sort (include/bms.h states the order): the n_records records in[rec_offset[i], rec_offset[i + 1]) in ascending
+    // bam_sort_key order, equal keys in the order they came in.  sorted = the sorted stream, perm[k] = the record at place
+    // k, sorted_offset[k] = where it starts (n_records + 1 values).  The default is the host's std::stable_sort and a copy;
+    // the product plugs in bms_sort.
+    virtual void sort_records(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint8_t> &sorted,
+                              std::vector<uint32_t> &perm, std::vector<uint64_t> &sorted_offset) {
+        (void)n;
+        perm.resize(n_records);
+        for (size_t i = 0; i < n_records; i++) perm[i] = static_cast<uint32_t>(i);
+        std::vector<uint64_t> key(n_records);
+        for (size_t i = 0; i < n_records; i++) key[i] = bam_sort_key(in + rec_offset[i]);
+        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
+        sorted_offset.assign(n_records + 1, 0);
+        sorted.resize(n);
+        for (size_t k = 0; k < n_records; k++) {
+            const uint64_t at = rec_offset[perm[k]], len = rec_offset[perm[k] + 1] - at;
+            std::memcpy(sorted.data() + sorted_offset[k], in + at, len);
+            sorted_offset[k + 1] = sorted_offset[k] + len;
+        }
+    }
+    // the same sort, then deflate() of the sorted stream, appended to out (bms_sort_deflate in the product: the sorted
+    // stream does not leave the device)
+    virtual void sort_deflate(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint8_t> &out,
+                              std::vector<uint32_t> &perm, std::vector<uint64_t> &sorted_offset) {
+        std::vector<uint8_t> sorted;
+        sort_records(in, n, rec_offset, n_records, sorted, perm, sorted_offset);
+        deflate(sorted.data(), sorted.size(), out);
+    }
+    // radix passes of the last sort_records / sort_deflate (the host sort has none)
+    virtual uint32_t last_sort_passes() const { return 0; }
 };
 
 }  // namespace bm

@@ -15,6 +15,7 @@
 
 #include "affine_realign.h"
 #include "bam.h"
+#include "bam_sort.h"
 #include "best_mapq.h"
 #include "bgzf.h"
 #include "bm_genome.h"
@@ -454,6 +455,9 @@ public:
 // flushes fell -- and hands the whole blocks to the compressor in one call (the device in the product, host/bgzf.h
 // elsewhere; the same bytes); the remainder is carried to the next flush, the header is a block of its own and close()
 // appends the BGZF end-of-file block.
+//
+// Sorted (-o x.bam --sort, host/bam_sort.h): the encoded records are not cut into blocks but kept by a bam_sorter, the
+// header says SO:coordinate, and close() writes the records in coordinate order, the EOF block and x.bam.bai.
 class sam_text {
     std::ofstream out_;
     std::string buf_, writing_;     // the buffer being filled / the one a writer thread is putting into the file
@@ -464,6 +468,9 @@ class sam_text {
     std::string stream_;                // BAM: encoded records not yet in a block
     std::vector<uint8_t> blocks_;
     bool closed_ = false;
+    std::unique_ptr<bam_sorter> sorter_;   // non-null: sorted BAM
+    uint64_t header_bytes_ = 0;            // sorted BAM: the header's blocks in the file
+    size_t n_ref_ = 0;
 
     // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer
     void encode_buffer(bool all) {
@@ -502,6 +509,12 @@ class sam_text {
         for (unsigned t = 0; t < T; t++)
             if (failed[t]) std::rethrow_exception(failed[t]);
         for (unsigned t = 1; t < T; t++) stream_.append(part[t]);
+        if (sorter_) {                                // sorted: the records wait for close(), nothing goes to the file yet
+            sorter_->add(reinterpret_cast<const uint8_t *>(stream_.data()), stream_.size());
+            stream_.clear();
+            buf_.clear();
+            return;
+        }
         const size_t take = all ? stream_.size() : stream_.size() / kBgzfBlockMax * kBgzfBlockMax;
         blocks_.clear();
         if (take) bam_->deflate(reinterpret_cast<const uint8_t *>(stream_.data()), take, blocks_);
@@ -522,8 +535,11 @@ class sam_text {
     void number(uint64_t v) { number(buf_, v); }
 
 public:
-    explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr) : out_(file, std::ios::binary), bam_(bam) {
+    // sort_run_bytes > 0 (BAM only): coordinate-sorted output in runs of that many bytes of BAM stream
+    explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr, size_t sort_run_bytes = 0)
+        : out_(file, std::ios::binary), bam_(bam) {
         if (!out_) throw std::runtime_error("cannot write " + file.string());
+        if (bam_ && sort_run_bytes) sorter_ = std::make_unique<bam_sorter>(bam_, file, sort_run_bytes);
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
@@ -548,7 +564,13 @@ public:
     }
     // everything written (call before reading the file back or reporting success)
     void close() {
-        if (bam_ && !closed_) {
+        if (sorter_ && !closed_) {
+            encode_buffer(true);
+            join_writer();
+            sorter_->finish(out_, header_bytes_, n_ref_);
+            std::cerr << "[INFO]\t\tSorted " << sorter_->n_records() << " records by coordinate in " << sorter_->n_runs() << " run(s), "
+                      << sorter_->n_passes() << " radix pass(es) on the device.\n";
+        } else if (bam_ && !closed_) {
             encode_buffer(true);
             buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
             join_writer();
@@ -563,7 +585,7 @@ public:
         if (!out_) throw std::runtime_error("writing the SAM file failed");
     }
     void header(const std::vector<std::string> &ref_ids, const std::vector<size_t> &ref_lengths) {
-        buf_ += "@HD\tVN:1.6\n";
+        buf_ += sorter_ ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\n";
         for (size_t i = 0; i < ref_ids.size(); i++) {
             buf_ += "@SQ\tSN:";
             buf_ += ref_ids[i];
@@ -578,6 +600,8 @@ public:
             bam_->deflate(reinterpret_cast<const uint8_t *>(head.data()), head.size(), blocks_);
             join_writer();
             out_.write(reinterpret_cast<const char *>(blocks_.data()), static_cast<std::streamsize>(blocks_.size()));
+            header_bytes_ = blocks_.size();
+            n_ref_ = ref_ids.size();
             buf_.clear();
         }
     }
@@ -627,6 +651,7 @@ private:
     offset_scanner *_s;
     alignment_verifier *_v = nullptr;            // non-null: the BM_ALIGN behaviour
     block_compressor *_bam = nullptr;            // non-null: the output file is BAM, its BGZF blocks made by this
+    size_t _sort_run_bytes = 0;                  // > 0: --sort, the BAM records in coordinate order with a .bai (host/bam_sort.h)
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
@@ -838,6 +863,7 @@ public:
     // bucketmap_align: every located candidate is verified by a pairwise alignment before it is written
     void set_verifier(alignment_verifier *v) { _v = v; }
     void set_compressor(block_compressor *c) { _bam = c; }   // the output file is BAM (-o x.bam)
+    void set_sort(size_t run_bytes) { _sort_run_bytes = run_bytes; }   // ... coordinate-sorted, in runs of this many bytes
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
     // --annotate: write_verified writes every record on the forward strand (POS, SEQ, QUAL, =/X/I/D CIGAR) with NM and MD
@@ -1094,7 +1120,7 @@ public:
         auto locate_res = locate_reads(sequence_file);
         const sam_header h = read_bucket_ids(index_file);
 
-        sam_text sam(sam_file, _bam);
+        sam_text sam(sam_file, _bam, _sort_run_bytes);
         sam.header(h.ref_ids, h.ref_lengths);
         unsigned int read_id = 0, mapped_locations = 0;
         auto t0 = std::chrono::steady_clock::now();

@@ -67,6 +67,9 @@ struct cmd_arguments {
     float split_overlap = 0.5f;   // --split-overlap R (implies --split), 0..1: what two segments may share of the shorter one's
                                   // part of the read; bmv_split takes (uint32_t)(R * 1000) permille
     unsigned int split_max = 8;   // --split-max N (implies --split), 1..16: segments per read
+    bool sort = false;            // --sort (-o x.bam only): the records in coordinate order, with a x.bam.bai index beside the file
+    unsigned long sort_mem = 2048;   // --sort-mem N (implies --sort), >= 1: MiB of BAM stream sorted in one run on the device; more
+                                  // is sorted in runs, which are merged on the host (the files are the same)
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -302,6 +305,14 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
                 throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be two numbers in 1..1024.");
             a.clip = true;
         }
+        else if (opt == "--sort") a.sort = true;
+        else if (opt == "--sort-mem") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            if (v < 1 || v > (1ul << 24)) throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number of MiB in 1..2^24.");
+            a.sort_mem = v;
+            a.sort = true;
+        }
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));
@@ -321,6 +332,12 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
                            (a.rescue ? "--rescue" : a.frag_auto ? "--frag-auto" : a.paired ? "--paired" : a.best ? "--best" : "--max-edit-rate") +
                            ": they judge a read by the edits of one end-to-end alignment, which mean nothing for a read that "
                            "spans a breakpoint.");
+    if (a.sort && !a.output_sam_path.empty() && a.output_sam_path.extension() != ".bam") {
+        std::filesystem::path bam = a.output_sam_path;
+        bam.replace_extension(".bam");
+        throw parser_error("Validation failed for option --sort: only BAM output is sorted and indexed; write -o " + bam.string() +
+                           " instead of -o " + a.output_sam_path.string() + ".");
+    }
     if (a.split) a.clip = a.annotate = true;
     if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;

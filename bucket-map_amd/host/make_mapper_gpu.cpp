@@ -1,6 +1,7 @@
 // make_mapper_gpu.cpp -- the product's factories: the MI355X filter behind bm::mapper and the MI355X
 // locator scan behind bm::offset_scanner.
 // (main.cpp:202-209: q_gram_mapper<BM_BUCKET_NUM> map(BM_BUCKET_LEN, read_len, k, q, S, fault, d, b))
+#include "../../include/bms.h"
 #include "../../include/bmz.h"
 #include "bgzf.h"
 #include "bm_indexer.h"
@@ -114,10 +115,13 @@ class gpu_block_compressor : public bm::block_compressor {
     bmz_ctx *ctx_ = nullptr;
 
 public:
-    explicit gpu_block_compressor(int device) {
+    explicit gpu_block_compressor(int device) : device_(device) {
         if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
     }
-    ~gpu_block_compressor() override { bmz_destroy(ctx_); }
+    ~gpu_block_compressor() override {
+        bms_destroy(sort_);
+        bmz_destroy(ctx_);
+    }
     gpu_block_compressor(const gpu_block_compressor &) = delete;
     gpu_block_compressor &operator=(const gpu_block_compressor &) = delete;
     void deflate(const uint8_t *in, size_t n, std::vector<uint8_t> &out) override {
@@ -127,6 +131,40 @@ public:
         if (bmz_deflate(ctx_, in, n, BMZ_BLOCK_MAX, out.data() + before, out.size() - before, &got) != BMZ_OK)
             throw std::runtime_error(std::string("bmz_deflate: ") + bmz_last_error());
         out.resize(before + got);
+    }
+    // --sort: the records are put in order on the same device (bms_sort, bms_sort_deflate: the order of include/bms.h, which
+    // is the host default's)
+    void sort_records(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint8_t> &sorted,
+                      std::vector<uint32_t> &perm, std::vector<uint64_t> &sorted_offset) override {
+        sorted.resize(n);
+        perm.resize(n_records);
+        sorted_offset.resize(n_records + 1);
+        if (bms_sort(sorter(), in, n, rec_offset, n_records, sorted.data(), perm.data(), sorted_offset.data()) != BMS_OK)
+            throw std::runtime_error(std::string("bms_sort: ") + bms_last_error());
+        (void)bms_last_stats(sort_, nullptr, nullptr, nullptr, &passes_);
+    }
+    void sort_deflate(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint8_t> &out,
+                      std::vector<uint32_t> &perm, std::vector<uint64_t> &sorted_offset) override {
+        const size_t before = out.size();
+        out.resize(before + bmz_bound(n, BMZ_BLOCK_MAX));
+        perm.resize(n_records);
+        sorted_offset.resize(n_records + 1);
+        uint64_t got = 0;
+        if (bms_sort_deflate(sorter(), in, n, rec_offset, n_records, BMZ_BLOCK_MAX, out.data() + before, out.size() - before, &got,
+                             perm.data(), sorted_offset.data()) != BMS_OK)
+            throw std::runtime_error(std::string("bms_sort_deflate: ") + bms_last_error());
+        out.resize(before + got);
+        (void)bms_last_stats(sort_, nullptr, nullptr, nullptr, &passes_);
+    }
+    uint32_t last_sort_passes() const override { return passes_; }
+
+private:
+    int device_ = 0;
+    bms_ctx *sort_ = nullptr;       // made by the first sort: a run without --sort pays nothing for it
+    uint32_t passes_ = 0;
+    bms_ctx *sorter() {
+        if (!sort_ && bms_create(device_, &sort_) != BMS_OK) throw std::runtime_error(std::string("bms_create: ") + bms_last_error());
+        return sort_;
     }
 };
 }  // namespace
