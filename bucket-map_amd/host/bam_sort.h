@@ -20,6 +20,16 @@
 //   - pseudo-bin 37450 for every reference with a record: (first, end) offsets, then (records without 0x4, records with 0x4);
 //   - n_no_coor = the records with refID = -1; a reference without records has n_bin = 0 and n_intv = 0.
 //   A record that ends beyond 2^29 cannot be binned by this format: it is refused (CSI is out of scope).
+//
+// MARK MODE (--markdup; include/bmd.h states the rule, who computes it is again the block_compressor).  Marking needs the
+// records in the order they came in, where mates are adjacent, so it happens before the sort.  One run: one mark_sort_deflate
+// call at finish(); 0x400 is then ORed into the host copy from the returned marks, because the index's pseudo-bin counts read
+// flags and the records it describes must be the written ones.  Several runs: each spill computes the run's descriptors
+// (dup_ends) and keeps them and the run's perm -- 17 + 4 bytes per record --, the raw run is sorted and written as before;
+// finish() makes one dup_mark over the concatenated descriptors, and the merge ORs 0x400 into record run_base[r] + perm_r[k]
+// as it copies the k-th record of run r.  A run never ends between two mates: when the run's last record has 0x1 and 0x40
+// (and not 0x80) and the incoming one has 0x80 (and not 0x40), that one is taken into the run first (the run may exceed run_bytes by one record).  Both
+// ways give the same files.
 #pragma once
 
 #include "bgzf.h"
@@ -156,6 +166,11 @@ class bam_sorter {
     std::vector<std::string> tmp_;
     uint64_t n_records_ = 0;
     uint32_t passes_ = 0;
+    bool mark_ = false;                              // mark mode
+    std::vector<uint64_t> desc_end_, desc_score_;    // several runs: the descriptors of all runs so far, in input order
+    std::vector<uint8_t> desc_kind_;
+    std::vector<std::vector<uint32_t>> run_perm_;    // ... and each run's perm
+    uint64_t counts_[4] = {0, 0, 0, 0};
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -171,8 +186,17 @@ class bam_sorter {
         std::vector<uint8_t> sorted;
         std::vector<uint32_t> perm;
         std::vector<uint64_t> so;
+        if (mark_) {
+            std::vector<uint64_t> end, score;
+            std::vector<uint8_t> kind;
+            z_->dup_ends(run_.data(), run_.size(), off_.data(), off_.size() - 1, end, score, kind);
+            desc_end_.insert(desc_end_.end(), end.begin(), end.end());
+            desc_score_.insert(desc_score_.end(), score.begin(), score.end());
+            desc_kind_.insert(desc_kind_.end(), kind.begin(), kind.end());
+        }
         z_->sort_records(run_.data(), run_.size(), off_.data(), off_.size() - 1, sorted, perm, so);
         passes_ = std::max(passes_, z_->last_sort_passes());
+        if (mark_) run_perm_.push_back(perm);
         tmp_.push_back(out_path_ + ".sort." + std::to_string(tmp_.size()) + ".tmp");   // listed first: removed whatever happens next
         std::ofstream f(tmp_.back(), std::ios::binary);
         f.write(reinterpret_cast<const char *>(sorted.data()), static_cast<std::streamsize>(sorted.size()));
@@ -197,8 +221,8 @@ class bam_sorter {
     };
 
 public:
-    bam_sorter(block_compressor *z, const std::filesystem::path &out_path, size_t run_bytes)
-        : z_(z), out_path_(out_path.string()), run_bytes_(std::max<size_t>(run_bytes, 1)) {}
+    bam_sorter(block_compressor *z, const std::filesystem::path &out_path, size_t run_bytes, bool mark = false)
+        : z_(z), out_path_(out_path.string()), run_bytes_(std::max<size_t>(run_bytes, 1)), mark_(mark) {}
     ~bam_sorter() { remove_tmp(); }
     bam_sorter(const bam_sorter &) = delete;
     bam_sorter &operator=(const bam_sorter &) = delete;
@@ -206,6 +230,8 @@ public:
     uint64_t n_records() const { return n_records_; }
     size_t n_runs() const { return n_runs_; }
     uint32_t n_passes() const { return passes_; }
+    // mark mode, after finish(): pair units, fragment units, duplicate records from pair units, duplicate fragment records
+    const uint64_t *dup_counts() const { return counts_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -213,7 +239,12 @@ public:
             if (n - at < 4) throw std::runtime_error("--sort: a truncated record");
             const size_t len = 4 + static_cast<size_t>(u32(recs + at));
             if (len < 36 || len > n - at) throw std::runtime_error("--sort: a record of " + std::to_string(len) + " bytes");
-            if (off_.size() > 1 && (run_.size() + len > run_bytes_ || off_.size() > 0x7FFFFFFFu)) spill();
+            if (off_.size() > 1 && (run_.size() + len > run_bytes_ || off_.size() > 0x7FFFFFFFu - (mark_ ? 1u : 0u))) {
+                // mark mode: no run ends between two mates
+                const uint8_t *last = run_.data() + off_[off_.size() - 2];
+                const bool keep = mark_ && (last[18] & 0xC1u) == 0x41u && (recs[at + 18] & 0xC0u) == 0x80u && off_.size() <= 0x7FFFFFFFu;
+                if (!keep) spill();
+            }
             run_.insert(run_.end(), recs + at, recs + at + len);
             off_.push_back(run_.size());
             n_records_++;
@@ -240,7 +271,14 @@ public:
             n_runs_ = off_.size() > 1 ? 1 : 0;
             std::vector<uint32_t> perm;
             std::vector<uint64_t> so;
-            z_->sort_deflate(run_.data(), run_.size(), off_.data(), off_.size() - 1, blocks, perm, so);
+            if (mark_) {
+                std::vector<uint8_t> dup;
+                z_->mark_sort_deflate(run_.data(), run_.size(), off_.data(), off_.size() - 1, blocks, perm, so, dup, counts_);
+                for (size_t i = 0; i + 1 < off_.size(); i++)
+                    if (dup[i]) run_[off_[i] + 19] |= 4;
+            } else {
+                z_->sort_deflate(run_.data(), run_.size(), off_.data(), off_.size() - 1, blocks, perm, so);
+            }
             passes_ = z_->last_sort_passes();
             for (size_t k = 0; k + 1 < off_.size(); k++) bai.add(run_.data() + off_[perm[k]], so[k], so[k + 1] - so[k]);
             emit();
@@ -248,6 +286,12 @@ public:
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
             std::vector<uint8_t>().swap(run_);
+            std::vector<uint8_t> dup;                    // mark mode: one marking over all runs' descriptors
+            std::vector<uint64_t> run_base(tmp_.size() + 1, 0), taken(tmp_.size(), 0);
+            if (mark_) {
+                z_->dup_mark(desc_end_.data(), desc_score_.data(), desc_kind_.data(), desc_kind_.size(), dup, counts_);
+                for (size_t r = 0; r < tmp_.size(); r++) run_base[r + 1] = run_base[r] + run_perm_[r].size();
+            }
             std::vector<std::unique_ptr<run_reader>> reader;
             using item = std::pair<uint64_t, size_t>;    // (key, run): the lower run wins a tie, and a run is in order already
             std::priority_queue<item, std::vector<item>, std::greater<item>> heap;
@@ -263,7 +307,8 @@ public:
             while (!heap.empty()) {
                 const size_t r = heap.top().second;
                 heap.pop();
-                const std::vector<uint8_t> &rec = reader[r]->rec;
+                std::vector<uint8_t> &rec = reader[r]->rec;
+                if (mark_ && dup[run_base[r] + run_perm_[r][taken[r]++]]) rec[19] |= 4;
                 bai.add(rec.data(), so, rec.size());
                 so += rec.size();
                 merged.insert(merged.end(), rec.begin(), rec.end());

@@ -5,6 +5,8 @@
 // and the reference the device is compared with.  A block's bytes depend on the block's input alone.
 #pragma once
 
+#include "markdup.h"
+
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -313,6 +315,32 @@ struct block_compressor {
     }
     // radix passes of the last sort_records / sort_deflate (the host sort has none)
     virtual uint32_t last_sort_passes() const { return 0; }
+
+    // --markdup (include/bmd.h states the rule): the descriptors of the records -- E or 0, the score, the kind --, the marks
+    // from descriptors of any origin with counts = (pair units, fragment units, duplicate records from pair units, duplicate
+    // fragment records), and both followed by sort_deflate() of the stream with 0x400 set in the duplicates' flags.  The
+    // defaults are the host rule of markdup.h; the product plugs in bmd_ends, bmd_mark and bmd_mark_sort_deflate.
+    virtual void dup_ends(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint64_t> &end,
+                          std::vector<uint64_t> &score, std::vector<uint8_t> &kind) {
+        (void)n;
+        markdup_ends(in, rec_offset, n_records, end, score, kind);
+    }
+    virtual void dup_mark(const uint64_t *end, const uint64_t *score, const uint8_t *kind, size_t n_records, std::vector<uint8_t> &dup,
+                          uint64_t counts[4]) {
+        markdup_mark(end, score, kind, n_records, dup, counts);
+    }
+    virtual void mark_sort_deflate(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint8_t> &out,
+                                   std::vector<uint32_t> &perm, std::vector<uint64_t> &sorted_offset, std::vector<uint8_t> &dup,
+                                   uint64_t counts[4]) {
+        std::vector<uint64_t> end, score;
+        std::vector<uint8_t> kind;
+        dup_ends(in, n, rec_offset, n_records, end, score, kind);
+        dup_mark(end.data(), score.data(), kind.data(), n_records, dup, counts);
+        std::vector<uint8_t> marked(in, in + n);
+        for (size_t i = 0; i < n_records; i++)
+            if (dup[i]) marked[rec_offset[i] + 19] |= 4;
+        sort_deflate(marked.data(), n, rec_offset, n_records, out, perm, sorted_offset);
+    }
 };
 
 }  // namespace bm

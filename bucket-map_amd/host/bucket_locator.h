@@ -471,6 +471,7 @@ class sam_text {
     std::unique_ptr<bam_sorter> sorter_;   // non-null: sorted BAM
     uint64_t header_bytes_ = 0;            // sorted BAM: the header's blocks in the file
     size_t n_ref_ = 0;
+    bool markdup_ = false;                 // sorted BAM: duplicates flagged
 
     // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer
     void encode_buffer(bool all) {
@@ -535,11 +536,13 @@ class sam_text {
     void number(uint64_t v) { number(buf_, v); }
 
 public:
-    // sort_run_bytes > 0 (BAM only): coordinate-sorted output in runs of that many bytes of BAM stream
-    explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr, size_t sort_run_bytes = 0)
+    // sort_run_bytes > 0 (BAM only): coordinate-sorted output in runs of that many bytes of BAM stream; markdup: the
+    // duplicates among the records are flagged 0x400 on the way (--markdup, include/bmd.h)
+    explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr, size_t sort_run_bytes = 0, bool markdup = false)
         : out_(file, std::ios::binary), bam_(bam) {
         if (!out_) throw std::runtime_error("cannot write " + file.string());
-        if (bam_ && sort_run_bytes) sorter_ = std::make_unique<bam_sorter>(bam_, file, sort_run_bytes);
+        if (bam_ && sort_run_bytes) sorter_ = std::make_unique<bam_sorter>(bam_, file, sort_run_bytes, markdup);
+        markdup_ = sorter_ && markdup;
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
@@ -570,6 +573,11 @@ public:
             sorter_->finish(out_, header_bytes_, n_ref_);
             std::cerr << "[INFO]\t\tSorted " << sorter_->n_records() << " records by coordinate in " << sorter_->n_runs() << " run(s), "
                       << sorter_->n_passes() << " radix pass(es) on the device.\n";
+            if (markdup_) {
+                const uint64_t *c = sorter_->dup_counts();
+                std::cerr << "[INFO]\t\tMarked " << c[2] + c[3] << " of " << sorter_->n_records() << " records as duplicates (" << c[0]
+                          << " pair units, " << c[1] << " fragment units)\n";
+            }
         } else if (bam_ && !closed_) {
             encode_buffer(true);
             buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -652,6 +660,7 @@ private:
     alignment_verifier *_v = nullptr;            // non-null: the BM_ALIGN behaviour
     block_compressor *_bam = nullptr;            // non-null: the output file is BAM, its BGZF blocks made by this
     size_t _sort_run_bytes = 0;                  // > 0: --sort, the BAM records in coordinate order with a .bai (host/bam_sort.h)
+    bool _markdup = false;                       // --markdup: duplicates flagged 0x400 before the sort (include/bmd.h)
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
@@ -864,6 +873,7 @@ public:
     void set_verifier(alignment_verifier *v) { _v = v; }
     void set_compressor(block_compressor *c) { _bam = c; }   // the output file is BAM (-o x.bam)
     void set_sort(size_t run_bytes) { _sort_run_bytes = run_bytes; }   // ... coordinate-sorted, in runs of this many bytes
+    void set_markdup(bool on) { _markdup = on; }                       // ... with its duplicates flagged
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
     // --annotate: write_verified writes every record on the forward strand (POS, SEQ, QUAL, =/X/I/D CIGAR) with NM and MD
@@ -1120,7 +1130,7 @@ public:
         auto locate_res = locate_reads(sequence_file);
         const sam_header h = read_bucket_ids(index_file);
 
-        sam_text sam(sam_file, _bam, _sort_run_bytes);
+        sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup);
         sam.header(h.ref_ids, h.ref_lengths);
         unsigned int read_id = 0, mapped_locations = 0;
         auto t0 = std::chrono::steady_clock::now();

@@ -70,6 +70,8 @@ struct cmd_arguments {
     bool sort = false;            // --sort (-o x.bam only): the records in coordinate order, with a x.bam.bai index beside the file
     unsigned long sort_mem = 2048;   // --sort-mem N (implies --sort), >= 1: MiB of BAM stream sorted in one run on the device; more
                                   // is sorted in runs, which are merged on the host (the files are the same)
+    bool markdup = false;         // --markdup (-o x.bam only, implies --sort): duplicate reads are flagged 0x400 on the device before
+                                  // the sort (include/bmd.h states the rule: unclipped 5' ends, sum of base qualities)
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -313,6 +315,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.sort_mem = v;
             a.sort = true;
         }
+        else if (opt == "--markdup") a.markdup = a.sort = true;
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));
@@ -335,8 +338,9 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (a.sort && !a.output_sam_path.empty() && a.output_sam_path.extension() != ".bam") {
         std::filesystem::path bam = a.output_sam_path;
         bam.replace_extension(".bam");
-        throw parser_error("Validation failed for option --sort: only BAM output is sorted and indexed; write -o " + bam.string() +
-                           " instead of -o " + a.output_sam_path.string() + ".");
+        throw parser_error(std::string("Validation failed for option ") + (a.markdup ? "--markdup" : "--sort") +
+                           ": only BAM output is sorted and indexed; write -o " + bam.string() + " instead of -o " +
+                           a.output_sam_path.string() + ".");
     }
     if (a.split) a.clip = a.annotate = true;
     if (a.rescue) a.paired = true;

@@ -135,6 +135,7 @@ int main(int argc, char **argv) {
             compressor = bm_make_compressor ? bm_make_compressor(args) : std::make_unique<bm::block_compressor>();
             loc.set_compressor(compressor.get());
             if (args.sort) loc.set_sort(bm::bam_sort_run_bytes(args.sort_mem));   // --sort: coordinate order and x.bam.bai
+            loc.set_markdup(args.markdup);                                        // --markdup: duplicates flagged before the sort
         }
 #ifdef BM_ALIGN
         std::unique_ptr<bm::alignment_verifier> verifier = bm_make_verifier(args);

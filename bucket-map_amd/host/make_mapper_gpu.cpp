@@ -1,6 +1,7 @@
 // make_mapper_gpu.cpp -- the product's factories: the MI355X filter behind bm::mapper and the MI355X
 // locator scan behind bm::offset_scanner.
 // (main.cpp:202-209: q_gram_mapper<BM_BUCKET_NUM> map(BM_BUCKET_LEN, read_len, k, q, S, fault, d, b))
+#include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
 #include "bgzf.h"
@@ -119,6 +120,7 @@ public:
         if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
     }
     ~gpu_block_compressor() override {
+        bmd_destroy(mark_);
         bms_destroy(sort_);
         bmz_destroy(ctx_);
     }
@@ -157,9 +159,45 @@ public:
         (void)bms_last_stats(sort_, nullptr, nullptr, nullptr, &passes_);
     }
     uint32_t last_sort_passes() const override { return passes_; }
+    // --markdup: the descriptors, the marks and the fused mark + sort + deflate on the same device (bmd_*: the rule of
+    // include/bmd.h, which is the host default's)
+    void dup_ends(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint64_t> &end,
+                  std::vector<uint64_t> &score, std::vector<uint8_t> &kind) override {
+        end.resize(n_records);
+        score.resize(n_records);
+        kind.resize(n_records);
+        if (bmd_ends(marker(), in, n, rec_offset, n_records, end.data(), score.data(), kind.data()) != BMD_OK)
+            throw std::runtime_error(std::string("bmd_ends: ") + bmd_last_error());
+    }
+    void dup_mark(const uint64_t *end, const uint64_t *score, const uint8_t *kind, size_t n_records, std::vector<uint8_t> &dup,
+                  uint64_t counts[4]) override {
+        dup.resize(n_records);
+        if (bmd_mark(marker(), end, score, kind, n_records, dup.data(), counts) != BMD_OK)
+            throw std::runtime_error(std::string("bmd_mark: ") + bmd_last_error());
+    }
+    void mark_sort_deflate(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, std::vector<uint8_t> &out,
+                           std::vector<uint32_t> &perm, std::vector<uint64_t> &sorted_offset, std::vector<uint8_t> &dup,
+                           uint64_t counts[4]) override {
+        const size_t before = out.size();
+        out.resize(before + bmz_bound(n, BMZ_BLOCK_MAX));
+        perm.resize(n_records);
+        sorted_offset.resize(n_records + 1);
+        dup.resize(n_records);
+        uint64_t got = 0;
+        if (bmd_mark_sort_deflate(marker(), in, n, rec_offset, n_records, BMZ_BLOCK_MAX, out.data() + before, out.size() - before, &got,
+                                  perm.data(), sorted_offset.data(), dup.data(), counts) != BMD_OK)
+            throw std::runtime_error(std::string("bmd_mark_sort_deflate: ") + bmd_last_error());
+        out.resize(before + got);
+        (void)bmd_last_sort_stats(mark_, nullptr, nullptr, nullptr, &passes_);
+    }
 
 private:
     int device_ = 0;
+    bmd_ctx *mark_ = nullptr;       // made by the first marking call: a run without --markdup pays nothing for it
+    bmd_ctx *marker() {
+        if (!mark_ && bmd_create(device_, &mark_) != BMD_OK) throw std::runtime_error(std::string("bmd_create: ") + bmd_last_error());
+        return mark_;
+    }
     bms_ctx *sort_ = nullptr;       // made by the first sort: a run without --sort pays nothing for it
     uint32_t passes_ = 0;
     bms_ctx *sorter() {
