@@ -4,6 +4,7 @@
 // iterate_through_buckets (bucket_map/utils.h:60-102).
 #pragma once
 
+#include "bgzf_in.h"
 #include "bm_common.h"
 
 #include <fcntl.h>
@@ -66,6 +67,8 @@ inline char fold_genome_char(char c) {
 // The file is mapped, record starts ('>' at the beginning of a line) are found in one memchr sweep, and the
 // records are parsed by a few threads, each into a string reserved to the record's size: a 1.7 Gbp genome has
 // 28 M lines, and appending them one by one to growing strings took as long as everything else the tool does.
+// A file that begins with the gzip magic is BGZF (bgzf_in.h): its text is inflated into an anonymous mapping first and
+// parsed from there; a plain file takes the path it always took.
 inline Genome read_fasta(const std::string &path, unsigned threads = 0) {
     static const auto fold_or_skip = [] {             // 0: white space inside a sequence line (dropped)
         std::array<char, 256> t{};
@@ -79,7 +82,7 @@ inline Genome read_fasta(const std::string &path, unsigned threads = 0) {
         ::close(fd);
         throw std::runtime_error("cannot stat FASTA file " + path);
     }
-    const size_t size = static_cast<size_t>(st.st_size);
+    size_t size = static_cast<size_t>(st.st_size);
     Genome g;
     if (size == 0) {
         ::close(fd);
@@ -88,6 +91,18 @@ inline Genome read_fasta(const std::string &path, unsigned threads = 0) {
     void *map = ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
     ::close(fd);
     if (map == MAP_FAILED) throw std::runtime_error("cannot map FASTA file " + path);
+    if (has_gzip_magic(map, size)) {
+        inflated_text text;
+        try {
+            text = inflate_file(static_cast<const uint8_t *>(map), size, "FASTA file " + path);
+        } catch (...) {
+            ::munmap(map, size);
+            throw;
+        }
+        ::munmap(map, size);
+        if (text.bytes == 0) return g;
+        map = text.text, size = text.bytes;                 // released below like the file's mapping
+    }
     const char *data = static_cast<const char *>(map);
     // first non-empty line must be a header
     size_t first = 0;
@@ -216,12 +231,16 @@ inline void for_each_fastq_stream(const std::string &path, const std::function<v
     FILE *f = file.get();
     std::vector<char> buf(io_block_bytes());
     size_t have = 0;
-    bool eof = false;
+    bool eof = false, started = false;
     auto fail = [&](const std::string &what) { throw std::runtime_error(what + " in " + path); };
     for (;;) {
         if (!eof) {
+            const bool first_read = !started;                        // a pipe cannot be laid out: refuse a compressed one
+            started = true;
             const size_t got = std::fread(buf.data() + have, 1, buf.size() - have, f);
             have += got;
+            if (first_read && has_gzip_magic(buf.data(), have))
+                throw std::runtime_error("compressed input needs a regular file (BGZF blocks are laid out from the whole file): " + path);
             if (got == 0) eof = true;
         }
         size_t pos = 0;
@@ -385,14 +404,28 @@ public:
         static std::shared_ptr<FastqFile> last;
         std::lock_guard<std::mutex> lock(mu);
         if (last && last->path_ == path && last->dev_ == st.st_dev && last->ino_ == st.st_ino &&
-            last->size_ == static_cast<size_t>(st.st_size) && last->mtime_ns_ == mtime_ns(st))
+            last->file_size_ == static_cast<size_t>(st.st_size) && last->mtime_ns_ == mtime_ns(st))
             return last;
         const int fd = ::open(path.c_str(), O_RDONLY);
         if (fd < 0) throw std::runtime_error("cannot open FASTQ file " + path);
-        const size_t size = static_cast<size_t>(st.st_size);
+        size_t size = static_cast<size_t>(st.st_size);
         void *map = size ? ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
         ::close(fd);
         if (map == MAP_FAILED) return nullptr;                       // no address space: the block reader
+        // A FASTQ begins with '@': the gzip magic means BGZF (bgzf_in.h).  The text is inflated into an anonymous mapping,
+        // which is data_ / size_ from here on; the key of the kept file stays the compressed file's.
+        const bool compressed = has_gzip_magic(map, size);
+        if (compressed) {
+            inflated_text text;
+            try {
+                text = inflate_file(static_cast<const uint8_t *>(map), size, "FASTQ file " + path);
+            } catch (...) {
+                ::munmap(map, size);
+                throw;
+            }
+            ::munmap(map, size);
+            map = text.text, size = text.bytes;
+        }
         std::shared_ptr<FastqFile> f(new FastqFile());
         f->path_ = path;
         f->dev_ = st.st_dev;
@@ -400,7 +433,8 @@ public:
         f->mtime_ns_ = mtime_ns(st);
         f->data_ = static_cast<const char *>(map);
         f->size_ = size;
-        if (size) ::madvise(map, size, MADV_SEQUENTIAL);
+        f->file_size_ = static_cast<size_t>(st.st_size);
+        if (size && !compressed) ::madvise(map, size, MADV_SEQUENTIAL);
         f->blocks_.resize(size / (6 * kBlock) + 2);                  // a record is at least "@\n\n+\n\n"
         f->builder_ = std::thread([raw = f.get()]() { raw->build(); });
         last = f;
@@ -522,6 +556,7 @@ private:
     int64_t mtime_ns_ = 0;
     const char *data_ = nullptr;
     size_t size_ = 0;
+    size_t file_size_ = 0;                                           // of the file on disk (size_ is the text's)
     std::vector<std::unique_ptr<Rec[]>> blocks_;
     std::atomic<size_t> ready_{0};
     bool done_ = false;

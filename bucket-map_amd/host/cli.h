@@ -163,7 +163,8 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         if (opt == "-x" || opt == "--run-index") a.only_indexer = true;
         else if (opt == "-q" || opt == "--query-file") {
             a.fastq_path = value();
-            if (!has_ext(a.fastq_path, {"fq", "fastq"}))
+            // x.fq.gz / x.fastq.gz: BGZF (bgzf_in.h); the extension below .gz decides as before
+            if (!has_ext(a.fastq_path.extension() == ".gz" ? a.fastq_path.stem() : a.fastq_path, {"fq", "fastq"}))
                 throw parser_error("Validation failed for option -q/--query-file: Expected one of the following valid extensions: [fq, fastq]!");
             if (!std::filesystem::exists(a.fastq_path))
                 throw parser_error("Validation failed for option -q/--query-file: The file " + a.fastq_path.string() + " does not exist!");

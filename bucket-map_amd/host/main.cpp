@@ -28,6 +28,9 @@ std::unique_ptr<bm::alignment_verifier> bm_make_verifier(const bm::cmd_arguments
 // -o x.bam: who deflates the BGZF blocks.  Weak: a build that does not define it (the oracle-backed test tools) gets the
 // host rule of bgzf.h, whose bytes are the same.
 std::unique_ptr<bm::block_compressor> bm_make_compressor(const bm::cmd_arguments &args) __attribute__((weak));
+// Compressed -q / --genome (BGZF, bgzf_in.h): who inflates the blocks.  Weak in the same way: without it the host decoder
+// of bgzf_in.h reads them.
+std::unique_ptr<bm::block_inflater> bm_make_inflater(const bm::cmd_arguments &args) __attribute__((weak));
 // --gpu-index: fills ix with the rows built on the device; false = not available in this build.
 bool bm_gpu_index(const bm::cmd_arguments &args, const bm::Genome &genome, unsigned int num_buckets, bm::QgramIndex &ix);
 // Whatever the build's devices need before their first use (HIP start-up and code objects: a third of a second), begun
@@ -62,7 +65,16 @@ int main(int argc, char **argv) {
             if (t.joinable()) t.join();
         }
     } warm{bm_warm_up(args)};
+    // outlives every reader of a compressed file; uninstalled before it goes
+    struct inflater_guard {
+        std::unique_ptr<bm::block_inflater> z;
+        ~inflater_guard() { bm::set_input_inflater(nullptr); }
+    } inflater;
     try {
+        if (bm_make_inflater) {
+            inflater.z = bm_make_inflater(args);
+            bm::set_input_inflater(inflater.z.get());
+        }
         auto t_fa = std::chrono::steady_clock::now();
         bm::Genome genome = bm::read_fasta(args.genome_path.string());
         std::cerr << "[BENCHMARK]\tElapsed time for reading the reference genome: "

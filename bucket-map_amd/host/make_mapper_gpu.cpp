@@ -8,6 +8,7 @@
 #include "bm_indexer.h"
 #include "cli.h"
 #include "gpu_alignment_verifier.h"
+#include "gpu_block_inflater.h"
 #include "gpu_offset_scanner.h"
 #include "gpu_q_gram_mapper.h"
 
@@ -209,6 +210,11 @@ private:
 
 std::unique_ptr<bm::block_compressor> bm_make_compressor(const bm::cmd_arguments &args) {
     return std::make_unique<gpu_block_compressor>(args.gpus.empty() ? 0 : args.gpus.front());
+}
+
+// Compressed -q / --genome: the BGZF blocks are inflated on the first device of --gpus (bmu_inflate).
+std::unique_ptr<bm::block_inflater> bm_make_inflater(const bm::cmd_arguments &args) {
+    return std::make_unique<bm::gpu_block_inflater>(args.gpus.empty() ? 0 : args.gpus.front());
 }
 
 void bm_report_resources(const bm::cmd_arguments &args) {

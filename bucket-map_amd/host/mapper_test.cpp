@@ -6,6 +6,7 @@
 //   mapper_test -i <name> --genome ref.fa -q reads.fastq --ground-truth reads.bucket_ground_truth [-r 150 ...]
 #include "bm_indexer.h"
 #include "cli.h"
+#include "gpu_block_inflater.h"
 #include "gpu_q_gram_mapper.h"
 
 #include <iostream>
@@ -23,6 +24,12 @@ int main(int argc, char **argv) {
             std::cerr << "[ERROR]\t\tusage: mapper_test -i <name> --genome ref.fa -q reads.fastq --ground-truth <file> [bucketmap flags]\n";
             return 1;
         }
+        // compressed --genome / -q (BGZF) are inflated on the first device of --gpus, as in `bucketmap`
+        bm::gpu_block_inflater inflater(args.gpus.empty() ? 0 : args.gpus.front());
+        struct uninstall {
+            ~uninstall() { bm::set_input_inflater(nullptr); }
+        } guard;
+        bm::set_input_inflater(&inflater);
         const bm::Genome genome = bm::read_fasta(args.genome_path.string());
         const unsigned int num_buckets = args.num_buckets ? args.num_buckets : bm::awk_bucket_num(genome, args.bucket_len);
         const unsigned int fault = bm::ceil_mul_f32(args.allowed_seed_miss_rate, args.mapper_sample_size);   // mapper_test.cpp:50
