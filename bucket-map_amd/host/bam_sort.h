@@ -30,6 +30,12 @@
 // as it copies the k-th record of run r.  A run never ends between two mates: when the run's last record has 0x1 and 0x40
 // (and not 0x80) and the incoming one has 0x80 (and not 0x40), that one is taken into the run first (the run may exceed run_bytes by one record).  Both
 // ways give the same files.
+//
+// DEPTH MODE (--depth / --coverage; include/bmc.h states the rule, who computes it is again the block_compressor).  The records
+// counted are the records written, with their final flags, so counting happens in finish(): one run -- the run buffer, after
+// the marks have been ORed into it, in one depth_add call; several runs -- the merged stream as it is made, cut at record
+// borders into pieces of about run_bytes, one depth_add call each.  The rule does not depend on the order or the cutting of
+// the records, so both ways give the same result; it is kept for the caller, who writes the files.
 #pragma once
 
 #include "bgzf.h"
@@ -171,6 +177,9 @@ class bam_sorter {
     std::vector<uint8_t> desc_kind_;
     std::vector<std::vector<uint32_t>> run_perm_;    // ... and each run's perm
     uint64_t counts_[4] = {0, 0, 0, 0};
+    bool depth_ = false;                             // depth mode
+    std::vector<uint32_t> depth_ref_len_;
+    depth_result depth_result_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -232,6 +241,16 @@ public:
     uint32_t n_passes() const { return passes_; }
     // mark mode, after finish(): pair units, fragment units, duplicate records from pair units, duplicate fragment records
     const uint64_t *dup_counts() const { return counts_; }
+    // depth mode: before the first add(), the references' lengths; after finish(), the runs and the sums per reference
+    void set_depth(const std::vector<size_t> &ref_lengths) {
+        depth_ = true;
+        depth_ref_len_.clear();
+        for (size_t len : ref_lengths) {
+            if (len > 0xFFFFFFFFull) throw std::runtime_error("--depth: a reference of " + std::to_string(len) + " bases");
+            depth_ref_len_.push_back(static_cast<uint32_t>(len));
+        }
+    }
+    const depth_result &depth() const { return depth_result_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -267,6 +286,7 @@ public:
             out.write(reinterpret_cast<const char *>(blocks.data()), static_cast<std::streamsize>(blocks.size()));
             blocks.clear();
         };
+        if (depth_) z_->depth_begin(depth_ref_len_.data(), depth_ref_len_.size());
         if (tmp_.empty()) {
             n_runs_ = off_.size() > 1 ? 1 : 0;
             std::vector<uint32_t> perm;
@@ -282,6 +302,7 @@ public:
             passes_ = z_->last_sort_passes();
             for (size_t k = 0; k + 1 < off_.size(); k++) bai.add(run_.data() + off_[perm[k]], so[k], so[k + 1] - so[k]);
             emit();
+            if (depth_) z_->depth_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
         } else {
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
@@ -302,7 +323,13 @@ public:
                 if (reader[r]->next()) heap.emplace(bam_sort_key(reader[r]->rec.data()), r);
             }
             constexpr size_t kPiece = size_t{64} * kBgzfBlockMax;
-            std::vector<uint8_t> merged;
+            std::vector<uint8_t> merged, counted;        // counted: depth mode, the merged records not yet handed to depth_add
+            std::vector<uint64_t> counted_off{0};
+            auto count = [&]() {
+                if (counted_off.size() > 1) z_->depth_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
+                counted.clear();
+                counted_off.assign(1, 0);
+            };
             uint64_t so = 0;
             while (!heap.empty()) {
                 const size_t r = heap.top().second;
@@ -312,6 +339,11 @@ public:
                 bai.add(rec.data(), so, rec.size());
                 so += rec.size();
                 merged.insert(merged.end(), rec.begin(), rec.end());
+                if (depth_) {
+                    counted.insert(counted.end(), rec.begin(), rec.end());
+                    counted_off.push_back(counted.size());
+                    if (counted.size() >= run_bytes_) count();
+                }
                 if (merged.size() >= kPiece) {
                     const size_t take = merged.size() / kBgzfBlockMax * kBgzfBlockMax;
                     z_->deflate(merged.data(), take, blocks);
@@ -322,6 +354,7 @@ public:
             }
             if (!merged.empty()) z_->deflate(merged.data(), merged.size(), blocks);
             emit();
+            if (depth_) count();
             reader.clear();
         }
         out.write(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -331,6 +364,7 @@ public:
         index.close();
         if (!index) throw std::runtime_error("--sort: cannot write " + out_path_ + ".bai");
         remove_tmp();
+        if (depth_) z_->depth_finish(depth_result_);
     }
 
 private:

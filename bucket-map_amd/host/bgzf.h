@@ -5,6 +5,7 @@
 // and the reference the device is compared with.  A block's bytes depend on the block's input alone.
 #pragma once
 
+#include "depth.h"
 #include "markdup.h"
 
 #include <algorithm>
@@ -341,6 +342,20 @@ struct block_compressor {
             if (dup[i]) marked[rec_offset[i] + 19] |= 4;
         sort_deflate(marked.data(), n, rec_offset, n_records, out, perm, sorted_offset);
     }
+
+    // --depth / --coverage (include/bmc.h states the rule): the references, then whole records in any order and over any
+    // number of calls (skip, where given, is a byte per record: not 0 leaves the record out), then the runs of equal depth
+    // and the seven sums per reference.  The defaults are the host rule of depth.h; the product plugs in bmc_begin, bmc_add
+    // and bmc_finish.
+    virtual void depth_begin(const uint32_t *ref_len, size_t n_ref) { depth_.begin(ref_len, n_ref); }
+    virtual void depth_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) {
+        (void)n;
+        depth_.add(in, rec_offset, n_records, skip);
+    }
+    virtual void depth_finish(depth_result &out) { depth_.finish(out); }
+
+private:
+    depth_counter depth_;
 };
 
 }  // namespace bm

@@ -472,6 +472,40 @@ class sam_text {
     uint64_t header_bytes_ = 0;            // sorted BAM: the header's blocks in the file
     size_t n_ref_ = 0;
     bool markdup_ = false;                 // sorted BAM: duplicates flagged
+    std::filesystem::path depth_file_, coverage_file_;   // sorted BAM: --depth / --coverage, either may be empty
+    std::vector<std::string> ref_ids_;     // ... the references, for the two files
+    std::vector<uint32_t> ref_len_;
+
+    // A file of --depth / --coverage: written beside its place and moved there when it is complete, so that a failure
+    // leaves nothing half-written (and nothing at all under the final name).
+    template <typename Fill>
+    static void write_whole(const std::filesystem::path &file, Fill &&fill) {
+        const std::filesystem::path tmp = file.string() + ".tmp";
+        try {
+            std::ofstream f(tmp, std::ios::binary);
+            if (!f) throw std::runtime_error("cannot write " + file.string());
+            fill(f);
+            f.close();
+            if (!f) throw std::runtime_error("writing " + file.string() + " failed");
+            std::filesystem::rename(tmp, file);
+        } catch (...) {
+            std::error_code ec;
+            std::filesystem::remove(tmp, ec);
+            throw;
+        }
+    }
+    void write_depth_files() {
+        const depth_result &res = sorter_->depth();
+        if (!depth_file_.empty()) write_whole(depth_file_, [&](std::ostream &f) { write_depth_file(f, res, ref_ids_); });
+        if (!coverage_file_.empty()) write_whole(coverage_file_, [&](std::ostream &f) { write_coverage_file(f, res, ref_ids_, ref_len_); });
+        uint64_t cov = 0, bases = 0, reads = 0, n_long = 0;
+        for (size_t r = 0; r < ref_len_.size(); r++) {
+            const uint64_t *st = res.stats.data() + r * kDepthStats;
+            cov += st[1], bases += ref_len_[r], reads += st[0], n_long += st[6];
+        }
+        std::cerr << "[INFO]\t\tCoverage: " << cov << " of " << bases << " bases covered by " << reads << " records (" << n_long
+                  << " long-CIGAR records left out)\n";
+    }
 
     // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer
     void encode_buffer(bool all) {
@@ -538,11 +572,16 @@ class sam_text {
 public:
     // sort_run_bytes > 0 (BAM only): coordinate-sorted output in runs of that many bytes of BAM stream; markdup: the
     // duplicates among the records are flagged 0x400 on the way (--markdup, include/bmd.h)
-    explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr, size_t sort_run_bytes = 0, bool markdup = false)
+    // depth_file / coverage_file (sorted BAM only, either may be empty): the bedGraph runs of equal depth and the table per
+    // reference of the records written (--depth, --coverage, include/bmc.h)
+    explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr, size_t sort_run_bytes = 0, bool markdup = false,
+                      std::filesystem::path const &depth_file = {}, std::filesystem::path const &coverage_file = {})
         : out_(file, std::ios::binary), bam_(bam) {
         if (!out_) throw std::runtime_error("cannot write " + file.string());
         if (bam_ && sort_run_bytes) sorter_ = std::make_unique<bam_sorter>(bam_, file, sort_run_bytes, markdup);
         markdup_ = sorter_ && markdup;
+        depth_file_ = sorter_ ? depth_file : std::filesystem::path();
+        coverage_file_ = sorter_ ? coverage_file : std::filesystem::path();
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
@@ -578,6 +617,7 @@ public:
                 std::cerr << "[INFO]\t\tMarked " << c[2] + c[3] << " of " << sorter_->n_records() << " records as duplicates (" << c[0]
                           << " pair units, " << c[1] << " fragment units)\n";
             }
+            if (!depth_file_.empty() || !coverage_file_.empty()) write_depth_files();
         } else if (bam_ && !closed_) {
             encode_buffer(true);
             buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -610,6 +650,11 @@ public:
             out_.write(reinterpret_cast<const char *>(blocks_.data()), static_cast<std::streamsize>(blocks_.size()));
             header_bytes_ = blocks_.size();
             n_ref_ = ref_ids.size();
+            if (!depth_file_.empty() || !coverage_file_.empty()) {
+                sorter_->set_depth(ref_lengths);
+                ref_ids_ = ref_ids;
+                ref_len_.assign(ref_lengths.begin(), ref_lengths.end());   // set_depth has refused what does not fit
+            }
             buf_.clear();
         }
     }
@@ -661,6 +706,7 @@ private:
     block_compressor *_bam = nullptr;            // non-null: the output file is BAM, its BGZF blocks made by this
     size_t _sort_run_bytes = 0;                  // > 0: --sort, the BAM records in coordinate order with a .bai (host/bam_sort.h)
     bool _markdup = false;                       // --markdup: duplicates flagged 0x400 before the sort (include/bmd.h)
+    std::filesystem::path _depth_file, _coverage_file;   // --depth / --coverage: the written records' depth and coverage (include/bmc.h)
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
@@ -874,6 +920,10 @@ public:
     void set_compressor(block_compressor *c) { _bam = c; }   // the output file is BAM (-o x.bam)
     void set_sort(size_t run_bytes) { _sort_run_bytes = run_bytes; }   // ... coordinate-sorted, in runs of this many bytes
     void set_markdup(bool on) { _markdup = on; }                       // ... with its duplicates flagged
+    void set_depth_files(std::filesystem::path const &depth, std::filesystem::path const &coverage) {   // ... and its depth reported
+        _depth_file = depth;
+        _coverage_file = coverage;
+    }
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
     // --annotate: write_verified writes every record on the forward strand (POS, SEQ, QUAL, =/X/I/D CIGAR) with NM and MD
@@ -1130,7 +1180,7 @@ public:
         auto locate_res = locate_reads(sequence_file);
         const sam_header h = read_bucket_ids(index_file);
 
-        sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup);
+        sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup, _depth_file, _coverage_file);
         sam.header(h.ref_ids, h.ref_lengths);
         unsigned int read_id = 0, mapped_locations = 0;
         auto t0 = std::chrono::steady_clock::now();

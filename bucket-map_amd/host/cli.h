@@ -72,6 +72,9 @@ struct cmd_arguments {
                                   // is sorted in runs, which are merged on the host (the files are the same)
     bool markdup = false;         // --markdup (-o x.bam only, implies --sort): duplicate reads are flagged 0x400 on the device before
                                   // the sort (include/bmd.h states the rule: unclipped 5' ends, sum of base qualities)
+    std::filesystem::path depth_path{}, coverage_path{};   // --depth FILE / --coverage FILE (-o x.bam only, either implies --sort):
+                                  // the per-base depth of the records written as bedGraph runs, and one line per reference of
+                                  // reads, covered bases, mean depth, base quality and MAPQ (include/bmc.h states the rule)
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -317,6 +320,10 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.sort = true;
         }
         else if (opt == "--markdup") a.markdup = a.sort = true;
+        else if (opt == "--depth" || opt == "--coverage") {
+            (opt == "--depth" ? a.depth_path : a.coverage_path) = value();
+            a.sort = true;
+        }
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));
@@ -339,10 +346,16 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (a.sort && !a.output_sam_path.empty() && a.output_sam_path.extension() != ".bam") {
         std::filesystem::path bam = a.output_sam_path;
         bam.replace_extension(".bam");
-        throw parser_error(std::string("Validation failed for option ") + (a.markdup ? "--markdup" : "--sort") +
+        throw parser_error(std::string("Validation failed for option ") +
+                           (!a.depth_path.empty() ? "--depth" : !a.coverage_path.empty() ? "--coverage" : a.markdup ? "--markdup" : "--sort") +
                            ": only BAM output is sorted and indexed; write -o " + bam.string() + " instead of -o " +
                            a.output_sam_path.string() + ".");
     }
+    if ((!a.depth_path.empty() || !a.coverage_path.empty()) && a.output_sam_path.empty() && !a.only_indexer)
+        throw parser_error(std::string("Validation failed for option ") + (!a.depth_path.empty() ? "--depth" : "--coverage") +
+                           ": depth and coverage are those of the records of a sorted BAM file; name one with -o x.bam.");
+    if (!a.depth_path.empty() && a.depth_path == a.coverage_path)
+        throw parser_error("Validation failed for option --coverage: " + a.coverage_path.string() + " is the file of --depth too.");
     if (a.split) a.clip = a.annotate = true;
     if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;

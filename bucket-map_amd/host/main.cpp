@@ -148,6 +148,7 @@ int main(int argc, char **argv) {
             loc.set_compressor(compressor.get());
             if (args.sort) loc.set_sort(bm::bam_sort_run_bytes(args.sort_mem));   // --sort: coordinate order and x.bam.bai
             loc.set_markdup(args.markdup);                                        // --markdup: duplicates flagged before the sort
+            loc.set_depth_files(args.depth_path, args.coverage_path);            // --depth / --coverage: of the records written
         }
 #ifdef BM_ALIGN
         std::unique_ptr<bm::alignment_verifier> verifier = bm_make_verifier(args);

@@ -1,6 +1,7 @@
 // make_mapper_gpu.cpp -- the product's factories: the MI355X filter behind bm::mapper and the MI355X
 // locator scan behind bm::offset_scanner.
 // (main.cpp:202-209: q_gram_mapper<BM_BUCKET_NUM> map(BM_BUCKET_LEN, read_len, k, q, S, fault, d, b))
+#include "../../include/bmc.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -121,6 +122,7 @@ public:
         if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
     }
     ~gpu_block_compressor() override {
+        bmc_destroy(cover_);
         bmd_destroy(mark_);
         bms_destroy(sort_);
         bmz_destroy(ctx_);
@@ -191,9 +193,32 @@ public:
         out.resize(before + got);
         (void)bmd_last_sort_stats(mark_, nullptr, nullptr, nullptr, &passes_);
     }
+    // --depth / --coverage: the depth of the written records on the same device (bmc_*: the rule of include/bmc.h, which is
+    // the host default's)
+    void depth_begin(const uint32_t *ref_len, size_t n_ref) override {
+        if (n_ref > 0xFFFFFFFFull) throw std::runtime_error("bmc_begin: " + std::to_string(n_ref) + " references");
+        if (bmc_begin(coverer(), ref_len, static_cast<uint32_t>(n_ref)) != BMC_OK) throw std::runtime_error(std::string("bmc_begin: ") + bmc_last_error());
+        n_ref_ = n_ref;
+    }
+    void depth_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) override {
+        if (bmc_add(coverer(), in, n, rec_offset, n_records, skip) != BMC_OK) throw std::runtime_error(std::string("bmc_add: ") + bmc_last_error());
+    }
+    void depth_finish(bm::depth_result &out) override {
+        uint64_t n_runs = 0;
+        out.stats.assign(n_ref_ * bm::kDepthStats, 0);
+        if (bmc_finish(coverer(), &n_runs, out.stats.data()) != BMC_OK) throw std::runtime_error(std::string("bmc_finish: ") + bmc_last_error());
+        out.runs.assign(static_cast<size_t>(n_runs) * 4, 0);
+        if (bmc_runs(cover_, 0, n_runs, out.runs.data()) != BMC_OK) throw std::runtime_error(std::string("bmc_runs: ") + bmc_last_error());
+    }
 
 private:
     int device_ = 0;
+    bmc_ctx *cover_ = nullptr;      // made by the first depth call: a run without --depth / --coverage pays nothing for it
+    size_t n_ref_ = 0;
+    bmc_ctx *coverer() {
+        if (!cover_ && bmc_create(device_, &cover_) != BMC_OK) throw std::runtime_error(std::string("bmc_create: ") + bmc_last_error());
+        return cover_;
+    }
     bmd_ctx *mark_ = nullptr;       // made by the first marking call: a run without --markdup pays nothing for it
     bmd_ctx *marker() {
         if (!mark_ && bmd_create(device_, &mark_) != BMD_OK) throw std::runtime_error(std::string("bmd_create: ") + bmd_last_error());
