@@ -11,6 +11,7 @@
 #include "bm_scan.hip.h"
 
 #include "../../include/bmf.h"
+#include "../host/lists_cells_rule.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -135,6 +136,8 @@ struct bmf_batch {
     DevBuf<uint32_t> q_counters, q_slow, q_live_n, q_left;   // two-pass pruning only (bmf::Pass2Queue)
     DevBuf<uint16_t> q_live_chunks;
     DevBuf<uint4> q_live_mask;
+    DevBuf<uint32_t> over;           // the cells form of the lists vote: its overflow list (bmf::kOverHead + an item each)
+    bool over_ran = false;           // ... and whether the last run wrote it
 };
 
 struct bmf_ctx {
@@ -163,6 +166,12 @@ struct bmf_ctx {
     size_t klist_lds = 0;
     int klist_waves = 0;             // waves that share one item of the vote kernel (kmer_item_waves): 1, 2 or 4
     double klist_mean_bytes = 0.0;   // list bytes a sample meets, as the estimate found them (BMF_LOG_TUNE prints it)
+    // The cells form (bmf_vote_kernel_cells; host/lists_cells_rule.h decides): klist_waves and klist_lds are then that
+    // kernel's, and the items it hands over are counted by bmf_vote_kernel_lists_over with the full-width kernel's own.
+    int klist_cells = 0;             // 0: bmf_vote_kernel_lists serves; 2 or 3: cells of 4 or 8 buckets
+    int klist_over_waves = 0;
+    size_t klist_over_lds = 0;
+    unsigned klist_over_grid = 0;    // resident workgroups of the overflow kernel
     uint32_t list_cap = 0;           // ids per (window, orientation) a batch's list buffer is sized for: the G-rows form
     // constants
     uint8_t *d_lut = nullptr;
@@ -449,6 +458,7 @@ static void free_pair_table(bmf_ctx *c) {
     c->d_koff = nullptr;
     c->d_kids = nullptr;
     c->klist_kmers = c->klist_bytes = 0;
+    c->klist_cells = 0;
     set_entries_per_sample(c, c->dp.G, 0u);
 }
 
@@ -673,6 +683,40 @@ static const void *kmer_vote_kernel(int bits, int waves) {
                         : reinterpret_cast<const void *>(bmf_vote_kernel_lists<8, 1>);
 }
 
+// bmf_vote_kernel_lists_over<bits, waves>
+static const void *kmer_over_kernel(int bits, int waves) {
+    using namespace bmf;
+    if (bits == 4)
+        return waves == 4   ? reinterpret_cast<const void *>(bmf_vote_kernel_lists_over<4, 4>)
+               : waves == 2 ? reinterpret_cast<const void *>(bmf_vote_kernel_lists_over<4, 2>)
+                            : reinterpret_cast<const void *>(bmf_vote_kernel_lists_over<4, 1>);
+    return waves == 4   ? reinterpret_cast<const void *>(bmf_vote_kernel_lists_over<8, 4>)
+           : waves == 2 ? reinterpret_cast<const void *>(bmf_vote_kernel_lists_over<8, 2>)
+                        : reinterpret_cast<const void *>(bmf_vote_kernel_lists_over<8, 1>);
+}
+
+// bmf_vote_kernel_cells<shift, waves>
+static const void *kmer_cells_kernel(int shift, int waves) {
+    using namespace bmf;
+    if (shift == 2)
+        return waves == 4   ? reinterpret_cast<const void *>(bmf_vote_kernel_cells<2, 4>)
+               : waves == 2 ? reinterpret_cast<const void *>(bmf_vote_kernel_cells<2, 2>)
+                            : reinterpret_cast<const void *>(bmf_vote_kernel_cells<2, 1>);
+    return waves == 4   ? reinterpret_cast<const void *>(bmf_vote_kernel_cells<3, 4>)
+           : waves == 2 ? reinterpret_cast<const void *>(bmf_vote_kernel_cells<3, 2>)
+                        : reinterpret_cast<const void *>(bmf_vote_kernel_cells<3, 1>);
+}
+
+// Waves per item under the cells form: bmf_rule::cells_item_waves (host/lists_cells_rule.h), measured there;
+// BMF_LISTS_ITEM_WAVES=1|2|4 forces a value as it does for the full-width kernel.
+static int kmer_cells_item_waves(uint32_t nb, int shift) {
+    if (const char *env = getenv("BMF_LISTS_ITEM_WAVES")) {
+        const int w = atoi(env);
+        if (w == 1 || w == 2 || w == 4) return w;
+    }
+    return bmf_rule::cells_item_waves(nb, (uint32_t)shift);
+}
+
 // Waves per item of the lists vote, chosen once per load.  The counters of an item take the LDS of one workgroup, and
 // the LDS decides how many workgroups c a CU holds (160 KiB over the one-wave kernel's bytes).  Items finish at the rate
 // resident workgroups / time per item, and W waves shorten an item's time, but not to 1 / W: the dependent loads ahead of
@@ -756,6 +800,34 @@ static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
         fprintf(stderr, "bmf: k-mer lists vote: %d wave(s) per item, %zu B of LDS per workgroup (%zu workgroups per CU by LDS)%s\n", waves, lds,
                 (size_t)(160u * 1024u) / lds, getenv("BMF_LISTS_ITEM_WAVES") ? " (BMF_LISTS_ITEM_WAVES)" : "");
     if (!pay && !forced) return give_up();
+    // The cells form (host/lists_cells_rule.h), from the same estimate.  BMF_LISTS_CELLS=0|2|3 forces the choice where
+    // the form can serve at all (S <= 31, F <= S).
+    double cells_lambda = 0.0, cells_p = 0.0;
+    int cells = bmf_rule::lists_cells(d.nb, d.S, d.F, c->klist_mean_bytes / 16.0, &cells_lambda, &cells_p);
+    const char *env_cells = getenv("BMF_LISTS_CELLS");
+    if (env_cells && (!strcmp(env_cells, "0") || !strcmp(env_cells, "2") || !strcmp(env_cells, "3"))) {
+        cells = bmf_rule::cells_possible(d.S, d.F) ? atoi(env_cells) : 0;
+        if (cells) bmf_rule::cells_model(d.nb, d.S, d.F, c->klist_mean_bytes / 16.0, (uint32_t)cells, &cells_lambda, &cells_p);
+    } else {
+        env_cells = nullptr;
+    }
+    const int cells_waves = cells ? kmer_cells_item_waves(d.nb, cells) : 0;
+    const size_t cells_lds = cells ? bmf::kmer_cells_lds_bytes(d.nb, (uint32_t)cells, (uint32_t)cells_waves) : 0;
+    unsigned over_grid = 0;
+    if (cells) {
+        // the overflow kernel: one resident round of the full-width kernel's workgroups, as many as the LDS and the
+        // wave slots of a CU hold
+        int n_cu = 0;
+        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->p.device) != hipSuccess || n_cu <= 0) return give_up();
+        const size_t per_cu = std::min<size_t>((size_t)(160u * 1024u) / std::max<size_t>(lds, 1), (size_t)(32 / waves));
+        over_grid = (unsigned)(std::max<size_t>(per_cu, 1) * (size_t)n_cu);
+        if (lds > 48 * 1024 && bmhip::raise_dynamic_lds(kmer_over_kernel(bits, waves), lds) != hipSuccess) return give_up();
+        if (cells_lds > 48 * 1024 && bmhip::raise_dynamic_lds(kmer_cells_kernel(cells, cells_waves), cells_lds) != hipSuccess) return give_up();
+    }
+    if (getenv("BMF_LOG_TUNE"))
+        fprintf(stderr, "bmf: k-mer lists vote: cells: lambda %.3f, %.4f cells kept by an item that cannot vote: %s%s; %d wave(s) per item, %zu B of LDS per workgroup\n",
+                cells_lambda, cells_p, cells == 3 ? "cells of 8" : (cells == 2 ? "cells of 4" : "full width"), env_cells ? " (BMF_LISTS_CELLS)" : "",
+                cells ? cells_waves : waves, cells ? cells_lds : lds);
     (void)hipFree(d_units);
     d_units = nullptr;
     // 2. count, scan, fill
@@ -784,8 +856,12 @@ static bool build_kmer_lists(bmf_ctx *c, uint64_t max_mb) {
     c->klist_kmers = n_k;
     c->klist_bytes = bytes;
     c->klist_bits = bits;
-    c->klist_lds = lds;
-    c->klist_waves = waves;
+    c->klist_lds = cells ? cells_lds : lds;
+    c->klist_waves = cells ? cells_waves : waves;
+    c->klist_cells = cells;
+    c->klist_over_lds = lds;
+    c->klist_over_waves = waves;
+    c->klist_over_grid = over_grid;
     set_entries_per_sample(c, 2u, 2u);       // one 64-bit extent per sample: two dwords
     return true;
 }
@@ -841,6 +917,7 @@ static void release_batch(bmf_batch *b) {
     b->offsets.release(); b->compact.release();
     b->slice_min.release(); b->slice_cnt.release(); b->slice_ids.release();
     b->q_counters.release(); b->q_slow.release(); b->q_live_n.release(); b->q_left.release(); b->q_live_chunks.release(); b->q_live_mask.release();
+    b->over.release();
 }
 
 static void free_map_slots(bmf_ctx *c) {
@@ -1235,6 +1312,7 @@ static hipError_t batch_reserve(bmf_ctx *c, bmf_batch *b, size_t n, size_t n_byt
     ok(b->rows_anded.need(n));
     ok(b->counts.need(2 * n));
     ok(b->buckets.need(2 * n * c->p.max_candidates));
+    if (c->dp.pair == 2u && c->klist_cells) ok(b->over.need(bmf::kOverHead + 2 * n));
     if (c->n_slices > 1) {
         ok(b->slice_min.need(2 * n * c->n_slices));
         ok(b->slice_cnt.need(2 * n * c->n_slices));
@@ -1295,6 +1373,7 @@ int bmf_batch_create(bmf_ctx *c, const uint8_t *bases, const uint8_t *quals, uin
 // Everything after the sample kernel for the first n_windows windows of `b` (row-id lists in b->lists), on the
 // context's stream: the vote kernel, or the exact-pruning kernels the context currently uses.
 static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
+    b->over_ran = false;
     if (c->dp.pass1_rows) {
         // two-pass pruning: full-width lower-bound pass, then the queued items' exact recount (bmf_vote2.hip.h)
         const size_t n_items = 2 * (size_t)n_windows;
@@ -1386,6 +1465,26 @@ static int launch_vote_stage(bmf_ctx *c, bmf_batch *b, uint32_t n_windows) {
             c->guard_items = n_items;
             c->guard_pending = true;
         }
+    } else if (c->dp.pair == 2u && c->klist_cells) {
+        // the cells form, then the items it handed over: the count is reset on the stream, the overflow kernel is
+        // launched whatever the count turns out to be -- no round trip to the host
+        const size_t n_items = 2 * (size_t)n_windows;
+        if (b->over.cap < bmf::kOverHead + n_items) {   // (a reload changed the form under a live batch)
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(b->over.need(bmf::kOverHead + n_items));
+        }
+        HIP_TRY(hipMemsetAsync(b->over.p, 0, bmf::kOverHead * sizeof(uint32_t), c->stream));
+        b->over_ran = true;
+        using CellsVote = void (*)(bmf::DevParams, const uint4 *, const uint64_t *, const uint32_t *, uint32_t *, uint32_t *, uint32_t *);
+        using OverVote = void (*)(bmf::DevParams, const uint4 *, const uint64_t *, const uint32_t *, uint32_t *, uint32_t *, const uint32_t *);
+        auto cv = reinterpret_cast<CellsVote>(const_cast<void *>(kmer_cells_kernel(c->klist_cells, c->klist_waves)));
+        auto ov = reinterpret_cast<OverVote>(const_cast<void *>(kmer_over_kernel(c->klist_bits, c->klist_over_waves)));
+        hipLaunchKernelGGL(cv, dim3(2 * n_windows), dim3(bmf::kWave * c->klist_waves), c->klist_lds, c->stream, c->dp,
+                           reinterpret_cast<const uint4 *>(c->d_kids), reinterpret_cast<const uint64_t *>(b->lists.p), b->list_n.p,
+                           b->counts.p, b->buckets.p, b->over.p);
+        hipLaunchKernelGGL(ov, dim3((unsigned)std::min<size_t>(c->klist_over_grid, n_items)), dim3(bmf::kWave * c->klist_over_waves),
+                           c->klist_over_lds, c->stream, c->dp, reinterpret_cast<const uint4 *>(c->d_kids),
+                           reinterpret_cast<const uint64_t *>(b->lists.p), b->list_n.p, b->counts.p, b->buckets.p, b->over.p);
     } else if (c->dp.pair == 2u) {
         using KmerVote = void (*)(bmf::DevParams, const uint4 *, const uint64_t *, const uint32_t *, uint32_t *, uint32_t *);
         auto kv = reinterpret_cast<KmerVote>(const_cast<void *>(kmer_vote_kernel(c->klist_bits, c->klist_waves)));
@@ -2032,6 +2131,21 @@ int bmf_derived_info(bmf_ctx *c, uint32_t *span, uint64_t *n_rows, uint64_t *byt
 int bmf_lists_item_waves(bmf_ctx *c, uint32_t *waves) {
     if (!c || !waves) return fail(BMF_ERR_ARG, "bmf_lists_item_waves: null argument");
     *waves = c->dp.pair == 2u ? (uint32_t)c->klist_waves : 0u;
+    return BMF_OK;
+}
+
+int bmf_lists_cells(bmf_ctx *c, uint32_t *shift) {
+    if (!c || !shift) return fail(BMF_ERR_ARG, "bmf_lists_cells: null argument");
+    *shift = c->dp.pair == 2u ? (uint32_t)c->klist_cells : 0u;
+    return BMF_OK;
+}
+
+int bmf_batch_lists_overflow(bmf_ctx *c, bmf_batch *b, uint32_t *items) {
+    if (!c || !b || !items) return fail(BMF_ERR_ARG, "bmf_batch_lists_overflow: null argument");
+    *items = 0;
+    HIP_TRY(hipSetDevice(c->p.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (b->over_ran && b->over.p) HIP_TRY(hipMemcpy(items, b->over.p, sizeof *items, hipMemcpyDeviceToHost));
     return BMF_OK;
 }
 

@@ -93,6 +93,20 @@
 //                          (W > 1).  W = 1 compiles to the one-wave kernel as it was (wavefront-scope fences, no
 //                          barrier).  Registers: W = 2 is held to 6 waves per SIMD (75 VGPRs), so that 11 workgroups =
 //                          22 waves fit; W = 4 to 7 (67 VGPRs: 7 workgroups = 28 waves; 8 per SIMD would spill).
+//   bmf_vote_kernel_cells  the same vote where the lists are sparse (host/lists_cells_rule.h decides, once per load;
+//                          S <= 31, F <= S): every id is counted into its CELL of 4 or 8 consecutive buckets first, in
+//                          byte counters half or a quarter the size of the 4-bit ones, plain adds only, in any order.  A
+//                          cell's sum is at least the highest hit count among its buckets, so an item none of whose
+//                          cells reaches S - F + 1 -- the wrong orientation of a read, a read that maps nowhere: half
+//                          of all items -- is empty and leaves after one scan; an item that keeps 1 .. 8 cells walks
+//                          its units again (two or four waves: the heads still in registers; one wave: from the L2)
+//                          and counts hits per bucket of those cells alone; one that keeps more is appended to the
+//                          overflow list.  The comment above the kernel has the argument, the LDS layout and the
+//                          registers.  LDS no longer limits the residency, the registers do (W = 2: 73 VGPRs, 6 waves
+//                          per SIMD, 12 items per CU; W = 1: 74 VGPRs, 24 items; W = 4: 50 VGPRs, 8 items).
+//   bmf_vote_kernel_lists_over  the overflow list's items, by the full-width vote (kmer_vote_item, the body of
+//                          bmf_vote_kernel_lists): one resident round of workgroups walks the list, launched behind
+//                          the cells kernel in every run, so the host makes no round trip.
 #pragma once
 
 #include "bmf_kernels.hip.h"
@@ -391,18 +405,18 @@ constexpr int kmer_vote_batch() { return W == 1 ? 16 : (W == 2 ? 8 : 4); }
 template <int W>
 constexpr int kmer_vote_waves_per_simd() { return W == 1 ? 1 : (W == 2 ? 6 : 7); }
 
-template <int BITS, int W = 1>
-__global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_vote_waves_per_simd<W>()))) void bmf_vote_kernel_lists(DevParams P, const uint4 *__restrict__ units,
-                                                                  const uint64_t *__restrict__ kmer_extents,
-                                                                  const uint32_t *__restrict__ list_n,
-                                                                  uint32_t *__restrict__ out_counts,
-                                                                  uint32_t *__restrict__ out_buckets) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_cnt[];
+// One item of the full-width vote (the header comment), by the whole workgroup: bmf_vote_kernel_lists calls it with
+// its block number, bmf_vote_kernel_lists_over with the items the cells form handed over.
+template <int BITS, int W>
+__device__ __forceinline__ void kmer_vote_item(uint32_t *lds_cnt, const DevParams &P, const uint4 *__restrict__ units,
+                                               const uint64_t *__restrict__ kmer_extents, const uint32_t *__restrict__ list_n,
+                                               uint32_t *__restrict__ out_counts, uint32_t *__restrict__ out_buckets,
+                                               const uint32_t item) {
     static_assert(W == 1 || W == 2 || W == 4, "waves per item");
     constexpr uint32_t kPer = 32u / BITS, kField = (1u << BITS) - 1u;
     constexpr uint32_t kTop = BITS == 4 ? 0x88888888u : 0x80808080u, kLow = ~kTop;
     constexpr int K = kmer_vote_batch<W>();
-    const uint32_t tid = threadIdx.x, item = blockIdx.x;
+    const uint32_t tid = threadIdx.x;
     // the wave's number within the item (scalar) and the lane within the wave
     const uint32_t wave = W == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / (uint32_t)kWave));
     const uint32_t lane = W == 1 ? tid : tid % (uint32_t)kWave;
@@ -552,6 +566,319 @@ __global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_
     // all <= max_candidates <= 64: every id of every wave is staged
     if (lane < total) out_buckets[(size_t)item * P.max_cand + base + lane] = stage[lane];
     if (tid == 0) out_counts[item] = all;
+}
+
+template <int BITS, int W = 1>
+__global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_vote_waves_per_simd<W>()))) void bmf_vote_kernel_lists(DevParams P, const uint4 *__restrict__ units,
+                                                                  const uint64_t *__restrict__ kmer_extents,
+                                                                  const uint32_t *__restrict__ list_n,
+                                                                  uint32_t *__restrict__ out_counts,
+                                                                  uint32_t *__restrict__ out_buckets) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_cnt[];
+    kmer_vote_item<BITS, W>(lds_cnt, P, units, kmer_extents, list_n, out_counts, out_buckets, blockIdx.x);
+}
+
+// ---- the cells form ----
+//
+// A bucket qualifies with h >= t = S - F + 1 hits.  Buckets are grouped into cells of C = 2^CELL consecutive ids and
+// every id of every list is counted into its cell first:
+//   - a cell's sum is the sum of h(b) over its buckets, so it is at least the highest h(b) among them;
+//   - a cell whose sum is below t therefore holds no qualifying bucket;
+//   - every qualifying bucket lies in a cell whose sum is at least t.
+// The ids of a list are distinct, so a cell's sum is at most C S <= 8 * 31 = 248: byte fields hold it (the host takes
+// the form only for 1 <= t, S <= 31).  The cell counters take ceil(NB / C) bytes, half or a quarter of the 4-bit
+// counters, every add is a plain ds_add_u32, and nothing depends on the order of the adds.  Only an item that keeps
+// 1 .. kCellsKeep cells counts hits per bucket, in kCellsKeep * C byte counters, over a second walk of its units that
+// adds the ids of the kept cells alone; an item that keeps more goes to the full-width kernel through the overflow list.
+constexpr uint32_t kCellsKeep = 8;       // T: cells an item may keep; T * C >= max_candidates + 1 is decided here for C = 8
+constexpr uint32_t kOverHead = 4;        // the overflow list: [0] the count (reset on the stream in every run), items from [4]
+
+// LDS bytes per workgroup of bmf_vote_kernel_cells: the cell counters rounded up to whole 16-byte stores, a dword per
+// lane of each wave (its padding ids add there; its kept cells are staged in the first kCellsKeep), the byte counters of
+// the kept cells' buckets (64 bytes) and the exchange words (a dword per wave, 16 bytes)
+inline uint32_t kmer_cells_counter_bytes(uint32_t nb, uint32_t cell) { return ((((nb + (1u << cell) - 1u) >> cell) + 15u) / 16u) * 16u; }
+inline uint32_t kmer_cells_lds_bytes(uint32_t nb, uint32_t cell, uint32_t waves) {
+    return kmer_cells_counter_bytes(nb, cell) + waves * 64u * 4u + kCellsKeep * 8u + 16u;
+}
+
+// The eight ids of one unit into their cells.  A padding id adds as well, where nobody reads: at the lane's dword of the
+// staging area, or, where its dword lies inside the counters, in a field that is no cell (the scan masks it) or in the
+// last cell's (NB > 65 535 - C: that cell is kept whatever it holds, see the scan).  Precondition, as for
+// kmer_unit_plain: the only id >= NB in a list is kPadId.  A lane that holds no unit (all ones) takes no part.
+template <int CELL>
+__device__ __forceinline__ void kmer_unit_cells(uint32_t *cnt, uint32_t spare, const uint4 &u) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+    if ((w[0] & 0xFFFFu) != kPadId) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t cell = (j & 1 ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu) >> CELL;
+            atomicAdd(&cnt[min(cell >> 2, spare)], 1u << ((cell & 3u) * 8u));
+        }
+    }
+}
+
+// The ids of one unit that lie in the kept cell whose first bucket is `base`, into that cell's C byte counters at
+// `small`.  A list ascends, so a unit meets [base, base + C) only if its first id lies below base + C and its last one
+// (a padding id is the highest) at or above base: two compares turn most units away.  A padding id counts in the field
+// of bucket 65 535, which is no bucket (only where the last cell is kept and NB > 65 535 - C); at most 7 S + 8 of them
+// meet a field the caller never reads as a bucket's, the top one of its dword.
+template <int CELL>
+__device__ __forceinline__ void kmer_unit_exact(uint32_t *small, uint32_t base, const uint4 &u) {
+    constexpr uint32_t C = 1u << CELL;
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+    if ((w[0] & 0xFFFFu) < base + C && (w[3] >> 16) >= base && (w[0] & 0xFFFFu) != kPadId) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t d = (j & 1 ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu) - base;
+            if (d < C) atomicAdd(&small[d >> 2], 1u << ((d & 3u) * 8u));
+        }
+    }
+}
+
+// Waves per SIMD the registers of the cells kernel must leave room for; the LDS no longer limits the residency.
+//   W = 1   6: 74 VGPRs, 24 items per CU (7 per SIMD spills 4 registers)
+//   W = 2   6: 73 VGPRs with the heads kept for the exact phase, 12 items per CU.  Loading them again instead needs 43
+//           VGPRs, 8 waves per SIMD, 16 items per CU -- and was measured SLOWER (vote 5.73 ms against 5.44 ms at the
+//           headline shape, profiles/r20/README.md): the second pass over the units costs more than the residency buys.
+//           (Keeping them at 7 per SIMD spills 4 registers.)
+//   W = 4   8: 50 VGPRs, 8 items per CU
+template <int W>
+constexpr int kmer_cells_waves_per_simd() { return W == 4 ? 8 : 6; }
+
+template <int CELL, int W>
+__global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_cells_waves_per_simd<W>()))) void bmf_vote_kernel_cells(DevParams P, const uint4 *__restrict__ units,
+                                                                  const uint64_t *__restrict__ kmer_extents,
+                                                                  const uint32_t *__restrict__ list_n,
+                                                                  uint32_t *__restrict__ out_counts,
+                                                                  uint32_t *__restrict__ out_buckets,
+                                                                  uint32_t *__restrict__ over) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_cnt[];
+    static_assert(W == 1 || W == 2 || W == 4, "waves per item");
+    static_assert(CELL == 2 || CELL == 3, "cells of 4 or 8 buckets");
+    constexpr uint32_t C = 1u << CELL;
+    constexpr int K = kmer_vote_batch<W>();
+    const uint32_t tid = threadIdx.x, item = blockIdx.x;
+    const uint32_t wave = W == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / (uint32_t)kWave));
+    const uint32_t lane = W == 1 ? tid : tid % (uint32_t)kWave;
+    // the wave's share of the item's lists, as in kmer_vote_item: s = wave + j W, lane j holds the extent of list j
+    const uint32_t n_mine = W == 1 ? P.S : (P.S > wave ? (P.S - wave + (uint32_t)W - 1u) / (uint32_t)W : 0u);
+    uint64_t extent = 0;
+    if (lane < n_mine) extent = kmer_extents[(size_t)item * (P.list_len >> 1) + wave + lane * (uint32_t)W];
+    if (list_n[item >> 1] == 0) {              // window rejected by the sample kernel (the whole workgroup leaves)
+        if (tid == 0) out_counts[item] = 0;
+        return;
+    }
+    const uint32_t n_cells = (P.nb + C - 1u) >> CELL, n_dw = (n_cells + 3u) >> 2, n_q = (n_dw + 3u) >> 2;
+    uint32_t *stage = lds_cnt + n_q * 4u;                            // [64 w + i]: wave w's i-th kept cell, i < kCellsKeep
+    uint32_t *small = stage + (uint32_t)(W * kWave);                 // [2 j ..]: the C byte counters of kept cell j (C = 4: [j])
+    uint32_t *xch = small + kCellsKeep * 2u;                         // [w]: cells wave w keeps
+    const uint32_t spare = n_q * 4u + tid;     // the lane's dword of the staging area, where its padding ids add
+
+    for (uint32_t i = tid; i < n_q; i += (uint32_t)(W * kWave)) reinterpret_cast<uint4 *>(lds_cnt)[i] = make_uint4(0, 0, 0, 0);
+    if (tid < kCellsKeep * 2u) small[tid] = 0;
+    kmer_item_sync<W>();
+
+    const uint64_t first = kmer_extent_first(extent);
+    const uint32_t n_units = kmer_extent_units(extent);
+    const KmerListExtents ext{(uint32_t)first, (uint32_t)(first >> 32), n_units};
+    const bool tails = __ballot(n_units > (uint32_t)kWave) != 0;
+    auto heads = [&](uint32_t s0, uint4 (&u)[K]) {
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            const uint32_t n = ext.units_of((s0 + i) & 63u);
+            u[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+            if (lane < n) u[i] = units[ext.first_of((s0 + i) & 63u) + lane];
+        }
+    };
+    // what lies beyond the first 64 units of the wave's lists, four wave loads at a time
+    auto walk_tails = [&](auto &&unit) {
+        for (uint32_t s = 0; s < n_mine; s++) {
+            const uint32_t n = ext.units_of(s);
+            if (n <= (uint32_t)kWave) continue;
+            const uint4 *list = units + ext.first_of(s);
+            for (uint32_t at = kWave; at < n; at += 4u * kWave) {
+                uint4 v[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t t = at + (uint32_t)i * kWave + lane;
+                    v[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+                    if (t < n) v[i] = list[t];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++) unit(v[i]);
+            }
+        }
+    };
+
+    // ---- cell phase: every id of every list ----
+    uint4 u[K];                                // the heads of the last batch stay: the exact phase reads them again
+    uint32_t s0 = 0;
+    do {                                       // (a wave with no list loads nothing: its u is all ones)
+        heads(s0, u);
+#pragma unroll
+        for (int i = 0; i < K; i++) kmer_unit_cells<CELL>(lds_cnt, spare, u[i]);
+        s0 += (uint32_t)K;
+    } while (s0 < n_mine);
+    if (tails) walk_tails([&](const uint4 &v) { kmer_unit_cells<CELL>(lds_cnt, spare, v); });
+    kmer_item_sync<W>();                       // every add of every wave precedes the scan
+
+    // ---- scan: the cells whose sum is at least t, in ascending order ----
+    // Field x of a dword, x <= 248, against t, 1 <= t <= 31: x >= 128 has its top bit set; else (x & 127) + (128 - t)
+    // stays below 256 and has its top bit set iff x >= t.
+    // The padding id's cell, where it is a cell at all (NB > 65 535 - C: the last one, the top field of the last
+    // dword), also counted up to 7 padding ids per list and may have wrapped: it is kept whatever it holds, and the
+    // exact phase decides.
+    const uint32_t t_min = P.S - P.F + 1u;
+    const uint32_t add_c = (128u - t_min) * 0x01010101u;
+    const uint32_t pad_dw = (kPadId >> CELL) < n_cells ? (kPadId >> CELL) >> 2 : 0xFFFFFFFFu;
+    uint32_t q_begin = 0, q_end = n_q;
+    if constexpr (W > 1) {
+        const uint32_t per_wave = (((n_q + (uint32_t)kWave - 1u) / (uint32_t)kWave + (uint32_t)W - 1u) / (uint32_t)W) * (uint32_t)kWave;
+        q_begin = min(wave * per_wave, n_q);
+        q_end = min(q_begin + per_wave, n_q);
+    }
+    uint32_t kept = 0;
+    for (uint32_t q0 = q_begin; q0 < q_end; q0 += kWave) {
+        const uint32_t qi = q0 + lane;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (qi < q_end) v = reinterpret_cast<const uint4 *>(lds_cnt)[qi];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        uint32_t ge[4], pc = 0;
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+            const uint32_t dw = qi * 4u + (uint32_t)x;
+            ge[x] = (((w[x] & 0x7F7F7F7Fu) + add_c) | w[x]) & 0x80808080u;
+            if (dw == pad_dw) ge[x] |= 0x80000000u;
+            const uint32_t left = dw * 4u < n_cells ? n_cells - dw * 4u : 0u;   // fields past the last cell are no cells
+            if (left < 4u) ge[x] &= (1u << (left * 8u)) - 1u;
+            if (qi >= q_end) ge[x] = 0;
+            pc += __popc(ge[x]);
+        }
+        if (__ballot(pc != 0) == 0) continue;
+        uint32_t incl = pc;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const uint32_t t = __shfl_up(incl, o, kWave);
+            if (lane >= (uint32_t)o) incl += t;
+        }
+        uint32_t pos = kept + incl - pc;
+        kept += __shfl(incl, kWave - 1, kWave);
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+            uint32_t bits = ge[x];
+            while (bits) {
+                if (pos < kCellsKeep) stage[wave * (uint32_t)kWave + pos] = (qi * 4u + (uint32_t)x) * 4u + (uint32_t)__builtin_ctz(bits) / 8u;
+                pos++;
+                bits &= bits - 1u;
+            }
+        }
+        if (kept > kCellsKeep) break;           // overflow whatever follows (wave-uniform)
+    }
+    uint32_t all = kept;
+    if constexpr (W > 1) {
+        if (lane == 0) xch[wave] = kept;
+        kmer_item_sync<W>();                    // the kept cells of every wave are staged
+        all = 0;
+#pragma unroll
+        for (int w = 0; w < W; w++) all += (uint32_t)__builtin_amdgcn_readfirstlane((int)xch[w]);
+    } else {
+        kmer_item_sync<W>();
+    }
+    if (all == 0) {                             // no cell reaches t: no bucket does (all waves leave, or none)
+        if (tid == 0) out_counts[item] = 0;
+        return;
+    }
+    if (all > kCellsKeep) {                     // the full-width kernel counts this item (bmf_vote_kernel_lists_over)
+        if (tid == 0) over[kOverHead + atomicAdd(&over[0], 1u)] = item;
+        return;
+    }
+
+    // ---- exact phase: hits per bucket of the kept cells ----
+    // Two or four waves: where one batch held the wave's whole share (S <= 16 with two waves) its heads are still in
+    // u.  One wave: 16 heads are 64 registers, which would halve the waves per SIMD; it loads them again.
+    const bool held = W > 1 && n_mine <= (uint32_t)K;
+    uint32_t j = 0;
+#pragma unroll 1
+    for (int w = 0; w < W; w++) {
+        const uint32_t n_w = W == 1 ? kept : (uint32_t)__builtin_amdgcn_readfirstlane((int)xch[w]);
+#pragma unroll 1
+        for (uint32_t i = 0; i < n_w; i++, j++) {
+            const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)stage[(uint32_t)w * (uint32_t)kWave + i]) << CELL;
+            uint32_t *small_j = small + j * (C / 4u);
+            if (held) {
+#pragma unroll
+                for (int x = 0; x < K; x++) kmer_unit_exact<CELL>(small_j, base, u[x]);
+            } else {
+                for (uint32_t s0 = 0; s0 < n_mine; s0 += (uint32_t)K) {   // again from the L2
+                    uint4 v[K];
+                    heads(s0, v);
+#pragma unroll
+                    for (int x = 0; x < K; x++) kmer_unit_exact<CELL>(small_j, base, v[x]);
+                }
+            }
+            if (tails) walk_tails([&](const uint4 &v) { kmer_unit_exact<CELL>(small_j, base, v); });
+        }
+    }
+    kmer_item_sync<W>();                        // every add of every wave precedes the reading of the byte counters
+    if (wave != 0) return;
+    // Lane l holds byte counter l: bucket l % C of kept cell l / C.  The kept cells ascend through the waves' staging
+    // areas, so the buckets ascend with the lane.
+    uint32_t bucket = 0xFFFFFFFFu, hits = 0;
+    if (lane < all * C) {
+        uint32_t jj = lane >> CELL, w_of = 0;
+        if constexpr (W > 1) {
+#pragma unroll
+            for (int w = 0; w < W - 1; w++) {
+                const uint32_t n_w = xch[w];
+                if (w_of == (uint32_t)w && jj >= n_w) {
+                    jj -= n_w;
+                    w_of++;
+                }
+            }
+        }
+        bucket = (stage[w_of * (uint32_t)kWave + jj] << CELL) + (lane & (C - 1u));
+        hits = (small[lane >> 2] >> ((lane & 3u) * 8u)) & 0xFFu;
+    }
+    const bool is_bucket = bucket < P.nb;       // (the last cell may reach past NB; the padding id's field is there)
+    uint32_t mx = is_bucket ? hits : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, kWave));
+    // fewest misses = S - mx; nothing below F misses: every level of the reference's filter is empty
+    if (mx + P.F <= P.S) {
+        if (lane == 0) out_counts[item] = 0;
+        return;
+    }
+    const uint64_t at_max = __ballot(is_bucket && hits == mx);
+    const uint32_t count = (uint32_t)__popcll(at_max);
+    if (count > P.max_cand) {                   // q_gram_mapper.h:471-476
+        if (lane == 0) out_counts[item] = 0;
+        return;
+    }
+    if ((at_max >> lane) & 1ull) out_buckets[(size_t)item * P.max_cand + (uint32_t)__popcll(at_max & ((1ull << lane) - 1ull))] = bucket;
+    if (lane == 0) out_counts[item] = count;
+}
+
+// The items the cells kernel could not decide (more than kCellsKeep cells kept: a k-mer with no indexed q-gram, dense
+// rows, repeats), counted by the full-width vote.  A fixed grid of resident workgroups walks over[kOverHead ..
+// kOverHead + over[0]); outputs are addressed by item, so the order of the list changes nothing.
+// (the loop over items takes a few registers more than one item does: a wave per SIMD fewer than bmf_vote_kernel_lists,
+// so that nothing spills -- a wave that needs scratch is slow to start, and this kernel is launched in every run)
+template <int W>
+constexpr int kmer_over_waves_per_simd() { return W == 1 ? 1 : (W == 2 ? 5 : 6); }
+
+template <int BITS, int W>
+__global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(kmer_over_waves_per_simd<W>()))) void bmf_vote_kernel_lists_over(DevParams P, const uint4 *__restrict__ units,
+                                                                  const uint64_t *__restrict__ kmer_extents,
+                                                                  const uint32_t *__restrict__ list_n,
+                                                                  uint32_t *__restrict__ out_counts,
+                                                                  uint32_t *__restrict__ out_buckets,
+                                                                  const uint32_t *__restrict__ over) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_cnt[];
+    const uint32_t n_over = over[0];
+    for (uint32_t i = blockIdx.x; i < n_over; i += gridDim.x) {
+        kmer_vote_item<BITS, W>(lds_cnt, P, units, kmer_extents, list_n, out_counts, out_buckets, over[kOverHead + i]);
+        kmer_item_sync<W>();                    // the next item's zeroing behind this item's last reads
+    }
 }
 
 }  // namespace bmf

@@ -81,6 +81,8 @@ SYMBOLS = {
     "bmf_derived_row": (C.c_int, [C.c_void_p, C.c_uint64, _u8p]),
     "bmf_derived_form": (C.c_int, [C.c_void_p, _u32p]),
     "bmf_lists_item_waves": (C.c_int, [C.c_void_p, _u32p]),
+    "bmf_lists_cells": (C.c_int, [C.c_void_p, _u32p]),
+    "bmf_batch_lists_overflow": (C.c_int, [C.c_void_p, C.c_void_p, _u32p]),
     "bmf_pass1_rows": (C.c_int, [C.c_void_p, _u32p]),
     "bmf_pass1_fold": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bmf_batch_pass2_counts": (C.c_int, [C.c_void_p, C.c_void_p, _u32p, _u32p]),
@@ -245,6 +247,12 @@ class Batch:
         a, b = C.c_uint32(), C.c_uint32()
         _check(lib().bmf_batch_pass2_counts(self._flt._h, self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def lists_overflow(self) -> int:
+        """Items of the last run that the cells form of the lists vote handed to the full-width kernel (0 without it)."""
+        v = C.c_uint32()
+        _check(lib().bmf_batch_lists_overflow(self._flt._h, self._h, C.byref(v)))
+        return int(v.value)
 
     def live_histogram(self):
         """(stored, lowest): items by stored chunks after pass 1 / by chunks at their lowest level; [33] = slow items."""
@@ -417,7 +425,9 @@ class Filter:
         _check(lib().bmf_derived_form(self._h, C.byref(form)))
         item_waves = C.c_uint32()
         _check(lib().bmf_lists_item_waves(self._h, C.byref(item_waves)))
-        return {"lists_item_waves": item_waves.value,
+        cells = C.c_uint32()
+        _check(lib().bmf_lists_cells(self._h, C.byref(cells)))
+        return {"lists_item_waves": item_waves.value, "lists_cells": cells.value,
 "derived_form": ("rows", "pairs", "kmer_lists")[form.value], "row_pitch_bytes": v[0].value, "chunks_per_lane": v[1].value, "planes": v[2].value,
                 "rows_in_flight": v[3].value, "pass1_rows": r.value, "pass1_fold": fold.value, "pass1_fold_rows": frows.value,
                 "derived_span": span.value, "derived_bytes": d_bytes.value}

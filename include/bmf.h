@@ -209,6 +209,14 @@ int  bmf_derived_form(bmf_ctx *ctx, uint32_t *form);
  * vote kernel -- 1, 2 or 4, chosen once at load from the LDS the counters take (BMF_LISTS_ITEM_WAVES=1|2|4 forces a
  * value); the outputs do not depend on it.  0 when the lists do not serve. */
 int  bmf_lists_item_waves(bmf_ctx *ctx, uint32_t *waves);
+/* With the per-k-mer lists: whether the vote counts cells of 2^shift consecutive buckets first and hits per bucket only
+ * for the cells that reach S - F + 1 -- shift 2 or 3, chosen once at load from the density of the lists (S <= 31 and
+ * F <= S; BMF_LISTS_CELLS=0|2|3 forces a value), 0 when the full-width kernel serves or the lists do not.  Under the
+ * cells form bmf_lists_item_waves reports that kernel's waves.  The outputs do not depend on it. */
+int  bmf_lists_cells(bmf_ctx *ctx, uint32_t *shift);
+/* ... and how many (window, orientation) items of the batch's last run kept more cells than the cells kernel follows
+ * and were counted by the full-width kernel; 0 when the cells form did not serve the run.  Waits for the run. */
+int  bmf_batch_lists_overflow(bmf_ctx *ctx, bmf_batch *batch, uint32_t *items);
 /* BMF_FLAG_EARLY_EXIT only: index rows per sample the first pass of the two-pass pruning kernel streams
  * for the loaded index; 0 = the single-pass pruning kernel (or no pruning) serves it. */
 int  bmf_pass1_rows(bmf_ctx *ctx, uint32_t *out);
