@@ -36,6 +36,9 @@
 // the marks have been ORed into it, in one depth_add call; several runs -- the merged stream as it is made, cut at record
 // borders into pieces of about run_bytes, one depth_add call each.  The rule does not depend on the order or the cutting of
 // the records, so both ways give the same result; it is kept for the caller, who writes the files.
+//
+// PILEUP MODE (--pileup; include/bmp.h states the rule).  The same pieces of the final stream go to pileup_add, beside or
+// without depth mode: pileup_begin with the references' bases and the thresholds before them, pileup_finish after them.
 #pragma once
 
 #include "bgzf.h"
@@ -180,6 +183,11 @@ class bam_sorter {
     bool depth_ = false;                             // depth mode
     std::vector<uint32_t> depth_ref_len_;
     depth_result depth_result_;
+    bool pileup_ = false;                            // pileup mode
+    std::vector<uint32_t> pileup_ref_len_;
+    std::vector<const uint8_t *> pileup_ref_bases_;
+    pileup_thresholds pileup_thresholds_;
+    pileup_result pileup_result_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -251,6 +259,19 @@ public:
         }
     }
     const depth_result &depth() const { return depth_result_; }
+    // pileup mode: before the first add(), the references' lengths, their bases (ref_bases[r]: ref_lengths[r] bytes that stay
+    // where they are until finish() is done) and the thresholds; after finish(), the sites and the sums per reference
+    void set_pileup(const std::vector<size_t> &ref_lengths, const std::vector<const uint8_t *> &ref_bases, const pileup_thresholds &th) {
+        pileup_ = true;
+        pileup_ref_len_.clear();
+        for (size_t len : ref_lengths) {
+            if (len > 0xFFFFFFFFull) throw std::runtime_error("--pileup: a reference of " + std::to_string(len) + " bases");
+            pileup_ref_len_.push_back(static_cast<uint32_t>(len));
+        }
+        pileup_ref_bases_ = ref_bases;
+        pileup_thresholds_ = th;
+    }
+    const pileup_result &pileup() const { return pileup_result_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -287,6 +308,7 @@ public:
             blocks.clear();
         };
         if (depth_) z_->depth_begin(depth_ref_len_.data(), depth_ref_len_.size());
+        if (pileup_) z_->pileup_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), pileup_ref_bases_.data(), pileup_thresholds_);
         if (tmp_.empty()) {
             n_runs_ = off_.size() > 1 ? 1 : 0;
             std::vector<uint32_t> perm;
@@ -303,6 +325,7 @@ public:
             for (size_t k = 0; k + 1 < off_.size(); k++) bai.add(run_.data() + off_[perm[k]], so[k], so[k + 1] - so[k]);
             emit();
             if (depth_) z_->depth_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
+            if (pileup_) z_->pileup_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
         } else {
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
@@ -323,10 +346,11 @@ public:
                 if (reader[r]->next()) heap.emplace(bam_sort_key(reader[r]->rec.data()), r);
             }
             constexpr size_t kPiece = size_t{64} * kBgzfBlockMax;
-            std::vector<uint8_t> merged, counted;        // counted: depth mode, the merged records not yet handed to depth_add
+            std::vector<uint8_t> merged, counted;        // counted: depth or pileup mode, the merged records not yet handed to depth_add / pileup_add
             std::vector<uint64_t> counted_off{0};
             auto count = [&]() {
-                if (counted_off.size() > 1) z_->depth_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
+                if (depth_ && counted_off.size() > 1) z_->depth_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
+                if (pileup_ && counted_off.size() > 1) z_->pileup_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 counted.clear();
                 counted_off.assign(1, 0);
             };
@@ -339,7 +363,7 @@ public:
                 bai.add(rec.data(), so, rec.size());
                 so += rec.size();
                 merged.insert(merged.end(), rec.begin(), rec.end());
-                if (depth_) {
+                if (depth_ || pileup_) {
                     counted.insert(counted.end(), rec.begin(), rec.end());
                     counted_off.push_back(counted.size());
                     if (counted.size() >= run_bytes_) count();
@@ -354,7 +378,7 @@ public:
             }
             if (!merged.empty()) z_->deflate(merged.data(), merged.size(), blocks);
             emit();
-            if (depth_) count();
+            if (depth_ || pileup_) count();
             reader.clear();
         }
         out.write(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -365,6 +389,7 @@ public:
         if (!index) throw std::runtime_error("--sort: cannot write " + out_path_ + ".bai");
         remove_tmp();
         if (depth_) z_->depth_finish(depth_result_);
+        if (pileup_) z_->pileup_finish(pileup_result_);
     }
 
 private:

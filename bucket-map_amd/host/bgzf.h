@@ -6,6 +6,7 @@
 #pragma once
 
 #include "depth.h"
+#include "pileup.h"
 #include "markdup.h"
 
 #include <algorithm>
@@ -354,8 +355,21 @@ struct block_compressor {
     }
     virtual void depth_finish(depth_result &out) { depth_.finish(out); }
 
+    // --pileup (include/bmp.h states the rule): the references with their bases (ref_bases[r]: ref_len[r] bytes) and the four
+    // thresholds, then whole records as for depth_add, then the sites and the six sums per reference.  The defaults are the
+    // host rule of pileup.h; the product plugs in bmp_begin, bmp_add, bmp_finish and bmp_sites.
+    virtual void pileup_begin(const uint32_t *ref_len, size_t n_ref, const uint8_t *const *ref_bases, const pileup_thresholds &th) {
+        pileup_.begin(ref_len, n_ref, ref_bases, th);
+    }
+    virtual void pileup_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) {
+        (void)n;
+        pileup_.add(in, rec_offset, n_records, skip);
+    }
+    virtual void pileup_finish(pileup_result &out) { pileup_.finish(out); }
+
 private:
     depth_counter depth_;
+    pileup_counter pileup_;
 };
 
 }  // namespace bm

@@ -475,8 +475,11 @@ class sam_text {
     std::filesystem::path depth_file_, coverage_file_;   // sorted BAM: --depth / --coverage, either may be empty
     std::vector<std::string> ref_ids_;     // ... the references, for the two files
     std::vector<uint32_t> ref_len_;
+    std::filesystem::path pileup_file_;    // sorted BAM: --pileup, may be empty
+    pileup_thresholds pileup_thresholds_;
+    const std::vector<std::string> *pileup_seqs_ = nullptr;   // ... the bases of the header's references, each of its length
 
-    // A file of --depth / --coverage: written beside its place and moved there when it is complete, so that a failure
+    // A file of --depth / --coverage / --pileup: written beside its place and moved there when it is complete, so that a failure
     // leaves nothing half-written (and nothing at all under the final name).
     template <typename Fill>
     static void write_whole(const std::filesystem::path &file, Fill &&fill) {
@@ -505,6 +508,32 @@ class sam_text {
         }
         std::cerr << "[INFO]\t\tCoverage: " << cov << " of " << bases << " bases covered by " << reads << " records (" << n_long
                   << " long-CIGAR records left out)\n";
+    }
+    void write_pileup() {
+        const pileup_result &res = sorter_->pileup();
+        write_whole(pileup_file_, [&](std::ostream &f) { write_pileup_file(f, res, ref_ids_); });
+        uint64_t sites = 0, bases = 0, reads = 0, left_out = 0, low_mapq = 0;
+        for (size_t r = 0; r < ref_ids_.size(); r++) {
+            const uint64_t *st = res.stats.data() + r * kPileupStats;
+            reads += st[0], low_mapq += st[1], left_out += st[2], bases += st[3], sites += st[5];
+        }
+        std::cerr << "[INFO]\t\tPileup: " << sites << " sites on " << bases << " bases from " << reads << " records (" << left_out
+                  << " left out, " << low_mapq << " below MAPQ)\n";
+    }
+    // --pileup: the references' bases for the sorter, one string of the header's length per reference
+    void set_pileup(const std::vector<std::string> &ref_ids, const std::vector<size_t> &ref_lengths) {
+        if (!pileup_seqs_ || pileup_seqs_->size() != ref_ids.size())
+            throw std::runtime_error("--pileup: " + std::to_string(pileup_seqs_ ? pileup_seqs_->size() : 0) + " sequences for the " +
+                                     std::to_string(ref_ids.size()) + " references of the header");
+        std::vector<const uint8_t *> bases(ref_ids.size());
+        for (size_t r = 0; r < ref_ids.size(); r++) {
+            const std::string &seq = (*pileup_seqs_)[r];
+            if (seq.size() != ref_lengths[r])
+                throw std::runtime_error("--pileup: " + std::to_string(seq.size()) + " bases for " + ref_ids[r] + ", which has " +
+                                         std::to_string(ref_lengths[r]));
+            bases[r] = reinterpret_cast<const uint8_t *>(seq.data());
+        }
+        sorter_->set_pileup(ref_lengths, bases, pileup_thresholds_);
     }
 
     // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer
@@ -574,14 +603,19 @@ public:
     // duplicates among the records are flagged 0x400 on the way (--markdup, include/bmd.h)
     // depth_file / coverage_file (sorted BAM only, either may be empty): the bedGraph runs of equal depth and the table per
     // reference of the records written (--depth, --coverage, include/bmc.h)
+    // pileup_file (sorted BAM only, may be empty): the table of variant sites of the records written (--pileup, include/bmp.h),
+    // under these thresholds and against ref_bases, the bases of the header's references (each as long as the header says)
     explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr, size_t sort_run_bytes = 0, bool markdup = false,
-                      std::filesystem::path const &depth_file = {}, std::filesystem::path const &coverage_file = {})
-        : out_(file, std::ios::binary), bam_(bam) {
+                      std::filesystem::path const &depth_file = {}, std::filesystem::path const &coverage_file = {},
+                      std::filesystem::path const &pileup_file = {}, pileup_thresholds const &pileup_th = {},
+                      const std::vector<std::string> *ref_bases = nullptr)
+        : out_(file, std::ios::binary), bam_(bam), pileup_thresholds_(pileup_th), pileup_seqs_(ref_bases) {
         if (!out_) throw std::runtime_error("cannot write " + file.string());
         if (bam_ && sort_run_bytes) sorter_ = std::make_unique<bam_sorter>(bam_, file, sort_run_bytes, markdup);
         markdup_ = sorter_ && markdup;
         depth_file_ = sorter_ ? depth_file : std::filesystem::path();
         coverage_file_ = sorter_ ? coverage_file : std::filesystem::path();
+        pileup_file_ = sorter_ ? pileup_file : std::filesystem::path();
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
@@ -618,6 +652,7 @@ public:
                           << " pair units, " << c[1] << " fragment units)\n";
             }
             if (!depth_file_.empty() || !coverage_file_.empty()) write_depth_files();
+            if (!pileup_file_.empty()) write_pileup();
         } else if (bam_ && !closed_) {
             encode_buffer(true);
             buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -654,6 +689,10 @@ public:
                 sorter_->set_depth(ref_lengths);
                 ref_ids_ = ref_ids;
                 ref_len_.assign(ref_lengths.begin(), ref_lengths.end());   // set_depth has refused what does not fit
+            }
+            if (!pileup_file_.empty()) {
+                set_pileup(ref_ids, ref_lengths);
+                ref_ids_ = ref_ids;
             }
             buf_.clear();
         }
@@ -707,6 +746,8 @@ private:
     size_t _sort_run_bytes = 0;                  // > 0: --sort, the BAM records in coordinate order with a .bai (host/bam_sort.h)
     bool _markdup = false;                       // --markdup: duplicates flagged 0x400 before the sort (include/bmd.h)
     std::filesystem::path _depth_file, _coverage_file;   // --depth / --coverage: the written records' depth and coverage (include/bmc.h)
+    std::filesystem::path _pileup_file;          // --pileup: the variant sites of the written records (include/bmp.h)
+    pileup_thresholds _pileup_thresholds{};
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
@@ -923,6 +964,10 @@ public:
     void set_depth_files(std::filesystem::path const &depth, std::filesystem::path const &coverage) {   // ... and its depth reported
         _depth_file = depth;
         _coverage_file = coverage;
+    }
+    void set_pileup(std::filesystem::path const &file, pileup_thresholds const &th) {   // ... and its variant sites listed
+        _pileup_file = file;
+        _pileup_thresholds = th;
     }
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
@@ -1180,7 +1225,21 @@ public:
         auto locate_res = locate_reads(sequence_file);
         const sam_header h = read_bucket_ids(index_file);
 
-        sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup, _depth_file, _coverage_file);
+        // --pileup: the bases of the header's references.  A reference is a run of kept buckets, bucket k of the run at
+        // [k * bucket_length, (k + 1) * bucket_length): for one FASTA record that is the record itself, cut or filled up to whole
+        // buckets; what no bucket's sequence fills has no reference allele (N).
+        std::vector<std::string> pileup_bases;
+        if (!_pileup_file.empty() && genome_) {
+            for (size_t b = 0, r = 0; r < h.ref_ids.size(); r++) {
+                pileup_bases.emplace_back(h.ref_lengths[r], 'N');
+                for (size_t at = 0; at < h.ref_lengths[r]; at += bucket_length, b++) {
+                    const std::string &seq = genome_->seqs[buckets_[b].record];
+                    const size_t start = buckets_[b].start, n = std::min<size_t>(bucket_length, seq.size() - std::min<size_t>(start, seq.size()));
+                    pileup_bases.back().replace(at, n, seq, start, n);
+                }
+            }
+        }
+        sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup, _depth_file, _coverage_file, _pileup_file, _pileup_thresholds, &pileup_bases);
         sam.header(h.ref_ids, h.ref_lengths);
         unsigned int read_id = 0, mapped_locations = 0;
         auto t0 = std::chrono::steady_clock::now();

@@ -75,6 +75,12 @@ struct cmd_arguments {
     std::filesystem::path depth_path{}, coverage_path{};   // --depth FILE / --coverage FILE (-o x.bam only, either implies --sort):
                                   // the per-base depth of the records written as bedGraph runs, and one line per reference of
                                   // reads, covered bases, mean depth, base quality and MAPQ (include/bmc.h states the rule)
+    std::filesystem::path pileup_path{};   // --pileup FILE (-o x.bam only, implies --sort, in bucketmap_align --annotate too): per
+                                  // base what the written records say, and the table of positions where enough of them disagree
+                                  // with the reference (include/bmp.h states the rule)
+    unsigned long pileup_min_bq = 13, pileup_min_mapq = 0, pileup_min_alt = 2;   // --pileup-min-bq / -min-mapq / -min-alt N
+    unsigned long pileup_min_frac_ppm = 200000;   // --pileup-min-frac F, a decimal in [0, 1] with at most six fractional digits
+    std::string pileup_threshold_opt;   // the first of those four given: refused without --pileup
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -122,6 +128,26 @@ inline std::vector<int> parse_gpu_list(const std::string &v) {
     }
     if (out.empty()) throw parser_error("--gpus needs a device list such as 0,1,2,3 or n8");
     return out;
+}
+
+// --pileup-min-frac: a decimal in [0, 1] with at most six fractional digits ("0", "1", "0.2", "0.000001", "1.000000"), as
+// parts per million, without floating point; false for everything else (a sign, an exponent, seven digits, above 1)
+inline bool parse_ppm(const std::string &s, unsigned long &ppm) {
+    size_t at = 0;
+    while (at < s.size() && s[at] >= '0' && s[at] <= '9') at++;
+    if (at == 0 || at > 1 || s[0] > '1') return false;   // one digit before the point: 0 or 1
+    unsigned long v = static_cast<unsigned long>(s[0] - '0') * 1000000ul;
+    if (at < s.size()) {
+        if (s[at] != '.' || s.size() - at - 1 < 1 || s.size() - at - 1 > 6) return false;
+        unsigned long scale = 100000ul;
+        for (size_t k = at + 1; k < s.size(); k++, scale /= 10) {
+            if (s[k] < '0' || s[k] > '9') return false;
+            v += static_cast<unsigned long>(s[k] - '0') * scale;
+        }
+    }
+    if (v > 1000000ul) return false;
+    ppm = v;
+    return true;
 }
 
 // Parses argv like sharg does for these options: `-k 9`, `--index-seed 9`, `--index-seed=9`.
@@ -324,6 +350,26 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             (opt == "--depth" ? a.depth_path : a.coverage_path) = value();
             a.sort = true;
         }
+        else if (opt == "--pileup") {
+            a.pileup_path = value();
+            a.sort = true;
+        }
+        else if (opt == "--pileup-min-bq" || opt == "--pileup-min-mapq" || opt == "--pileup-min-alt") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            const bool alt = opt == "--pileup-min-alt";
+            if (s[0] < '0' || s[0] > '9' || v > 0xFFFFFFFFul || (alt && v < 1))
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in " + (alt ? "1" : "0") + "..2^32-1.");
+            (alt ? a.pileup_min_alt : opt == "--pileup-min-bq" ? a.pileup_min_bq : a.pileup_min_mapq) = v;
+            if (a.pileup_threshold_opt.empty()) a.pileup_threshold_opt = opt;
+        }
+        else if (opt == "--pileup-min-frac") {
+            const std::string s = value();
+            if (!parse_ppm(s, a.pileup_min_frac_ppm))
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s +
+                                   " must be a decimal between 0 and 1 with at most six fractional digits, such as 0.2.");
+            if (a.pileup_threshold_opt.empty()) a.pileup_threshold_opt = opt;
+        }
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));
@@ -347,10 +393,18 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         std::filesystem::path bam = a.output_sam_path;
         bam.replace_extension(".bam");
         throw parser_error(std::string("Validation failed for option ") +
-                           (!a.depth_path.empty() ? "--depth" : !a.coverage_path.empty() ? "--coverage" : a.markdup ? "--markdup" : "--sort") +
+                           (!a.depth_path.empty() ? "--depth" : !a.coverage_path.empty() ? "--coverage" : !a.pileup_path.empty() ? "--pileup" :
+                            a.markdup ? "--markdup" : "--sort") +
                            ": only BAM output is sorted and indexed; write -o " + bam.string() + " instead of -o " +
                            a.output_sam_path.string() + ".");
     }
+    if (!a.pileup_threshold_opt.empty() && a.pileup_path.empty())
+        throw parser_error("Validation failed for option " + a.pileup_threshold_opt + ": it is a threshold of --pileup FILE, which is not given.");
+    if (!a.pileup_path.empty() && a.output_sam_path.empty() && !a.only_indexer)
+        throw parser_error("Validation failed for option --pileup: the pileup is that of the records of a sorted BAM file; name one with -o x.bam.");
+    if (!a.pileup_path.empty() && (a.pileup_path == a.depth_path || a.pileup_path == a.coverage_path))
+        throw parser_error("Validation failed for option --pileup: " + a.pileup_path.string() + " is the file of " +
+                           (a.pileup_path == a.depth_path ? "--depth" : "--coverage") + " too.");
     if ((!a.depth_path.empty() || !a.coverage_path.empty()) && a.output_sam_path.empty() && !a.only_indexer)
         throw parser_error(std::string("Validation failed for option ") + (!a.depth_path.empty() ? "--depth" : "--coverage") +
                            ": depth and coverage are those of the records of a sorted BAM file; name one with -o x.bam.");
@@ -360,6 +414,9 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;
     if (a.affine || a.left_align) a.annotate = true;
+#ifdef BM_ALIGN
+    if (!a.pileup_path.empty()) a.annotate = true;   // the reference's own record layout is not forward-strand: a pileup over it would be wrong
+#endif
     return a;
 }
 

@@ -149,6 +149,10 @@ int main(int argc, char **argv) {
             if (args.sort) loc.set_sort(bm::bam_sort_run_bytes(args.sort_mem));   // --sort: coordinate order and x.bam.bai
             loc.set_markdup(args.markdup);                                        // --markdup: duplicates flagged before the sort
             loc.set_depth_files(args.depth_path, args.coverage_path);            // --depth / --coverage: of the records written
+            if (!args.pileup_path.empty())                                        // --pileup: their variant sites against the genome
+                loc.set_pileup(args.pileup_path, bm::pileup_thresholds{static_cast<uint32_t>(args.pileup_min_mapq), static_cast<uint32_t>(args.pileup_min_bq),
+                                                                       static_cast<uint32_t>(args.pileup_min_alt),
+                                                                       static_cast<uint32_t>(args.pileup_min_frac_ppm)});
         }
 #ifdef BM_ALIGN
         std::unique_ptr<bm::alignment_verifier> verifier = bm_make_verifier(args);

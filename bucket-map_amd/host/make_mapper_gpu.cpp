@@ -2,6 +2,7 @@
 // locator scan behind bm::offset_scanner.
 // (main.cpp:202-209: q_gram_mapper<BM_BUCKET_NUM> map(BM_BUCKET_LEN, read_len, k, q, S, fault, d, b))
 #include "../../include/bmc.h"
+#include "../../include/bmp.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -122,6 +123,7 @@ public:
         if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
     }
     ~gpu_block_compressor() override {
+        bmp_destroy(pile_);
         bmc_destroy(cover_);
         bmd_destroy(mark_);
         bms_destroy(sort_);
@@ -210,10 +212,35 @@ public:
         out.runs.assign(static_cast<size_t>(n_runs) * 4, 0);
         if (bmc_runs(cover_, 0, n_runs, out.runs.data()) != BMC_OK) throw std::runtime_error(std::string("bmc_runs: ") + bmc_last_error());
     }
+    // --pileup: the allele counts and variant sites of the written records on the same device (bmp_*: the rule of
+    // include/bmp.h, which is the host default's)
+    void pileup_begin(const uint32_t *ref_len, size_t n_ref, const uint8_t *const *ref_bases, const bm::pileup_thresholds &th) override {
+        if (n_ref > 0xFFFFFFFFull) throw std::runtime_error("bmp_begin: " + std::to_string(n_ref) + " references");
+        const uint32_t t[BMP_N_THRESHOLDS] = {th.min_mapq, th.min_bq, th.min_alt, th.min_frac_ppm};
+        if (bmp_begin(piler(), ref_len, static_cast<uint32_t>(n_ref), ref_bases, t) != BMP_OK)
+            throw std::runtime_error(std::string("bmp_begin: ") + bmp_last_error());
+        pile_n_ref_ = n_ref;
+    }
+    void pileup_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) override {
+        if (bmp_add(piler(), in, n, rec_offset, n_records, skip) != BMP_OK) throw std::runtime_error(std::string("bmp_add: ") + bmp_last_error());
+    }
+    void pileup_finish(bm::pileup_result &out) override {
+        uint64_t n_sites = 0;
+        out.stats.assign(pile_n_ref_ * bm::kPileupStats, 0);
+        if (bmp_finish(piler(), &n_sites, out.stats.data()) != BMP_OK) throw std::runtime_error(std::string("bmp_finish: ") + bmp_last_error());
+        out.sites.assign(static_cast<size_t>(n_sites) * bm::kPileupSiteWords, 0);
+        if (bmp_sites(pile_, 0, n_sites, out.sites.data()) != BMP_OK) throw std::runtime_error(std::string("bmp_sites: ") + bmp_last_error());
+    }
 
 private:
     int device_ = 0;
-    bmc_ctx *cover_ = nullptr;      // made by the first depth call: a run without --depth / --coverage pays nothing for it
+    bmp_ctx *pile_ = nullptr;       // made by the first pileup call: a run without --pileup pays nothing for it
+    size_t pile_n_ref_ = 0;
+    bmp_ctx *piler() {
+        if (!pile_ && bmp_create(device_, &pile_) != BMP_OK) throw std::runtime_error(std::string("bmp_create: ") + bmp_last_error());
+        return pile_;
+    }
+    bmc_ctx *cover_ = nullptr;     // made by the first depth call: a run without --depth / --coverage pays nothing for it
     size_t n_ref_ = 0;
     bmc_ctx *coverer() {
         if (!cover_ && bmc_create(device_, &cover_) != BMC_OK) throw std::runtime_error(std::string("bmc_create: ") + bmc_last_error());
