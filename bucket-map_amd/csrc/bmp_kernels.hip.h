@@ -22,6 +22,8 @@
 //               a border falls back to per-thread sums, as bmc's runs_count does.
 //   sites_emit  the same tiles with the scanned tile counts: the k-th site in place order writes its twelve words at 12 k;
 //               ranks, not atomics, place every value.
+// The walk itself -- which records count, the two classes, the word-wise reads -- is bmp_walk.hip.h, templates over the action
+// at a base, a deleted position and an insertion; bmg_kernels.hip.h instantiates them with another action.
 // No kernel waits for another workgroup.
 #pragma once
 
@@ -29,17 +31,13 @@
 #include <stdint.h>
 
 #include "bm_scan.hip.h"
+#include "bmp_walk.hip.h"
 
 namespace bmp {
 
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kShortOps = 8, kShortSeq = 512;       // add: what one lane walks alone
-constexpr uint32_t kWideSpan = 16;                       // add: positions of an op from which the wave shares them
 constexpr uint32_t kItems = bmscan::kItems, kTile = bmscan::kTile;
 constexpr uint32_t kCounters = 8, kDel = 5, kIns = 6, kLowq = 7;   // BMP_N_COUNTERS and the places in it
-constexpr uint32_t kStats = 6;                           // BMP_N_STATS; n_reads n_low_mapq n_left_out n_bases n_lowq n_sites
 constexpr uint32_t kSiteWords = 12;                      // BMP_SITE_WORDS
-constexpr uint32_t kSkipFlags = 0x4u | 0x100u | 0x200u | 0x400u, kQualNone = 0xFF;
 constexpr uint32_t kRefPad = 8;                          // bytes of room behind ref: sites_* read whole 8-byte words
 static_assert(kThreads == (uint32_t)bmscan::kThreads && kItems == 8, "the site passes use the scan's tiles and 8-byte reference words");
 
@@ -47,199 +45,31 @@ struct thresholds {
     uint32_t min_mapq, min_bq, min_alt, min_frac_ppm;
 };
 
-__device__ __forceinline__ uint32_t load32(const uint8_t *p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-__device__ __forceinline__ uint32_t load16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-    for (uint32_t d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ bool is_block(uint32_t op) { return op == 0 || op == 7 || op == 8; }
-__device__ __forceinline__ bool takes_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-__device__ __forceinline__ bool takes_query(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
-
 // the counter of a base with the quality q and the 4-bit code
 __device__ __forceinline__ uint32_t counter_of(uint32_t q, uint32_t code, uint32_t min_bq) {
     if (q != kQualNone && q < min_bq) return kLowq;
     return code == 1 ? 0u : code == 2 ? 1u : code == 4 ? 2u : code == 8 ? 3u : 4u;
 }
 
-// the no-return add: the result is not used, so the compiler issues global_atomic_add_u32 without a returned value
-__device__ __forceinline__ void count(uint32_t *__restrict__ c, uint64_t position, uint32_t which) {
-    atomicAdd(&c[position * kCounters + which], 1u);
-}
+// the action of bmp_walk.hip.h's walkers: every count is a no-return add -- the result is not used, so the compiler issues
+// global_atomic_add_u32 without a returned value
+struct count_action {
+    static constexpr bool kIndels = true, kStats = true;
+    uint32_t *__restrict__ c;
+    uint32_t min_bq;
+    __device__ __forceinline__ count_action on(uint64_t first) const { return count_action{c + first * kCounters, min_bq}; }
+    __device__ __forceinline__ void count(uint64_t position, uint32_t which) const { atomicAdd(&c[position * kCounters + which], 1u); }
+    __device__ __forceinline__ void base(uint64_t position, uint32_t q, uint32_t code) const { count(position, counter_of(q, code, min_bq)); }
+    __device__ __forceinline__ void del(uint64_t position) const { count(position, kDel); }
+    __device__ __forceinline__ void ins(uint64_t position) const { count(position, kIns); }
+};
 
-// bases [q0, q0 + n) of the query at positions [s, s + n), one base at a time (byte loads): a lane's own short stretch
-__device__ __forceinline__ void bases_alone(const uint8_t *seq, const uint8_t *qual, uint64_t q0, uint64_t n, uint64_t s, uint32_t *__restrict__ c,
-                                            uint32_t min_bq) {
-    for (uint64_t j = 0; j < n; j++) {
-        const uint64_t at = q0 + j;
-        const uint32_t code = (seq[at >> 1] >> ((at & 1u) ? 0 : 4)) & 15u;
-        count(c, s + j, counter_of(qual[at], code, min_bq));
-    }
-}
-
-// the same by all lanes (every argument is the same in all of them).  A lane takes the aligned word of four quality bytes
-// at w; a word may reach up to 3 bytes before qual + q0 (the same record) and behind the last byte (the stream's buffer has
-// 16 bytes of room behind its end); those bytes are masked out.  The bases' nibbles lie in at most 3 consecutive bytes of
-// seq, read as the two aligned words from the first one's on (the second at most 4 bytes behind a byte of seq: inside the
-// qualities or the room).
-__device__ __forceinline__ void bases_shared(const uint8_t *seq, const uint8_t *qual, uint64_t q0, uint64_t n, uint64_t s, uint32_t *__restrict__ c,
-                                             uint32_t lane, uint32_t min_bq) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(qual + q0), b = a + n;
-    for (uintptr_t w = (a & ~uintptr_t{3}) + 4u * lane; w < b; w += 4u * 64u) {
-        const uint32_t x = *reinterpret_cast<const uint32_t *>(w);
-        const uintptr_t first = w < a ? a : w;           // the first byte of the word that counts
-        const uint64_t at0 = q0 + (first - a);           // its query index
-        const uintptr_t sb = reinterpret_cast<uintptr_t>(seq + (at0 >> 1));
-        const uint32_t *sw = reinterpret_cast<const uint32_t *>(sb & ~uintptr_t{3});
-        const uint64_t packed = ((uint64_t)sw[0] | (uint64_t)sw[1] << 32) >> (8u * (uint32_t)(sb & 3u));   // byte i: seq[(at0 >> 1) + i]
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-            const uintptr_t addr = w + j;
-            if (addr < first || addr >= b) continue;
-            const uint64_t at = q0 + (addr - a);
-            const uint32_t byte = (uint32_t)(packed >> (8u * (uint32_t)((at >> 1) - (at0 >> 1)))) & 255u;
-            const uint32_t code = (byte >> ((at & 1u) ? 0 : 4)) & 15u;
-            count(c, s + (addr - a), counter_of((x >> (8 * j)) & 255u, code, min_bq));
-        }
-    }
-}
-
-// one counted record by its lane alone: at most kShortOps ops, kShortSeq bases and kShortSeq deleted positions
-__device__ __forceinline__ void walk_alone(const uint8_t *cigar, uint32_t n_cigar, const uint8_t *seq, const uint8_t *qual, uint32_t pos, uint32_t rlen,
-                                           uint32_t *__restrict__ c, uint32_t min_bq) {
-    uint64_t rc = pos, qc = 0;
-    bool anchored = false;                               // an M, =, X or D of a length > 0 came before
-    for (uint32_t k = 0; k < n_cigar; k++) {
-        const uint32_t w = load32(cigar + 4ull * k), op = w & 15u, len = w >> 4;
-        if ((is_block(op) || op == 2) && len && rc < rlen) {
-            const uint64_t e = rc + len < rlen ? rc + len : rlen;
-            if (op == 2)
-                for (uint64_t p = rc; p < e; p++) count(c, p, kDel);
-            else
-                bases_alone(seq, qual, qc, e - rc, rc, c, min_bq);   // qc + (e - rc) <= l_seq: the host has checked the query length
-        }
-        if (op == 1 && len && anchored && rc >= 1 && rc - 1 < rlen) count(c, rc - 1, kIns);
-        if ((is_block(op) || op == 2) && len) anchored = true;
-        if (takes_ref(op)) rc += len;
-        if (takes_query(op)) qc += len;
-    }
-}
-
-// one counted record by the whole wave (every argument is the same in all lanes)
-__device__ __forceinline__ void walk_wave(const uint8_t *cigar, uint32_t n_cigar, const uint8_t *seq, const uint8_t *qual, uint32_t pos, uint32_t rlen,
-                                          uint32_t *__restrict__ c, uint32_t lane, uint32_t min_bq) {
-    uint64_t rc = pos, qc = 0;
-    bool anchored = false;
-    for (uint32_t c0 = 0; c0 < n_cigar; c0 += 64) {      // the same trips in every lane: shuffles and ballots below
-        const uint32_t k = c0 + lane;
-        uint32_t op = 15, len = 0;
-        if (k < n_cigar) {
-            const uint32_t w = load32(cigar + 4ull * k);
-            op = w & 15u, len = w >> 4;
-        }
-        const uint64_t r_adv = takes_ref(op) ? len : 0u, q_adv = takes_query(op) ? len : 0u;
-        const uint64_t r_incl = bmscan::wave_inclusive<uint64_t>(r_adv, lane), q_incl = bmscan::wave_inclusive<uint64_t>(q_adv, lane);
-        const uint64_t s = rc + r_incl - r_adv, q0 = qc + q_incl - q_adv;
-        const uint64_t anchors = __ballot((is_block(op) || op == 2) && len);
-        const bool before = anchored || (anchors & ((uint64_t{1} << lane) - 1)) != 0;
-        if (op == 1 && len && before && s >= 1 && s - 1 < rlen) count(c, s - 1, kIns);
-        const bool del = op == 2;
-        const bool has = (is_block(op) || del) && len && s < rlen;
-        const uint64_t span = has ? (s + len < rlen ? s + len : rlen) - s : 0u;   // q0 + span <= l_seq for a block (host check)
-        if (span && span < kWideSpan) {
-            if (del)
-                for (uint64_t p = 0; p < span; p++) count(c, s + p, kDel);
-            else
-                bases_alone(seq, qual, q0, span, s, c, min_bq);
-        }
-        uint64_t wide = __ballot(span >= kWideSpan);
-        while (wide) {
-            const int src = __ffsll((unsigned long long)wide) - 1;
-            wide &= wide - 1;
-            const uint64_t at = __shfl(q0, src, 64), n = __shfl(span, src, 64), from = __shfl(s, src, 64);
-            if (__shfl((int)del, src, 64))
-                for (uint64_t p = lane; p < n; p += 64) count(c, from + p, kDel);
-            else
-                bases_shared(seq, qual, at, n, from, c, lane, min_bq);
-        }
-        anchored = anchored || anchors != 0;
-        rc += __shfl(r_incl, 63, 64);
-        qc += __shfl(q_incl, 63, 64);
-    }
-}
-
-// cnt += the bases, deletions and insertions of the counted records, stats += n_reads, n_low_mapq, n_left_out.  `in` has 16
-// bytes of room behind n_bytes; the fields of a record fit its extent, ops are 0 .. 8, the query length is l_seq (host checks).
+// cnt += the bases, deletions and insertions of the counted records, stats += n_reads, n_low_mapq, n_left_out
 __global__ __launch_bounds__(kThreads) void add_kernel(const uint8_t *__restrict__ in, const uint64_t *__restrict__ rec_offset, uint32_t n,
                                                        const uint8_t *__restrict__ skip, const uint32_t *__restrict__ ref_len,
                                                        const uint64_t *__restrict__ ref_base, uint32_t n_ref, thresholds th,
                                                        uint32_t *__restrict__ cnt, unsigned long long *__restrict__ stats) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x, wave_first = i - lane;
-    bool placed = false, counted = false, left_out = false, wide = false;
-    uint32_t ref = 0;
-    if (i < n) {
-        const uint8_t *r = in + rec_offset[i];
-        const int32_t ref_i = (int32_t)load32(r + 4), pos_i = (int32_t)load32(r + 8);
-        const uint32_t l_name = r[12], n_cigar = load16(r + 16), flag = load16(r + 18), l_seq = load32(r + 20);
-        placed = !(flag & kSkipFlags) && !(skip && skip[i]) && ref_i >= 0 && (uint32_t)ref_i < n_ref && pos_i >= 0 && n_cigar > 0;
-        uint32_t rlen = 0;
-        if (placed) {
-            ref = (uint32_t)ref_i;
-            rlen = ref_len[ref];
-            placed = (uint32_t)pos_i < rlen;
-        }
-        if (placed) {
-            const uint8_t *cigar = r + 36 + l_name;
-            left_out = l_seq == 0 || (n_cigar == 2 && load32(cigar) == (l_seq << 4 | 4u) && (load32(cigar + 4) & 15u) == 3u);   // the long-CIGAR placeholder
-            counted = !left_out && r[13] >= th.min_mapq;
-            if (counted) {
-                wide = n_cigar > kShortOps || l_seq > kShortSeq;
-                uint64_t deleted = 0;
-                for (uint32_t k = 0; !wide && k < n_cigar; k++) {
-                    const uint32_t w = load32(cigar + 4ull * k);
-                    if ((w & 15u) == 2) deleted += w >> 4;
-                }
-                wide = wide || deleted > kShortSeq;
-                if (!wide) {
-                    const uint8_t *seq = cigar + 4ull * n_cigar;
-                    walk_alone(cigar, n_cigar, seq, seq + ((uint64_t)l_seq + 1) / 2, (uint32_t)pos_i, rlen, cnt + ref_base[ref] * kCounters, th.min_bq);
-                }
-            }
-        }
-    }
-    uint64_t todo = __ballot(wide);
-    while (todo) {                                       // the wave's other counted records, by all lanes
-        const int src = __ffsll((unsigned long long)todo) - 1;
-        todo &= todo - 1;
-        const uint8_t *r = in + rec_offset[wave_first + src];
-        const uint32_t w_ref = load32(r + 4), w_pos = load32(r + 8), l_name = r[12], n_cigar = load16(r + 16), l_seq = load32(r + 20);
-        const uint8_t *cigar = r + 36 + l_name, *seq = cigar + 4ull * n_cigar;
-        walk_wave(cigar, n_cigar, seq, seq + ((uint64_t)l_seq + 1) / 2, w_pos, ref_len[w_ref], cnt + ref_base[w_ref] * kCounters, lane, th.min_bq);
-    }
-    uint64_t left = __ballot(placed);
-    while (left) {                                       // per reference among the wave's lanes: one atomic per value
-        const int src = __ffsll((unsigned long long)left) - 1;
-        const uint32_t r0 = __shfl(ref, src, 64);
-        const bool mine = placed && ref == r0;
-        left &= ~__ballot(mine);
-        const uint32_t reads = wave_sum32(mine && counted ? 1u : 0u), low = wave_sum32(mine && !counted && !left_out ? 1u : 0u);
-        const uint32_t out = wave_sum32(mine && left_out ? 1u : 0u);
-        if ((int)lane == src) {
-            unsigned long long *st = stats + (uint64_t)r0 * kStats;
-            if (reads) atomicAdd(&st[0], (unsigned long long)reads);
-            if (low) atomicAdd(&st[1], (unsigned long long)low);
-            if (out) atomicAdd(&st[2], (unsigned long long)out);
-        }
-    }
+    add_records(in, rec_offset, n, skip, ref_len, ref_base, n_ref, th.min_mapq, count_action{cnt, th.min_bq}, stats);
 }
 
 // the reference that holds slot: ref_base[r] <= slot < ref_base[r + 1] (slot < ref_base[n_ref])

@@ -39,6 +39,9 @@
 //
 // PILEUP MODE (--pileup; include/bmp.h states the rule).  The same pieces of the final stream go to pileup_add, beside or
 // without depth mode: pileup_begin with the references' bases and the thresholds before them, pileup_finish after them.
+//
+// GENOTYPE MODE (--vcf; include/bmg.h states the rule), on top of pileup mode: every piece that goes to pileup_add goes to
+// genotype_add too, and after pileup_finish the sites it lists go to genotype_call.
 #pragma once
 
 #include "bgzf.h"
@@ -188,6 +191,9 @@ class bam_sorter {
     std::vector<const uint8_t *> pileup_ref_bases_;
     pileup_thresholds pileup_thresholds_;
     pileup_result pileup_result_;
+    bool genotype_ = false;                          // genotype mode (with pileup mode)
+    genotype_params genotype_params_;
+    genotype_result genotype_result_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -272,6 +278,14 @@ public:
         pileup_thresholds_ = th;
     }
     const pileup_result &pileup() const { return pileup_result_; }
+    // genotype mode: after set_pileup (whose references and sites it uses) and before the first add(); after finish(), one call
+    // per site of the pileup
+    void set_genotype(const genotype_params &pr) {
+        if (!pileup_) throw std::runtime_error("--vcf: genotypes are called at the sites of the pileup");
+        genotype_ = true;
+        genotype_params_ = pr;
+    }
+    const genotype_result &genotype() const { return genotype_result_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -309,6 +323,7 @@ public:
         };
         if (depth_) z_->depth_begin(depth_ref_len_.data(), depth_ref_len_.size());
         if (pileup_) z_->pileup_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), pileup_ref_bases_.data(), pileup_thresholds_);
+        if (genotype_) z_->genotype_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), genotype_params_);
         if (tmp_.empty()) {
             n_runs_ = off_.size() > 1 ? 1 : 0;
             std::vector<uint32_t> perm;
@@ -326,6 +341,7 @@ public:
             emit();
             if (depth_) z_->depth_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
             if (pileup_) z_->pileup_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
+            if (genotype_) z_->genotype_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
         } else {
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
@@ -351,6 +367,7 @@ public:
             auto count = [&]() {
                 if (depth_ && counted_off.size() > 1) z_->depth_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 if (pileup_ && counted_off.size() > 1) z_->pileup_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
+                if (genotype_ && counted_off.size() > 1) z_->genotype_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 counted.clear();
                 counted_off.assign(1, 0);
             };
@@ -390,6 +407,11 @@ public:
         remove_tmp();
         if (depth_) z_->depth_finish(depth_result_);
         if (pileup_) z_->pileup_finish(pileup_result_);
+        if (genotype_) {
+            z_->genotype_call(pileup_result_.sites.data(), pileup_result_.n_sites(), genotype_result_.calls);
+            genotype_result_.n_snv_sites = 0;
+            for (size_t k = 0; k < pileup_result_.n_sites(); k++) genotype_result_.n_snv_sites += pileup_result_.sites[kPileupSiteWords * k + 11] & 1u;
+        }
     }
 
 private:

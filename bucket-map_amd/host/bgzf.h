@@ -7,6 +7,7 @@
 
 #include "depth.h"
 #include "pileup.h"
+#include "genotype.h"
 #include "markdup.h"
 
 #include <algorithm>
@@ -367,9 +368,20 @@ struct block_compressor {
     }
     virtual void pileup_finish(pileup_result &out) { pileup_.finish(out); }
 
+    // --vcf (include/bmg.h states the rule): the references and the five parameters, then whole records as for pileup_add,
+    // then the calls of sites as pileup_finish lists them (kGenotypeSiteWords each; kGenotypeCallWords per call).  The defaults
+    // are the host rule of genotype.h; the product plugs in bmg_begin, bmg_add and bmg_call.
+    virtual void genotype_begin(const uint32_t *ref_len, size_t n_ref, const genotype_params &pr) { genotype_.begin(ref_len, n_ref, pr); }
+    virtual void genotype_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) {
+        (void)n;
+        genotype_.add(in, rec_offset, n_records, skip);
+    }
+    virtual void genotype_call(const uint32_t *sites, size_t n_sites, std::vector<uint32_t> &out) { genotype_.call(sites, n_sites, out); }
+
 private:
     depth_counter depth_;
     pileup_counter pileup_;
+    genotype_counter genotype_;
 };
 
 }  // namespace bm

@@ -458,6 +458,14 @@ public:
 //
 // Sorted (-o x.bam --sort, host/bam_sort.h): the encoded records are not cut into blocks but kept by a bam_sorter, the
 // header says SO:coordinate, and close() writes the records in coordinate order, the EOF block and x.bam.bai.
+// --vcf: the file, the rule's parameters, the QUAL (phred) below which a call is LowQual and the sample's name
+struct vcf_options {
+    std::filesystem::path file;
+    genotype_params params{};
+    uint32_t min_qual = 20;
+    std::string sample = "sample";
+};
+
 class sam_text {
     std::ofstream out_;
     std::string buf_, writing_;     // the buffer being filled / the one a writer thread is putting into the file
@@ -478,6 +486,8 @@ class sam_text {
     std::filesystem::path pileup_file_;    // sorted BAM: --pileup, may be empty
     pileup_thresholds pileup_thresholds_;
     const std::vector<std::string> *pileup_seqs_ = nullptr;   // ... the bases of the header's references, each of its length
+    vcf_options vcf_;                      // sorted BAM: --vcf, its file may be empty; it counts the pileup whether that has a file or not
+    bool pileup_on() const { return !pileup_file_.empty() || !vcf_.file.empty(); }
 
     // A file of --depth / --coverage / --pileup: written beside its place and moved there when it is complete, so that a failure
     // leaves nothing half-written (and nothing at all under the final name).
@@ -509,6 +519,15 @@ class sam_text {
         std::cerr << "[INFO]\t\tCoverage: " << cov << " of " << bases << " bases covered by " << reads << " records (" << n_long
                   << " long-CIGAR records left out)\n";
     }
+    void write_vcf() {
+        const genotype_result &res = sorter_->genotype();
+        std::vector<uint32_t> lens;
+        for (size_t r = 0; r < ref_ids_.size(); r++) lens.push_back((*pileup_seqs_)[r].size());   // set_pileup has checked them
+        write_whole(vcf_.file, [&](std::ostream &f) { write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual); });
+        const genotype_summary s = summarize_genotypes(res, vcf_.min_qual);
+        std::cerr << "[INFO]\t\tGenotypes: " << s.variants << " variants (" << s.het << " het, " << s.hom << " hom, " << s.low_qual
+                  << " below QUAL) at " << res.n_snv_sites << " SNV sites\n";
+    }
     void write_pileup() {
         const pileup_result &res = sorter_->pileup();
         write_whole(pileup_file_, [&](std::ostream &f) { write_pileup_file(f, res, ref_ids_); });
@@ -534,6 +553,7 @@ class sam_text {
             bases[r] = reinterpret_cast<const uint8_t *>(seq.data());
         }
         sorter_->set_pileup(ref_lengths, bases, pileup_thresholds_);
+        if (!vcf_.file.empty()) sorter_->set_genotype(vcf_.params);
     }
 
     // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer
@@ -605,17 +625,20 @@ public:
     // reference of the records written (--depth, --coverage, include/bmc.h)
     // pileup_file (sorted BAM only, may be empty): the table of variant sites of the records written (--pileup, include/bmp.h),
     // under these thresholds and against ref_bases, the bases of the header's references (each as long as the header says)
+    // vcf (sorted BAM only, its file may be empty): the genotypes at the pileup's SNV sites as a VCF file (--vcf, include/bmg.h);
+    // it counts the pileup under pileup_th with or without a pileup_file
     explicit sam_text(std::filesystem::path const &file, block_compressor *bam = nullptr, size_t sort_run_bytes = 0, bool markdup = false,
                       std::filesystem::path const &depth_file = {}, std::filesystem::path const &coverage_file = {},
                       std::filesystem::path const &pileup_file = {}, pileup_thresholds const &pileup_th = {},
-                      const std::vector<std::string> *ref_bases = nullptr)
-        : out_(file, std::ios::binary), bam_(bam), pileup_thresholds_(pileup_th), pileup_seqs_(ref_bases) {
+                      const std::vector<std::string> *ref_bases = nullptr, vcf_options const &vcf = {})
+        : out_(file, std::ios::binary), bam_(bam), pileup_thresholds_(pileup_th), pileup_seqs_(ref_bases), vcf_(vcf) {
         if (!out_) throw std::runtime_error("cannot write " + file.string());
         if (bam_ && sort_run_bytes) sorter_ = std::make_unique<bam_sorter>(bam_, file, sort_run_bytes, markdup);
         markdup_ = sorter_ && markdup;
         depth_file_ = sorter_ ? depth_file : std::filesystem::path();
         coverage_file_ = sorter_ ? coverage_file : std::filesystem::path();
         pileup_file_ = sorter_ ? pileup_file : std::filesystem::path();
+        if (!sorter_) vcf_.file.clear();
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
@@ -653,6 +676,7 @@ public:
             }
             if (!depth_file_.empty() || !coverage_file_.empty()) write_depth_files();
             if (!pileup_file_.empty()) write_pileup();
+            if (!vcf_.file.empty()) write_vcf();
         } else if (bam_ && !closed_) {
             encode_buffer(true);
             buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -690,7 +714,7 @@ public:
                 ref_ids_ = ref_ids;
                 ref_len_.assign(ref_lengths.begin(), ref_lengths.end());   // set_depth has refused what does not fit
             }
-            if (!pileup_file_.empty()) {
+            if (pileup_on()) {
                 set_pileup(ref_ids, ref_lengths);
                 ref_ids_ = ref_ids;
             }
@@ -748,6 +772,7 @@ private:
     std::filesystem::path _depth_file, _coverage_file;   // --depth / --coverage: the written records' depth and coverage (include/bmc.h)
     std::filesystem::path _pileup_file;          // --pileup: the variant sites of the written records (include/bmp.h)
     pileup_thresholds _pileup_thresholds{};
+    vcf_options _vcf{};                          // --vcf: the genotypes at the pileup's SNV sites (include/bmg.h)
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
     bool _clip = false;                          // --clip: those records with soft-clipped ends and AS, under these scores
@@ -967,6 +992,11 @@ public:
     }
     void set_pileup(std::filesystem::path const &file, pileup_thresholds const &th) {   // ... and its variant sites listed
         _pileup_file = file;
+        _pileup_thresholds = th;
+    }
+    // --vcf: genotypes at the SNV sites of the pileup under th, which is counted whether set_pileup names a file or not
+    void set_vcf(vcf_options const &vcf, pileup_thresholds const &th) {
+        _vcf = vcf;
         _pileup_thresholds = th;
     }
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
@@ -1229,7 +1259,7 @@ public:
         // [k * bucket_length, (k + 1) * bucket_length): for one FASTA record that is the record itself, cut or filled up to whole
         // buckets; what no bucket's sequence fills has no reference allele (N).
         std::vector<std::string> pileup_bases;
-        if (!_pileup_file.empty() && genome_) {
+        if ((!_pileup_file.empty() || !_vcf.file.empty()) && genome_) {
             for (size_t b = 0, r = 0; r < h.ref_ids.size(); r++) {
                 pileup_bases.emplace_back(h.ref_lengths[r], 'N');
                 for (size_t at = 0; at < h.ref_lengths[r]; at += bucket_length, b++) {
@@ -1239,7 +1269,7 @@ public:
                 }
             }
         }
-        sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup, _depth_file, _coverage_file, _pileup_file, _pileup_thresholds, &pileup_bases);
+        sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup, _depth_file, _coverage_file, _pileup_file, _pileup_thresholds, &pileup_bases, _vcf);
         sam.header(h.ref_ids, h.ref_lengths);
         unsigned int read_id = 0, mapped_locations = 0;
         auto t0 = std::chrono::steady_clock::now();

@@ -80,7 +80,13 @@ struct cmd_arguments {
                                   // with the reference (include/bmp.h states the rule)
     unsigned long pileup_min_bq = 13, pileup_min_mapq = 0, pileup_min_alt = 2;   // --pileup-min-bq / -min-mapq / -min-alt N
     unsigned long pileup_min_frac_ppm = 200000;   // --pileup-min-frac F, a decimal in [0, 1] with at most six fractional digits
-    std::string pileup_threshold_opt;   // the first of those four given: refused without --pileup
+    std::string pileup_threshold_opt;   // the first of those four given: refused without --pileup and without --vcf
+    std::filesystem::path vcf_path{};   // --vcf FILE (-o x.bam only, implies --sort, the pileup counting and, in bucketmap_align,
+                                  // --annotate): the diploid genotypes at the pileup's SNV sites as VCF 4.2 (include/bmg.h states
+                                  // the rule); the pileup's own file is written only with --pileup
+    unsigned long vcf_prior = 30, vcf_min_qual = 20;   // --vcf-prior N (phred, 0..255) / --vcf-min-qual N (phred)
+    std::string vcf_sample = "sample";   // --vcf-sample NAME: the sample column's name, no tab or newline
+    std::string vcf_opt;          // the first of those three given: refused without --vcf
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -370,6 +376,25 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
                                    " must be a decimal between 0 and 1 with at most six fractional digits, such as 0.2.");
             if (a.pileup_threshold_opt.empty()) a.pileup_threshold_opt = opt;
         }
+        else if (opt == "--vcf") {
+            a.vcf_path = value();
+            a.sort = true;
+        }
+        else if (opt == "--vcf-prior" || opt == "--vcf-min-qual") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            const bool prior = opt == "--vcf-prior";
+            if (s[0] < '0' || s[0] > '9' || v > (prior ? 255ul : 0xFFFFFFFFul / 100))
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in 0.." + (prior ? "255" : "42949672") + ".");
+            (prior ? a.vcf_prior : a.vcf_min_qual) = v;
+            if (a.vcf_opt.empty()) a.vcf_opt = opt;
+        }
+        else if (opt == "--vcf-sample") {
+            a.vcf_sample = value();
+            if (a.vcf_sample.empty() || a.vcf_sample.find_first_of("\t\n\r") != std::string::npos)
+                throw parser_error("Value parse failed for " + opt + ": a sample name is not empty and holds no tab or newline.");
+            if (a.vcf_opt.empty()) a.vcf_opt = opt;
+        }
         else if (opt == "--version-check") (void)value();   // Sharg built-in used by the benchmark scripts
         else if (opt == "--genome") a.genome_path = value();
         else if (opt == "--bucket-len") a.bucket_len = static_cast<unsigned>(as_uint(value()));
@@ -394,17 +419,24 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         bam.replace_extension(".bam");
         throw parser_error(std::string("Validation failed for option ") +
                            (!a.depth_path.empty() ? "--depth" : !a.coverage_path.empty() ? "--coverage" : !a.pileup_path.empty() ? "--pileup" :
-                            a.markdup ? "--markdup" : "--sort") +
+                            !a.vcf_path.empty() ? "--vcf" : a.markdup ? "--markdup" : "--sort") +
                            ": only BAM output is sorted and indexed; write -o " + bam.string() + " instead of -o " +
                            a.output_sam_path.string() + ".");
     }
-    if (!a.pileup_threshold_opt.empty() && a.pileup_path.empty())
+    if (!a.pileup_threshold_opt.empty() && a.pileup_path.empty() && a.vcf_path.empty())
         throw parser_error("Validation failed for option " + a.pileup_threshold_opt + ": it is a threshold of --pileup FILE, which is not given.");
     if (!a.pileup_path.empty() && a.output_sam_path.empty() && !a.only_indexer)
         throw parser_error("Validation failed for option --pileup: the pileup is that of the records of a sorted BAM file; name one with -o x.bam.");
     if (!a.pileup_path.empty() && (a.pileup_path == a.depth_path || a.pileup_path == a.coverage_path))
         throw parser_error("Validation failed for option --pileup: " + a.pileup_path.string() + " is the file of " +
                            (a.pileup_path == a.depth_path ? "--depth" : "--coverage") + " too.");
+    if (!a.vcf_opt.empty() && a.vcf_path.empty())
+        throw parser_error("Validation failed for option " + a.vcf_opt + ": it is an option of --vcf FILE, which is not given.");
+    if (!a.vcf_path.empty() && a.output_sam_path.empty() && !a.only_indexer)
+        throw parser_error("Validation failed for option --vcf: the genotypes are those of the records of a sorted BAM file; name one with -o x.bam.");
+    if (!a.vcf_path.empty() && (a.vcf_path == a.pileup_path || a.vcf_path == a.depth_path || a.vcf_path == a.coverage_path))
+        throw parser_error("Validation failed for option --vcf: " + a.vcf_path.string() + " is the file of " +
+                           (a.vcf_path == a.pileup_path ? "--pileup" : a.vcf_path == a.depth_path ? "--depth" : "--coverage") + " too.");
     if ((!a.depth_path.empty() || !a.coverage_path.empty()) && a.output_sam_path.empty() && !a.only_indexer)
         throw parser_error(std::string("Validation failed for option ") + (!a.depth_path.empty() ? "--depth" : "--coverage") +
                            ": depth and coverage are those of the records of a sorted BAM file; name one with -o x.bam.");
@@ -415,7 +447,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (a.paired) a.best = a.annotate = true;
     if (a.affine || a.left_align) a.annotate = true;
 #ifdef BM_ALIGN
-    if (!a.pileup_path.empty()) a.annotate = true;   // the reference's own record layout is not forward-strand: a pileup over it would be wrong
+    if (!a.pileup_path.empty() || !a.vcf_path.empty()) a.annotate = true;   // the reference's own record layout is not forward-strand: a pileup over it would be wrong
 #endif
     return a;
 }

@@ -149,10 +149,18 @@ int main(int argc, char **argv) {
             if (args.sort) loc.set_sort(bm::bam_sort_run_bytes(args.sort_mem));   // --sort: coordinate order and x.bam.bai
             loc.set_markdup(args.markdup);                                        // --markdup: duplicates flagged before the sort
             loc.set_depth_files(args.depth_path, args.coverage_path);            // --depth / --coverage: of the records written
-            if (!args.pileup_path.empty())                                        // --pileup: their variant sites against the genome
-                loc.set_pileup(args.pileup_path, bm::pileup_thresholds{static_cast<uint32_t>(args.pileup_min_mapq), static_cast<uint32_t>(args.pileup_min_bq),
-                                                                       static_cast<uint32_t>(args.pileup_min_alt),
-                                                                       static_cast<uint32_t>(args.pileup_min_frac_ppm)});
+            const bm::pileup_thresholds pileup_th{static_cast<uint32_t>(args.pileup_min_mapq), static_cast<uint32_t>(args.pileup_min_bq),
+                                                  static_cast<uint32_t>(args.pileup_min_alt), static_cast<uint32_t>(args.pileup_min_frac_ppm)};
+            if (!args.pileup_path.empty()) loc.set_pileup(args.pileup_path, pileup_th);   // --pileup: their variant sites against the genome
+            if (!args.vcf_path.empty()) {                                         // --vcf: the genotypes at those sites; MAPQ and base quality as the pileup's
+                bm::vcf_options vcf;
+                vcf.file = args.vcf_path;
+                vcf.params.min_mapq = pileup_th.min_mapq, vcf.params.min_bq = pileup_th.min_bq;
+                vcf.params.prior = static_cast<uint32_t>(100 * args.vcf_prior);
+                vcf.min_qual = static_cast<uint32_t>(args.vcf_min_qual);
+                vcf.sample = args.vcf_sample;
+                loc.set_vcf(vcf, pileup_th);
+            }
         }
 #ifdef BM_ALIGN
         std::unique_ptr<bm::alignment_verifier> verifier = bm_make_verifier(args);

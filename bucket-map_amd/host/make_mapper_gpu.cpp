@@ -3,6 +3,7 @@
 // (main.cpp:202-209: q_gram_mapper<BM_BUCKET_NUM> map(BM_BUCKET_LEN, read_len, k, q, S, fault, d, b))
 #include "../../include/bmc.h"
 #include "../../include/bmp.h"
+#include "../../include/bmg.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -123,6 +124,7 @@ public:
         if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
     }
     ~gpu_block_compressor() override {
+        bmg_destroy(geno_);
         bmp_destroy(pile_);
         bmc_destroy(cover_);
         bmd_destroy(mark_);
@@ -231,9 +233,28 @@ public:
         out.sites.assign(static_cast<size_t>(n_sites) * bm::kPileupSiteWords, 0);
         if (bmp_sites(pile_, 0, n_sites, out.sites.data()) != BMP_OK) throw std::runtime_error(std::string("bmp_sites: ") + bmp_last_error());
     }
+    // --vcf: the genotypes at the pileup's sites on the same device (bmg_*: the rule of include/bmg.h, which is the host
+    // default's)
+    void genotype_begin(const uint32_t *ref_len, size_t n_ref, const bm::genotype_params &pr) override {
+        if (n_ref > 0xFFFFFFFFull) throw std::runtime_error("bmg_begin: " + std::to_string(n_ref) + " references");
+        const uint32_t p[BMG_N_PARAMS] = {pr.min_mapq, pr.min_bq, pr.q_absent, pr.q_cap, pr.prior};
+        if (bmg_begin(genotyper(), ref_len, static_cast<uint32_t>(n_ref), p) != BMG_OK) throw std::runtime_error(std::string("bmg_begin: ") + bmg_last_error());
+    }
+    void genotype_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) override {
+        if (bmg_add(genotyper(), in, n, rec_offset, n_records, skip) != BMG_OK) throw std::runtime_error(std::string("bmg_add: ") + bmg_last_error());
+    }
+    void genotype_call(const uint32_t *sites, size_t n_sites, std::vector<uint32_t> &out) override {
+        out.assign(n_sites * bm::kGenotypeCallWords, 0);
+        if (bmg_call(genotyper(), sites, n_sites, out.data()) != BMG_OK) throw std::runtime_error(std::string("bmg_call: ") + bmg_last_error());
+    }
 
 private:
     int device_ = 0;
+    bmg_ctx *geno_ = nullptr;       // made by the first genotype call: a run without --vcf pays nothing for it
+    bmg_ctx *genotyper() {
+        if (!geno_ && bmg_create(device_, &geno_) != BMG_OK) throw std::runtime_error(std::string("bmg_create: ") + bmg_last_error());
+        return geno_;
+    }
     bmp_ctx *pile_ = nullptr;       // made by the first pileup call: a run without --pileup pays nothing for it
     size_t pile_n_ref_ = 0;
     bmp_ctx *piler() {
