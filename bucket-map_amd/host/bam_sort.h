@@ -42,6 +42,8 @@
 //
 // GENOTYPE MODE (--vcf; include/bmg.h states the rule), on top of pileup mode: every piece that goes to pileup_add goes to
 // genotype_add too, and after pileup_finish the sites it lists go to genotype_call.
+// INDEL MODE (--vcf-indels; include/bmn.h states the rule), on top of genotype mode: every piece that goes to genotype_add
+// goes to indel_add too, indel_begin before them and indel_finish after them.
 #pragma once
 
 #include "bgzf.h"
@@ -194,6 +196,9 @@ class bam_sorter {
     bool genotype_ = false;                          // genotype mode (with pileup mode)
     genotype_params genotype_params_;
     genotype_result genotype_result_;
+    bool indel_ = false;                             // indel mode (with genotype mode)
+    indel_params indel_params_;
+    indel_result indel_result_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -286,6 +291,13 @@ public:
         genotype_params_ = pr;
     }
     const genotype_result &genotype() const { return genotype_result_; }
+    // indel mode: after set_genotype and before the first add(); after finish(), the alleles and calls of the indels
+    void set_indel(const indel_params &pr) {
+        if (!genotype_) throw std::runtime_error("--vcf-indels: the indel calls go into the file of --vcf");
+        indel_ = true;
+        indel_params_ = pr;
+    }
+    const indel_result &indel() const { return indel_result_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -324,6 +336,7 @@ public:
         if (depth_) z_->depth_begin(depth_ref_len_.data(), depth_ref_len_.size());
         if (pileup_) z_->pileup_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), pileup_ref_bases_.data(), pileup_thresholds_);
         if (genotype_) z_->genotype_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), genotype_params_);
+        if (indel_) z_->indel_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), indel_params_);
         if (tmp_.empty()) {
             n_runs_ = off_.size() > 1 ? 1 : 0;
             std::vector<uint32_t> perm;
@@ -342,6 +355,7 @@ public:
             if (depth_) z_->depth_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
             if (pileup_) z_->pileup_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
             if (genotype_) z_->genotype_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
+            if (indel_) z_->indel_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
         } else {
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
@@ -368,6 +382,7 @@ public:
                 if (depth_ && counted_off.size() > 1) z_->depth_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 if (pileup_ && counted_off.size() > 1) z_->pileup_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 if (genotype_ && counted_off.size() > 1) z_->genotype_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
+                if (indel_ && counted_off.size() > 1) z_->indel_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 counted.clear();
                 counted_off.assign(1, 0);
             };
@@ -412,6 +427,7 @@ public:
             genotype_result_.n_snv_sites = 0;
             for (size_t k = 0; k < pileup_result_.n_sites(); k++) genotype_result_.n_snv_sites += pileup_result_.sites[kPileupSiteWords * k + 11] & 1u;
         }
+        if (indel_) z_->indel_finish(indel_result_);
     }
 
 private:

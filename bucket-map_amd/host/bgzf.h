@@ -8,6 +8,7 @@
 #include "depth.h"
 #include "pileup.h"
 #include "genotype.h"
+#include "indel.h"
 #include "markdup.h"
 
 #include <algorithm>
@@ -378,10 +379,21 @@ struct block_compressor {
     }
     virtual void genotype_call(const uint32_t *sites, size_t n_sites, std::vector<uint32_t> &out) { genotype_.call(sites, n_sites, out); }
 
+    // --vcf-indels (include/bmn.h states the rule): the references and the five parameters, then whole records as for
+    // pileup_add, then the alleles, the calls and the three sums per reference.  The defaults are the host rule of indel.h; the
+    // product plugs in bmn_begin, bmn_add, bmn_finish, bmn_alleles and bmn_calls.
+    virtual void indel_begin(const uint32_t *ref_len, size_t n_ref, const indel_params &pr) { indel_.begin(ref_len, n_ref, pr); }
+    virtual void indel_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) {
+        (void)n;
+        indel_.add(in, rec_offset, n_records, skip);
+    }
+    virtual void indel_finish(indel_result &out) { indel_.finish(out); }
+
 private:
     depth_counter depth_;
     pileup_counter pileup_;
     genotype_counter genotype_;
+    indel_caller indel_;
 };
 
 }  // namespace bm

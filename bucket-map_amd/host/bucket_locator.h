@@ -464,6 +464,8 @@ struct vcf_options {
     genotype_params params{};
     uint32_t min_qual = 20;
     std::string sample = "sample";
+    bool indels = false;            // --vcf-indels: the indel calls of include/bmn.h, merged into the file by (reference, POS)
+    indel_params indel{};
 };
 
 class sam_text {
@@ -523,10 +525,27 @@ class sam_text {
         const genotype_result &res = sorter_->genotype();
         std::vector<uint32_t> lens;
         for (size_t r = 0; r < ref_ids_.size(); r++) lens.push_back((*pileup_seqs_)[r].size());   // set_pileup has checked them
-        write_whole(vcf_.file, [&](std::ostream &f) { write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual); });
+        if (!vcf_.indels) write_whole(vcf_.file, [&](std::ostream &f) { write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual); });
+        else {
+            // the indel lines go between the SNV lines by (reference, POS); at an equal POS the SNV comes first
+            const indel_result &ind = sorter_->indel();
+            size_t next = 0;
+            const vcf_between between = [&](std::string &buf, uint32_t ref, uint64_t pos) {
+                for (; next < ind.n_calls(); next++) {
+                    const uint32_t *c = ind.calls.data() + kIndelCallWords * next;
+                    if (c[0] > ref || (c[0] == ref && static_cast<uint64_t>(c[1]) + 1 >= pos)) break;
+                    if (c[5] & kIndelVariant) append_indel_vcf_line(buf, c, ref_ids_.at(c[0]), (*pileup_seqs_)[c[0]], vcf_.min_qual);
+                }
+            };
+            write_whole(vcf_.file, [&](std::ostream &f) {
+                next = 0;
+                write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, indel_vcf_header(), &between);
+            });
+        }
         const genotype_summary s = summarize_genotypes(res, vcf_.min_qual);
         std::cerr << "[INFO]\t\tGenotypes: " << s.variants << " variants (" << s.het << " het, " << s.hom << " hom, " << s.low_qual
                   << " below QUAL) at " << res.n_snv_sites << " SNV sites\n";
+        if (vcf_.indels) std::cerr << "[INFO]\t\t" << indel_summary_line(summarize_indels(sorter_->indel(), vcf_.min_qual)) << "\n";
     }
     void write_pileup() {
         const pileup_result &res = sorter_->pileup();
@@ -554,6 +573,7 @@ class sam_text {
         }
         sorter_->set_pileup(ref_lengths, bases, pileup_thresholds_);
         if (!vcf_.file.empty()) sorter_->set_genotype(vcf_.params);
+        if (!vcf_.file.empty() && vcf_.indels) sorter_->set_indel(vcf_.indel);
     }
 
     // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer

@@ -86,7 +86,11 @@ struct cmd_arguments {
                                   // the rule); the pileup's own file is written only with --pileup
     unsigned long vcf_prior = 30, vcf_min_qual = 20;   // --vcf-prior N (phred, 0..255) / --vcf-min-qual N (phred)
     std::string vcf_sample = "sample";   // --vcf-sample NAME: the sample column's name, no tab or newline
-    std::string vcf_opt;          // the first of those three given: refused without --vcf
+    std::string vcf_opt;          // the first of those three or of the three below given: refused without --vcf
+    bool vcf_indels = false;      // --vcf-indels: the VCF also carries the insertions and deletions of the records (include/bmn.h states
+                                  // the rule); sites by --pileup-min-mapq / -min-alt / -min-frac.  It does not imply --affine --left-align
+    unsigned long vcf_indel_qual = 30, vcf_indel_prior = 40;   // --vcf-indel-qual N (phred, 1..93) / --vcf-indel-prior N (phred, 0..255)
+    std::string vcf_indel_opt;    // the first of those two given: refused without --vcf-indels
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -389,6 +393,20 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             (prior ? a.vcf_prior : a.vcf_min_qual) = v;
             if (a.vcf_opt.empty()) a.vcf_opt = opt;
         }
+        else if (opt == "--vcf-indels") {
+            a.vcf_indels = true;
+            if (a.vcf_opt.empty()) a.vcf_opt = opt;
+        }
+        else if (opt == "--vcf-indel-qual" || opt == "--vcf-indel-prior") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            const bool prior = opt == "--vcf-indel-prior";
+            if (s[0] < '0' || s[0] > '9' || v > (prior ? 255ul : 93ul) || (!prior && v == 0))
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in " + (prior ? "0..255" : "1..93") + ".");
+            (prior ? a.vcf_indel_prior : a.vcf_indel_qual) = v;
+            if (a.vcf_opt.empty()) a.vcf_opt = opt;
+            if (a.vcf_indel_opt.empty()) a.vcf_indel_opt = opt;
+        }
         else if (opt == "--vcf-sample") {
             a.vcf_sample = value();
             if (a.vcf_sample.empty() || a.vcf_sample.find_first_of("\t\n\r") != std::string::npos)
@@ -432,6 +450,8 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
                            (a.pileup_path == a.depth_path ? "--depth" : "--coverage") + " too.");
     if (!a.vcf_opt.empty() && a.vcf_path.empty())
         throw parser_error("Validation failed for option " + a.vcf_opt + ": it is an option of --vcf FILE, which is not given.");
+    if (!a.vcf_indel_opt.empty() && !a.vcf_indels)
+        throw parser_error("Validation failed for option " + a.vcf_indel_opt + ": it is an option of --vcf-indels, which is not given.");
     if (!a.vcf_path.empty() && a.output_sam_path.empty() && !a.only_indexer)
         throw parser_error("Validation failed for option --vcf: the genotypes are those of the records of a sorted BAM file; name one with -o x.bam.");
     if (!a.vcf_path.empty() && (a.vcf_path == a.pileup_path || a.vcf_path == a.depth_path || a.vcf_path == a.coverage_path))

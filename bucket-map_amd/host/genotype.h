@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <ostream>
 #include <stdexcept>
 #include <string>
@@ -196,12 +197,18 @@ inline genotype_summary summarize_genotypes(const genotype_result &res, uint32_t
     return s;
 }
 
-// --vcf FILE: VCF 4.2, the header, then one line per VARIANT call in the order of the calls
+// what --vcf-indels puts between the SNV lines: called before the line at (reference, POS) and, with (2^32 - 1, 2^64 - 1), after
+// the last one; it appends the lines that belong before that place to buf
+using vcf_between = std::function<void(std::string &buf, uint32_t ref, uint64_t pos)>;
+
+// --vcf FILE: VCF 4.2, the header, then one line per VARIANT call in the order of the calls.  more_info, where given, is a
+// further INFO line of the header.
 inline void write_vcf_file(std::ostream &out, const genotype_result &res, const std::vector<std::string> &ref_ids, const std::vector<uint32_t> &ref_len,
-                           const std::string &sample, uint32_t min_qual) {
+                           const std::string &sample, uint32_t min_qual, const char *more_info = nullptr, const vcf_between *between = nullptr) {
     std::string buf = "##fileformat=VCFv4.2\n##source=bucketmap --vcf\n";
     for (size_t r = 0; r < ref_ids.size(); r++) buf += "##contig=<ID=" + ref_ids[r] + ",length=" + std::to_string(ref_len.at(r)) + ">\n";
     buf += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Counted bases A, C, G and T of sufficient base quality\">\n";
+    if (more_info) buf += more_info;
     buf += "##FILTER=<ID=LowQual,Description=\"QUAL below " + std::to_string(min_qual) + "\">\n";
     buf += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
     buf += "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Counted bases A, C, G and T of sufficient base quality\">\n";
@@ -223,6 +230,7 @@ inline void write_vcf_file(std::ostream &out, const genotype_result &res, const 
         };
         char qual[32];
         std::snprintf(qual, sizeof qual, "%u.%02u", c[7] / 100, c[7] % 100);
+        if (between) (*between)(buf, c[0], static_cast<uint64_t>(c[1]) + 1);
         buf += ref_ids.at(c[0]);
         buf += '\t', buf += std::to_string(static_cast<uint64_t>(c[1]) + 1);
         buf += "\t.\t", buf += "ACGT"[R];
@@ -243,6 +251,7 @@ inline void write_vcf_file(std::ostream &out, const genotype_result &res, const 
         buf += '\n';
         if (buf.size() > (1u << 20)) out.write(buf.data(), static_cast<std::streamsize>(buf.size())), buf.clear();
     }
+    if (between) (*between)(buf, 0xFFFFFFFFu, ~uint64_t{0});
     out.write(buf.data(), static_cast<std::streamsize>(buf.size()));
 }
 

@@ -159,6 +159,9 @@ int main(int argc, char **argv) {
                 vcf.params.prior = static_cast<uint32_t>(100 * args.vcf_prior);
                 vcf.min_qual = static_cast<uint32_t>(args.vcf_min_qual);
                 vcf.sample = args.vcf_sample;
+                vcf.indels = args.vcf_indels;                                     // --vcf-indels: the indels of the CIGARs into the same file
+                vcf.indel.min_mapq = pileup_th.min_mapq, vcf.indel.min_alt = pileup_th.min_alt, vcf.indel.min_frac_ppm = pileup_th.min_frac_ppm;
+                vcf.indel.q_indel = static_cast<uint32_t>(args.vcf_indel_qual), vcf.indel.prior = static_cast<uint32_t>(100 * args.vcf_indel_prior);
                 loc.set_vcf(vcf, pileup_th);
             }
         }

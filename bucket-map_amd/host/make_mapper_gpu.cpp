@@ -4,6 +4,7 @@
 #include "../../include/bmc.h"
 #include "../../include/bmp.h"
 #include "../../include/bmg.h"
+#include "../../include/bmn.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -124,6 +125,7 @@ public:
         if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
     }
     ~gpu_block_compressor() override {
+        bmn_destroy(indel_);
         bmg_destroy(geno_);
         bmp_destroy(pile_);
         bmc_destroy(cover_);
@@ -247,9 +249,36 @@ public:
         out.assign(n_sites * bm::kGenotypeCallWords, 0);
         if (bmg_call(genotyper(), sites, n_sites, out.data()) != BMG_OK) throw std::runtime_error(std::string("bmg_call: ") + bmg_last_error());
     }
+    // --vcf-indels: the indel alleles and calls of the written records on the same device (bmn_*: the rule of include/bmn.h,
+    // which is the host default's)
+    void indel_begin(const uint32_t *ref_len, size_t n_ref, const bm::indel_params &pr) override {
+        if (n_ref > 0xFFFFFFFFull) throw std::runtime_error("bmn_begin: " + std::to_string(n_ref) + " references");
+        const uint32_t p[BMN_N_PARAMS] = {pr.min_mapq, pr.min_alt, pr.min_frac_ppm, pr.q_indel, pr.prior};
+        if (bmn_begin(indeler(), ref_len, static_cast<uint32_t>(n_ref), p) != BMN_OK) throw std::runtime_error(std::string("bmn_begin: ") + bmn_last_error());
+        indel_n_ref_ = n_ref;
+    }
+    void indel_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) override {
+        if (bmn_add(indeler(), in, n, rec_offset, n_records, skip) != BMN_OK) throw std::runtime_error(std::string("bmn_add: ") + bmn_last_error());
+    }
+    void indel_finish(bm::indel_result &out) override {
+        uint64_t n_alleles = 0, n_calls = 0;
+        out.stats.assign(indel_n_ref_ * bm::kIndelStats, 0);
+        if (bmn_finish(indeler(), &out.n_events, &n_alleles, &n_calls, out.stats.data()) != BMN_OK)
+            throw std::runtime_error(std::string("bmn_finish: ") + bmn_last_error());
+        out.alleles.assign(static_cast<size_t>(n_alleles) * bm::kIndelAlleleWords, 0);
+        out.calls.assign(static_cast<size_t>(n_calls) * bm::kIndelCallWords, 0);
+        if (bmn_alleles(indel_, 0, n_alleles, out.alleles.data()) != BMN_OK) throw std::runtime_error(std::string("bmn_alleles: ") + bmn_last_error());
+        if (bmn_calls(indel_, 0, n_calls, out.calls.data()) != BMN_OK) throw std::runtime_error(std::string("bmn_calls: ") + bmn_last_error());
+    }
 
 private:
     int device_ = 0;
+    bmn_ctx *indel_ = nullptr;      // made by the first indel call: a run without --vcf-indels pays nothing for it
+    size_t indel_n_ref_ = 0;
+    bmn_ctx *indeler() {
+        if (!indel_ && bmn_create(device_, &indel_) != BMN_OK) throw std::runtime_error(std::string("bmn_create: ") + bmn_last_error());
+        return indel_;
+    }
     bmg_ctx *geno_ = nullptr;       // made by the first genotype call: a run without --vcf pays nothing for it
     bmg_ctx *genotyper() {
         if (!geno_ && bmg_create(device_, &geno_) != BMG_OK) throw std::runtime_error(std::string("bmg_create: ") + bmg_last_error());
