@@ -24,7 +24,7 @@ CSRC = $(PKG)/csrc
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bmf.h include/bml.h include/bmv.h include/bmz.h include/bms.h include/bmd.h include/bmu.h include/bmc.h include/bmp.h include/bmg.h include/bmn.h $(HOST)/inflate_rule.h $(HOST)/bgzf_in.h $(HOST)/bgzf.h
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-result -c -o $@ $<
 
-$(PKG)/libbmf.so: $(CSRC)/bmf_api.o $(CSRC)/bml_api.o $(CSRC)/bmv_api.o $(CSRC)/bmv_variants.o $(CSRC)/bmv_variants2.o $(CSRC)/bmv_variants3.o $(CSRC)/bmv_long.o $(CSRC)/bmv_screen.o $(CSRC)/bmv_annotate.o $(CSRC)/bmv_clip.o $(CSRC)/bmv_best.o $(CSRC)/bmv_pair.o $(CSRC)/bmv_frag.o $(CSRC)/bmv_rescue.o $(CSRC)/bmv_realign.o $(CSRC)/bmv_leftalign.o $(CSRC)/bmv_split.o $(CSRC)/bmz_api.o $(CSRC)/bms_api.o $(CSRC)/bmd_api.o $(CSRC)/bmu_api.o $(CSRC)/bmc_api.o $(CSRC)/bmp_api.o $(CSRC)/bmg_api.o $(CSRC)/bmn_api.o
+$(PKG)/libbmf.so: $(CSRC)/bmf_api.o $(CSRC)/bml_api.o $(CSRC)/bmv_api.o $(CSRC)/bmv_variants.o $(CSRC)/bmv_variants2.o $(CSRC)/bmv_variants3.o $(CSRC)/bmv_long.o $(CSRC)/bmv_screen.o $(CSRC)/bmv_annotate.o $(CSRC)/bmv_clip.o $(CSRC)/bmv_overlap.o $(CSRC)/bmv_best.o $(CSRC)/bmv_pair.o $(CSRC)/bmv_frag.o $(CSRC)/bmv_rescue.o $(CSRC)/bmv_realign.o $(CSRC)/bmv_leftalign.o $(CSRC)/bmv_split.o $(CSRC)/bmz_api.o $(CSRC)/bms_api.o $(CSRC)/bmd_api.o $(CSRC)/bmu_api.o $(CSRC)/bmc_api.o $(CSRC)/bmp_api.o $(CSRC)/bmg_api.o $(CSRC)/bmn_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 $(PKG)/libbmhost.so: $(HOST)/bm_host_api.cpp $(HOST_HDRS)

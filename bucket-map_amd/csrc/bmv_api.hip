@@ -12,6 +12,7 @@
 #include "bmv_annotate.hip.h"
 #include "bmv_best.hip.h"
 #include "bmv_clip.hip.h"
+#include "bmv_overlap.hip.h"
 #include "bmv_frag.hip.h"
 #include "bmv_leftalign.hip.h"
 #include "bmv_long.hip.h"
@@ -199,6 +200,18 @@ struct bmv_ctx {
     DevBuf<uint32_t> cl_pos0, cl_left, cl_right;
     std::vector<int64_t> h_cl_score;
     std::vector<uint32_t> h_cl_left, h_cl_right;
+    // bmv_overlap: the pair arrays, what its passes hand to each other (the base range, its ends in the genome, the cut and
+    // the roles; the final range goes through bmv_clip's buffers), the host results of bmv_overlapped and what
+    // bmv_last_overlap_stats reports
+    DevBuf<uint32_t> ov_mate, ov_contig, ov_role, ov_found, ov_cut_q, ov_cut;
+    DevBuf<uint64_t> ov_l0, ov_r0, ov_edge;
+    DevBuf<int64_t> ov_g0, ov_g1, ov_m;
+    DevBuf<uint8_t> ov_was_cut;
+    EmitHost h_ov;
+    std::vector<int64_t> h_ov_score;
+    std::vector<uint32_t> h_ov_left, h_ov_right, h_ov_cut;
+    std::vector<uint8_t> h_ov_was_cut;
+    uint64_t ov_pairs_cut = 0, ov_bases_cut = 0;
     // bmv_align_best: the distance round's and the pick's buffers (the batch's views go through the aligners' own), the
     // host results of bmv_best and what bmv_last_best_stats reports
     DevBuf<uint32_t> bs_bound, bs_list, bs_d, bs_end, bs_full, bs_group_offset, bs_margin, bs_winner, bs_need, bs_need_at,
@@ -2439,6 +2452,143 @@ int bmv_last_clip_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns) {
     if (!c) return fail(BMV_ERR_ARG, "bmv_last_clip_stats: null context");
     if (ms_kernels) *ms_kernels = c->h_cl.ms;
     if (n_columns) *n_columns = c->h_cl.n_columns;
+    return BMV_OK;
+}
+
+// The overlap pass (include/bmv.h, bmv_overlap.hip.h): bmv_clip's checks and upload; the base range (bmv_clip's range kernel, or
+// all columns), the span, decide, restrict and commit passes in front of bmv_clip's count pass, the score pass behind it, two
+// exclusive sums, bmv_clip's write pass, download (two_pass_emit) -- into results of its own.
+int bmv_overlap(bmv_ctx *c, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                const uint64_t *cigar_offset, const uint32_t *cigar, const uint32_t *mate, const uint32_t *contig, uint32_t n,
+                uint32_t match, uint32_t penalty, uint64_t *total_xcigar, uint64_t *total_ref_bases) {
+    if (!c || !total_xcigar || !total_ref_bases || (n && !mate)) return fail(BMV_ERR_ARG, "bmv_overlap: null argument");
+    const bool scored = match != 0u || penalty != 0u;
+    if (scored && (match < 1u || match > 1024u || penalty < 1u || penalty > 1024u))
+        return fail(BMV_ERR_ARG, "bmv_overlap: match and penalty must be 0 and 0 or in 1..1024 (got %u and %u)", match, penalty);
+    const Views v{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+    if (const int rc = check_view_args(c, "bmv_overlap", v, true, begin && cigar_offset)) return rc;
+    uint64_t columns = 0;
+    if (const int rc = check_annotate_batch(c, "bmv_overlap", v, begin, cigar_offset, cigar, &columns)) return rc;
+    for (uint32_t a = 0; a < n; a++) {
+        if (text_start[a] >= (1ull << 62))
+            return fail(BMV_ERR_ARG, "alignment %u: text_start %llu is not below 2^62", a, (unsigned long long)text_start[a]);
+        if (mate[a] == BMV_NO_MATE) continue;
+        if (mate[a] >= n) return fail(BMV_ERR_ARG, "alignment %u: mate %u, the batch has %u alignments", a, mate[a], n);
+        if (mate[a] == a) return fail(BMV_ERR_ARG, "alignment %u: it is its own mate", a);
+        if (mate[mate[a]] != a)
+            return fail(BMV_ERR_ARG, "alignment %u: its mate %u names %u as its mate", a, mate[a], mate[mate[a]]);
+    }
+    c->h_ov_score.assign(n, 0);
+    c->h_ov_left.assign(n, 0);
+    c->h_ov_right.assign(n, 0);
+    c->h_ov_cut.assign(n, 0);
+    c->h_ov_was_cut.assign(n, 0);
+    c->ov_pairs_cut = c->ov_bases_cut = 0;
+    reset_emit(c->h_ov, n, columns);
+    *total_xcigar = 0;
+    *total_ref_bases = 0;
+    if (n == 0) return BMV_OK;
+
+    bmv::OverlapJob j{};
+    std::vector<uint64_t> rebased;
+    if (const int rc = upload_annotate_batch(c, v, begin, cigar_offset, cigar, rebased, j.c.a)) return rc;
+    HIP_TRY(need_exact_all(n, c->cl_score, c->cl_l, c->cl_r, c->cl_pos0, c->cl_left, c->cl_right));
+    HIP_TRY(need_exact_all(n, c->ov_mate, c->ov_role, c->ov_found, c->ov_cut_q, c->ov_cut, c->ov_l0, c->ov_r0, c->ov_edge, c->ov_g0,
+                           c->ov_g1, c->ov_m, c->ov_was_cut));
+    HIP_TRY(hipMemcpyAsync(c->ov_mate.p, mate, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (contig) {
+        HIP_TRY(c->ov_contig.need_exact(n));
+        HIP_TRY(hipMemcpyAsync(c->ov_contig.p, contig, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    j.c.match = match;
+    j.c.penalty = penalty;
+    j.c.score = c->cl_score.p;
+    j.c.l = c->cl_l.p;
+    j.c.r = c->cl_r.p;
+    j.c.pos0 = c->cl_pos0.p;
+    j.c.clip_left = c->cl_left.p;
+    j.c.clip_right = c->cl_right.p;
+    j.mate = c->ov_mate.p;
+    j.contig = contig ? c->ov_contig.p : nullptr;
+    j.l0 = c->ov_l0.p;
+    j.r0 = c->ov_r0.p;
+    j.g0 = c->ov_g0.p;
+    j.g1 = c->ov_g1.p;
+    j.m = c->ov_m.p;
+    j.role = c->ov_role.p;
+    j.edge = c->ov_edge.p;
+    j.found = c->ov_found.p;
+    j.cut_q = c->ov_cut_q.p;
+    j.cut = c->ov_cut.p;
+    j.was_cut = c->ov_was_cut.p;
+    const dim3 grid((n + bmv::kAnnotateWaves - 1u) / bmv::kAnnotateWaves), block(64u * bmv::kAnnotateWaves);
+    const dim3 tgrid((n + bmv::kOverlapThreads - 1u) / bmv::kOverlapThreads), tblock(bmv::kOverlapThreads);
+    const int rc = two_pass_emit(
+        c, "overlap", "range, span, decide, restrict, commit, count and score passes", j.c.a, c->h_ov,
+        [&] {
+            if (scored) {
+                bmv::ClipJob base = j.c;                            // bmv_clip's range kernel writes the BASE range
+                base.l = j.l0;
+                base.r = j.r0;
+                hipLaunchKernelGGL(bmv::bmv_clip_range_kernel<bmv::kAnnotateWaves>, grid, block, 0, c->stream, base);
+                if (const hipError_t e = hipGetLastError()) return e;
+                hipLaunchKernelGGL(bmv::bmv_overlap_span_kernel<true>, grid, block, 0, c->stream, j);
+            } else {
+                hipLaunchKernelGGL(bmv::bmv_overlap_span_kernel<false>, grid, block, 0, c->stream, j);
+            }
+            if (const hipError_t e = hipGetLastError()) return e;
+            hipLaunchKernelGGL(bmv::bmv_overlap_decide_kernel<bmv::kOverlapThreads>, tgrid, tblock, 0, c->stream, j);
+            if (const hipError_t e = hipGetLastError()) return e;
+            hipLaunchKernelGGL(bmv::bmv_overlap_restrict_kernel<bmv::kAnnotateWaves>, grid, block, 0, c->stream, j);
+            if (const hipError_t e = hipGetLastError()) return e;
+            hipLaunchKernelGGL(bmv::bmv_overlap_commit_kernel<bmv::kOverlapThreads>, tgrid, tblock, 0, c->stream, j);
+            if (const hipError_t e = hipGetLastError()) return e;
+            hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<false>, grid, block, 0, c->stream, j.c);
+            if (const hipError_t e = hipGetLastError()) return e;
+            hipLaunchKernelGGL(bmv::bmv_overlap_score_kernel<bmv::kOverlapThreads>, tgrid, tblock, 0, c->stream, j);
+            return hipGetLastError();
+        },
+        [&] {
+            hipLaunchKernelGGL(bmv::bmv_clip_emit_kernel<true>, grid, block, 0, c->stream, j.c);
+            return hipGetLastError();
+        },
+        [&] {
+            if (const hipError_t e = hipMemcpyAsync(c->h_ov_score.data(), c->cl_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream)) return e;
+            if (const hipError_t e = hipMemcpyAsync(c->h_ov_left.data(), c->cl_left.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)) return e;
+            if (const hipError_t e = hipMemcpyAsync(c->h_ov_right.data(), c->cl_right.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)) return e;
+            if (const hipError_t e = hipMemcpyAsync(c->h_ov_cut.data(), c->ov_cut.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)) return e;
+            return hipMemcpyAsync(c->h_ov_was_cut.data(), c->ov_was_cut.p, (size_t)n, hipMemcpyDeviceToHost, c->stream);
+        },
+        total_xcigar, total_ref_bases);
+    if (rc) return rc;
+    uint64_t mates_cut = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        mates_cut += c->h_ov_was_cut[a] != 0;
+        c->ov_bases_cut += c->h_ov_cut[a];
+    }
+    c->ov_pairs_cut = mates_cut / 2u;
+    return BMV_OK;
+}
+
+int bmv_overlapped(bmv_ctx *c, int64_t *out_score, uint32_t *out_clip_left, uint32_t *out_clip_right, uint32_t *out_nm,
+                   uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset, uint32_t *out_xcigar,
+                   uint64_t *out_ref_offset, uint8_t *out_ref_bases, uint32_t *out_cut) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_overlapped: null context");
+    copy_out(out_score, c->h_ov_score);
+    copy_out(out_clip_left, c->h_ov_left);
+    copy_out(out_clip_right, c->h_ov_right);
+    copy_out(out_cut, c->h_ov_cut);
+    copy_emit(c->h_ov, out_nm, out_pos, out_ref_len, out_xcigar_offset, out_xcigar, out_ref_offset, out_ref_bases);
+    return BMV_OK;
+}
+
+int bmv_last_overlap_stats(bmv_ctx *c, float *ms_kernels, uint64_t *n_columns, uint64_t *pairs_cut, uint64_t *bases_cut) {
+    if (!c) return fail(BMV_ERR_ARG, "bmv_last_overlap_stats: null context");
+    if (ms_kernels) *ms_kernels = c->h_ov.ms;
+    if (n_columns) *n_columns = c->h_ov.n_columns;
+    if (pairs_cut) *pairs_cut = c->ov_pairs_cut;
+    if (bases_cut) *bases_cut = c->ov_bases_cut;
     return BMV_OK;
 }
 

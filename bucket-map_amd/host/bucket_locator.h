@@ -21,6 +21,7 @@
 #include "bm_genome.h"
 #include "frag_range.h"
 #include "left_align.h"
+#include "overlap_clip.h"
 #include "mapper.h"
 #include "pair_mapq.h"
 #include "pair_rescue.h"
@@ -161,6 +162,22 @@ public:
         (void)reads; (void)n_read_bytes; (void)text_start; (void)text_len; (void)text_rc; (void)query_start; (void)query_len;
         (void)begin; (void)cigar_offset; (void)cigar; (void)n; (void)match; (void)penalty; (void)out;
         throw std::runtime_error("--clip: this build's alignment verifier has no clipping pass");
+    }
+    // The same for pairs (bmv_overlap's contract, include/bmv.h): clip's record -- all columns kept when match == penalty == 0 --,
+    // and where the two mates of a pair (mate[a]: the index of a's mate, overlap::kNoMate for none; contig: per alignment, or null
+    // for one contig) overlap on the reference without containment, both soft-clipped at one cut so that no base lies under both.
+    // cut[a]: the query bases the cut clipped; pairs_cut, bases_cut: the pairs cut and the sum of cut.  This default restates the
+    // rule on the host (overlap_clip.h), whatever the scores, and needs `genome` as realign's does; the GPU verifier clips on the
+    // device (can_clip_overlap() true) and ignores it.
+    virtual bool can_clip_overlap() const { return false; }
+    virtual void clip_overlap(const uint8_t *genome, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start,
+                              const uint32_t *text_len, const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len,
+                              const uint32_t *begin, const uint64_t *cigar_offset, const uint32_t *cigar, const uint32_t *mate,
+                              const uint32_t *contig, uint32_t n, uint32_t match, uint32_t penalty, clipping &out,
+                              std::vector<uint32_t> &cut, uint64_t &pairs_cut, uint64_t &bases_cut) {
+        (void)n_read_bytes;
+        clip_overlap_on_host(genome, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, mate, contig, n,
+                             match, penalty, out, cut, pairs_cut, bases_cut);
     }
     // Split alignments (bmv_split's contract, include/bmv.h): per alignment the stretch clip would keep as a query interval in read
     // orientation and a reference interval in genome coordinates, per group -- a read's candidates -- the non-conflicting
@@ -800,6 +817,8 @@ private:
     bool _affine = false;                        // --affine: the written alignments realigned under affine gap costs, with AS
     affine_scores _affine_scores{};
     bool _left_align = false;                    // --left-align: the written alignments' indels at their leftmost forward place
+    bool _clip_overlap = false;                  // --clip-overlap: the two records of a pair soft-clipped where they overlap
+    uint64_t _overlap_pairs = 0, _overlap_cut = 0, _overlap_bases = 0;   // ... the pairs handed to the pass, cut, and the bases clipped
     bool _split = false;                         // --split: per read the non-conflicting clipped stretches of its candidates, a
     split_params _split_params{};                // primary and 0x800 supplementary records tied by SA:Z (the scores are --clip's)
     float _best_margin = -1.f;                   // >= 0: --best, one record per read; the margin is this rate x read length
@@ -1066,6 +1085,10 @@ public:
         _clip_match = match;
         _clip_penalty = penalty;
     }
+    // --clip-overlap (needs set_paired): the written alignments go through the verifier's overlap pass instead of annotate or clip --
+    // under --clip with its scores, else without scores --, which soft-clips the two records of a pair that can carry 0x2 at one
+    // cut where they overlap on the reference: POS, CIGAR, NM, MD, PNEXT (and AS:i) follow, TLEN stays, as the outer ends do
+    void set_clip_overlap() { _clip_overlap = _annotate = true; }
     // --split: the --clip layout; of a read's candidates the verifier's split pass chooses the segments, only those go through
     // realign / left_align / clip, and they are written in chosen order: the first as the primary record, the others with flag
     // 0x800, MAPQ from split_mapq, and -- two or more -- each with an SA:Z tag naming the others (split_pick.h).  Needs set_clip.
@@ -1401,6 +1424,7 @@ private:
             std::vector<uint32_t> ann_slot;      // --annotate: per alignment its place in `ann`, ~0u = not written
             clipping ann;                        // (--clip fills score and the clips too)
             std::vector<int32_t> affine_score;   // --affine: per slot of `ann` the realigned path's score
+            std::vector<uint32_t> cut;           // --clip-overlap: per slot of `ann` the query bases the cut clipped
             split_result split;                  // --split: the verifier's answer for the block, a group per read ...
             std::vector<uint8_t> chosen;         // ... and per alignment whether it is one of its read's segments
             unsigned int first_read = 0;
@@ -1431,13 +1455,21 @@ private:
                 bucket_ref.push_back(bk == 0 ? 0u : bucket_ref[bk - 1] + (h.bucket_name[bk] == h.bucket_name[bk - 1] ? 0u : 1u));
         }
         // --annotate with a verifier that has no annotation pass (the oracle-backed test tools): sam_tags::annotate_on_host
-        const bool annotate_here = _annotate && !_clip && !_v->can_annotate();
-        if ((annotate_here || (_affine && !_v->can_realign()) || (_left_align && !_v->can_left_align())) && flat_genome_.empty())
+        const bool annotate_here = _annotate && !_clip && !_clip_overlap && !_v->can_annotate();
+        if (_clip_overlap && !paired) throw std::runtime_error("--clip-overlap clips the mates of pairs: set_paired comes first");
+        if ((annotate_here || (_affine && !_v->can_realign()) || (_left_align && !_v->can_left_align()) ||
+             (_clip_overlap && !_v->can_clip_overlap())) && flat_genome_.empty())
             for (const auto &seq : genome_->seqs) flat_genome_.insert(flat_genome_.end(), seq.begin(), seq.end());
         auto is_written = [&](const Block &b, size_t a) {       // :570-573, and the edit bound
             if (split) return b.chosen[a] != 0;                 // (--split: 60 + score means nothing for a part of a read)
             const size_t map_qual = 60u + static_cast<unsigned int>(b.score[a]);
             return !((bounded || best) && b.score[a] == alignment_verifier::kRejected) && !(map_qual < quality_threshold);
+        };
+        // --clip: the kept range of written alignment a is empty.  A kept column scores at least `match`, so bmv_clip's score tells;
+        // after --clip-overlap's cut a kept range may score 0 or less, but it holds a reference base
+        auto nothing_kept = [&](const Block &b, size_t a) {
+            const uint32_t s = b.ann_slot[a];
+            return _clip_overlap ? b.ann.ref_len[s] == 0 : b.ann.score[s] == 0;
         };
         // --rescue, after paired(): the jobs of every pair that is not proper, the verifier's answer, and for each mate it
         // places a full alignment appended behind the groups' -- on its view narrowed to the m + d columns before the end the
@@ -1616,7 +1648,38 @@ private:
                         co.swap(la.cigar_offset);
                         cg.swap(la.cigar);
                     }
-                    if (_clip)
+                    if (_clip_overlap) {
+                        // the two records of every pair that can carry 0x2 name each other: the picks of a proper pair, a rescued
+                        // mate and its anchor.  A rescued alignment lies on its anchor's contig.
+                        const uint32_t kNone = alignment_verifier::kBeyond;
+                        std::vector<uint32_t> mate(ts.size(), overlap::kNoMate), ct(ts.size(), 0);
+                        auto record_of = [&](size_t r) {        // the alignment read r's record is written from, or kNone
+                            if (b.rescued_at[r] != kNone) return b.rescued_at[r];
+                            return b.group_offset[r + 1] == b.group_offset[r] ? kNone : b.pick[r];
+                        };
+                        for (size_t a = 0; a < n && a < b.contig.size(); a++)
+                            if (b.ann_slot[a] != ~0u) ct[b.ann_slot[a]] = b.contig[a];
+                        uint64_t handed = 0;
+                        for (size_t p = 0; p < b.reads.size() / 2; p++) {
+                            const bool rescued = b.rescued_at[2 * p] != kNone || b.rescued_at[2 * p + 1] != kNone;
+                            for (size_t r = 2 * p; rescued && r < 2 * p + 2; r++)
+                                if (b.rescued_at[r] != kNone && b.ann_slot[b.rescued_at[r]] != ~0u && b.winner[r ^ 1u] != kNone)
+                                    ct[b.ann_slot[b.rescued_at[r]]] = b.contig[b.winner[r ^ 1u]];
+                            if (!rescued && !(p < b.proper.size() && b.proper[p] != 0)) continue;
+                            const uint32_t a0 = record_of(2 * p), a1 = record_of(2 * p + 1);
+                            if (a0 == kNone || a1 == kNone || b.ann_slot[a0] == ~0u || b.ann_slot[a1] == ~0u) continue;
+                            mate[b.ann_slot[a0]] = b.ann_slot[a1];
+                            mate[b.ann_slot[a1]] = b.ann_slot[a0];
+                            handed++;
+                        }
+                        uint64_t pairs_cut = 0, bases_cut = 0;
+                        _v->clip_overlap(flat_genome_.data(), b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(),
+                                         ql.data(), bg.data(), co.data(), cg.data(), mate.data(), ct.data(), static_cast<uint32_t>(ts.size()),
+                                         _clip ? _clip_match : 0u, _clip ? _clip_penalty : 0u, b.ann, b.cut, pairs_cut, bases_cut);
+                        _overlap_pairs += handed;
+                        _overlap_cut += pairs_cut;
+                        _overlap_bases += bases_cut;
+                    } else if (_clip)
                         _v->clip(b.bases.data(), b.bases.size(), ts.data(), tl.data(), trc.data(), qs.data(), ql.data(), bg.data(),
                                  co.data(), cg.data(), static_cast<uint32_t>(ts.size()), _clip_match, _clip_penalty, b.ann);
                     else if (annotate_here)
@@ -1656,7 +1719,7 @@ private:
             mate_record m;
             if (rescue && b.rescued_at[r] != alignment_verifier::kBeyond) {
                 const uint32_t a = b.rescued_at[r];
-                if (!is_written(b, a) || (_clip && b.ann.score[b.ann_slot[a]] == 0)) return m;
+                if (!is_written(b, a) || (_clip && nothing_kept(b, a))) return m;
                 const auto [bucket, offset] = rescued_place(b, r);
                 m.has = true;
                 m.rc = b.text_rc[a] != 0;
@@ -1668,7 +1731,7 @@ private:
             const uint32_t a0 = b.group_offset[r];
             if (b.group_offset[r + 1] == a0 || b.pick[r] == alignment_verifier::kBeyond) return m;
             const uint32_t a = b.pick[r];
-            if (!is_written(b, a) || (_clip && b.ann.score[b.ann_slot[a]] == 0)) return m;
+            if (!is_written(b, a) || (_clip && nothing_kept(b, a))) return m;
             const locate_t &loc = locate_res[b.first_read + r][a - a0];
             const int offset = std::get<1>(loc);
             m.has = true;
@@ -1697,12 +1760,13 @@ private:
                 tags += "\tMD:Z:";
                 sam_tags::append_md(tags, entry, n_entries, b.ann.ref_bases.data() + b.ann.ref_offset[s]);
                 if (_clip) {
-                    tags += "\tAS:i:";
-                    sam_tags::number(tags, static_cast<uint64_t>(b.ann.score[s]));
+                    tags += b.ann.score[s] < 0 ? "\tAS:i:-" : "\tAS:i:";   // (below 0 only after --clip-overlap's cut)
+                    sam_tags::number(tags, static_cast<uint64_t>(std::abs(b.ann.score[s])));
                 } else if (_affine) {                           // (--left-align: merges and drops change the score)
-                    const int64_t as = _left_align ? sam_tags::affine_score(entry, n_entries, _affine_scores.match, _affine_scores.mismatch,
+                    const int64_t as = _left_align || (_clip_overlap && b.cut[s] > 0)
+                                           ? sam_tags::affine_score(entry, n_entries, _affine_scores.match, _affine_scores.mismatch,
                                                                             _affine_scores.gap_open, _affine_scores.gap_extend)
-                                                   : static_cast<int64_t>(b.affine_score[s]);
+                                           : static_cast<int64_t>(b.affine_score[s]);
                     tags += as < 0 ? "\tAS:i:-" : "\tAS:i:";
                     sam_tags::number(tags, static_cast<uint64_t>(std::abs(as)));
                 }
@@ -1785,7 +1849,7 @@ private:
                     }
                     const unsigned int wrapped = 60u + static_cast<unsigned int>(b.score[a]);        // :570
                     const size_t map_qual = best ? bq.mapq : wrapped;
-                    if (is_written(b, a) && _clip && b.ann.score[b.ann_slot[a]] == 0) {
+                    if (is_written(b, a) && _clip && nothing_kept(b, a)) {
                         // --clip: the kept range is empty (a kept column scores at least `match`): no record
                     } else if (is_written(b, a) && _annotate) {
                         annotated(r, a, h.bucket_name[bucket_id], h.bucket_offsets[bucket_id] + static_cast<size_t>(offset < 0 ? 0 : offset), is_original,
@@ -1814,7 +1878,7 @@ private:
                     std::vector<segment> segs;
                     for (uint32_t k = 0; k < b.split.n_seg[r]; k++) {
                         const uint32_t c = b.split.seg[r * ms + k];
-                        if (b.ann.score[b.ann_slot[c]] == 0) continue;
+                        if (nothing_kept(b, c)) continue;
                         const locate_t &loc = locate_res[b.first_read + r][c - a0];
                         const int offset = std::get<1>(loc);
                         segs.push_back({c, split_mapq(b.split.score[c], b.split.s2[r * ms + k]), std::get<0>(loc),
@@ -1841,7 +1905,7 @@ private:
                 }
                 if (rescued) {
                     const uint32_t ra = b.rescued_at[r];
-                    if (is_written(b, ra) && !(_clip && b.ann.score[b.ann_slot[ra]] == 0)) {
+                    if (is_written(b, ra) && !(_clip && nothing_kept(b, ra))) {
                         const auto [bucket, offset] = rescued_place(b, r);
                         annotated(r, ra, h.bucket_name[bucket], h.bucket_offsets[bucket] + static_cast<size_t>(offset), b.text_rc[ra] == 0, pair_flags,
                                   bq.mapq, "XR:i:1", rnext, pnext, tlen);
@@ -1926,6 +1990,9 @@ private:
             if (worker.joinable()) worker.join();
             throw;
         }
+        if (_clip_overlap)
+            std::cerr << "[INFO]\t\tOverlap: " << _overlap_cut << " of " << _overlap_pairs << " pairs cut, " << _overlap_bases
+                      << " bases clipped\n";
         return mapped_locations;
     }
 };

@@ -52,6 +52,8 @@ struct cmd_arguments {
                                   // its partner's alignment (mate rescue) and written with XR:i:1
     float rescue_rate = 0.1f;     // --rescue-rate R (implies --rescue): an anchor may have (uint32_t)(R * its length) edits, and so
                                   // may the rescued mate
+    bool clip_overlap = false;    // --clip-overlap (bucketmap_align, implies --paired): where the two records of a pair overlap on
+                                  // the reference, both are soft-clipped at one cut so that no base is covered twice (bmv_overlap)
     bool affine = false;          // --affine (bucketmap_align): the written alignments are realigned under affine gap costs beside
                                   // their edit path (bmv_realign); POS, CIGAR, NM and MD are the realigned path's, AS:i its score
                                   // (implies --annotate)
@@ -277,6 +279,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             a.rescue_rate = r;
             a.rescue = true;
         }
+        else if (opt == "--clip-overlap") a.clip_overlap = a.paired = true;
         else if (opt == "--affine") a.affine = true;
         else if (opt == "--affine-scores") {
             const std::string s = value();
@@ -334,7 +337,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         else if (opt == "--affine" || opt == "--affine-scores" || opt == "--affine-band")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it has nothing to realign.");
         else if (opt == "--paired" || opt == "--frag-range" || opt == "--frag-auto" || opt == "--frag-cap" || opt == "--frag-min-pairs" ||
-                 opt == "--rescue" || opt == "--rescue-rate")
+                 opt == "--rescue" || opt == "--rescue-rate" || opt == "--clip-overlap")
             throw parser_error("Option " + opt + " belongs to bucketmap_align: this tool does not align, so it cannot place mates together.");
 #endif
         else if (opt == "--clip-scores") {
@@ -429,7 +432,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (!have_indicator) throw parser_error("Option -i/--index-indicator is required but not set.");
     if (a.split && (a.best || a.paired || a.rescue || a.max_edit_rate >= 0.f))
         throw parser_error(std::string("Option --split cannot be combined with ") +
-                           (a.rescue ? "--rescue" : a.frag_auto ? "--frag-auto" : a.paired ? "--paired" : a.best ? "--best" : "--max-edit-rate") +
+                           (a.clip_overlap ? "--clip-overlap" : a.rescue ? "--rescue" : a.frag_auto ? "--frag-auto" : a.paired ? "--paired" : a.best ? "--best" : "--max-edit-rate") +
                            ": they judge a read by the edits of one end-to-end alignment, which mean nothing for a read that "
                            "spans a breakpoint.");
     if (a.sort && !a.output_sam_path.empty() && a.output_sam_path.extension() != ".bam") {

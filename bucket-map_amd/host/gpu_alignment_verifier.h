@@ -270,6 +270,133 @@ public:
                   penalty);
     }
 
+    // bmv_overlap per device.  The alignments are first put in an order in which mates are neighbours and the cut between two
+    // devices' shares never falls inside a pair, so a pair never straddles two shares; the rule looks at one pair at a time, so
+    // the result does not depend on the number of devices.  The results come back in the caller's order.
+    bool can_clip_overlap() const override { return true; }
+    void clip_overlap(const uint8_t *genome, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                      const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                      const uint64_t *cigar_offset, const uint32_t *cigar, const uint32_t *mate, const uint32_t *contig, uint32_t n,
+                      uint32_t match, uint32_t penalty, clipping &out, std::vector<uint32_t> &cut, uint64_t &pairs_cut,
+                      uint64_t &bases_cut) override {
+        (void)genome;
+        const size_t D = ctx_.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        const char *failed = "the GPU overlap pass failed: ";
+        for (uint32_t a = 0; a < n; a++)
+            if (mate[a] != BMV_NO_MATE && (mate[a] >= n || mate[a] == a || mate[mate[a]] != a))
+                throw std::runtime_error(std::string(failed) + "alignment " + std::to_string(a) + " and its mate do not name each other");
+        // the batch as the devices see it: the caller's (one device), or a copy with mates side by side
+        std::vector<uint32_t> order, p_tl, p_ql, p_bg, p_cg, p_mate, p_contig;
+        std::vector<uint64_t> p_ts, p_qs, p_co;
+        std::vector<uint8_t> p_trc;
+        if (D > 1) {
+            std::vector<uint32_t> where(n);
+            for (uint32_t a = 0; a < n; a++) {
+                if (mate[a] != BMV_NO_MATE && mate[a] < a) continue;
+                where[a] = static_cast<uint32_t>(order.size());
+                order.push_back(a);
+                if (mate[a] == BMV_NO_MATE) continue;
+                where[mate[a]] = static_cast<uint32_t>(order.size());
+                order.push_back(mate[a]);
+            }
+            p_co.push_back(0);
+            for (const uint32_t a : order) {
+                p_ts.push_back(text_start[a]); p_tl.push_back(text_len[a]); p_trc.push_back(text_rc[a]);
+                p_qs.push_back(query_start[a]); p_ql.push_back(query_len[a]); p_bg.push_back(begin[a]);
+                p_mate.push_back(mate[a] == BMV_NO_MATE ? BMV_NO_MATE : where[mate[a]]);
+                if (contig) p_contig.push_back(contig[a]);
+                p_cg.insert(p_cg.end(), cigar + cigar_offset[a], cigar + cigar_offset[a + 1]);
+                p_co.push_back(p_cg.size());
+            }
+            text_start = p_ts.data(); text_len = p_tl.data(); text_rc = p_trc.data(); query_start = p_qs.data(); query_len = p_ql.data();
+            begin = p_bg.data(); cigar_offset = p_co.data(); cigar = p_cg.data(); mate = p_mate.data();
+            if (contig) contig = p_contig.data();
+        }
+        const batch all{reads, n_read_bytes, text_start, text_len, text_rc, query_start, query_len, n};
+        std::vector<uint32_t> share_at =
+            cut_by_cost(n, D, [&](uint32_t a) { return static_cast<uint64_t>(all.query_len[a]) * all.text_len[a] + 1u; });
+        for (size_t d = 1; d < D; d++)
+            if (share_at[d] > 0 && share_at[d] < n && mate[share_at[d] - 1u] == share_at[d]) share_at[d]++;
+        clipping got;                                           // in the devices' order
+        std::vector<uint32_t> got_cut(n, 0);
+        got.score.assign(n, 0);
+        got.clip_left.assign(n, 0);
+        got.clip_right.assign(n, 0);
+        got.nm.assign(n, 0);
+        got.pos.assign(n, 0);
+        got.ref_len.assign(n, 0);
+        got.xcigar_offset.assign(static_cast<size_t>(n) + 1, 0);
+        got.ref_offset.assign(static_cast<size_t>(n) + 1, 0);
+        std::vector<uint64_t> n_x(D, 0), n_r(D, 0), columns(D, 0), pairs(D, 0), bases(D, 0);
+        std::vector<float> ms(D, 0.f);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t a0 = share_at[d], m = share_at[d + 1] - share_at[d];
+            if (m == 0) return;
+            const share s = slice(all, a0, m);
+            std::vector<uint32_t> local(mate + a0, mate + a0 + m);      // the mates' places inside the share
+            for (uint32_t &x : local)
+                if (x != BMV_NO_MATE) x -= a0;
+            check(bmv_overlap(ctx_[d], s.reads, s.n_read_bytes, s.text_start, s.text_len, s.text_rc, s.query_start, s.query_len,
+                              begin + a0, cigar_offset + a0, cigar, local.data(), contig ? contig + a0 : nullptr, s.n, match, penalty,
+                              &n_x[d], &n_r[d]), failed);
+            bmv_last_overlap_stats(ctx_[d], &ms[d], &columns[d], &pairs[d], &bases[d]);
+        });
+        const std::vector<uint64_t> at_x = starts(n_x), at_r = starts(n_r);
+        got.xcigar.assign(at_x[D], 0);
+        got.ref_bases.assign(at_r[D], 0);
+        for_each_device(D, [&](size_t d) {
+            const uint32_t a0 = share_at[d], m = share_at[d + 1] - share_at[d];
+            if (m == 0) return;
+            std::vector<uint64_t> xo(static_cast<size_t>(m) + 1), ro(static_cast<size_t>(m) + 1);
+            check(bmv_overlapped(ctx_[d], got.score.data() + a0, got.clip_left.data() + a0, got.clip_right.data() + a0, got.nm.data() + a0,
+                                 got.pos.data() + a0, got.ref_len.data() + a0, xo.data(), got.xcigar.data() + at_x[d], ro.data(),
+                                 got.ref_bases.data() + at_r[d], got_cut.data() + a0),
+                  "reading the overlap-clipped alignments failed: ");
+            stitch(got.xcigar_offset, a0, m, xo, at_x[d]);
+            stitch(got.ref_offset, a0, m, ro, at_r[d]);
+        });
+        got.xcigar_offset[n] = at_x[D];
+        got.ref_offset[n] = at_r[D];
+        if (D == 1) {
+            out = std::move(got);
+            cut = std::move(got_cut);
+        } else {                                                // back into the caller's order
+            out.score.assign(n, 0); out.clip_left.assign(n, 0); out.clip_right.assign(n, 0);
+            out.nm.assign(n, 0); out.pos.assign(n, 0); out.ref_len.assign(n, 0);
+            cut.assign(n, 0);
+            out.xcigar_offset.assign(static_cast<size_t>(n) + 1, 0);
+            out.ref_offset.assign(static_cast<size_t>(n) + 1, 0);
+            for (uint32_t k = 0; k < n; k++) {
+                const uint32_t a = order[k];
+                out.score[a] = got.score[k]; out.clip_left[a] = got.clip_left[k]; out.clip_right[a] = got.clip_right[k];
+                out.nm[a] = got.nm[k]; out.pos[a] = got.pos[k]; out.ref_len[a] = got.ref_len[k];
+                cut[a] = got_cut[k];
+                out.xcigar_offset[a + 1] = got.xcigar_offset[k + 1] - got.xcigar_offset[k];
+                out.ref_offset[a + 1] = got.ref_offset[k + 1] - got.ref_offset[k];
+            }
+            for (uint32_t a = 0; a < n; a++) {
+                out.xcigar_offset[a + 1] += out.xcigar_offset[a];
+                out.ref_offset[a + 1] += out.ref_offset[a];
+            }
+            out.xcigar.assign(got.xcigar.size(), 0);
+            out.ref_bases.assign(got.ref_bases.size(), 0);
+            for (uint32_t k = 0; k < n; k++) {
+                const uint32_t a = order[k];
+                std::copy(got.xcigar.begin() + static_cast<ptrdiff_t>(got.xcigar_offset[k]),
+                          got.xcigar.begin() + static_cast<ptrdiff_t>(got.xcigar_offset[k + 1]),
+                          out.xcigar.begin() + static_cast<ptrdiff_t>(out.xcigar_offset[a]));
+                std::copy(got.ref_bases.begin() + static_cast<ptrdiff_t>(got.ref_offset[k]),
+                          got.ref_bases.begin() + static_cast<ptrdiff_t>(got.ref_offset[k + 1]),
+                          out.ref_bases.begin() + static_cast<ptrdiff_t>(out.ref_offset[a]));
+            }
+        }
+        pairs_cut = sum(pairs);
+        bases_cut = sum(bases);
+        std::cerr << "[BENCHMARK]\tGPU overlap clipping: " << n << " alignments, " << sum(columns) << " columns, " << pairs_cut
+                  << " pairs cut; " << timing(ms, t0);
+    }
+
     // bmv_split per device: the batch is cut at GROUP borders into ranges of about equal column count (a read's candidates stay
     // on one device: the pick compares them with each other); the chosen indices are rebased to the batch
     void split(const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len, const uint8_t *text_rc,

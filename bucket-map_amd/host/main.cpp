@@ -3,7 +3,7 @@
 // located candidate is verified by a pairwise alignment and written with MAPQ = 60 + score and a CIGAR
 // (--annotate: as forward-strand records with an =/X CIGAR, NM and MD; --clip: those with low-identity ends soft-clipped;
 // --paired: an interleaved FASTQ file, mates placed together and written as pairs; --rescue: a mate without a proper
-// placement sought beside its partner).
+// placement sought beside its partner; --clip-overlap: the two records of a pair soft-clipped where they overlap).
 //
 //   bucketmap -x -i <name> --genome ref.fa                       index only (writes into the cwd)
 //   bucketmap -i <name> -q reads.fq -o out.sam --genome ref.fa    map (indexes first if needed)
@@ -181,6 +181,7 @@ int main(int argc, char **argv) {
         if (args.paired) loc.set_paired(args.frag_min, args.frag_max);
         if (args.frag_auto) loc.set_frag_auto(args.frag_cap, args.frag_min_pairs);
         if (args.rescue) loc.set_rescue(args.rescue_rate);
+        if (args.clip_overlap) loc.set_clip_overlap();
 #endif
         run_indexer();
         loc.initialize(genome, cwd, args.index_indicator);                                    // main.cpp:221

@@ -13,6 +13,7 @@ BEYOND = 2 ** 32 - 1      # BMV_BEYOND: no winner (an empty group) / edits beyon
 PAIR_NONE = 2 ** 64 - 1   # BMV_PAIR_NONE: no proper combination (s1) / none at another locus (s2)
 SPLIT_NONE = -(2 ** 63)   # BMV_SPLIT_NONE: a chosen segment without a competitor (s2)
 SPLIT_MAX_SEGMENTS = 16   # BMV_SPLIT_MAX_SEGMENTS
+NO_MATE = 2 ** 32 - 1     # BMV_NO_MATE: an alignment without a mate in the batch (overlap)
 
 
 class BmvError(RuntimeError):
@@ -68,6 +69,10 @@ SYMBOLS = {
                            C.c_uint32, C.c_uint32, _u64p, _u64p]),
     "bmv_clipped": (C.c_int, [C.c_void_p, _i64p, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p, _u64p, _u8p]),
     "bmv_last_clip_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p]),
+    "bmv_overlap": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p,
+                              C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p]),
+    "bmv_overlapped": (C.c_int, [C.c_void_p, _i64p, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p, _u64p, _u8p, _u32p]),
+    "bmv_last_overlap_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), _u64p, _u64p, _u64p]),
     "bmv_realign": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, _u64p, _u32p, _u8p, _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32,
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
     "bmv_realigned": (C.c_int, [C.c_void_p, _i32p, _u32p, _u8p, _u64p, _u32p]),
@@ -962,6 +967,40 @@ class Verifier:
         ms, cols = C.c_float(), C.c_uint64()
         _check(lib().bmv_last_clip_stats(self._h, C.byref(ms), C.byref(cols)))
         return {"ms_kernels": ms.value, "columns": cols.value}
+
+    def overlap(self, reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset, cigar, mate, contig=None,
+                match=1, penalty=2) -> dict:
+        """bmv_overlap on the alignments clip takes: clip's record (all columns kept when match == penalty == 0), and where
+        the two mates of a pair -- mate[a] the batch index of a's mate, or NO_MATE -- overlap on one contig without
+        containment, both soft-clipped at one cut so that no reference base lies under both (include/bmv.h).  Returns clip's
+        dict plus cut u32[n] (the query bases the cut clipped), pairs_cut and bases_cut.  Leaves the results of every other
+        call untouched."""
+        _keep, n, args = self._annotate_args(reads, text_start, text_len, text_rc, query_start, query_len, begin, cigar_offset,
+                                             cigar)
+        mt = np.ascontiguousarray(mate, np.uint32)
+        ct = None if contig is None else np.ascontiguousarray(contig, np.uint32)
+        if len(mt) != n or (ct is not None and len(ct) != n):
+            raise ValueError("one mate (and one contig) per alignment")
+        n_x, n_r = C.c_uint64(), C.c_uint64()
+        _check(lib().bmv_overlap(self._h, *args[:-1], _p(mt, _u32p), None if ct is None else _p(ct, _u32p), n, int(match),
+                                 int(penalty), C.byref(n_x), C.byref(n_r)))
+        score = np.zeros(n, np.int64)
+        left, right, nm, pos, ref_len, cut = (np.zeros(n, np.uint32) for _ in range(6))
+        xo, ro = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        xc, rb = np.zeros(max(n_x.value, 1), np.uint32), np.zeros(max(n_r.value, 1), np.uint8)
+        _check(lib().bmv_overlapped(self._h, _p(score, _i64p), _p(left, _u32p), _p(right, _u32p), _p(nm, _u32p), _p(pos, _u32p),
+                                    _p(ref_len, _u32p), _p(xo, _u64p), _p(xc, _u32p), _p(ro, _u64p), _p(rb, _u8p), _p(cut, _u32p)))
+        st = self.overlap_stats()
+        return {"score": score, "clip_left": left, "clip_right": right, "nm": nm, "pos": pos, "ref_len": ref_len,
+                "xcigar_offset": xo, "xcigar": xc[: n_x.value], "ref_offset": ro, "ref_bases": rb[: n_r.value], "cut": cut,
+                "pairs_cut": st["pairs_cut"], "bases_cut": st["bases_cut"]}
+
+    def overlap_stats(self) -> dict:
+        """Of the last overlap: kernel ms (all passes and the prefix sums), the alignment columns walked, the pairs cut and the
+        query bases the cuts clipped."""
+        ms, cols, pairs, bases = C.c_float(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().bmv_last_overlap_stats(self._h, C.byref(ms), C.byref(cols), C.byref(pairs), C.byref(bases)))
+        return {"ms_kernels": ms.value, "columns": cols.value, "pairs_cut": pairs.value, "bases_cut": bases.value}
 
     def _segments(self, n, n_groups, max_segments) -> dict:
         score, g_lo, g_hi = (np.zeros(max(n, 1), np.int64) for _ in range(3))

@@ -28,7 +28,8 @@
  *   [0, ref_len[refID]): what lies beyond the end of the reference is not counted, and its query bases are not either.
  *
  *   DEPTH.  depth(r, p) = the number of (clipped) blocks of counted records on r that hold p.  D and N do not count, mates
- *   that overlap count twice, and there is no base-quality or MAPQ threshold.
+ *   that overlap count twice (unless the records were written with `--clip-overlap`, which soft-clips the overlap away), and
+ *   there is no base-quality or MAPQ threshold.
  *
  *   RUNS.  Per reference in ascending order, the maximal intervals [start, end) of equal depth > 0, as (r, start, end,
  *   depth): references ascending, starts ascending.  A run never spans two references.

@@ -49,7 +49,7 @@
  *   2^32 - 1), 12 DP = D, 13 .. 15 PL[RR, RA, AA].  Calls are listed in (reference, anchor) order.
  *
  * LEFT OUT, on purpose: more than one ALT per anchor; the base qualities of inserted bases; a homopolymer- or repeat-aware
- * error model; realignment of reads around a candidate; the overlap of two mates; insertions above 32 bases as alleles (they
+ * error model; realignment of reads around a candidate; the overlap of two mates (unless the records were written with `--clip-overlap`); insertions above 32 bases as alleles (they
  * count as `other`); other ploidies and several samples; windows for genomes whose state does not fit.
  *
  * A context is used as bmn_begin, any number of bmn_add, bmn_finish, then any number of bmn_alleles / bmn_calls / bmn_cover_at;

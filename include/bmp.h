@@ -48,7 +48,7 @@
  *
  * LEFT OUT, on purpose: the alleles, lengths and sequences of indels (only that there is one); the CG:B,I tag of a record
  * with the placeholder (KNOWN DEPARTURE, as in bmc.h: such a record is left out and counted in n_left_out); removing the
- * overlap of two mates (a fragment's overlap counts twice); genotypes and their likelihoods; VCF; windows for genomes whose
+ * overlap of two mates (a fragment's overlap counts twice, unless the records were written with `--clip-overlap`); genotypes and their likelihoods; VCF; windows for genomes whose
  * state does not fit.
  *
  * A context is used as bmp_begin, any number of bmp_add, bmp_finish, then any number of bmp_sites / bmp_counts_at; bmp_begin

@@ -303,6 +303,7 @@ int  bmv_last_rescue_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_cells, u
  *                                        puts bmv_results and bmv_last_stats back as it found them
  *   bmv_segments, bmv_last_split_stats   bmv_split, bmv_split_pick
  *   bmv_annotations, bmv_clipped, bmv_realigned, bmv_leftaligned and their stats: the one call each is named after
+ *   bmv_overlapped, bmv_last_overlap_stats   bmv_overlap
  * A call changes nothing outside its row.  n = 0 is a successful call: it leaves empty results and zero counts in its row.  A
  * call refused by its checks before anything runs -- every BMV_ERR_ARG, and BMV_ERR_UNSUPPORTED from bmv_align_long,
  * bmv_realign and bmv_leftalign -- changes nothing at all.  One refusal comes later: bmv_align_bounded, bmv_align_best and
@@ -396,6 +397,60 @@ int  bmv_clipped(bmv_ctx *ctx, int64_t *out_score, uint32_t *out_clip_left, uint
 /* Kernel time of the last bmv_clip in ms (range pass, count pass, prefix sums, write pass) and the alignment columns it walked
  * (sum of all CIGAR entry lengths). */
 int  bmv_last_clip_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_columns);
+
+/* The overlap pass: bmv_clip's record for the two mates of a pair, soft-clipped at one cut so that no reference base lies under
+ * both.  In short-insert libraries most proper pairs overlap, and everything that counts bases per reference position (depth,
+ * pileup, genotypes) sees the fragment twice there; this is what fgbio ClipBam --clip-overlapping-reads and bamUtil clipOverlap
+ * do to a finished BAM, done where both mates and their edit paths are at hand.  A call of its own, of the bmv_annotate /
+ * bmv_clip family.
+ * Inputs: bmv_clip's (the views, begin, M/I/D entries 5' to 3' of the query, match, penalty) plus
+ *   mate[a]             the batch index of alignment a's mate, or BMV_NO_MATE
+ *   contig[a]           as bmv_pair takes it; NULL: all on one contig
+ * Mode.  match == 0 && penalty == 0 means "no score clipping": the base range of every alignment is all its columns [0, C) and
+ * out_score is 0.  Otherwise 1 <= match, penalty <= 1024 and the base range [l, r) is exactly bmv_clip's.
+ * Coordinates.  Columns are in FORWARD-strand order, as bmv_annotate emits them.  g(i) = text_start[a] + (bmv_annotate's pos) +
+ * (the reference-consuming columns before i), in signed 64-bit arithmetic, in the concatenated genome; G0 = g(l), G1 = g(r).
+ * Which pairs are cut.  A pair (a, b = mate[a]) is cut only if all of these hold, otherwise both mates come back exactly as the
+ * base pass gives them:
+ *   both base ranges are non-empty;  contig[a] == contig[b];
+ *   with `first` the mate of smaller (G0, index) and `second` the other: G1(first) <= G1(second);
+ *   o = G1(first) - G0(second) > 0;
+ *   both columns named under "kept ranges" exist.
+ * Containment (G1(first) > G1(second)), disjoint spans, different contigs and an empty range are all "not cut".  Strands are not
+ * looked at.
+ * The cut.  m = G0(second) + floor(o / 2).
+ * Kept ranges.  `first` keeps [l, r'): r' - 1 is the last M column (= or X, not I or D) of [l, r) with g < m.  `second` keeps
+ * [l', r): l' is the first M column of [l, r) with g >= m.  So the kept ranges never begin or end on I or D at the cut, no
+ * reference position lies under both, and G0(first) and G1(second) do not move.
+ * Output per alignment: bmv_clipped's layout, value for value, for the final range -- out_clip_left, out_clip_right, out_pos,
+ * out_ref_len, out_nm, out_xcigar with S entries, out_ref_bases and the offsets -- with
+ *   out_score[a]        match x (the = columns kept) - penalty x (the X, I and D columns kept)
+ *   out_cut[a]          the query bases the cut added to the soft clips; 0 for an untouched alignment
+ * Two identities follow.  With mate[a] == BMV_NO_MATE everywhere and match > 0 the outputs are bmv_clipped's, byte for byte.  With
+ * match == penalty == 0 (and no mates) they are bmv_annotations' (no S entries, clips 0).
+ * LEFT OUT: merging the two mates' base qualities where they agree; hard clips; any tag that records the cut; containment and
+ * dovetail pairs; an insertion exactly at the cut, which is clipped in BOTH mates (its columns carry g = m in the first and lie
+ * before l' in the second), so its bases are seen in neither.
+ * Checks on the host before anything is launched: bmv_clip's, plus: the scores are (0, 0) or in range; mate[a] < n or
+ * BMV_NO_MATE; mate[a] != a; mate[mate[a]] == a; text_start below 2^62.  BMV_ERR_ARG, the message names the alignment, nothing
+ * ran and the context stays usable.  n = 0 succeeds.  The call leaves untouched what every other result or stats call returns,
+ * and a pending bmv_paired_begin stays pending.
+ * How (bmv_overlap.hip.h): a wave per alignment and bmv_annotate's walk; the two mates meet between launches, no kernel waits
+ * for another workgroup.  bmv_clip's range pass (or nothing) gives l, r; a span pass G0, G1; a pass per alignment reads both mates'
+ * spans and decides m; a pass restricts the range -- l' and r' depend on the CIGAR entries alone, every M column being = or X --;
+ * then bmv_clip's count pass, two prefix sums and its write pass run on the final range. */
+#define BMV_NO_MATE UINT32_MAX
+int  bmv_overlap(bmv_ctx *ctx, const uint8_t *reads, uint64_t n_read_bytes, const uint64_t *text_start, const uint32_t *text_len,
+                 const uint8_t *text_rc, const uint64_t *query_start, const uint32_t *query_len, const uint32_t *begin,
+                 const uint64_t *cigar_offset, const uint32_t *cigar, const uint32_t *mate, const uint32_t *contig, uint32_t n,
+                 uint32_t match, uint32_t penalty, uint64_t *total_xcigar, uint64_t *total_ref_bases);
+/* Results of the last bmv_overlap; any pointer may be NULL. */
+int  bmv_overlapped(bmv_ctx *ctx, int64_t *out_score, uint32_t *out_clip_left, uint32_t *out_clip_right, uint32_t *out_nm,
+                    uint32_t *out_pos, uint32_t *out_ref_len, uint64_t *out_xcigar_offset, uint32_t *out_xcigar,
+                    uint64_t *out_ref_offset, uint8_t *out_ref_bases, uint32_t *out_cut);
+/* Of the last bmv_overlap: the kernels' time in ms (every pass and the prefix sums), the alignment columns it walked (sum of all
+ * CIGAR entry lengths), the pairs cut and the sum of out_cut.  Any pointer may be NULL. */
+int  bmv_last_overlap_stats(bmv_ctx *ctx, float *ms_kernels, uint64_t *n_columns, uint64_t *pairs_cut, uint64_t *bases_cut);
 
 /* The realignment pass: an affine-gap alignment beside a known edit path.  Everything the aligners return comes from unit
  * costs, under which a 6-base deletion and six scattered 1-base gaps cost the same, so the traceback's tie rules decide where
