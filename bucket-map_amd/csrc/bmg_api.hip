@@ -4,6 +4,7 @@
 #include "../../include/bmg.h"
 
 #include "bm_hip_util.h"
+#include "bmg_ctx.hip.h"
 #include "bmg_kernels.hip.h"
 #include "bms_ctx.hip.h"
 
@@ -15,22 +16,6 @@ static_assert(BMG_OK == BMS_OK && BMG_ERR_ARG == BMS_ERR_ARG && BMG_ERR_HIP == B
 static_assert(BMG_N_CELLS == bmg::kCells && BMG_N_GENOTYPES == bmg::kGenotypes && BMG_SITE_WORDS == bmg::kSiteWords && BMG_CALL_WORDS == bmg::kCallWords &&
                   BMG_GENOTYPED == bmg::kGenotyped && BMG_VARIANT == bmg::kVariant,
               "bmg.h and bmg_kernels.hip.h disagree");
-
-struct bmg_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool begun = false;
-    std::vector<uint32_t> ref_len;
-    std::vector<uint64_t> ref_base;         // n_ref + 1: reference r has the slots ref_base[r] .. ref_base[r + 1] - 1
-    bmg::params pr{0, 13, 30, 60, 3000};
-    uint64_t n_slots = 0;
-    DevBuf<uint8_t> in, skip;
-    DevBuf<uint64_t> rec_offset, d_ref_base;
-    DevBuf<uint32_t> d_ref_len, sites, calls;
-    DevBuf<unsigned long long> cell;
-    float ms_add = 0.f, ms_call = 0.f;
-};
 
 namespace {
 

@@ -13,19 +13,14 @@
 // No kernel waits for another workgroup.
 #pragma once
 
+#include "bmg_rule.hip.h"
 #include "bmp_walk.hip.h"
 
 namespace bmg {
 
 constexpr uint32_t kThreads = bmp::kThreads;
-constexpr uint32_t kCells = 4, kGenotypes = 10;          // BMG_N_CELLS, BMG_N_GENOTYPES
 constexpr uint32_t kSiteWords = 12, kCallWords = 24;     // BMG_SITE_WORDS, BMG_CALL_WORDS
 constexpr uint32_t kGenotyped = 1, kVariant = 2, kKindSnv = 1;
-constexpr uint64_t kU32Max = 0xFFFFFFFFull;
-
-struct params {
-    uint32_t min_mapq, min_bq, q_absent, q_cap, prior;
-};
 
 // the action of bmp's walkers: a base of sufficient quality and a plain letter adds its count and its quality in one atomic
 struct cell_action {
@@ -50,8 +45,6 @@ __global__ __launch_bounds__(kThreads) void add_kernel(const uint8_t *__restrict
                                                        unsigned long long *__restrict__ cell) {
     bmp::add_records(in, rec_offset, n, skip, ref_len, ref_base, n_ref, pr.min_mapq, cell_action{cell, pr.min_bq, pr.q_absent, pr.q_cap}, nullptr);
 }
-
-__device__ __forceinline__ uint32_t sat32(uint64_t v) { return v > kU32Max ? (uint32_t)kU32Max : (uint32_t)v; }
 
 // out[24 i ..] = the call of sites[12 i ..] from the cells.  The host has checked every site's reference and position; a
 // site that fails the check here all the same reads no cell and is written as not genotyped with n = 0.
@@ -80,23 +73,14 @@ __global__ __launch_bounds__(kThreads) void call_kernel(const uint32_t *__restri
         o[3] = o[4] = o[5] = make_uint4(0, 0, 0, 0);
         return;
     }
-    uint64_t M[4], T[4], all = 0;
-#pragma unroll
-    for (uint32_t a = 0; a < 4; a++) {
-        M[a] = 100u * Q[a] + 477u * n[a];                // < 2^42
-        T[a] = 301u * n[a];
-        all += M[a];
-    }
     uint64_t L[kGenotypes];
+    costs(n, Q, R, prior, L);
     uint64_t least = 0, l_rr = 0;                        // tracked in registers: L is only ever indexed by unrolled counters
     uint32_t k = 0, best = 0, best_a = 0, best_b = 0, k_rr = 0;
 #pragma unroll
     for (uint32_t b = 0; b < 4; b++)
 #pragma unroll
         for (uint32_t a = 0; a <= b; a++, k++) {
-            const uint64_t like = a == b ? all - M[a] : T[a] + T[b] + all - M[a] - M[b];
-            const uint32_t others = (a != R ? 1u : 0u) + (b != R && b != a ? 1u : 0u);
-            L[k] = like + (uint64_t)prior * others;
             if (a == R && b == R) k_rr = k, l_rr = L[k];
             if (k == 0 || L[k] < least) least = L[k], best = k, best_a = a, best_b = b;   // the smallest k among equals
         }

@@ -44,6 +44,8 @@
 // genotype_add too, and after pileup_finish the sites it lists go to genotype_call.
 // INDEL MODE (--vcf-indels; include/bmn.h states the rule), on top of genotype mode: every piece that goes to genotype_add
 // goes to indel_add too, indel_begin before them and indel_finish after them.
+// BLOCK MODE (--gvcf; include/bmr.h states the rule), on top of genotype mode: after genotype_call, and after indel_finish where
+// there is one, the positions of the variant calls go to refblocks as excluded intervals.
 #pragma once
 
 #include "bgzf.h"
@@ -199,6 +201,9 @@ class bam_sorter {
     bool indel_ = false;                             // indel mode (with genotype mode)
     indel_params indel_params_;
     indel_result indel_result_;
+    bool refblocks_ = false;                         // block mode (with genotype mode)
+    std::vector<uint32_t> refblock_bands_;
+    refblock_result refblock_result_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -298,6 +303,13 @@ public:
         indel_params_ = pr;
     }
     const indel_result &indel() const { return indel_result_; }
+    // block mode: after set_genotype and before the first add(); after finish(), the reference blocks between the variant calls
+    void set_refblocks(const std::vector<uint32_t> &bands) {
+        if (!genotype_) throw std::runtime_error("--gvcf: the blocks are made of the genotype caller's cells");
+        refblocks_ = true;
+        refblock_bands_ = bands;
+    }
+    const refblock_result &refblocks() const { return refblock_result_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -428,6 +440,9 @@ public:
             for (size_t k = 0; k < pileup_result_.n_sites(); k++) genotype_result_.n_snv_sites += pileup_result_.sites[kPileupSiteWords * k + 11] & 1u;
         }
         if (indel_) z_->indel_finish(indel_result_);
+        if (refblocks_)
+            z_->refblocks(pileup_ref_len_.data(), pileup_ref_len_.size(), pileup_ref_bases_.data(), refblock_bands_,
+                          refblock_excluded(genotype_result_, indel_ ? &indel_result_.calls : nullptr, pileup_ref_len_), refblock_result_);
     }
 
 private:

@@ -9,6 +9,7 @@
 #include "pileup.h"
 #include "genotype.h"
 #include "indel.h"
+#include "refblocks.h"
 #include "markdup.h"
 
 #include <algorithm>
@@ -388,6 +389,14 @@ struct block_compressor {
         indel_.add(in, rec_offset, n_records, skip);
     }
     virtual void indel_finish(indel_result &out) { indel_.finish(out); }
+
+    // --gvcf (include/bmr.h states the rule): after genotype_begin and the genotype_add calls, the reference blocks of the cells
+    // they filled, against ref_bases (ref_len[r] bytes each), under the band bounds and outside the excluded intervals (three
+    // words each).  The default is the host rule of refblocks.h; the product plugs in bmr_run and bmr_blocks.
+    virtual void refblocks(const uint32_t *ref_len, size_t n_ref, const uint8_t *const *ref_bases, const std::vector<uint32_t> &bands,
+                           const std::vector<uint32_t> &exclude, refblock_result &out) {
+        refblocks_of(genotype_.cells(), std::vector<uint32_t>(ref_len, ref_len + n_ref), ref_bases, bands, exclude, out);
+    }
 
 private:
     depth_counter depth_;

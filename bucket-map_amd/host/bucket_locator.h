@@ -483,6 +483,9 @@ struct vcf_options {
     std::string sample = "sample";
     bool indels = false;            // --vcf-indels: the indel calls of include/bmn.h, merged into the file by (reference, POS)
     indel_params indel{};
+    std::filesystem::path gvcf;     // --gvcf: the same calls and the reference blocks of include/bmr.h between them; with or without `file`
+    std::vector<uint32_t> gvcf_bands;
+    bool on() const { return !file.empty() || !gvcf.empty(); }
 };
 
 class sam_text {
@@ -506,7 +509,7 @@ class sam_text {
     pileup_thresholds pileup_thresholds_;
     const std::vector<std::string> *pileup_seqs_ = nullptr;   // ... the bases of the header's references, each of its length
     vcf_options vcf_;                      // sorted BAM: --vcf, its file may be empty; it counts the pileup whether that has a file or not
-    bool pileup_on() const { return !pileup_file_.empty() || !vcf_.file.empty(); }
+    bool pileup_on() const { return !pileup_file_.empty() || vcf_.on(); }
 
     // A file of --depth / --coverage / --pileup: written beside its place and moved there when it is complete, so that a failure
     // leaves nothing half-written (and nothing at all under the final name).
@@ -542,8 +545,9 @@ class sam_text {
         const genotype_result &res = sorter_->genotype();
         std::vector<uint32_t> lens;
         for (size_t r = 0; r < ref_ids_.size(); r++) lens.push_back((*pileup_seqs_)[r].size());   // set_pileup has checked them
-        if (!vcf_.indels) write_whole(vcf_.file, [&](std::ostream &f) { write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual); });
-        else {
+        // with --gvcf alone there is no file of --vcf: the calls go into the gVCF only
+        if (!vcf_.file.empty() && !vcf_.indels) write_whole(vcf_.file, [&](std::ostream &f) { write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual); });
+        else if (!vcf_.file.empty()) {
             // the indel lines go between the SNV lines by (reference, POS); at an equal POS the SNV comes first
             const indel_result &ind = sorter_->indel();
             size_t next = 0;
@@ -563,6 +567,34 @@ class sam_text {
         std::cerr << "[INFO]\t\tGenotypes: " << s.variants << " variants (" << s.het << " het, " << s.hom << " hom, " << s.low_qual
                   << " below QUAL) at " << res.n_snv_sites << " SNV sites\n";
         if (vcf_.indels) std::cerr << "[INFO]\t\t" << indel_summary_line(summarize_indels(sorter_->indel(), vcf_.min_qual)) << "\n";
+        if (!vcf_.gvcf.empty()) write_gvcf(res, lens);
+    }
+    // --gvcf: the lines of --vcf, and between them by (reference, POS) one line per reference block.  No two lines share a POS:
+    // the position of every variant line is excluded from the blocks.
+    void write_gvcf(const genotype_result &res, const std::vector<uint32_t> &lens) {
+        const refblock_result &blk = sorter_->refblocks();
+        const indel_result &ind = sorter_->indel();
+        size_t next = 0, next_block = 0;
+        const vcf_between between = [&](std::string &buf, uint32_t ref, uint64_t pos) {
+            for (;;) {
+                while (vcf_.indels && next < ind.n_calls() && !(ind.calls[kIndelCallWords * next + 5] & kIndelVariant)) next++;
+                const uint32_t *c = vcf_.indels && next < ind.n_calls() ? ind.calls.data() + kIndelCallWords * next : nullptr;
+                const uint32_t *b = next_block < blk.n_blocks() ? blk.blocks.data() + kRefBlockWords * next_block : nullptr;
+                if (c && (c[0] > ref || (c[0] == ref && static_cast<uint64_t>(c[1]) + 1 >= pos))) c = nullptr;
+                if (b && (b[0] > ref || (b[0] == ref && static_cast<uint64_t>(b[1]) + 1 >= pos))) b = nullptr;
+                if (!c && !b) break;
+                if (c && (!b || c[0] < b[0] || (c[0] == b[0] && c[1] <= b[1])))
+                    append_indel_vcf_line(buf, c, ref_ids_.at(c[0]), (*pileup_seqs_)[c[0]], vcf_.min_qual), next++;
+                else
+                    append_block_line(buf, b, ref_ids_.at(b[0]), reinterpret_cast<const uint8_t *>((*pileup_seqs_)[b[0]].data())), next_block++;
+            }
+        };
+        const char *const more[3] = {gvcf_alt_header(), gvcf_info_header(), gvcf_format_header()};
+        write_whole(vcf_.gvcf, [&](std::ostream &f) {
+            next = next_block = 0;
+            write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, vcf_.indels ? indel_vcf_header() : nullptr, &between, more);
+        });
+        std::cerr << "[INFO]\t\t" << refblock_summary_line(blk, lens) << "\n";
     }
     void write_pileup() {
         const pileup_result &res = sorter_->pileup();
@@ -589,8 +621,9 @@ class sam_text {
             bases[r] = reinterpret_cast<const uint8_t *>(seq.data());
         }
         sorter_->set_pileup(ref_lengths, bases, pileup_thresholds_);
-        if (!vcf_.file.empty()) sorter_->set_genotype(vcf_.params);
-        if (!vcf_.file.empty() && vcf_.indels) sorter_->set_indel(vcf_.indel);
+        if (vcf_.on()) sorter_->set_genotype(vcf_.params);
+        if (vcf_.on() && vcf_.indels) sorter_->set_indel(vcf_.indel);
+        if (!vcf_.gvcf.empty()) sorter_->set_refblocks(vcf_.gvcf_bands);
     }
 
     // BAM: buf_ (whole lines) -> records -> the whole blocks among them (all of them when `all`), left in buf_ for the writer
@@ -675,7 +708,7 @@ public:
         depth_file_ = sorter_ ? depth_file : std::filesystem::path();
         coverage_file_ = sorter_ ? coverage_file : std::filesystem::path();
         pileup_file_ = sorter_ ? pileup_file : std::filesystem::path();
-        if (!sorter_) vcf_.file.clear();
+        if (!sorter_) vcf_.file.clear(), vcf_.gvcf.clear();
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
@@ -713,7 +746,7 @@ public:
             }
             if (!depth_file_.empty() || !coverage_file_.empty()) write_depth_files();
             if (!pileup_file_.empty()) write_pileup();
-            if (!vcf_.file.empty()) write_vcf();
+            if (vcf_.on()) write_vcf();
         } else if (bam_ && !closed_) {
             encode_buffer(true);
             buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -1302,7 +1335,7 @@ public:
         // [k * bucket_length, (k + 1) * bucket_length): for one FASTA record that is the record itself, cut or filled up to whole
         // buckets; what no bucket's sequence fills has no reference allele (N).
         std::vector<std::string> pileup_bases;
-        if ((!_pileup_file.empty() || !_vcf.file.empty()) && genome_) {
+        if ((!_pileup_file.empty() || _vcf.on()) && genome_) {
             for (size_t b = 0, r = 0; r < h.ref_ids.size(); r++) {
                 pileup_bases.emplace_back(h.ref_lengths[r], 'N');
                 for (size_t at = 0; at < h.ref_lengths[r]; at += bucket_length, b++) {

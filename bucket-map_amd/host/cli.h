@@ -93,6 +93,10 @@ struct cmd_arguments {
                                   // the rule); sites by --pileup-min-mapq / -min-alt / -min-frac.  It does not imply --affine --left-align
     unsigned long vcf_indel_qual = 30, vcf_indel_prior = 40;   // --vcf-indel-qual N (phred, 1..93) / --vcf-indel-prior N (phred, 0..255)
     std::string vcf_indel_opt;    // the first of those two given: refused without --vcf-indels
+    std::filesystem::path gvcf_path{};  // --gvcf FILE (-o x.bam only, implies what --vcf implies; with or without --vcf FILE): the calls of
+                                  // --vcf and, between them, the hom-ref blocks of every other base as VCF 4.2 (include/bmr.h states the rule)
+    std::vector<uint32_t> gvcf_bands{1, 10, 20, 30, 40, 50, 60, 70, 80, 90, 99};   // --gvcf-bands B1,B2,...: the GQ bounds at which a block ends
+    bool gvcf_bands_given = false;   // refused without --gvcf
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -410,6 +414,28 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             if (a.vcf_opt.empty()) a.vcf_opt = opt;
             if (a.vcf_indel_opt.empty()) a.vcf_indel_opt = opt;
         }
+        else if (opt == "--gvcf") {
+            a.gvcf_path = value();
+            a.sort = true;
+        }
+        else if (opt == "--gvcf-bands") {
+            const std::string s = value();
+            std::vector<uint32_t> bands;
+            bool good = !s.empty();
+            for (size_t at = 0; good && at <= s.size();) {
+                const size_t e = std::min(s.find(',', at), s.size());
+                unsigned long v = 0;
+                good = e > at && e - at <= 2;
+                for (size_t k = at; good && k < e; k++) good = s[k] >= '0' && s[k] <= '9', v = 10 * v + static_cast<unsigned long>(s[k] - '0');
+                good = good && v >= 1 && v <= 99 && (bands.empty() || v > bands.back()) && bands.size() < 16;
+                if (good) bands.push_back(static_cast<uint32_t>(v));
+                at = e + 1;
+            }
+            if (!good)
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be at most 16 ascending numbers in 1..99 with commas between them, such as 20,60.");
+            a.gvcf_bands = bands;
+            a.gvcf_bands_given = true;
+        }
         else if (opt == "--vcf-sample") {
             a.vcf_sample = value();
             if (a.vcf_sample.empty() || a.vcf_sample.find_first_of("\t\n\r") != std::string::npos)
@@ -440,18 +466,18 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         bam.replace_extension(".bam");
         throw parser_error(std::string("Validation failed for option ") +
                            (!a.depth_path.empty() ? "--depth" : !a.coverage_path.empty() ? "--coverage" : !a.pileup_path.empty() ? "--pileup" :
-                            !a.vcf_path.empty() ? "--vcf" : a.markdup ? "--markdup" : "--sort") +
+                            !a.vcf_path.empty() ? "--vcf" : !a.gvcf_path.empty() ? "--gvcf" : a.markdup ? "--markdup" : "--sort") +
                            ": only BAM output is sorted and indexed; write -o " + bam.string() + " instead of -o " +
                            a.output_sam_path.string() + ".");
     }
-    if (!a.pileup_threshold_opt.empty() && a.pileup_path.empty() && a.vcf_path.empty())
+    if (!a.pileup_threshold_opt.empty() && a.pileup_path.empty() && a.vcf_path.empty() && a.gvcf_path.empty())
         throw parser_error("Validation failed for option " + a.pileup_threshold_opt + ": it is a threshold of --pileup FILE, which is not given.");
     if (!a.pileup_path.empty() && a.output_sam_path.empty() && !a.only_indexer)
         throw parser_error("Validation failed for option --pileup: the pileup is that of the records of a sorted BAM file; name one with -o x.bam.");
     if (!a.pileup_path.empty() && (a.pileup_path == a.depth_path || a.pileup_path == a.coverage_path))
         throw parser_error("Validation failed for option --pileup: " + a.pileup_path.string() + " is the file of " +
                            (a.pileup_path == a.depth_path ? "--depth" : "--coverage") + " too.");
-    if (!a.vcf_opt.empty() && a.vcf_path.empty())
+    if (!a.vcf_opt.empty() && a.vcf_path.empty() && a.gvcf_path.empty())
         throw parser_error("Validation failed for option " + a.vcf_opt + ": it is an option of --vcf FILE, which is not given.");
     if (!a.vcf_indel_opt.empty() && !a.vcf_indels)
         throw parser_error("Validation failed for option " + a.vcf_indel_opt + ": it is an option of --vcf-indels, which is not given.");
@@ -460,6 +486,13 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (!a.vcf_path.empty() && (a.vcf_path == a.pileup_path || a.vcf_path == a.depth_path || a.vcf_path == a.coverage_path))
         throw parser_error("Validation failed for option --vcf: " + a.vcf_path.string() + " is the file of " +
                            (a.vcf_path == a.pileup_path ? "--pileup" : a.vcf_path == a.depth_path ? "--depth" : "--coverage") + " too.");
+    if (a.gvcf_bands_given && a.gvcf_path.empty())
+        throw parser_error("Validation failed for option --gvcf-bands: it is an option of --gvcf FILE, which is not given.");
+    if (!a.gvcf_path.empty() && a.output_sam_path.empty() && !a.only_indexer)
+        throw parser_error("Validation failed for option --gvcf: the genotypes are those of the records of a sorted BAM file; name one with -o x.bam.");
+    if (!a.gvcf_path.empty() && (a.gvcf_path == a.vcf_path || a.gvcf_path == a.pileup_path || a.gvcf_path == a.depth_path || a.gvcf_path == a.coverage_path))
+        throw parser_error("Validation failed for option --gvcf: " + a.gvcf_path.string() + " is the file of " +
+                           (a.gvcf_path == a.vcf_path ? "--vcf" : a.gvcf_path == a.pileup_path ? "--pileup" : a.gvcf_path == a.depth_path ? "--depth" : "--coverage") + " too.");
     if ((!a.depth_path.empty() || !a.coverage_path.empty()) && a.output_sam_path.empty() && !a.only_indexer)
         throw parser_error(std::string("Validation failed for option ") + (!a.depth_path.empty() ? "--depth" : "--coverage") +
                            ": depth and coverage are those of the records of a sorted BAM file; name one with -o x.bam.");
@@ -470,7 +503,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
     if (a.paired) a.best = a.annotate = true;
     if (a.affine || a.left_align) a.annotate = true;
 #ifdef BM_ALIGN
-    if (!a.pileup_path.empty() || !a.vcf_path.empty()) a.annotate = true;   // the reference's own record layout is not forward-strand: a pileup over it would be wrong
+    if (!a.pileup_path.empty() || !a.vcf_path.empty() || !a.gvcf_path.empty()) a.annotate = true;   // the reference's own record layout is not forward-strand: a pileup over it would be wrong
 #endif
     return a;
 }

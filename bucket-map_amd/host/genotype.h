@@ -204,17 +204,22 @@ using vcf_between = std::function<void(std::string &buf, uint32_t ref, uint64_t 
 // --vcf FILE: VCF 4.2, the header, then one line per VARIANT call in the order of the calls.  more_info, where given, is a
 // further INFO line of the header.
 inline void write_vcf_file(std::ostream &out, const genotype_result &res, const std::vector<std::string> &ref_ids, const std::vector<uint32_t> &ref_len,
-                           const std::string &sample, uint32_t min_qual, const char *more_info = nullptr, const vcf_between *between = nullptr) {
-    std::string buf = "##fileformat=VCFv4.2\n##source=bucketmap --vcf\n";
+                           const std::string &sample, uint32_t min_qual, const char *more_info = nullptr, const vcf_between *between = nullptr,
+                           const char *const *gvcf = nullptr) {
+    // gvcf, where given, makes it the header of --gvcf: three more lines, one for ALT, one for INFO and one for FORMAT
+    std::string buf = gvcf ? "##fileformat=VCFv4.2\n##source=bucketmap --gvcf\n" : "##fileformat=VCFv4.2\n##source=bucketmap --vcf\n";
     for (size_t r = 0; r < ref_ids.size(); r++) buf += "##contig=<ID=" + ref_ids[r] + ",length=" + std::to_string(ref_len.at(r)) + ">\n";
+    if (gvcf) buf += gvcf[0];
     buf += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Counted bases A, C, G and T of sufficient base quality\">\n";
     if (more_info) buf += more_info;
+    if (gvcf) buf += gvcf[1];
     buf += "##FILTER=<ID=LowQual,Description=\"QUAL below " + std::to_string(min_qual) + "\">\n";
     buf += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
     buf += "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Counted bases A, C, G and T of sufficient base quality\">\n";
     buf += "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Counted bases of the reference and of each alternative allele\">\n";
     buf += "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the cost of the second-best genotype, at most 99\">\n";
     buf += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype costs with the prior, the best at 0\">\n";
+    if (gvcf) buf += gvcf[2];
     buf += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample + "\n";
     for (size_t k = 0; k < res.n_calls(); k++) {
         const uint32_t *c = res.calls.data() + kGenotypeCallWords * k;

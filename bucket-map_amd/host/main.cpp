@@ -152,9 +152,10 @@ int main(int argc, char **argv) {
             const bm::pileup_thresholds pileup_th{static_cast<uint32_t>(args.pileup_min_mapq), static_cast<uint32_t>(args.pileup_min_bq),
                                                   static_cast<uint32_t>(args.pileup_min_alt), static_cast<uint32_t>(args.pileup_min_frac_ppm)};
             if (!args.pileup_path.empty()) loc.set_pileup(args.pileup_path, pileup_th);   // --pileup: their variant sites against the genome
-            if (!args.vcf_path.empty()) {                                         // --vcf: the genotypes at those sites; MAPQ and base quality as the pileup's
+            if (!args.vcf_path.empty() || !args.gvcf_path.empty()) {              // --vcf: the genotypes at those sites; MAPQ and base quality as the pileup's
                 bm::vcf_options vcf;
                 vcf.file = args.vcf_path;
+                vcf.gvcf = args.gvcf_path, vcf.gvcf_bands = args.gvcf_bands;      // --gvcf: the same calls and the hom-ref blocks between them
                 vcf.params.min_mapq = pileup_th.min_mapq, vcf.params.min_bq = pileup_th.min_bq;
                 vcf.params.prior = static_cast<uint32_t>(100 * args.vcf_prior);
                 vcf.min_qual = static_cast<uint32_t>(args.vcf_min_qual);

@@ -5,6 +5,7 @@
 #include "../../include/bmp.h"
 #include "../../include/bmg.h"
 #include "../../include/bmn.h"
+#include "../../include/bmr.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -125,6 +126,7 @@ public:
         if (bmz_create(device, &ctx_) != BMZ_OK) throw std::runtime_error(std::string("bmz_create: ") + bmz_last_error());
     }
     ~gpu_block_compressor() override {
+        bmr_destroy(blocks_);
         bmn_destroy(indel_);
         bmg_destroy(geno_);
         bmp_destroy(pile_);
@@ -270,9 +272,22 @@ public:
         if (bmn_alleles(indel_, 0, n_alleles, out.alleles.data()) != BMN_OK) throw std::runtime_error(std::string("bmn_alleles: ") + bmn_last_error());
         if (bmn_calls(indel_, 0, n_calls, out.calls.data()) != BMN_OK) throw std::runtime_error(std::string("bmn_calls: ") + bmn_last_error());
     }
+    // --gvcf: the reference blocks of the genotype caller's cells on the same device (bmr_*: the rule of include/bmr.h, which
+    // is the host default's)
+    void refblocks(const uint32_t *ref_len, size_t n_ref, const uint8_t *const *ref_bases, const std::vector<uint32_t> &bands,
+                   const std::vector<uint32_t> &exclude, bm::refblock_result &out) override {
+        if (!blocks_ && bmr_create(device_, &blocks_) != BMR_OK) throw std::runtime_error(std::string("bmr_create: ") + bmr_last_error());
+        uint64_t n_blocks = 0;
+        if (bmr_run(blocks_, genotyper(), ref_bases, bands.data(), static_cast<uint32_t>(bands.size()), exclude.data(), exclude.size() / 3, &n_blocks) != BMR_OK)
+            throw std::runtime_error(std::string("bmr_run: ") + bmr_last_error());
+        out.blocks.assign(static_cast<size_t>(n_blocks) * bm::kRefBlockWords, 0);
+        if (bmr_blocks(blocks_, 0, n_blocks, out.blocks.data()) != BMR_OK) throw std::runtime_error(std::string("bmr_blocks: ") + bmr_last_error());
+        bm::refblock_count_rest(out, std::vector<uint32_t>(ref_len, ref_len + n_ref), exclude);
+    }
 
 private:
     int device_ = 0;
+    bmr_ctx *blocks_ = nullptr;     // made by the first call: a run without --gvcf pays nothing for it
     bmn_ctx *indel_ = nullptr;      // made by the first indel call: a run without --vcf-indels pays nothing for it
     size_t indel_n_ref_ = 0;
     bmn_ctx *indeler() {
