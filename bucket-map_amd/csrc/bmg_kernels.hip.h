@@ -27,7 +27,7 @@ struct cell_action {
     static constexpr bool kIndels = false, kStats = false;
     unsigned long long *__restrict__ c;
     uint32_t min_bq, q_absent, q_cap;
-    __device__ __forceinline__ cell_action on(uint64_t first) const { return cell_action{c + first * kCells, min_bq, q_absent, q_cap}; }
+    __device__ __forceinline__ cell_action on(uint64_t first, uint32_t, uint32_t) const { return cell_action{c + first * kCells, min_bq, q_absent, q_cap}; }
     __device__ __forceinline__ void base(uint64_t position, uint32_t q, uint32_t code) const {
         if (q != bmp::kQualNone && q < min_bq) return;
         const uint32_t letter = code == 1 ? 0u : code == 2 ? 1u : code == 4 ? 2u : code == 8 ? 3u : 4u;

@@ -57,7 +57,7 @@ struct count_action {
     static constexpr bool kIndels = true, kStats = true;
     uint32_t *__restrict__ c;
     uint32_t min_bq;
-    __device__ __forceinline__ count_action on(uint64_t first) const { return count_action{c + first * kCounters, min_bq}; }
+    __device__ __forceinline__ count_action on(uint64_t first, uint32_t, uint32_t) const { return count_action{c + first * kCounters, min_bq}; }
     __device__ __forceinline__ void count(uint64_t position, uint32_t which) const { atomicAdd(&c[position * kCounters + which], 1u); }
     __device__ __forceinline__ void base(uint64_t position, uint32_t q, uint32_t code) const { count(position, counter_of(q, code, min_bq)); }
     __device__ __forceinline__ void del(uint64_t position) const { count(position, kDel); }

@@ -1,6 +1,6 @@
-// bmp_walk.hip.h -- the walk of a BAM record stream that the pileup counter (bmp_kernels.hip.h) and the genotype caller
-// (bmg_kernels.hip.h) share: which records are counted (include/bmp.h: PLACED, COUNTED RECORD), the two-class walk of their
-// CIGARs with the clipping to the reference, and the word-wise reads of qualities and packed sequence.  What happens at a
+// bmp_walk.hip.h -- the walk of a BAM record stream that the pileup counter (bmp_kernels.hip.h), the genotype caller
+// (bmg_kernels.hip.h) and the bias annotator (bmb_kernels.hip.h) share: which records are counted (include/bmp.h: PLACED,
+// COUNTED RECORD), the two-class walk of their CIGARs with the clipping to the reference, and the word-wise reads of qualities and packed sequence.  What happens at a
 // base, a deleted position and an insertion's anchor is the ACTION the walkers are templates over; each module has its own.
 // Templates and inline functions only: no kernel is defined here.
 #pragma once
@@ -36,7 +36,8 @@ __device__ __forceinline__ bool takes_ref(uint32_t op) { return op == 0 || op ==
 __device__ __forceinline__ bool takes_query(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
 
 // WHAT THE WALK DOES AT A BASE, A DELETED POSITION AND AN INSERTION'S ANCHOR is its action, a small struct:
-//   Act on(first) const          the action on the reference whose first slot is `first`; positions count from there
+//   Act on(first, flag, mapq) const  the action on the reference whose first slot is `first`, for a record with that flag
+//                                and that mapq byte (bmb's action keeps them, the others ignore them); positions count from first
 //   void base(p, q, code) const  a base of an M, = or X op at position p with the quality byte q and the 4-bit code
 //   void del(p) const            a deleted position;  void ins(p) const  an insertion anchored at p
 //   kIndels                      false: del and ins do nothing, and the walkers leave their loops out
@@ -192,7 +193,7 @@ __device__ __forceinline__ void add_records(const uint8_t *__restrict__ in, cons
                 wide = wide || deleted > kShortSeq;
                 if (!wide) {
                     const uint8_t *seq = cigar + 4ull * n_cigar;
-                    walk_alone(cigar, n_cigar, seq, seq + ((uint64_t)l_seq + 1) / 2, (uint32_t)pos_i, rlen, act.on(ref_base[ref]));
+                    walk_alone(cigar, n_cigar, seq, seq + ((uint64_t)l_seq + 1) / 2, (uint32_t)pos_i, rlen, act.on(ref_base[ref], flag, r[13]));
                 }
             }
         }
@@ -203,8 +204,9 @@ __device__ __forceinline__ void add_records(const uint8_t *__restrict__ in, cons
         todo &= todo - 1;
         const uint8_t *r = in + rec_offset[wave_first + src];
         const uint32_t w_ref = load32(r + 4), w_pos = load32(r + 8), l_name = r[12], n_cigar = load16(r + 16), l_seq = load32(r + 20);
+        const uint32_t w_flag = load16(r + 18), w_mapq = r[13];   // dead code where the action ignores them
         const uint8_t *cigar = r + 36 + l_name, *seq = cigar + 4ull * n_cigar;
-        walk_wave(cigar, n_cigar, seq, seq + ((uint64_t)l_seq + 1) / 2, w_pos, ref_len[w_ref], act.on(ref_base[w_ref]), lane);
+        walk_wave(cigar, n_cigar, seq, seq + ((uint64_t)l_seq + 1) / 2, w_pos, ref_len[w_ref], act.on(ref_base[w_ref], w_flag, w_mapq), lane);
     }
     if constexpr (Act::kStats) {
         uint64_t left = __ballot(placed);

@@ -46,6 +46,8 @@
 // goes to indel_add too, indel_begin before them and indel_finish after them.
 // BLOCK MODE (--gvcf; include/bmr.h states the rule), on top of genotype mode: after genotype_call, and after indel_finish where
 // there is one, the positions of the variant calls go to refblocks as excluded intervals.
+// BIAS MODE (--vcf-bias; include/bmb.h states the rule), on top of genotype mode: every piece that goes to genotype_add goes to
+// bias_add too, and after genotype_call the calls go to bias_annotate.
 #pragma once
 
 #include "bgzf.h"
@@ -204,6 +206,10 @@ class bam_sorter {
     bool refblocks_ = false;                         // block mode (with genotype mode)
     std::vector<uint32_t> refblock_bands_;
     refblock_result refblock_result_;
+    bool bias_ = false;                              // bias mode (with genotype mode)
+    bias_params bias_params_;
+    const bias_tables *bias_tables_ = nullptr;
+    std::vector<uint32_t> bias_notes_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -310,6 +316,15 @@ public:
         refblock_bands_ = bands;
     }
     const refblock_result &refblocks() const { return refblock_result_; }
+    // bias mode: after set_genotype and before the first add(); after finish(), one annotation per call of the genotype
+    // caller.  The tables are bmb_tables's and outlive the sorter.
+    void set_bias(const bias_params &pr, const bias_tables &tables) {
+        if (!genotype_) throw std::runtime_error("--vcf-bias: the annotations belong to the calls of --vcf");
+        bias_ = true;
+        bias_params_ = pr;
+        bias_tables_ = &tables;
+    }
+    const std::vector<uint32_t> &bias_notes() const { return bias_notes_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -349,6 +364,7 @@ public:
         if (pileup_) z_->pileup_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), pileup_ref_bases_.data(), pileup_thresholds_);
         if (genotype_) z_->genotype_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), genotype_params_);
         if (indel_) z_->indel_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), indel_params_);
+        if (bias_) z_->bias_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), bias_params_);
         if (tmp_.empty()) {
             n_runs_ = off_.size() > 1 ? 1 : 0;
             std::vector<uint32_t> perm;
@@ -368,6 +384,7 @@ public:
             if (pileup_) z_->pileup_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
             if (genotype_) z_->genotype_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
             if (indel_) z_->indel_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
+            if (bias_) z_->bias_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
         } else {
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
@@ -395,6 +412,7 @@ public:
                 if (pileup_ && counted_off.size() > 1) z_->pileup_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 if (genotype_ && counted_off.size() > 1) z_->genotype_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 if (indel_ && counted_off.size() > 1) z_->indel_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
+                if (bias_ && counted_off.size() > 1) z_->bias_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 counted.clear();
                 counted_off.assign(1, 0);
             };
@@ -439,6 +457,7 @@ public:
             genotype_result_.n_snv_sites = 0;
             for (size_t k = 0; k < pileup_result_.n_sites(); k++) genotype_result_.n_snv_sites += pileup_result_.sites[kPileupSiteWords * k + 11] & 1u;
         }
+        if (bias_) z_->bias_annotate(genotype_result_.calls.data(), genotype_result_.n_calls(), *bias_tables_, bias_notes_);
         if (indel_) z_->indel_finish(indel_result_);
         if (refblocks_)
             z_->refblocks(pileup_ref_len_.data(), pileup_ref_len_.size(), pileup_ref_bases_.data(), refblock_bands_,

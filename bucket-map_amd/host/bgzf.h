@@ -390,6 +390,19 @@ struct block_compressor {
     }
     virtual void indel_finish(indel_result &out) { indel_.finish(out); }
 
+    // --vcf-bias (include/bmb.h states the rule): the references and the two parameters, then whole records as for
+    // genotype_add, then the annotations of calls as genotype_call writes them (kBiasOutWords per call) from the two tables
+    // bmb_tables makes.  The defaults are the host rule of bias.h; the product plugs in bmb_begin, bmb_add and bmb_annotate,
+    // whose context has uploaded the same tables.
+    virtual void bias_begin(const uint32_t *ref_len, size_t n_ref, const bias_params &pr) { bias_.begin(ref_len, n_ref, pr); }
+    virtual void bias_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) {
+        (void)n;
+        bias_.add(in, rec_offset, n_records, skip);
+    }
+    virtual void bias_annotate(const uint32_t *calls, size_t n_calls, const bias_tables &tables, std::vector<uint32_t> &out) {
+        bias_.annotate(calls, n_calls, tables, out);
+    }
+
     // --gvcf (include/bmr.h states the rule): after genotype_begin and the genotype_add calls, the reference blocks of the cells
     // they filled, against ref_bases (ref_len[r] bytes each), under the band bounds and outside the excluded intervals (three
     // words each).  The default is the host rule of refblocks.h; the product plugs in bmr_run and bmr_blocks.
@@ -403,6 +416,7 @@ private:
     pileup_counter pileup_;
     genotype_counter genotype_;
     indel_caller indel_;
+    bias_counter bias_;
 };
 
 }  // namespace bm

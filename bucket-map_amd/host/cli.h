@@ -97,6 +97,9 @@ struct cmd_arguments {
                                   // --vcf and, between them, the hom-ref blocks of every other base as VCF 4.2 (include/bmr.h states the rule)
     std::vector<uint32_t> gvcf_bands{1, 10, 20, 30, 40, 50, 60, 70, 80, 90, 99};   // --gvcf-bands B1,B2,...: the GQ bounds at which a block ends
     bool gvcf_bands_given = false;   // refused without --gvcf
+    bool vcf_bias = false;        // --vcf-bias: FS, MQ, ADF and ADR on the SNV lines of --vcf / --gvcf (include/bmb.h states the rule)
+    unsigned long vcf_max_fs = 60, vcf_min_mq = 0;   // --vcf-max-fs N (phred, 1..60): FS >= N is StrandBias / --vcf-min-mq N (0..255, 0 is off): MQ < N is LowMQ
+    std::string vcf_bias_opt;     // the first of those two given: refused without --vcf-bias
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -414,6 +417,18 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             if (a.vcf_opt.empty()) a.vcf_opt = opt;
             if (a.vcf_indel_opt.empty()) a.vcf_indel_opt = opt;
         }
+        else if (opt == "--vcf-bias") {
+            a.vcf_bias = true;
+        }
+        else if (opt == "--vcf-max-fs" || opt == "--vcf-min-mq") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            const bool fs = opt == "--vcf-max-fs";
+            if (s[0] < '0' || s[0] > '9' || v > (fs ? 60ul : 255ul) || (fs && v == 0))
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in " + (fs ? "1..60" : "0..255") + ".");
+            (fs ? a.vcf_max_fs : a.vcf_min_mq) = v;
+            if (a.vcf_bias_opt.empty()) a.vcf_bias_opt = opt;
+        }
         else if (opt == "--gvcf") {
             a.gvcf_path = value();
             a.sort = true;
@@ -479,6 +494,10 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
                            (a.pileup_path == a.depth_path ? "--depth" : "--coverage") + " too.");
     if (!a.vcf_opt.empty() && a.vcf_path.empty() && a.gvcf_path.empty())
         throw parser_error("Validation failed for option " + a.vcf_opt + ": it is an option of --vcf FILE, which is not given.");
+    if (a.vcf_bias && a.vcf_path.empty() && a.gvcf_path.empty())
+        throw parser_error("Validation failed for option --vcf-bias: it annotates the lines of --vcf FILE or --gvcf FILE, neither is given.");
+    if (!a.vcf_bias_opt.empty() && !a.vcf_bias)
+        throw parser_error("Validation failed for option " + a.vcf_bias_opt + ": it is an option of --vcf-bias, which is not given.");
     if (!a.vcf_indel_opt.empty() && !a.vcf_indels)
         throw parser_error("Validation failed for option " + a.vcf_indel_opt + ": it is an option of --vcf-indels, which is not given.");
     if (!a.vcf_path.empty() && a.output_sam_path.empty() && !a.only_indexer)

@@ -17,6 +17,8 @@
 #include <string>
 #include <vector>
 
+#include "bias.h"
+
 namespace bm {
 
 constexpr size_t kGenotypeCells = 4;        // BMG_N_CELLS: A C G T
@@ -202,10 +204,11 @@ inline genotype_summary summarize_genotypes(const genotype_result &res, uint32_t
 using vcf_between = std::function<void(std::string &buf, uint32_t ref, uint64_t pos)>;
 
 // --vcf FILE: VCF 4.2, the header, then one line per VARIANT call in the order of the calls.  more_info, where given, is a
-// further INFO line of the header.
+// further INFO line of the header.  bias, where given (--vcf-bias, host/bias.h), holds one annotation per call: the header gains
+// six lines, a line FS and MQ in INFO, ADF and ADR after AD, and the filters StrandBias and LowMQ.
 inline void write_vcf_file(std::ostream &out, const genotype_result &res, const std::vector<std::string> &ref_ids, const std::vector<uint32_t> &ref_len,
                            const std::string &sample, uint32_t min_qual, const char *more_info = nullptr, const vcf_between *between = nullptr,
-                           const char *const *gvcf = nullptr) {
+                           const char *const *gvcf = nullptr, const vcf_bias *bias = nullptr) {
     // gvcf, where given, makes it the header of --gvcf: three more lines, one for ALT, one for INFO and one for FORMAT
     std::string buf = gvcf ? "##fileformat=VCFv4.2\n##source=bucketmap --gvcf\n" : "##fileformat=VCFv4.2\n##source=bucketmap --vcf\n";
     for (size_t r = 0; r < ref_ids.size(); r++) buf += "##contig=<ID=" + ref_ids[r] + ",length=" + std::to_string(ref_len.at(r)) + ">\n";
@@ -213,10 +216,13 @@ inline void write_vcf_file(std::ostream &out, const genotype_result &res, const 
     buf += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Counted bases A, C, G and T of sufficient base quality\">\n";
     if (more_info) buf += more_info;
     if (gvcf) buf += gvcf[1];
+    if (bias) buf += bias_info_lines();
     buf += "##FILTER=<ID=LowQual,Description=\"QUAL below " + std::to_string(min_qual) + "\">\n";
+    if (bias) buf += bias_filter_lines(*bias);
     buf += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
     buf += "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Counted bases A, C, G and T of sufficient base quality\">\n";
     buf += "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Counted bases of the reference and of each alternative allele\">\n";
+    if (bias) buf += bias_format_lines();
     buf += "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the cost of the second-best genotype, at most 99\">\n";
     buf += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype costs with the prior, the best at 0\">\n";
     if (gvcf) buf += gvcf[2];
@@ -242,11 +248,22 @@ inline void write_vcf_file(std::ostream &out, const genotype_result &res, const 
         buf += '\t';
         for (uint32_t j = 1; j < n_alleles; j++) buf += j > 1 ? "," : "", buf += "ACGT"[allele[j]];
         buf += '\t', buf += qual;
-        buf += c[7] >= static_cast<uint64_t>(100) * min_qual ? "\tPASS" : "\tLowQual";
-        buf += "\tDP=" + std::to_string(c[22]) + "\tGT:DP:AD:GQ:PL\t";
+        const uint32_t *note = bias ? bias->at(k) : nullptr;
+        std::string filters = c[7] >= static_cast<uint64_t>(100) * min_qual ? "" : "LowQual";
+        if (note && bias->strand_bias(note)) filters += filters.empty() ? "StrandBias" : ";StrandBias";
+        if (note && bias->low_mq(note)) filters += filters.empty() ? "LowMQ" : ";LowMQ";
+        buf += '\t', buf += filters.empty() ? "PASS" : filters;
+        buf += "\tDP=" + std::to_string(c[22]);
+        if (note) buf += bias_info(note);
+        buf += note ? "\tGT:DP:AD:ADF:ADR:GQ:PL\t" : "\tGT:DP:AD:GQ:PL\t";
         const uint32_t g0 = number_of(c[4]), g1 = number_of(c[5]);
         buf += std::to_string(std::min(g0, g1)) + "/" + std::to_string(std::max(g0, g1)) + ":" + std::to_string(c[22]) + ":";
         for (uint32_t j = 0; j < n_alleles; j++) buf += j ? "," : "", buf += std::to_string(c[8 + allele[j]]);
+        if (note)
+            for (size_t w : {kBiasWFwd, kBiasWRev}) {
+                buf += ':';
+                for (uint32_t j = 0; j < n_alleles; j++) buf += j ? "," : "", buf += std::to_string(note[w + allele[j]]);
+            }
         buf += ":" + std::to_string(c[6]) + ":";
         for (uint32_t hi = 0; hi < n_alleles; hi++)      // VCF order: the genotype j/hi at hi (hi + 1) / 2 + j
             for (uint32_t lo = 0; lo <= hi; lo++) {

@@ -15,6 +15,7 @@
 #include "cli.h"
 #include "bm_indexer.h"
 #include "mapper.h"
+#include "../../include/bmb.h"   // bmb_tables: the two tables of --vcf-bias, made by the library on the host
 
 #include <iostream>
 #include <memory>
@@ -163,6 +164,13 @@ int main(int argc, char **argv) {
                 vcf.indels = args.vcf_indels;                                     // --vcf-indels: the indels of the CIGARs into the same file
                 vcf.indel.min_mapq = pileup_th.min_mapq, vcf.indel.min_alt = pileup_th.min_alt, vcf.indel.min_frac_ppm = pileup_th.min_frac_ppm;
                 vcf.indel.q_indel = static_cast<uint32_t>(args.vcf_indel_qual), vcf.indel.prior = static_cast<uint32_t>(100 * args.vcf_indel_prior);
+                if (args.vcf_bias) {                                              // --vcf-bias: strand and MAPQ evidence on the SNV lines
+                    auto tables = std::make_shared<bm::bias_tables>();
+                    tables->lf.resize(BMB_N_LF), tables->e.resize(BMB_N_E);
+                    if (bmb_tables(tables->lf.data(), tables->e.data()) != BMB_OK) throw std::runtime_error(std::string("bmb_tables: ") + bmb_last_error());
+                    vcf.bias = true, vcf.bias_tables_of = tables;
+                    vcf.max_fs = static_cast<uint32_t>(args.vcf_max_fs), vcf.min_mq = static_cast<uint32_t>(args.vcf_min_mq);
+                }
                 loc.set_vcf(vcf, pileup_th);
             }
         }

@@ -6,6 +6,7 @@
 #include "../../include/bmg.h"
 #include "../../include/bmn.h"
 #include "../../include/bmr.h"
+#include "../../include/bmb.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -127,6 +128,7 @@ public:
     }
     ~gpu_block_compressor() override {
         bmr_destroy(blocks_);
+        bmb_destroy(bias_);
         bmn_destroy(indel_);
         bmg_destroy(geno_);
         bmp_destroy(pile_);
@@ -272,6 +274,20 @@ public:
         if (bmn_alleles(indel_, 0, n_alleles, out.alleles.data()) != BMN_OK) throw std::runtime_error(std::string("bmn_alleles: ") + bmn_last_error());
         if (bmn_calls(indel_, 0, n_calls, out.calls.data()) != BMN_OK) throw std::runtime_error(std::string("bmn_calls: ") + bmn_last_error());
     }
+    // --vcf-bias: strand and MAPQ evidence of the written records and the annotations of the calls on the same device (bmb_*:
+    // the rule of include/bmb.h, which is the host default's; the context has uploaded bmb_tables's tables, the argument's)
+    void bias_begin(const uint32_t *ref_len, size_t n_ref, const bm::bias_params &pr) override {
+        if (n_ref > 0xFFFFFFFFull) throw std::runtime_error("bmb_begin: " + std::to_string(n_ref) + " references");
+        const uint32_t p[BMB_N_PARAMS] = {pr.min_mapq, pr.min_bq};
+        if (bmb_begin(biaser(), ref_len, static_cast<uint32_t>(n_ref), p) != BMB_OK) throw std::runtime_error(std::string("bmb_begin: ") + bmb_last_error());
+    }
+    void bias_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) override {
+        if (bmb_add(biaser(), in, n, rec_offset, n_records, skip) != BMB_OK) throw std::runtime_error(std::string("bmb_add: ") + bmb_last_error());
+    }
+    void bias_annotate(const uint32_t *calls, size_t n_calls, const bm::bias_tables &, std::vector<uint32_t> &out) override {
+        out.assign(n_calls * bm::kBiasOutWords, 0);
+        if (bmb_annotate(biaser(), calls, n_calls, out.data()) != BMB_OK) throw std::runtime_error(std::string("bmb_annotate: ") + bmb_last_error());
+    }
     // --gvcf: the reference blocks of the genotype caller's cells on the same device (bmr_*: the rule of include/bmr.h, which
     // is the host default's)
     void refblocks(const uint32_t *ref_len, size_t n_ref, const uint8_t *const *ref_bases, const std::vector<uint32_t> &bands,
@@ -288,6 +304,11 @@ public:
 private:
     int device_ = 0;
     bmr_ctx *blocks_ = nullptr;     // made by the first call: a run without --gvcf pays nothing for it
+    bmb_ctx *bias_ = nullptr;       // made by the first bias call: a run without --vcf-bias pays nothing for it
+    bmb_ctx *biaser() {
+        if (!bias_ && bmb_create(device_, &bias_) != BMB_OK) throw std::runtime_error(std::string("bmb_create: ") + bmb_last_error());
+        return bias_;
+    }
     bmn_ctx *indel_ = nullptr;      // made by the first indel call: a run without --vcf-indels pays nothing for it
     size_t indel_n_ref_ = 0;
     bmn_ctx *indeler() {

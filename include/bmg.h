@@ -43,7 +43,7 @@
  *   12 .. 23; its words 0 .. 2 and its n are filled all the same.
  *
  * LEFT OUT, on purpose: indel alleles and calls; capping a base's quality by its record's MAPQ; removing the overlap of two
- * mates (a fragment's overlap counts twice, unless the records were written with `--clip-overlap`); a ploidy other than 2; several samples; strand or position bias; windows for
+ * mates (a fragment's overlap counts twice, unless the records were written with `--clip-overlap`); a ploidy other than 2; several samples; strand or position bias in the calls (bmb.h annotates the strands and the MAPQ beside them); windows for
  * genomes whose state does not fit.
  *
  * A context is used as bmg_begin, then any number of bmg_add, bmg_call and bmg_cells_at in any order: bmg_call does not end

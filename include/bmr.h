@@ -43,7 +43,7 @@
  *   L(RR) = 2477, h = 3010 and gq 5.
  *
  * LEFT OUT, on purpose: <NON_REF> likelihoods on the variant lines; PL in the blocks; a median DP; a maximal block length;
- * strand and position bias; several samples; windows for genomes whose state does not fit.
+ * strand and position bias (bmb.h annotates the variant lines, not the blocks); several samples; windows for genomes whose state does not fit.
  *
  * bmr_run does not end the counting of the bmg_ctx and changes nothing in it: a bmg_add followed by a second bmr_run gives
  * the blocks of everything added by then, a bmg_begin followed by bmr_run starts from the new references, and it may be
