@@ -48,6 +48,11 @@
 // there is one, the positions of the variant calls go to refblocks as excluded intervals.
 // BIAS MODE (--vcf-bias; include/bmb.h states the rule), on top of genotype mode: every piece that goes to genotype_add goes to
 // bias_add too, and after genotype_call the calls go to bias_annotate.
+// PHASE MODE (--vcf-phase; include/bmk.h states the rule), on top of genotype mode: the phase sites are het calls, so the links
+// are counted in a SECOND PASS over the final records after genotype_call: phase_begin with the calls, the records to phase_add,
+// phase_finish.  The rule does not depend on the order of the records, so nothing is merged: with one run the pass reads the run
+// buffer, which is still in memory with the duplicate marks in it; with several it reads each run file in pieces of at most
+// run_bytes, ORs the duplicate marks in as the merge does, and the files are removed only after it.
 #pragma once
 
 #include "bgzf.h"
@@ -210,6 +215,9 @@ class bam_sorter {
     bias_params bias_params_;
     const bias_tables *bias_tables_ = nullptr;
     std::vector<uint32_t> bias_notes_;
+    bool phase_ = false;                             // phase mode (with genotype mode)
+    phase_params phase_params_;
+    phase_result phase_result_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -325,6 +333,13 @@ public:
         bias_tables_ = &tables;
     }
     const std::vector<uint32_t> &bias_notes() const { return bias_notes_; }
+    // phase mode: after set_genotype and before the first add(); after finish(), eight words per het SNV call and the sums
+    void set_phase(const phase_params &pr) {
+        if (!genotype_) throw std::runtime_error("--vcf-phase: the phase belongs to the calls of --vcf");
+        phase_ = true;
+        phase_params_ = pr;
+    }
+    const phase_result &phase() const { return phase_result_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -365,6 +380,8 @@ public:
         if (genotype_) z_->genotype_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), genotype_params_);
         if (indel_) z_->indel_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), indel_params_);
         if (bias_) z_->bias_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), bias_params_);
+        std::vector<uint8_t> dup;                        // mark mode, several runs: one marking over all runs' descriptors;
+        std::vector<uint64_t> run_base;                  // run r's records are dup[run_base[r] ..] in input order (the phase pass reads both again)
         if (tmp_.empty()) {
             n_runs_ = off_.size() > 1 ? 1 : 0;
             std::vector<uint32_t> perm;
@@ -389,8 +406,8 @@ public:
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
             std::vector<uint8_t>().swap(run_);
-            std::vector<uint8_t> dup;                    // mark mode: one marking over all runs' descriptors
-            std::vector<uint64_t> run_base(tmp_.size() + 1, 0), taken(tmp_.size(), 0);
+            std::vector<uint64_t> taken(tmp_.size(), 0);
+            run_base.assign(tmp_.size() + 1, 0);
             if (mark_) {
                 z_->dup_mark(desc_end_.data(), desc_score_.data(), desc_kind_.data(), desc_kind_.size(), dup, counts_);
                 for (size_t r = 0; r < tmp_.size(); r++) run_base[r + 1] = run_base[r] + run_perm_[r].size();
@@ -449,7 +466,7 @@ public:
         bai.write(index, [&](uint64_t so) { return block_at[static_cast<size_t>(so / kBgzfBlockMax)] << 16 | so % kBgzfBlockMax; });
         index.close();
         if (!index) throw std::runtime_error("--sort: cannot write " + out_path_ + ".bai");
-        remove_tmp();
+        if (!phase_) remove_tmp();                       // phase mode reads the run files once more
         if (depth_) z_->depth_finish(depth_result_);
         if (pileup_) z_->pileup_finish(pileup_result_);
         if (genotype_) {
@@ -458,6 +475,10 @@ public:
             for (size_t k = 0; k < pileup_result_.n_sites(); k++) genotype_result_.n_snv_sites += pileup_result_.sites[kPileupSiteWords * k + 11] & 1u;
         }
         if (bias_) z_->bias_annotate(genotype_result_.calls.data(), genotype_result_.n_calls(), *bias_tables_, bias_notes_);
+        if (phase_) {
+            phase_pass(dup, run_base);
+            remove_tmp();
+        }
         if (indel_) z_->indel_finish(indel_result_);
         if (refblocks_)
             z_->refblocks(pileup_ref_len_.data(), pileup_ref_len_.size(), pileup_ref_bases_.data(), refblock_bands_,
@@ -466,6 +487,37 @@ public:
 
 private:
     size_t n_runs_ = 0;
+
+    // phase mode, after genotype_call: the final records once more, in any order.  One run: run_, as add() filled it and
+    // finish() marked it.  Several: each run file in pieces of at most run_bytes_ (a longer record is a piece of its own), the
+    // k-th record of file r marked from dup[run_base[r] + run_perm_[r][k]] as the merge marks it.
+    void phase_pass(const std::vector<uint8_t> &dup, const std::vector<uint64_t> &run_base) {
+        z_->phase_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), phase_params_, genotype_result_.calls.data(), genotype_result_.n_calls());
+        if (tmp_.empty()) {
+            if (off_.size() > 1) z_->phase_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
+        } else {
+            std::vector<uint8_t> piece;
+            std::vector<uint64_t> piece_off{0};
+            auto hand_over = [&]() {
+                if (piece_off.size() > 1) z_->phase_add(piece.data(), piece.size(), piece_off.data(), piece_off.size() - 1, nullptr);
+                piece.clear();
+                piece_off.assign(1, 0);
+            };
+            for (size_t r = 0; r < tmp_.size(); r++) {
+                run_reader reader;
+                reader.f.open(tmp_[r], std::ios::binary);
+                if (!reader.f) throw std::runtime_error("--sort: cannot read " + tmp_[r]);
+                for (uint64_t k = 0; reader.next(); k++) {
+                    if (mark_ && dup[run_base[r] + run_perm_[r][k]]) reader.rec[19] |= 4;
+                    if (piece_off.size() > 1 && piece.size() + reader.rec.size() > run_bytes_) hand_over();
+                    piece.insert(piece.end(), reader.rec.begin(), reader.rec.end());
+                    piece_off.push_back(piece.size());
+                }
+                hand_over();
+            }
+        }
+        z_->phase_finish(phase_result_);
+    }
 };
 
 }  // namespace bm

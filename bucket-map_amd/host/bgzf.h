@@ -403,6 +403,19 @@ struct block_compressor {
         bias_.annotate(calls, n_calls, tables, out);
     }
 
+    // --vcf-phase (include/bmk.h states the rule): the references, the five parameters and the calls of genotype_call, whose
+    // het SNVs are the phase sites (returns their number); then whole records as for genotype_add, in any order and cut
+    // anywhere; then the eight words per site and the four sums.  The defaults are the host rule of phase.h; the product plugs
+    // in bmk_begin, bmk_add, bmk_finish and bmk_phase.
+    virtual size_t phase_begin(const uint32_t *ref_len, size_t n_ref, const phase_params &pr, const uint32_t *calls, size_t n_calls) {
+        return phase_.begin(ref_len, n_ref, pr, calls, n_calls);
+    }
+    virtual void phase_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) {
+        (void)n;
+        phase_.add(in, rec_offset, n_records, skip);
+    }
+    virtual void phase_finish(phase_result &out) { phase_.finish(out); }
+
     // --gvcf (include/bmr.h states the rule): after genotype_begin and the genotype_add calls, the reference blocks of the cells
     // they filled, against ref_bases (ref_len[r] bytes each), under the band bounds and outside the excluded intervals (three
     // words each).  The default is the host rule of refblocks.h; the product plugs in bmr_run and bmr_blocks.
@@ -417,6 +430,7 @@ private:
     genotype_counter genotype_;
     indel_caller indel_;
     bias_counter bias_;
+    phase_linker phase_;
 };
 
 }  // namespace bm

@@ -488,6 +488,8 @@ struct vcf_options {
     bool bias = false;              // --vcf-bias: FS, MQ, ADF and ADR on the SNV lines (include/bmb.h); tables are bmb_tables's
     std::shared_ptr<const bias_tables> bias_tables_of;
     uint32_t max_fs = 60, min_mq = 0;
+    bool phase = false;             // --vcf-phase: read-backed phase of the het SNV lines (include/bmk.h); min_mapq and min_bq are `params`'s
+    phase_params phase_params_of{};
     bool on() const { return !file.empty() || !gvcf.empty(); }
 };
 
@@ -551,8 +553,11 @@ class sam_text {
         vcf_bias noted;                                  // --vcf-bias: one annotation per call
         if (vcf_.bias) noted.notes = sorter_->bias_notes(), noted.max_fs = vcf_.max_fs, noted.min_mq = vcf_.min_mq;
         const vcf_bias *bias = vcf_.bias ? &noted : nullptr;
+        vcf_phase linked;                                // --vcf-phase: eight words per het SNV call
+        if (vcf_.phase) linked.sites = sorter_->phase().sites, linked.index(res.n_calls());
+        const vcf_phase *phase = vcf_.phase ? &linked : nullptr;
         // with --gvcf alone there is no file of --vcf: the calls go into the gVCF only
-        if (!vcf_.file.empty() && !vcf_.indels) write_whole(vcf_.file, [&](std::ostream &f) { write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, nullptr, nullptr, nullptr, bias); });
+        if (!vcf_.file.empty() && !vcf_.indels) write_whole(vcf_.file, [&](std::ostream &f) { write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, nullptr, nullptr, nullptr, bias, phase); });
         else if (!vcf_.file.empty()) {
             // the indel lines go between the SNV lines by (reference, POS); at an equal POS the SNV comes first
             const indel_result &ind = sorter_->indel();
@@ -566,19 +571,20 @@ class sam_text {
             };
             write_whole(vcf_.file, [&](std::ostream &f) {
                 next = 0;
-                write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, indel_vcf_header(), &between, nullptr, bias);
+                write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, indel_vcf_header(), &between, nullptr, bias, phase);
             });
         }
         const genotype_summary s = summarize_genotypes(res, vcf_.min_qual);
         std::cerr << "[INFO]\t\tGenotypes: " << s.variants << " variants (" << s.het << " het, " << s.hom << " hom, " << s.low_qual
                   << " below QUAL) at " << res.n_snv_sites << " SNV sites\n";
         if (vcf_.indels) std::cerr << "[INFO]\t\t" << indel_summary_line(summarize_indels(sorter_->indel(), vcf_.min_qual)) << "\n";
-        if (!vcf_.gvcf.empty()) write_gvcf(res, lens, bias);
+        if (!vcf_.gvcf.empty()) write_gvcf(res, lens, bias, phase);
         if (bias) std::cerr << "[INFO]\t\t" << bias_summary_line(summarize_bias(noted)) << "\n";
+        if (phase) std::cerr << "[INFO]\t\t" << phase_summary_line(summarize_phase(sorter_->phase(), res.calls.data())) << "\n";
     }
     // --gvcf: the lines of --vcf, and between them by (reference, POS) one line per reference block.  No two lines share a POS:
     // the position of every variant line is excluded from the blocks.
-    void write_gvcf(const genotype_result &res, const std::vector<uint32_t> &lens, const vcf_bias *bias) {
+    void write_gvcf(const genotype_result &res, const std::vector<uint32_t> &lens, const vcf_bias *bias, const vcf_phase *phase) {
         const refblock_result &blk = sorter_->refblocks();
         const indel_result &ind = sorter_->indel();
         size_t next = 0, next_block = 0;
@@ -599,7 +605,7 @@ class sam_text {
         const char *const more[3] = {gvcf_alt_header(), gvcf_info_header(), gvcf_format_header()};
         write_whole(vcf_.gvcf, [&](std::ostream &f) {
             next = next_block = 0;
-            write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, vcf_.indels ? indel_vcf_header() : nullptr, &between, more, bias);
+            write_vcf_file(f, res, ref_ids_, lens, vcf_.sample, vcf_.min_qual, vcf_.indels ? indel_vcf_header() : nullptr, &between, more, bias, phase);
         });
         std::cerr << "[INFO]\t\t" << refblock_summary_line(blk, lens) << "\n";
     }
@@ -634,6 +640,11 @@ class sam_text {
         if (vcf_.on() && vcf_.bias) {
             if (!vcf_.bias_tables_of) throw std::runtime_error("--vcf-bias: no tables");
             sorter_->set_bias(bias_params{vcf_.params.min_mapq, vcf_.params.min_bq}, *vcf_.bias_tables_of);
+        }
+        if (vcf_.on() && vcf_.phase) {
+            phase_params pr = vcf_.phase_params_of;
+            pr.min_mapq = vcf_.params.min_mapq, pr.min_bq = vcf_.params.min_bq;
+            sorter_->set_phase(pr);
         }
     }
 

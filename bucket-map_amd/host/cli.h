@@ -100,6 +100,9 @@ struct cmd_arguments {
     bool vcf_bias = false;        // --vcf-bias: FS, MQ, ADF and ADR on the SNV lines of --vcf / --gvcf (include/bmb.h states the rule)
     unsigned long vcf_max_fs = 60, vcf_min_mq = 0;   // --vcf-max-fs N (phred, 1..60): FS >= N is StrandBias / --vcf-min-mq N (0..255, 0 is off): MQ < N is LowMQ
     std::string vcf_bias_opt;     // the first of those two given: refused without --vcf-bias
+    bool vcf_phase = false;       // --vcf-phase: read-backed phase of the het SNV lines of --vcf / --gvcf (include/bmk.h states the rule)
+    unsigned long phase_min_links = 2, phase_min_frac_ppm = 800000, phase_reach = 4;   // --phase-min-links N (>= 1) / --phase-min-frac F (above 0.5, at most 1) / --phase-reach N (1..8)
+    std::string phase_opt;        // the first of those three given: refused without --vcf-phase
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -429,6 +432,27 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             (fs ? a.vcf_max_fs : a.vcf_min_mq) = v;
             if (a.vcf_bias_opt.empty()) a.vcf_bias_opt = opt;
         }
+        else if (opt == "--vcf-phase") {
+            a.vcf_phase = true;
+        }
+        else if (opt == "--phase-min-links" || opt == "--phase-reach") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            const bool reach = opt == "--phase-reach";
+            if (s[0] < '0' || s[0] > '9' || v < 1 || v > (reach ? 8ul : 0xFFFFFFFFul))
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in " + (reach ? "1..8" : "1..2^32-1") + ".");
+            (reach ? a.phase_reach : a.phase_min_links) = v;
+            if (a.phase_opt.empty()) a.phase_opt = opt;
+        }
+        else if (opt == "--phase-min-frac") {
+            const std::string s = value();
+            unsigned long ppm = 0;
+            if (!parse_ppm(s, ppm) || ppm < 500001ul)
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s +
+                                   " must be a decimal above 0.5 and at most 1 with at most six fractional digits, such as 0.8.");
+            a.phase_min_frac_ppm = ppm;
+            if (a.phase_opt.empty()) a.phase_opt = opt;
+        }
         else if (opt == "--gvcf") {
             a.gvcf_path = value();
             a.sort = true;
@@ -498,6 +522,10 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         throw parser_error("Validation failed for option --vcf-bias: it annotates the lines of --vcf FILE or --gvcf FILE, neither is given.");
     if (!a.vcf_bias_opt.empty() && !a.vcf_bias)
         throw parser_error("Validation failed for option " + a.vcf_bias_opt + ": it is an option of --vcf-bias, which is not given.");
+    if (a.vcf_phase && a.vcf_path.empty() && a.gvcf_path.empty())
+        throw parser_error("Validation failed for option --vcf-phase: it phases the het lines of --vcf FILE or --gvcf FILE, neither is given.");
+    if (!a.phase_opt.empty() && !a.vcf_phase)
+        throw parser_error("Validation failed for option " + a.phase_opt + ": it is an option of --vcf-phase, which is not given.");
     if (!a.vcf_indel_opt.empty() && !a.vcf_indels)
         throw parser_error("Validation failed for option " + a.vcf_indel_opt + ": it is an option of --vcf-indels, which is not given.");
     if (!a.vcf_path.empty() && a.output_sam_path.empty() && !a.only_indexer)

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "bias.h"
+#include "phase.h"
 
 namespace bm {
 
@@ -205,10 +206,13 @@ using vcf_between = std::function<void(std::string &buf, uint32_t ref, uint64_t 
 
 // --vcf FILE: VCF 4.2, the header, then one line per VARIANT call in the order of the calls.  more_info, where given, is a
 // further INFO line of the header.  bias, where given (--vcf-bias, host/bias.h), holds one annotation per call: the header gains
-// six lines, a line FS and MQ in INFO, ADF and ADR after AD, and the filters StrandBias and LowMQ.
+// six lines, a line FS and MQ in INFO, ADF and ADR after AD, and the filters StrandBias and LowMQ.  phase, where given
+// (--vcf-phase, host/phase.h), knows the phase sites: the header gains FORMAT=PS after PL, and the line of a PHASED call reads
+// g(haplotype 1)|g(haplotype 2) and ends its keys with :PS and its sample column with the 1-based POS of the block's root; every
+// other line is the line without it.
 inline void write_vcf_file(std::ostream &out, const genotype_result &res, const std::vector<std::string> &ref_ids, const std::vector<uint32_t> &ref_len,
                            const std::string &sample, uint32_t min_qual, const char *more_info = nullptr, const vcf_between *between = nullptr,
-                           const char *const *gvcf = nullptr, const vcf_bias *bias = nullptr) {
+                           const char *const *gvcf = nullptr, const vcf_bias *bias = nullptr, const vcf_phase *phase = nullptr) {
     // gvcf, where given, makes it the header of --gvcf: three more lines, one for ALT, one for INFO and one for FORMAT
     std::string buf = gvcf ? "##fileformat=VCFv4.2\n##source=bucketmap --gvcf\n" : "##fileformat=VCFv4.2\n##source=bucketmap --vcf\n";
     for (size_t r = 0; r < ref_ids.size(); r++) buf += "##contig=<ID=" + ref_ids[r] + ",length=" + std::to_string(ref_len.at(r)) + ">\n";
@@ -225,6 +229,7 @@ inline void write_vcf_file(std::ostream &out, const genotype_result &res, const 
     if (bias) buf += bias_format_lines();
     buf += "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the cost of the second-best genotype, at most 99\">\n";
     buf += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype costs with the prior, the best at 0\">\n";
+    if (phase) buf += phase_format_line();
     if (gvcf) buf += gvcf[2];
     buf += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample + "\n";
     for (size_t k = 0; k < res.n_calls(); k++) {
@@ -255,9 +260,14 @@ inline void write_vcf_file(std::ostream &out, const genotype_result &res, const 
         buf += '\t', buf += filters.empty() ? "PASS" : filters;
         buf += "\tDP=" + std::to_string(c[22]);
         if (note) buf += bias_info(note);
-        buf += note ? "\tGT:DP:AD:ADF:ADR:GQ:PL\t" : "\tGT:DP:AD:GQ:PL\t";
+        const uint32_t *linked = phase ? phase->phased(k) : nullptr;
+        buf += note ? "\tGT:DP:AD:ADF:ADR:GQ:PL" : "\tGT:DP:AD:GQ:PL";
+        buf += linked ? ":PS\t" : "\t";
         const uint32_t g0 = number_of(c[4]), g1 = number_of(c[5]);
-        buf += std::to_string(std::min(g0, g1)) + "/" + std::to_string(std::max(g0, g1)) + ":" + std::to_string(c[22]) + ":";
+        if (linked)                                      // haplotype 1 carries allele hap of the site: the call's first letter at hap 0
+            buf += std::to_string(linked[kPhaseWHap] ? g1 : g0) + "|" + std::to_string(linked[kPhaseWHap] ? g0 : g1) + ":" + std::to_string(c[22]) + ":";
+        else
+            buf += std::to_string(std::min(g0, g1)) + "/" + std::to_string(std::max(g0, g1)) + ":" + std::to_string(c[22]) + ":";
         for (uint32_t j = 0; j < n_alleles; j++) buf += j ? "," : "", buf += std::to_string(c[8 + allele[j]]);
         if (note)
             for (size_t w : {kBiasWFwd, kBiasWRev}) {
@@ -270,6 +280,7 @@ inline void write_vcf_file(std::ostream &out, const genotype_result &res, const 
                 const uint32_t a = std::min(allele[lo], allele[hi]), b = std::max(allele[lo], allele[hi]);
                 buf += hi ? "," : "", buf += std::to_string(c[12 + b * (b + 1) / 2 + a] / 100);
             }
+        if (linked) buf += ":" + std::to_string(static_cast<uint64_t>(linked[kPhaseWRootPos]) + 1);
         buf += '\n';
         if (buf.size() > (1u << 20)) out.write(buf.data(), static_cast<std::streamsize>(buf.size())), buf.clear();
     }

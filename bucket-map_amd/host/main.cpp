@@ -171,6 +171,12 @@ int main(int argc, char **argv) {
                     vcf.bias = true, vcf.bias_tables_of = tables;
                     vcf.max_fs = static_cast<uint32_t>(args.vcf_max_fs), vcf.min_mq = static_cast<uint32_t>(args.vcf_min_mq);
                 }
+                if (args.vcf_phase) {                                             // --vcf-phase: which het SNVs the records link
+                    vcf.phase = true;
+                    vcf.phase_params_of.min_links = static_cast<uint32_t>(args.phase_min_links);
+                    vcf.phase_params_of.min_frac_ppm = static_cast<uint32_t>(args.phase_min_frac_ppm);
+                    vcf.phase_params_of.reach = static_cast<uint32_t>(args.phase_reach);
+                }
                 loc.set_vcf(vcf, pileup_th);
             }
         }

@@ -7,6 +7,7 @@
 #include "../../include/bmn.h"
 #include "../../include/bmr.h"
 #include "../../include/bmb.h"
+#include "../../include/bmk.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -128,6 +129,7 @@ public:
     }
     ~gpu_block_compressor() override {
         bmr_destroy(blocks_);
+        bmk_destroy(phase_);
         bmb_destroy(bias_);
         bmn_destroy(indel_);
         bmg_destroy(geno_);
@@ -288,6 +290,26 @@ public:
         out.assign(n_calls * bm::kBiasOutWords, 0);
         if (bmb_annotate(biaser(), calls, n_calls, out.data()) != BMB_OK) throw std::runtime_error(std::string("bmb_annotate: ") + bmb_last_error());
     }
+    // --vcf-phase: the links between the het SNV calls that the written records observe, and the phase from them, on the same
+    // device (bmk_*: the rule of include/bmk.h, which is the host default's)
+    size_t phase_begin(const uint32_t *ref_len, size_t n_ref, const bm::phase_params &pr, const uint32_t *calls, size_t n_calls) override {
+        if (n_ref > 0xFFFFFFFFull) throw std::runtime_error("bmk_begin: " + std::to_string(n_ref) + " references");
+        const uint32_t p[BMK_N_PARAMS] = {pr.min_mapq, pr.min_bq, pr.min_links, pr.min_frac_ppm, pr.reach};
+        uint64_t n_sites = 0;
+        if (bmk_begin(phaser(), ref_len, static_cast<uint32_t>(n_ref), p, calls, n_calls, &n_sites) != BMK_OK)
+            throw std::runtime_error(std::string("bmk_begin: ") + bmk_last_error());
+        return static_cast<size_t>(n_sites);
+    }
+    void phase_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) override {
+        if (bmk_add(phaser(), in, n, rec_offset, n_records, skip) != BMK_OK) throw std::runtime_error(std::string("bmk_add: ") + bmk_last_error());
+    }
+    void phase_finish(bm::phase_result &out) override {
+        uint64_t stats[BMK_N_STATS];
+        if (bmk_finish(phaser(), stats) != BMK_OK) throw std::runtime_error(std::string("bmk_finish: ") + bmk_last_error());
+        for (size_t k = 0; k < bm::kPhaseStats; k++) out.stats[k] = stats[k];
+        out.sites.assign(static_cast<size_t>(stats[BMK_S_SITES]) * bm::kPhaseOutWords, 0);
+        if (bmk_phase(phaser(), 0, stats[BMK_S_SITES], out.sites.data()) != BMK_OK) throw std::runtime_error(std::string("bmk_phase: ") + bmk_last_error());
+    }
     // --gvcf: the reference blocks of the genotype caller's cells on the same device (bmr_*: the rule of include/bmr.h, which
     // is the host default's)
     void refblocks(const uint32_t *ref_len, size_t n_ref, const uint8_t *const *ref_bases, const std::vector<uint32_t> &bands,
@@ -304,6 +326,11 @@ public:
 private:
     int device_ = 0;
     bmr_ctx *blocks_ = nullptr;     // made by the first call: a run without --gvcf pays nothing for it
+    bmk_ctx *phase_ = nullptr;      // made by the first phase call: a run without --vcf-phase pays nothing for it
+    bmk_ctx *phaser() {
+        if (!phase_ && bmk_create(device_, &phase_) != BMK_OK) throw std::runtime_error(std::string("bmk_create: ") + bmk_last_error());
+        return phase_;
+    }
     bmb_ctx *bias_ = nullptr;       // made by the first bias call: a run without --vcf-bias pays nothing for it
     bmb_ctx *biaser() {
         if (!bias_ && bmb_create(device_, &bias_) != BMB_OK) throw std::runtime_error(std::string("bmb_create: ") + bmb_last_error());
