@@ -11,7 +11,7 @@ CFLAGS   = -O3 -std=c11 -fPIC -shared -Wall -Wextra
 
 PKG  = bucket-map_amd
 HOST = $(PKG)/host
-HOST_HDRS = $(wildcard $(HOST)/*.h) include/bmf.h include/bml.h include/bmv.h include/bmz.h include/bms.h include/bmd.h include/bmu.h include/bmc.h include/bmp.h include/bmg.h include/bmn.h include/bmr.h include/bmb.h include/bmk.h
+HOST_HDRS = $(wildcard $(HOST)/*.h) include/bmf.h include/bml.h include/bmv.h include/bmz.h include/bms.h include/bmd.h include/bmu.h include/bmc.h include/bmp.h include/bmg.h include/bmn.h include/bmr.h include/bmb.h include/bmk.h include/bmq.h
 
 PRODUCT = $(PKG)/libbmf.so $(PKG)/libbmhost.so $(PKG)/bucketmap $(PKG)/bucketmap_align $(PKG)/mapper_test
 TESTINFRA = oracle/libbm_oracle.so tests/cpp/bucketmap_oracle tests/cpp/bucketmap_align_oracle tests/cpp/umm_order
@@ -19,12 +19,12 @@ TESTINFRA = oracle/libbm_oracle.so tests/cpp/bucketmap_oracle tests/cpp/bucketma
 all: $(PRODUCT) $(TESTINFRA)
 
 # one product library: the candidate-bucket filter (bmf_*), the locator scan (bml_*), the verifier (bmv_*), the BGZF compressor (bmz_*), the BAM record sorter (bms_*), the duplicate marker (bmd_*),
-# the BGZF inflater (bmu_*; its serial lines are host/inflate_rule.h, shared with the host decoder of host/bgzf_in.h), the coverage counter (bmc_*), the pileup counter (bmp_*), the genotype caller (bmg_*), the indel caller (bmn_*), the reference-block pass (bmr_*), the strand-bias and mapping-quality annotator (bmb_*), the read-backed phaser (bmk_*)
+# the BGZF inflater (bmu_*; its serial lines are host/inflate_rule.h, shared with the host decoder of host/bgzf_in.h), the coverage counter (bmc_*), the pileup counter (bmp_*), the genotype caller (bmg_*), the indel caller (bmn_*), the reference-block pass (bmr_*), the strand-bias and mapping-quality annotator (bmb_*), the read-backed phaser (bmk_*), the mapping statistics (bmq_*)
 CSRC = $(PKG)/csrc
-$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bmf.h include/bml.h include/bmv.h include/bmz.h include/bms.h include/bmd.h include/bmu.h include/bmc.h include/bmp.h include/bmg.h include/bmn.h include/bmr.h include/bmb.h include/bmk.h $(HOST)/inflate_rule.h $(HOST)/bgzf_in.h $(HOST)/bgzf.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bmf.h include/bml.h include/bmv.h include/bmz.h include/bms.h include/bmd.h include/bmu.h include/bmc.h include/bmp.h include/bmg.h include/bmn.h include/bmr.h include/bmb.h include/bmk.h include/bmq.h $(HOST)/inflate_rule.h $(HOST)/bgzf_in.h $(HOST)/bgzf.h
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-result -c -o $@ $<
 
-$(PKG)/libbmf.so: $(CSRC)/bmf_api.o $(CSRC)/bml_api.o $(CSRC)/bmv_api.o $(CSRC)/bmv_variants.o $(CSRC)/bmv_variants2.o $(CSRC)/bmv_variants3.o $(CSRC)/bmv_long.o $(CSRC)/bmv_screen.o $(CSRC)/bmv_annotate.o $(CSRC)/bmv_clip.o $(CSRC)/bmv_overlap.o $(CSRC)/bmv_best.o $(CSRC)/bmv_pair.o $(CSRC)/bmv_frag.o $(CSRC)/bmv_rescue.o $(CSRC)/bmv_realign.o $(CSRC)/bmv_leftalign.o $(CSRC)/bmv_split.o $(CSRC)/bmz_api.o $(CSRC)/bms_api.o $(CSRC)/bmd_api.o $(CSRC)/bmu_api.o $(CSRC)/bmc_api.o $(CSRC)/bmp_api.o $(CSRC)/bmg_api.o $(CSRC)/bmn_api.o $(CSRC)/bmr_api.o $(CSRC)/bmb_api.o $(CSRC)/bmk_api.o
+$(PKG)/libbmf.so: $(CSRC)/bmf_api.o $(CSRC)/bml_api.o $(CSRC)/bmv_api.o $(CSRC)/bmv_variants.o $(CSRC)/bmv_variants2.o $(CSRC)/bmv_variants3.o $(CSRC)/bmv_long.o $(CSRC)/bmv_screen.o $(CSRC)/bmv_annotate.o $(CSRC)/bmv_clip.o $(CSRC)/bmv_overlap.o $(CSRC)/bmv_best.o $(CSRC)/bmv_pair.o $(CSRC)/bmv_frag.o $(CSRC)/bmv_rescue.o $(CSRC)/bmv_realign.o $(CSRC)/bmv_leftalign.o $(CSRC)/bmv_split.o $(CSRC)/bmz_api.o $(CSRC)/bms_api.o $(CSRC)/bmd_api.o $(CSRC)/bmu_api.o $(CSRC)/bmc_api.o $(CSRC)/bmp_api.o $(CSRC)/bmg_api.o $(CSRC)/bmn_api.o $(CSRC)/bmr_api.o $(CSRC)/bmb_api.o $(CSRC)/bmk_api.o $(CSRC)/bmq_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 $(PKG)/libbmhost.so: $(HOST)/bm_host_api.cpp $(HOST_HDRS)

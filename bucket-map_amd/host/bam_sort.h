@@ -53,6 +53,9 @@
 // phase_finish.  The rule does not depend on the order of the records, so nothing is merged: with one run the pass reads the run
 // buffer, which is still in memory with the duplicate marks in it; with several it reads each run file in pieces of at most
 // run_bytes, ORs the duplicate marks in as the merge does, and the files are removed only after it.
+// STATS MODE (--stats; include/bmq.h states the rule), beside or without every other mode: stats_begin before the pieces, every
+// piece that goes to depth_add / pileup_add goes to stats_add, stats_finish after them.  The rule needs no reference and does not
+// depend on the order or the cutting of the records, so one run and several give the same result.
 #pragma once
 
 #include "bgzf.h"
@@ -218,6 +221,9 @@ class bam_sorter {
     bool phase_ = false;                             // phase mode (with genotype mode)
     phase_params phase_params_;
     phase_result phase_result_;
+    bool stats_ = false;                             // stats mode
+    stats_params stats_params_;
+    stats_result stats_result_;
 
     static uint32_t u32(const uint8_t *p) {
         uint32_t v;
@@ -340,6 +346,12 @@ public:
         phase_params_ = pr;
     }
     const phase_result &phase() const { return phase_result_; }
+    // stats mode: before the first add(); after finish(), the tallies and tables of the records written
+    void set_stats(const stats_params &pr) {
+        stats_ = true;
+        stats_params_ = pr;
+    }
+    const stats_result &stats() const { return stats_result_; }
 
     // whole records, back to back
     void add(const uint8_t *recs, size_t n) {
@@ -380,6 +392,7 @@ public:
         if (genotype_) z_->genotype_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), genotype_params_);
         if (indel_) z_->indel_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), indel_params_);
         if (bias_) z_->bias_begin(pileup_ref_len_.data(), pileup_ref_len_.size(), bias_params_);
+        if (stats_) z_->stats_begin(stats_params_);
         std::vector<uint8_t> dup;                        // mark mode, several runs: one marking over all runs' descriptors;
         std::vector<uint64_t> run_base;                  // run r's records are dup[run_base[r] ..] in input order (the phase pass reads both again)
         if (tmp_.empty()) {
@@ -402,6 +415,7 @@ public:
             if (genotype_) z_->genotype_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
             if (indel_) z_->indel_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
             if (bias_) z_->bias_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
+            if (stats_) z_->stats_add(run_.data(), run_.size(), off_.data(), off_.size() - 1, nullptr);
         } else {
             if (off_.size() > 1) spill();
             n_runs_ = tmp_.size();
@@ -422,7 +436,7 @@ public:
                 if (reader[r]->next()) heap.emplace(bam_sort_key(reader[r]->rec.data()), r);
             }
             constexpr size_t kPiece = size_t{64} * kBgzfBlockMax;
-            std::vector<uint8_t> merged, counted;        // counted: depth or pileup mode, the merged records not yet handed to depth_add / pileup_add
+            std::vector<uint8_t> merged, counted;        // counted: depth, pileup or stats mode, the merged records not yet handed to depth_add / pileup_add
             std::vector<uint64_t> counted_off{0};
             auto count = [&]() {
                 if (depth_ && counted_off.size() > 1) z_->depth_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
@@ -430,6 +444,7 @@ public:
                 if (genotype_ && counted_off.size() > 1) z_->genotype_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 if (indel_ && counted_off.size() > 1) z_->indel_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 if (bias_ && counted_off.size() > 1) z_->bias_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
+                if (stats_ && counted_off.size() > 1) z_->stats_add(counted.data(), counted.size(), counted_off.data(), counted_off.size() - 1, nullptr);
                 counted.clear();
                 counted_off.assign(1, 0);
             };
@@ -442,7 +457,7 @@ public:
                 bai.add(rec.data(), so, rec.size());
                 so += rec.size();
                 merged.insert(merged.end(), rec.begin(), rec.end());
-                if (depth_ || pileup_) {
+                if (depth_ || pileup_ || stats_) {
                     counted.insert(counted.end(), rec.begin(), rec.end());
                     counted_off.push_back(counted.size());
                     if (counted.size() >= run_bytes_) count();
@@ -457,7 +472,7 @@ public:
             }
             if (!merged.empty()) z_->deflate(merged.data(), merged.size(), blocks);
             emit();
-            if (depth_ || pileup_) count();
+            if (depth_ || pileup_ || stats_) count();
             reader.clear();
         }
         out.write(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -469,6 +484,7 @@ public:
         if (!phase_) remove_tmp();                       // phase mode reads the run files once more
         if (depth_) z_->depth_finish(depth_result_);
         if (pileup_) z_->pileup_finish(pileup_result_);
+        if (stats_) z_->stats_finish(stats_result_);
         if (genotype_) {
             z_->genotype_call(pileup_result_.sites.data(), pileup_result_.n_sites(), genotype_result_.calls);
             genotype_result_.n_snv_sites = 0;

@@ -11,6 +11,7 @@
 #include "indel.h"
 #include "refblocks.h"
 #include "markdup.h"
+#include "stats.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -416,6 +417,16 @@ struct block_compressor {
     }
     virtual void phase_finish(phase_result &out) { phase_.finish(out); }
 
+    // --stats (include/bmq.h states the rule): the two parameters; then whole records as for depth_add, in any order and cut
+    // anywhere; then the 35 tallies and the eight tables.  The defaults are the host rule of stats.h; the product plugs in
+    // bmq_begin, bmq_add, bmq_finish and bmq_table.
+    virtual void stats_begin(const stats_params &pr) { stats_.begin(pr); }
+    virtual void stats_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) {
+        (void)n;
+        stats_.add(in, rec_offset, n_records, skip);
+    }
+    virtual void stats_finish(stats_result &out) { stats_.finish(out); }
+
     // --gvcf (include/bmr.h states the rule): after genotype_begin and the genotype_add calls, the reference blocks of the cells
     // they filled, against ref_bases (ref_len[r] bytes each), under the band bounds and outside the excluded intervals (three
     // words each).  The default is the host rule of refblocks.h; the product plugs in bmr_run and bmr_blocks.
@@ -431,6 +442,7 @@ private:
     indel_caller indel_;
     bias_counter bias_;
     phase_linker phase_;
+    stats_counter stats_;
 };
 
 }  // namespace bm

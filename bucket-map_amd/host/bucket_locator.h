@@ -515,6 +515,8 @@ class sam_text {
     const std::vector<std::string> *pileup_seqs_ = nullptr;   // ... the bases of the header's references, each of its length
     vcf_options vcf_;                      // sorted BAM: --vcf, its file may be empty; it counts the pileup whether that has a file or not
     bool pileup_on() const { return !pileup_file_.empty() || vcf_.on(); }
+    std::filesystem::path stats_file_;     // sorted BAM: --stats, may be empty
+    stats_params stats_params_;
 
     // A file of --depth / --coverage / --pileup: written beside its place and moved there when it is complete, so that a failure
     // leaves nothing half-written (and nothing at all under the final name).
@@ -545,6 +547,11 @@ class sam_text {
         }
         std::cerr << "[INFO]\t\tCoverage: " << cov << " of " << bases << " bases covered by " << reads << " records (" << n_long
                   << " long-CIGAR records left out)\n";
+    }
+    void write_stats() {
+        const stats_result &res = sorter_->stats();
+        write_whole(stats_file_, [&](std::ostream &f) { write_stats_file(f, res); });
+        std::cerr << "[INFO]\t\t" << stats_summary_line(res) << "\n";
     }
     void write_vcf() {
         const genotype_result &res = sorter_->genotype();
@@ -734,6 +741,11 @@ public:
         buf_.reserve(5u << 20);
         writing_.reserve(5u << 20);
     }
+    // --stats FILE (sorted BAM only, before header()): the mapping statistics of the records written (include/bmq.h)
+    void set_stats(std::filesystem::path const &file, stats_params const &pr) {
+        stats_file_ = sorter_ ? file : std::filesystem::path();
+        stats_params_ = pr;
+    }
     ~sam_text() {
         try {
             if (!closed_) flush();
@@ -769,6 +781,7 @@ public:
             if (!depth_file_.empty() || !coverage_file_.empty()) write_depth_files();
             if (!pileup_file_.empty()) write_pileup();
             if (vcf_.on()) write_vcf();
+            if (!stats_file_.empty()) write_stats();
         } else if (bam_ && !closed_) {
             encode_buffer(true);
             buf_.append(reinterpret_cast<const char *>(kBgzfEof), sizeof kBgzfEof);
@@ -810,6 +823,7 @@ public:
                 set_pileup(ref_ids, ref_lengths);
                 ref_ids_ = ref_ids;
             }
+            if (!stats_file_.empty()) sorter_->set_stats(stats_params_);
             buf_.clear();
         }
     }
@@ -864,6 +878,8 @@ private:
     std::filesystem::path _depth_file, _coverage_file;   // --depth / --coverage: the written records' depth and coverage (include/bmc.h)
     std::filesystem::path _pileup_file;          // --pileup: the variant sites of the written records (include/bmp.h)
     pileup_thresholds _pileup_thresholds{};
+    std::filesystem::path _stats_file;           // --stats: the mapping statistics of the written records (include/bmq.h)
+    stats_params _stats_params{};
     vcf_options _vcf{};                          // --vcf: the genotypes at the pileup's SNV sites (include/bmg.h)
     float _max_edit_rate = -1.f;                 // >= 0: the BM_ALIGN behaviour under an edit bound (--max-edit-rate)
     bool _annotate = false;                      // --annotate: forward-strand records with =/X CIGAR, NM and MD
@@ -1092,6 +1108,10 @@ public:
     void set_vcf(vcf_options const &vcf, pileup_thresholds const &th) {
         _vcf = vcf;
         _pileup_thresholds = th;
+    }
+    void set_stats(std::filesystem::path const &file, stats_params const &pr) {   // ... and its mapping statistics reported
+        _stats_file = file;
+        _stats_params = pr;
     }
     // --max-edit-rate R: write_verified keeps only alignments within (uint32_t)(R * read length) edits; negative = unset
     void set_max_edit_rate(float r) { _max_edit_rate = r; }
@@ -1368,6 +1388,7 @@ public:
             }
         }
         sam_text sam(sam_file, _bam, _sort_run_bytes, _markdup, _depth_file, _coverage_file, _pileup_file, _pileup_thresholds, &pileup_bases, _vcf);
+        sam.set_stats(_stats_file, _stats_params);
         sam.header(h.ref_ids, h.ref_lengths);
         unsigned int read_id = 0, mapped_locations = 0;
         auto t0 = std::chrono::steady_clock::now();

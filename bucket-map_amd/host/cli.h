@@ -103,6 +103,9 @@ struct cmd_arguments {
     bool vcf_phase = false;       // --vcf-phase: read-backed phase of the het SNV lines of --vcf / --gvcf (include/bmk.h states the rule)
     unsigned long phase_min_links = 2, phase_min_frac_ppm = 800000, phase_reach = 4;   // --phase-min-links N (>= 1) / --phase-min-frac F (above 0.5, at most 1) / --phase-reach N (1..8)
     std::string phase_opt;        // the first of those three given: refused without --vcf-phase
+    std::filesystem::path stats_path{};   // --stats FILE (-o x.bam only, implies --sort): the mapping statistics of the records written (include/bmq.h states the rule)
+    unsigned long stats_max_cycle = 1024, stats_max_insert = 8000;   // --stats-max-cycle N / --stats-max-insert N (1..65535): the rows of the per-cycle tables / of the insert sizes
+    std::string stats_opt;        // the first of those two given: refused without --stats
     // run-time replacements of the compile-time configuration
 #ifdef BM_GENOME_PATH
     std::filesystem::path genome_path = BM_GENOME_PATH;
@@ -373,6 +376,18 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
             (opt == "--depth" ? a.depth_path : a.coverage_path) = value();
             a.sort = true;
         }
+        else if (opt == "--stats") {
+            a.stats_path = value();
+            a.sort = true;
+        }
+        else if (opt == "--stats-max-cycle" || opt == "--stats-max-insert") {
+            const std::string s = value();
+            const unsigned long v = as_uint(s);
+            if (s[0] < '0' || s[0] > '9' || v < 1 || v > 65535ul)
+                throw parser_error("Value parse failed for " + opt + ": Argument " + s + " must be a number in 1..65535.");
+            (opt == "--stats-max-cycle" ? a.stats_max_cycle : a.stats_max_insert) = v;
+            if (a.stats_opt.empty()) a.stats_opt = opt;
+        }
         else if (opt == "--pileup") {
             a.pileup_path = value();
             a.sort = true;
@@ -505,7 +520,7 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
         bam.replace_extension(".bam");
         throw parser_error(std::string("Validation failed for option ") +
                            (!a.depth_path.empty() ? "--depth" : !a.coverage_path.empty() ? "--coverage" : !a.pileup_path.empty() ? "--pileup" :
-                            !a.vcf_path.empty() ? "--vcf" : !a.gvcf_path.empty() ? "--gvcf" : a.markdup ? "--markdup" : "--sort") +
+                            !a.vcf_path.empty() ? "--vcf" : !a.gvcf_path.empty() ? "--gvcf" : a.markdup ? "--markdup" : !a.stats_path.empty() ? "--stats" : "--sort") +
                            ": only BAM output is sorted and indexed; write -o " + bam.string() + " instead of -o " +
                            a.output_sam_path.string() + ".");
     }
@@ -545,6 +560,15 @@ inline cmd_arguments parse_arguments(int argc, char **argv) {
                            ": depth and coverage are those of the records of a sorted BAM file; name one with -o x.bam.");
     if (!a.depth_path.empty() && a.depth_path == a.coverage_path)
         throw parser_error("Validation failed for option --coverage: " + a.coverage_path.string() + " is the file of --depth too.");
+    if (!a.stats_opt.empty() && a.stats_path.empty())
+        throw parser_error("Validation failed for option " + a.stats_opt + ": it is an option of --stats FILE, which is not given.");
+    if (!a.stats_path.empty() && a.output_sam_path.empty() && !a.only_indexer)
+        throw parser_error("Validation failed for option --stats: the statistics are those of the records of a sorted BAM file; name one with -o x.bam.");
+    if (!a.stats_path.empty() && (a.stats_path == a.depth_path || a.stats_path == a.coverage_path || a.stats_path == a.pileup_path || a.stats_path == a.vcf_path ||
+                                  a.stats_path == a.gvcf_path))
+        throw parser_error("Validation failed for option --stats: " + a.stats_path.string() + " is the file of " +
+                           (a.stats_path == a.depth_path ? "--depth" : a.stats_path == a.coverage_path ? "--coverage" : a.stats_path == a.pileup_path ? "--pileup" :
+                            a.stats_path == a.vcf_path ? "--vcf" : "--gvcf") + " too.");
     if (a.split) a.clip = a.annotate = true;
     if (a.rescue) a.paired = true;
     if (a.paired) a.best = a.annotate = true;

@@ -150,6 +150,8 @@ int main(int argc, char **argv) {
             if (args.sort) loc.set_sort(bm::bam_sort_run_bytes(args.sort_mem));   // --sort: coordinate order and x.bam.bai
             loc.set_markdup(args.markdup);                                        // --markdup: duplicates flagged before the sort
             loc.set_depth_files(args.depth_path, args.coverage_path);            // --depth / --coverage: of the records written
+            if (!args.stats_path.empty())                                         // --stats: how the records written mapped
+                loc.set_stats(args.stats_path, bm::stats_params{static_cast<uint32_t>(args.stats_max_cycle), static_cast<uint32_t>(args.stats_max_insert)});
             const bm::pileup_thresholds pileup_th{static_cast<uint32_t>(args.pileup_min_mapq), static_cast<uint32_t>(args.pileup_min_bq),
                                                   static_cast<uint32_t>(args.pileup_min_alt), static_cast<uint32_t>(args.pileup_min_frac_ppm)};
             if (!args.pileup_path.empty()) loc.set_pileup(args.pileup_path, pileup_th);   // --pileup: their variant sites against the genome

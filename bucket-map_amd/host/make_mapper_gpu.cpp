@@ -8,6 +8,7 @@
 #include "../../include/bmr.h"
 #include "../../include/bmb.h"
 #include "../../include/bmk.h"
+#include "../../include/bmq.h"
 #include "../../include/bmd.h"
 #include "../../include/bms.h"
 #include "../../include/bmz.h"
@@ -129,6 +130,7 @@ public:
     }
     ~gpu_block_compressor() override {
         bmr_destroy(blocks_);
+        bmq_destroy(stats_);
         bmk_destroy(phase_);
         bmb_destroy(bias_);
         bmn_destroy(indel_);
@@ -310,6 +312,28 @@ public:
         out.sites.assign(static_cast<size_t>(stats[BMK_S_SITES]) * bm::kPhaseOutWords, 0);
         if (bmk_phase(phaser(), 0, stats[BMK_S_SITES], out.sites.data()) != BMK_OK) throw std::runtime_error(std::string("bmk_phase: ") + bmk_last_error());
     }
+    // --stats: the mapping statistics of the written records on the same device (bmq_*: the rule of include/bmq.h, which is the
+    // host default's)
+    void stats_begin(const bm::stats_params &pr) override {
+        const uint32_t p[BMQ_N_PARAMS] = {pr.max_cycle, pr.max_insert};
+        if (bmq_begin(counter(), p) != BMQ_OK) throw std::runtime_error(std::string("bmq_begin: ") + bmq_last_error());
+        stats_params_ = pr;
+    }
+    void stats_add(const uint8_t *in, size_t n, const uint64_t *rec_offset, size_t n_records, const uint8_t *skip) override {
+        if (bmq_add(counter(), in, n, rec_offset, n_records, skip) != BMQ_OK) throw std::runtime_error(std::string("bmq_add: ") + bmq_last_error());
+    }
+    void stats_finish(bm::stats_result &out) override {
+        static_assert(BMQ_N_TALLIES == bm::kStatsTallies && BMQ_N_TABLES == bm::kStatsTables, "bmq.h and host/stats.h disagree");
+        out = bm::stats_result{};
+        out.params = stats_params_;
+        if (bmq_finish(counter(), out.tallies) != BMQ_OK) throw std::runtime_error(std::string("bmq_finish: ") + bmq_last_error());
+        for (size_t t = 0; t < bm::kStatsTables; t++) {
+            const size_t rows = bm::stats_rows(t, stats_params_);
+            out.table[t].assign(rows * bm::kStatsWidth[t], 0);
+            if (bmq_table(counter(), static_cast<uint32_t>(t), 0, rows, out.table[t].data()) != BMQ_OK)
+                throw std::runtime_error(std::string("bmq_table: ") + bmq_last_error());
+        }
+    }
     // --gvcf: the reference blocks of the genotype caller's cells on the same device (bmr_*: the rule of include/bmr.h, which
     // is the host default's)
     void refblocks(const uint32_t *ref_len, size_t n_ref, const uint8_t *const *ref_bases, const std::vector<uint32_t> &bands,
@@ -326,6 +350,12 @@ public:
 private:
     int device_ = 0;
     bmr_ctx *blocks_ = nullptr;     // made by the first call: a run without --gvcf pays nothing for it
+    bmq_ctx *stats_ = nullptr;      // made by the first stats call: a run without --stats pays nothing for it
+    bm::stats_params stats_params_;
+    bmq_ctx *counter() {
+        if (!stats_ && bmq_create(device_, &stats_) != BMQ_OK) throw std::runtime_error(std::string("bmq_create: ") + bmq_last_error());
+        return stats_;
+    }
     bmk_ctx *phase_ = nullptr;      // made by the first phase call: a run without --vcf-phase pays nothing for it
     bmk_ctx *phaser() {
         if (!phase_ && bmk_create(device_, &phase_) != BMK_OK) throw std::runtime_error(std::string("bmk_create: ") + bmk_last_error());
